@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: LiDAR frames/s for encode + match + register at 65 536 points per frame.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of 64 synthetic scans per GPU
 (deeppointmap_amd/synthetic.py, BASELINE.json config 2): Encoder.forward on the batch, then for
@@ -12,9 +12,13 @@ resident in HBM before the timed region.  With N > 1 (launched by torch.distribu
 process per GPU) every rank runs its own batch (weak scaling) and ships its descriptors and
 edge table to rank 0 with one RCCL gather per step.
 
-Prints ONE JSON line on rank 0 (contract in the task description) carrying `roofline` for the
-dominant kernel (HIP-event timed inside the timed region) and `cpu_baseline` (the oracle timed on
-the host cores over a bounded sample; N == 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step`); nothing else runs.  --full adds everything else the benchmark measures or checks:
+`roofline` for the dominant kernel (HIP-event timed inside the timed region) and `roofline_mfma`, `parity_gate` (the
+last timed step against the reference's results; a failed gate voids `value` and exits 1), the extra measurements
+(`sustained`, the kernels alone, PCIe-inclusive rate, latency mode, rank-0 consumer; --no-extras skips them) and
+`cpu_baseline` (the oracle timed on the host cores over a bounded sample; N == 1 only; --cpu-frames 0 skips it).
+--dump-outputs DIR writes what the last timed step returned on rank 0 (descriptors, edge table) as float32 .npy files.
 """
 from __future__ import annotations
 
@@ -141,6 +145,25 @@ def cpu_baseline(n_frames: int, n_points: int, threads: int):
     return n_frames / (t2 - t0), (t1 - t0) / n_frames, (t2 - t1) / n_frames
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(directory: str, desc: torch.Tensor, table: torch.Tensor) -> dict:
+    """--dump-outputs: what the last timed step returned on rank 0, as a caller of HotPath.submit / flush receives it --
+    `descriptors.npy` (frames, 131, S): 128 features over the key points' coordinates in metres, and `edges.npy` (frames, 56):
+    row f is the edge (f - 1, f), 20-float registration header | 6x6 information matrix (pipeline.EDGE_FLOATS) -- in float32.
+    The scans are the seeded synthetic sequence, so two builds run with the same arguments compare file for file.  Whole frames
+    are kept in order while both files fit DUMP_BYTES (all of them at the default 64 frames: 8.6 MB)."""
+    import numpy as np
+    d = desc.detach().float().cpu().numpy()
+    e = table.detach().float().cpu().numpy()
+    keep = min(d.shape[0], e.shape[0], (DUMP_BYTES - 2 * 4096) // (d[0].nbytes + e[0].nbytes))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "descriptors.npy"), np.ascontiguousarray(d[:keep]))
+    np.save(os.path.join(directory, "edges.npy"), np.ascontiguousarray(e[:keep]))
+    return {"frames": int(keep), "of": int(d.shape[0])}
+
+
 class Guard:
     """Makes a run unable to hang or to die silently (the first N > 1 run on hardware happens under the driver, unobserved):
       * every phase leaves a rank-tagged breadcrumb on stderr and has a deadline; a watchdog thread that finds the deadline passed
@@ -211,8 +234,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=64, help="frames per GPU per step")
     ap.add_argument("--points", type=int, default=65536)
-    ap.add_argument("--cpu-frames", type=int, default=64, help="frames of the cpu_baseline sample (0 = skip; default: the whole batch)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra measurements (PCIe-inclusive rate, latency mode, rank-0 consumer)")
+    ap.add_argument("--cpu-frames", type=int, default=64, help="--full: frames of the cpu_baseline sample (0 = skip; default: the whole batch)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra measurements (PCIe-inclusive rate, latency mode, rank-0 consumer)")
     ap.add_argument("--no-pipeline", action="store_true", help="run every step start-to-finish on one stream")
     ap.add_argument("--geometry-depth", type=int, default=None, help="geometry passes kept in flight (pipeline tuning)")
     ap.add_argument("--geometry-group", type=int, default=None, help="batches per first-level sampling launch (pipeline tuning)")
@@ -237,7 +260,15 @@ def main():
                          "path on a single-GPU box; recorded in config.parallelism)")
     ap.add_argument("--inject-failure", default="none", choices=("none", "hang-in-gather", "raise-in-step"),
                     help="test hook for the guard: the named failure happens in the first timed step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline figures, the parity gate against "
+                         "the reference's results, the extra measurements and the cpu_baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned on rank 0 as DIR/<name>.npy (float32): "
+                         "descriptors (frames, 131, 256) and edges (frames, 56); at most 64 MB, whole frames kept in order")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as `python bench.py --gpus N` (the N = 1 command form): become the launcher -- one process per GPU, rendezvous on
         # the loopback address.  exec, not spawn: signals and the exit code are the launcher's, stdout carries rank 0's one line.
@@ -343,7 +374,7 @@ def run(args, guard, rank, world):
     pcd_m = (pts * synthetic.COOR_SCALE).contiguous()  # ScanPack.full_pcd: the scans in metres
     torch.cuda.synchronize()
 
-    # HIP events around the dominant kernel (first-stage FPS), recorded on the launch stream
+    # --full: HIP events around the dominant kernel (first-stage FPS), recorded on the launch stream
     fps_events, fps_frames = [], [0]
     orig_fps = ops.fps
 
@@ -359,7 +390,8 @@ def run(args, guard, rank, world):
         return out
 
     import deeppointmap_amd.encoder as enc_mod
-    enc_mod.ops.fps = timed_fps
+    if args.full:
+        enc_mod.ops.fps = timed_fps
 
     # ... and around the widest dense contraction of the path (the decoder's 256 -> 768 attention projections over
     # all tokens of the batch), the MFMA-bound representative reported as `roofline_mfma`
@@ -379,7 +411,8 @@ def run(args, guard, rank, world):
         gemm_flops[0] = 2 * x.shape[0] * W.shape[0] * W.shape[1]
         return out
 
-    ops.linear = timed_linear
+    if args.full:
+        ops.linear = timed_linear
     # (since round 5 that projection hands K / V to the attention kernel as operand planes: ops.linear_kvplanes, same contraction)
     orig_kvplanes = ops.linear_kvplanes
     gemm_kvp = [False]
@@ -397,7 +430,8 @@ def run(args, guard, rank, world):
             gemm_kvp[0] = True
         return out
 
-    ops.linear_kvplanes = timed_kvplanes
+    if args.full:
+        ops.linear_kvplanes = timed_kvplanes
 
     last_gathered = [None]
 
@@ -472,23 +506,29 @@ def run(args, guard, rank, world):
     fence()
     dt = time.perf_counter() - t0
     timed[0] = False
-    guard.phase("after the timed region (parity gate, extra measurements)", 600)
+    guard.phase("after the timed region (parity gate, extra measurements)" if args.full else "after the timed region", 600)
     if world > 1:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
-    # the rows the last timed step gathered, held against the reference's results before anything else touches the pipeline's buffers
+    # the rows the last timed step gathered: written out and held against the reference's results before anything else touches
+    # the pipeline's buffers
     gate = None
     if rank == 0:
         gd, gt = last_gathered[0] if last_gathered[0] is not None else (None, None)
-        gate = parity_gate(gd, gt, N) if gd is not None else {"checked": False, "why": "nothing gathered"}
+        if args.dump_outputs is not None:
+            if gd is None:
+                raise RuntimeError("--dump-outputs: the timed steps gathered nothing")
+            dump_outputs(args.dump_outputs, gd, gt)
+        if args.full:
+            gate = parity_gate(gd, gt, N) if gd is not None else {"checked": False, "why": "nothing gathered"}
     fps_ms = sum(a.elapsed_time(b) for a, b in fps_events) / max(len(fps_events), 1)
     gemm_ms = sum(a.elapsed_time(b) for a, b in gemm_events) / max(len(gemm_events), 1)
 
     # ---- extra measurements, outside the timed region and never part of `value` ---------------------------------
     extras = {}
     alone = {}
-    if not args.no_extras and not args.no_pipeline:
+    if args.full and not args.no_extras and not args.no_pipeline:
         # (-1) the same steps again for a few seconds (round-5 review: the timed region of the default run is 0.09 s, too short for a
         #      device monitor sampling beside the run to see a busy GPU): frames/s over >= 2.5 s with the parity gate on its last step.
         #      Every rank runs it (the steps carry the gather).
@@ -506,7 +546,7 @@ def run(args, guard, rank, world):
             extras["sustained"] = {"steps": n_sus, "seconds": round(sus, 2), "value": round(world * F * n_sus / sus, 1), "unit": "frames/s",
                                    "ms_per_step": round(sus / n_sus * 1e3, 3), "clock": "rank 0", "parity_gate_ok": g2.get("ok"),
                                    "max_dT_m": g2.get("max_dT_m"), "descriptor_max_err": g2.get("descriptor_max_err")}
-    if not args.no_extras and rank == 0:
+    if args.full and not args.no_extras and rank == 0:
         # (0) the two roofline kernels ALONE on the chip (the figures inside the timed region include what the other
         #     pipeline stages cost them): first-stage sampling of one 64-frame batch, and the 256 -> 768 projection
         def alone_ms(fn, n):
@@ -531,7 +571,7 @@ def run(args, guard, rank, world):
                 alone["gemm_ms"] = alone_ms(lambda: orig_linear(gx, gw, gb, out=go), 20)
             del gx, gw, gb, go
         del xyz0, len0
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world == 1 and not args.no_pipeline:
             # (1) PCIe-inclusive rate: the scans start in pinned host memory and are copied in every step (the metres copy
             #     for the information matrix is derived on the device, as a caller holding one scan buffer would)
@@ -644,8 +684,8 @@ def run(args, guard, rank, world):
         pairs = [((f - 1) % F, f) for f in range(F)]
         print(f"[stages] encode {tm(lambda: hot.extract(pts, pad)):.2f} ms | "
               f"register x{F} {tm(lambda: hot.register(desc, None, pairs)):.2f} ms | "
-              f"register+info x{F} {tm(lambda: hot.register(desc, pcd_m, pairs)):.2f} ms | fps0 kernel pair {fps_ms:.3f} ms",
-              file=sys.stderr)
+              f"register+info x{F} {tm(lambda: hot.register(desc, pcd_m, pairs)):.2f} ms | fps0 kernel pair " +
+              (f"{fps_ms:.3f} ms" if args.full else "timed with --full"), file=sys.stderr)
 
     if rank == 0:
         value = world * F * args.steps / dt
@@ -670,26 +710,28 @@ def run(args, guard, rank, world):
                        "weights": "procedural (deeppointmap_amd/weights.py)",
                        "allocator_reserve_gib": 0 if args.no_pipeline else hot.reserve_bytes >> 30,
                        "geometry_waits_for_caller_stream": bool(hot.inputs_on_caller_stream)},
-            "roofline": {"kernel": "str_chunk/str_xoffsets/str_ysort kernels + fps_bucket_kernel (stage-0 farthest point sampling: Sort-Tile-Recursive packing, then the sampling rounds)",
-                         "bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(achieved / (HBM_PEAK / 1e9), 6), "traffic": pmc_traffic_bytes(F),
-                         "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of these "
-                                           "kernels at this batch size, committed; not re-measured in this run)",
-                         "avg_launch_ms": round(fps_ms, 4), "algorithmic_bytes_per_launch": alg,
-                         "whole_path_frac": round(value / world * B_ALG_FRAME / HBM_PEAK, 6),
-                         "us_per_round": round(fps_ms * 1e3 / (cfg.encoder.npoint[0] - 1), 3),
-                         "note": "avg_launch_ms exceeds ms_per_step because two launches (two batches' geometry stages) are "
-                                 "in flight on alternating streams; "
-                                 "FPS is a chain of 4095 dependent argmax rounds per frame, one CU per frame: latency-"
-                                 "bound by construction (us_per_round is the figure that matters); traffic > algorithmic "
-                                 "bytes because each round re-reads the ~7 buckets the new point can change -- the "
-                                 "reference's loop re-reads the WHOLE frame every round (4095 x 65536 x 16 B = 4.3 GB "
-                                 "per frame, 275 GB per launch), the bucket pruning cuts that ~85x; see DESIGN.md"},
         }
+        if args.full:   # the dominant kernel, HIP-event timed inside the timed region
+            line["roofline"] = {"kernel": "str_chunk/str_xoffsets/str_ysort kernels + fps_bucket_kernel (stage-0 farthest point sampling: Sort-Tile-Recursive packing, then the sampling rounds)",
+                                "bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                                "frac": round(achieved / (HBM_PEAK / 1e9), 6), "traffic": pmc_traffic_bytes(F),
+                                "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of these "
+                                                  "kernels at this batch size, committed; not re-measured in this run)",
+                                "avg_launch_ms": round(fps_ms, 4), "algorithmic_bytes_per_launch": alg,
+                                "whole_path_frac": round(value / world * B_ALG_FRAME / HBM_PEAK, 6),
+                                "us_per_round": round(fps_ms * 1e3 / (cfg.encoder.npoint[0] - 1), 3),
+                                "note": "avg_launch_ms exceeds ms_per_step because two launches (two batches' geometry stages) are "
+                                        "in flight on alternating streams; "
+                                        "FPS is a chain of 4095 dependent argmax rounds per frame, one CU per frame: latency-"
+                                        "bound by construction (us_per_round is the figure that matters); traffic > algorithmic "
+                                        "bytes because each round re-reads the ~7 buckets the new point can change -- the "
+                                        "reference's loop re-reads the WHOLE frame every round (4095 x 65536 x 16 B = 4.3 GB "
+                                        "per frame, 275 GB per launch), the bucket pruning cuts that ~85x; see DESIGN.md"}
         if ranks_seen is not None:    # N ranks on N distinct devices, as the process group itself reported them
             line["ranks"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "collective_timeout_s": args.collective_timeout,
                              "members": ranks_seen}
-        line["parity_gate"] = gate   # what the timed steps computed against the reference's results for this workload
+        if args.full:
+            line["parity_gate"] = gate   # what the timed steps computed against the reference's results for this workload
         if "fps_ms" in alone:   # the same kernel pair with the chip to itself (outside the timed region)
             line["roofline"]["alone"] = {"launch_ms": round(alone["fps_ms"], 4),
                                          "us_per_round": round(alone["fps_ms"] * 1e3 / (cfg.encoder.npoint[0] - 1), 3),
@@ -701,7 +743,7 @@ def run(args, guard, rank, world):
         line.update(extras)
         if "rank0_serial_ms" in extras:
             line["value_with_rank0_consumer"] = round(world * F / (dt / args.steps + extras["rank0_serial_ms"] * 1e-3), 1)
-        if gemm_ms > 0:
+        if args.full and gemm_ms > 0:
             rows = gemm_flops[0] // (2 * 768 * 256)
             if knobs.GEMM_BF16X3:
                 # the projection runs on the bf16 matrix pipe: every fp32 operand split exactly into three bf16 terms, six
@@ -732,7 +774,7 @@ def run(args, guard, rank, world):
                                                   "frac": round(mult * ta / PEAK, 4)}
                 if mult > 1:
                     line["roofline_mfma"]["alone"]["fp32_equivalent_frac"] = round(ta / 157.3, 4)
-        if world == 1 and args.cpu_frames > 0:
+        if args.full and world == 1 and args.cpu_frames > 0:
             guard.phase("cpu_baseline (oracle on the host cores)", 1200)
             # torch's intra-op pool stops scaling (and then collapses) well below the box's core count on
             # these small ops: 16 threads measured fastest on the 256-core GPU host (8: 0.83, 16: 0.63,
@@ -747,7 +789,7 @@ def run(args, guard, rank, world):
         # flushed first, the JSON line is the last thing on stdout
         import ctypes
         ctypes.CDLL(None).fflush(None)
-        gate_failed = line["parity_gate"].get("checked") and not line["parity_gate"]["ok"]
+        gate_failed = args.full and line["parity_gate"].get("checked") and not line["parity_gate"]["ok"]
         if gate_failed:   # like Guard.fail: a run that did not reproduce the reference has no headline number
             line["value_measured_but_void"], line["value"] = line["value"], None
             line["error"] = "parity gate failed: the timed steps did not reproduce the reference's results (see parity_gate)"

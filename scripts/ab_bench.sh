@@ -4,6 +4,6 @@
 # and add DPM_LIB=/tmp/libdpm_exp.so to every setting; bench.py needs --allow-knobs to run with any DPM_* variable set.
 for rep in 1 2; do
 for setting in "$@"; do
-  env $setting python bench.py --allow-knobs --steps 60 --warmup 5 --cpu-frames 0 --no-extras 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$setting', j['value'], j['ms_per_step'], j['roofline']['us_per_round'])"
+  env $setting python bench.py --full --allow-knobs --steps 60 --warmup 5 --cpu-frames 0 --no-extras 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$setting', j['value'], j['ms_per_step'], j['roofline']['us_per_round'])"
 done
 done

@@ -7,7 +7,7 @@ for i in $(seq 1 $reps); do
 for s in "$@"; do
   tag=${s%%=*}; lib=${s#*=}
   if [ "$lib" = shipped ]; then envs=""; else envs="DPM_LIB=$lib"; fi
-  env $envs python bench.py --steps $steps --warmup 10 --allow-knobs --no-extras --cpu-frames 0 > $out/${tag}_$i.json 2> $out/${tag}_$i.err
+  env $envs python bench.py --full --steps $steps --warmup 10 --allow-knobs --no-extras --cpu-frames 0 > $out/${tag}_$i.json 2> $out/${tag}_$i.err
   python - <<PY
 import json
 try:

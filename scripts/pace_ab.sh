@@ -7,7 +7,7 @@
 out=${1:-gpurun_out/pace}; mkdir -p $out
 run() {  # tag, env...
   tag=$1; shift
-  env "$@" python bench.py --allow-knobs --steps 40 --warmup 5 --cpu-frames 0 --no-extras > $out/$tag.json 2> $out/$tag.err
+  env "$@" python bench.py --full --allow-knobs --steps 40 --warmup 5 --cpu-frames 0 --no-extras > $out/$tag.json 2> $out/$tag.err
   python - "$tag" $out/$tag.json <<'PY'
 import json, sys
 try:

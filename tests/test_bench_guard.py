@@ -114,6 +114,25 @@ def test_parity_gate_accepts_the_reference_rows_and_refuses_perturbed_ones():
     assert bench.parity_gate(desc, table, 16384) == {"checked": False, "why": "fixtures cover the 65 536-point synthetic sequence, frames 0-5"}
 
 
+def test_dump_outputs_writes_float32_whole_frames_within_the_cap(tmp_path, monkeypatch):
+    """bench.py::dump_outputs (--dump-outputs): descriptors and edge rows as float32 .npy, all frames when they fit, else the first
+    whole frames that do -- the same frames on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    desc, table = torch.randn(12, 131, 256, generator=g), torch.randn(12, 56, generator=g).double()
+    assert bench.dump_outputs(str(tmp_path / "all"), desc, table) == {"frames": 12, "of": 12}
+    d, e = np.load(tmp_path / "all" / "descriptors.npy"), np.load(tmp_path / "all" / "edges.npy")
+    assert d.dtype == e.dtype == np.float32 and np.array_equal(d, desc.numpy()) and np.array_equal(e, table.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 5 * (131 * 256 + 56) * 4 + 2 * 4096)
+    assert bench.dump_outputs(str(tmp_path / "cap"), desc, table) == {"frames": 5, "of": 12}
+    d = np.load(tmp_path / "cap" / "descriptors.npy")
+    assert np.array_equal(d, desc[:5].numpy()) and np.load(tmp_path / "cap" / "edges.npy").shape == (5, 56)
+    assert sum(f.stat().st_size for f in (tmp_path / "cap").iterdir()) <= bench.DUMP_BYTES
+
+
 def test_self_launch_command_line():
     """`python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run: one process per GPU of this
     node, rendezvous on the loopback address, its own arguments passed through."""

@@ -49,12 +49,18 @@ def _three(g, k):
     return float((a - b).norm()), rot_angle(torch.from_numpy(g[k + ".ref32.R"]), torch.from_numpy(g[k + ".ref64.R"]))
 
 
-CASES = margin_cases.all_cases() if torch.cuda.is_available() else []
+# the same case ids on every machine (the inputs are replayed once, where the cases run)
+KEYS = sorted(margin_cases.CASES)
 
 
-@pytest.mark.parametrize("case", CASES, ids=[f"s{s}_n{n}_{cls}" for (s, n), cls, _ in CASES])
-def test_fuzz_cases_against_the_reference_in_fp64(case, dec):
-    (seed, n), cls, (s, d, ms, md, ns) = case
+@pytest.fixture(scope="module")
+def case_inputs():
+    return {key: inputs for key, _, inputs in margin_cases.all_cases()}
+
+
+@pytest.mark.parametrize("key", KEYS, ids=[f"s{s}_n{n}_{margin_cases.CASES[(s, n)]}" for s, n in KEYS])
+def test_fuzz_cases_against_the_reference_in_fp64(key, case_inputs, dec):
+    (seed, n), cls, (s, d, ms, md, ns) = key, margin_cases.CASES[key], case_inputs[key]
     g = load_golden("margin.npz")
     k = f"s{seed}_n{n}"
     R, T, conf, rmse = dec.registration_forward(s, d, ms, md, num_sample=ns)

@@ -114,7 +114,7 @@ def test_bench_two_ranks_dry_run():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29950 + os.getpid() % 40), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--cpu-frames", "0", "--frames", "8", "--points", "16384", "--backend", "gloo"]
+           "--warmup", "1", "--cpu-frames", "0", "--frames", "8", "--points", "16384", "--backend", "gloo", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

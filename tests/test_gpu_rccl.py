@@ -106,7 +106,7 @@ def test_bench_over_a_one_rank_rccl_group_records_its_ranks():
     """bench.py's N > 1 code path (process group with a timeout, rank census, the step's gather on the communication stream) on the
     one GPU there is: the line must say which ranks on which devices the process group saw."""
     import json
-    out = _bench()
+    out = _bench("--full")
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["ranks"]["world_size"] == 1 and line["ranks"]["backend"] == "nccl" and len(line["ranks"]["members"]) == 1

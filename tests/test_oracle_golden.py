@@ -100,6 +100,23 @@ def test_position_embedding():
     assert np.all(out.numpy()[:, 252:] == 0)
 
 
+def assert_same_correspondences(src, dst, w, want_src, want_dst, want_w, atol, tie=1e-4):
+    """Correspondences (3, n) in top-k order of their confidence.  Confidences of different pairs can tie at rounding level
+    (map1024_vs_256: adjacent gaps of 2e-6 relative, while two fp32 evaluations differ by 1e-5), and topk then orders the tied
+    pairs as the host's arithmetic decides (vector width, thread count).  Column i must equal the reference's column i within
+    `atol`, or -- a reordering of tied pairs -- the column at a position whose reference weight equals w[i] within `tie` relative;
+    every reference column is matched once."""
+    n = want_src.shape[1]
+    assert src.shape == want_src.shape and dst.shape == want_dst.shape and w.shape == want_w.shape == (n,)
+    taken = np.zeros(n, dtype=bool)
+    for i in range(n):
+        tied = np.nonzero(np.abs(want_w - w[i]) <= tie * abs(w[i]))[0]
+        match = [j for j in [i] + [j for j in tied if j != i]
+                 if not taken[j] and np.abs(src[:, i] - want_src[:, j]).max() <= atol and np.abs(dst[:, i] - want_dst[:, j]).max() <= atol]
+        assert match, f"correspondence {i} (weight {w[i]:.6g}) matches no reference correspondence of the same weight"
+        taken[match[0]] = True
+
+
 @pytest.mark.parametrize("name", ["synthetic01", "kitti01", "map1024_vs_256"])
 def test_registration_stages(name, cfg_full, sd_dec):
     g = load_golden("decoder.npz")
@@ -110,8 +127,8 @@ def test_registration_stages(name, cfg_full, sd_dec):
     np.testing.assert_allclose(tr["y"][0].t().numpy(), g[name + ".dst_corr"][:-3], atol=2e-4, rtol=0)
     np.testing.assert_allclose(tr["conf"].numpy(), g[name + ".pair_conf"], rtol=2e-3, atol=0)
     assert tr["src"].shape == g[name + ".corr_src"].shape
-    np.testing.assert_allclose(tr["src"].numpy(), g[name + ".corr_src"], atol=2e-3, rtol=0)
-    np.testing.assert_allclose(tr["dst"].numpy(), g[name + ".corr_dst"], atol=2e-3, rtol=0)
+    assert_same_correspondences(tr["src"].numpy(), tr["dst"].numpy(), tr["w"].numpy(),
+                                g[name + ".corr_src"], g[name + ".corr_dst"], g[name + ".corr_w"], atol=2e-3)
     # the pose tolerance north_star states: 1e-4 m / 1e-4 rad
     assert float((Tt - T(g[name + ".T"])).norm()) < 1e-4
     assert rot_angle(R, g[name + ".R"]) < 1e-4
