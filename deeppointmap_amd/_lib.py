@@ -96,6 +96,12 @@ SIGNATURES = {
     "dpm_information_matrix_batched": (I, [P, I, P, P, I, P, I, D, P, I, P, P]),
     "dpm_infomat_build_grids": (I, [P, I, P, I, D, P, P]),
     "dpm_infomat_search_grids": (I, [P, I, P, P, I, P, I, D, P, I, P, P]),
+    "dpm_voxel_map_workspace_bytes": (c_size_t, [LL]),
+    "dpm_voxel_map_init": (I, [LL, P, P]),
+    "dpm_voxel_map_bounds": (I, [P, P, P, I, LL, P, P]),
+    "dpm_voxel_map_insert": (I, [P, P, P, I, LL, LL, LL, D, D, D, D, P, P]),
+    "dpm_voxel_map_finish": (I, [LL, P, P]),
+    "dpm_voxel_map_emit": (I, [P, LL, D, D, D, D, P, P, I, P]),
 }
 
 

@@ -169,6 +169,14 @@ class Rank0Consumer:
         self.desc: Dict[int, torch.Tensor] = {}        # key-frames and the scan at hand: descriptors on the device
         # full clouds (3,N) in metres, when the caller has them: on the device up to a budget, the rest on the host
         self.pcd = ScanCloudStore(self.device, int(self.args.get("scan_cloud_device_bytes", 4 << 30)))
+        # slam_system.result_maps (off unless set): the end-of-run map of ResultLogger.draw_trajectory / export_map needs the
+        # cloud of EVERY accepted scan, non-key frames included (ScanPack.nonkeyframe() keeps full_pcd, pose_graph.py:86-100),
+        # and the ground-truth pose of each (core.py:379).  A store of its own, with the same budget and host spill, so that
+        # the edge path's LRU above is untouched.
+        self.result_maps = bool(self.args.get("result_maps", False))
+        self.map_clouds = (ScanCloudStore(self.device, int(self.args.get("scan_cloud_device_bytes", 4 << 30)))
+                           if self.result_maps else None)
+        self.gt: Dict[int, torch.Tensor] = {}          # token -> SE3_gt (4,4) CPU (result_maps only)
         self.coor: Dict[int, int] = {}                 # token -> coordinate system (multi-agent: one per agent until loops merge them)
         self.coor_sys = agent_id                       # SlamSystem.coor_sys (core.py:44)
         self.last_known_keyframe: Optional[int] = None
@@ -583,6 +591,7 @@ class Rank0Consumer:
             self.pcd[tok] = pcd
         cands = self._odometry_candidates()
         if not cands:                                   # first scan of the graph (core.py:383-388)
+            self._retain(tok, pcd)
             self.poses[tok], self.desc[tok] = torch.eye(4), desc
             self._add_vertex(tok, "full")
             self._store_put(tok, desc)
@@ -608,6 +617,7 @@ class Rank0Consumer:
             self.pcd.pop(tok, None), self.desc.pop(tok, None)
             self.codes.append(code)
             return code
+        self._retain(tok, pcd)                          # accepted: a key frame or a non-key frame of the graph
         self.last_known_keyframe = edge["src"]
         code = self._keyframe_check(tok, edge)
         if code != ACPT:
@@ -641,6 +651,10 @@ class Rank0Consumer:
         self.codes.append(ACPT)
         return ACPT
 
+    def _retain(self, tok: int, pcd: Optional[torch.Tensor]) -> None:
+        if self.map_clouds is not None and pcd is not None:
+            self.map_clouds[tok] = pcd
+
     def step(self, desc: torch.Tensor, pcd: Optional[torch.Tensor] = None) -> Tuple[int, str]:
         """SlamSystem.step after the extraction (core.py:382-407) for one agent: token = (agent << 16) + frame number
         counted from zero (core.py:361, pose_graph.py:39).  -> (token, exit code)"""
@@ -653,6 +667,8 @@ class Rank0Consumer:
         odometry edge and its other edges (the loop edges this step found)"""
         scan = dict(token=tok, agent_id=tok >> 16, timestep=tok & 0xFFFF, type=self.type[tok], key_points=self.desc[tok],
                     full_pcd=self.pcd.get(tok), SE3_pred=self.poses[tok].clone(), coor_sys=self.coor[tok])
+        if self.result_maps:
+            scan["SE3_gt"] = self.gt.get(tok)
         odom = next((e for (a, b), e in self.edges.items() if b == tok and e["type"] == "odom"), None)
         others = [e for n, e in self.adj.get(tok, ()) if e is not odom]
         pack = lambda e: None if e is None else {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in e.items()}
@@ -670,6 +686,9 @@ class Rank0Consumer:
         self.desc[tok] = scan["key_points"].to(dev)
         if scan.get("full_pcd") is not None:
             self.pcd[tok] = scan["full_pcd"].to(dev)
+            self._retain(tok, self.pcd[tok])
+        if self.result_maps and scan.get("SE3_gt") is not None:
+            self.gt[tok] = scan["SE3_gt"].cpu().clone()
         self.poses[tok] = scan["SE3_pred"].cpu().clone()
         self._add_vertex(tok, "full", scan["coor_sys"])
         self._store_put(tok, self.desc[tok])

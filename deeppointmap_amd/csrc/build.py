@@ -44,6 +44,7 @@ SOURCES = {
     "preprocess.hip": [],
     "voxel_sample.hip": [],
     "posegraph.hip": [],
+    "voxel_map.hip": [],
 }
 
 

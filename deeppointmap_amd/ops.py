@@ -978,3 +978,47 @@ def information_matrix_grids(pcd: torch.Tensor, dst_frame: torch.Tensor, radius:
     _lib.check(lib.dpm_infomat_build_grids(_ptr(pcd), N, _ptr(dst_frame), P_, float(radius), _ptr(ws), _stream(pcd)),
                "dpm_infomat_build_grids")
     return ws
+
+
+# -- the global map (csrc/voxel_map.hip; orchestration in globalmap.py) ------------------------------------------------------
+VOXEL_MAP_HDR_BYTES = 256   # the workspace header globalmap.py reads back between the calls (include/dpm_hip.h)
+
+
+def voxel_map_workspace_bytes(n_points: int) -> int:
+    return int(_lib.load().dpm_voxel_map_workspace_bytes(int(n_points)))
+
+
+def voxel_map_init(ws: torch.Tensor, n_points: int) -> None:
+    _chk(ws, torch.uint8, "workspace")
+    _lib.check(_lib.load().dpm_voxel_map_init(int(n_points), _ptr(ws), _stream(ws)), "dpm_voxel_map_init")
+
+
+def voxel_map_bounds(ws: torch.Tensor, clouds: int, offsets: int, poses: int, n_scans: int, n_batch: int) -> None:
+    """clouds / offsets / poses: device addresses of the batch's pointer, offset (int64) and pose (12 fp32 per scan) arrays"""
+    _chk(ws, torch.uint8, "workspace")
+    _lib.check(_lib.load().dpm_voxel_map_bounds(clouds, offsets, poses, int(n_scans), int(n_batch), _ptr(ws), _stream(ws)),
+               "dpm_voxel_map_bounds")
+
+
+def voxel_map_insert(ws: torch.Tensor, clouds: int, offsets: int, poses: int, n_scans: int, n_batch: int, base: int,
+                     n_points: int, min_b, voxel_size: float) -> None:
+    _chk(ws, torch.uint8, "workspace")
+    _lib.check(_lib.load().dpm_voxel_map_insert(clouds, offsets, poses, int(n_scans), int(n_batch), int(base), int(n_points),
+                                                float(min_b[0]), float(min_b[1]), float(min_b[2]), float(voxel_size),
+                                                _ptr(ws), _stream(ws)), "dpm_voxel_map_insert")
+
+
+def voxel_map_finish(ws: torch.Tensor, n_points: int) -> None:
+    _chk(ws, torch.uint8, "workspace")
+    _lib.check(_lib.load().dpm_voxel_map_finish(int(n_points), _ptr(ws), _stream(ws)), "dpm_voxel_map_finish")
+
+
+def voxel_map_emit(ws: torch.Tensor, n_points: int, min_b, voxel_size: float, M: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> centroids (3,M) fp32, counts (M,) int32 on the workspace's device"""
+    _chk(ws, torch.uint8, "workspace")
+    out = torch.empty(3, M, device=ws.device, dtype=torch.float32)
+    cnt = torch.empty(M, device=ws.device, dtype=torch.int32)
+    _lib.check(_lib.load().dpm_voxel_map_emit(_ptr(ws), int(n_points), float(min_b[0]), float(min_b[1]), float(min_b[2]),
+                                              float(voxel_size), _ptr(out), _ptr(cnt), int(M), _stream(ws)),
+               "dpm_voxel_map_emit")
+    return out, cnt

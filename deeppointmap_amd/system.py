@@ -1,7 +1,7 @@
 """The callers of the hot path, mapped onto streams and ranks: drop-ins for the reference's
 `SlamSystem`, `AgentSystem` and `CloudSystem` (system/core.py:36-546) as far as they drive the path -- extraction, odometry,
-mapping, loop closure, optimisation, the upload to the cloud and the cloud's multi-agent loop closure.  What the reference
-hangs on the side of these classes (ResultLogger files and plots, ROS publishers, tqdm bars) is not here.
+mapping, loop closure, optimisation, the upload to the cloud and the cloud's multi-agent loop closure.  The ResultLogger's
+files are here (its plot and point-cloud map behind `slam_system.result_maps`); ROS publishers and tqdm bars are not.
 
   SlamSystem.step(sensor_data)          core.py:360-423   one scan through extractor -> back end, exit code returned;
   SlamSystem.MT_Init/MT_Step/MT_Done/MT_Wait  core.py:102-358   the multi-thread mode.  The reference runs six threads over five
@@ -47,15 +47,40 @@ class EXIT_CODE(Enum):      # system/modules/utils.py:21-27
     exit = 21
 
 
+def agent_color(agent_id: int):
+    """the colour of an agent's scans (the reference's system/modules/utils.py:15: tab20, odd entries)"""
+    import matplotlib
+    return tuple(float(c) for c in matplotlib.colormaps["tab20"](2 * agent_id + 1)[:3])
+
+
+def agent_color_darker(agent_id: int):
+    """utils.py:16: the even tab20 entry, halved"""
+    import matplotlib
+    return tuple(float(c) / 2 for c in matplotlib.colormaps["tab20"](2 * agent_id)[:3])
+
+
+EDGE_STYLE = {"locz": ("lime", 0.5, 8), "loop": ("yellow", 0.75, 20), "odom": ("cyan", 0.75, 8), "prxy": ("purple", 0.75, 8)}
+PLOT_FACE_COLOR = (0.075, 0.075, 0.075, 1)
+
+
 class ResultLogger:
-    """The part of the reference's ResultLogger (system/modules/recoder.py:24-110) that pipeline/infer.py reads and that is
-    text: stage timings (`record_perf` / `log_time` / `get_time_list`), the trajectory files (`save_trajectory`,
-    recoder.py:76-97: every scan's and every key-frame's SE3_pred as twelve numbers per line, KITTI style, plus the step
-    numbers) and the pose graph as g2o (`save_posegraph` -> PoseGraph.to_g2o_file, pose_graph.py:821-842).  The plots and the
-    point-cloud map (`draw_trajectory`, `save_map`) are not provided: the calls are accepted and do nothing."""
+    """The reference's ResultLogger (system/modules/recoder.py:24-203) as pipeline/infer.py uses it: stage timings
+    (`record_perf` / `log_time` / `get_time_list`), the trajectory files (`save_trajectory`, recoder.py:76-97: every scan's and
+    every key-frame's SE3_pred as twelve numbers per line, KITTI style, plus the step numbers), the pose graph as g2o
+    (`save_posegraph` -> PoseGraph.to_g2o_file, pose_graph.py:821-842) and, when the back end was built with
+    `slam_system.result_maps: True`, the map:
+      draw_trajectory(file_name, draft)  <file_name>.map.jpg (recoder.py:99-203): scan markers by type and agent colour,
+                                         ground-truth dots, edges coloured by type and, unless draft, the 0.5 m voxel maps
+                                         of the full clouds and of the key points (globalmap.voxel_map on the device);
+      plot_data(draft)                   the layers of that picture as arrays (what the renderer draws);
+      export_map(file_name, voxel_size)  <file_name>.fullpoints.pcd / .keypoints.pcd, the files the reference's commented-out
+                                         save_map body names, from the same voxel maps.
+    Without the key the back end retains no clouds, and draw_trajectory / save_map / export_map do nothing (as before).
+    save_map stays a no-op in every case, as the reference's live body writes nothing."""
 
     def __init__(self, backend: Rank0Consumer, log_dir: Optional[str]):
         self.backend, self.log_dir = backend, log_dir
+        self._map_cache = None      # (graph signature, maps) of the last _maps call
         self.time_recorder: Dict[str, List[float]] = {}
 
     def record_perf(self, name: str, time_s: float) -> None:
@@ -94,8 +119,114 @@ class ResultLogger:
                  for (a, c), e in b.edges.items()]
         write_g2o(self._path(file_name + ".pg.g2o"), {t: b.poses[t].numpy() for t in b.type}, edges)
 
-    def draw_trajectory(self, *a, **k) -> None:
-        pass
+    # -- the map (slam_system.result_maps) ---------------------------------------------------------------------------
+    def map_inputs(self):
+        """What the two voxel maps are made of, as ((clouds, poses) of the full map, (clouds, poses) of the key-point map):
+        the graph's scans in insertion order (PoseGraph.get_all_scans), moved by their SE3_pred (recoder.py:167-177) -- the
+        retained cloud of every scan that has one, the key points (last three descriptor rows) of every key frame."""
+        b = self.backend
+        toks = list(b.type)
+        full = [t for t in toks if t in b.map_clouds]
+        key = [t for t in toks if b.type[t] == "full" and t in b.desc]
+        return (([b.map_clouds[t] for t in full], [b.poses[t] for t in full]),
+                ([b.desc[t][-3:] for t in key], [b.poses[t] for t in key]))
+
+    def _maps(self, voxel_size: float = 0.5):
+        """(full-cloud map, key-point map): (3,M) centroids on the device each, or None when there are no points.  The
+        last result is kept for as long as the graph (scans, types, poses, retained clouds) and the voxel size stay the
+        same: draw_trajectory and export_map at the end of a run build the maps once."""
+        from .globalmap import voxel_map
+        b = self.backend
+        toks = list(b.type)
+        sig = (float(voxel_size), tuple(b.type.items()), tuple(t in b.map_clouds for t in toks),
+               tuple(t in b.desc for t in toks),
+               torch.stack([b.poses[t] for t in toks]).numpy().tobytes() if toks else b"")
+        if self._map_cache is not None and self._map_cache[0] == sig:
+            return self._map_cache[1]
+        out = []
+        for clouds, poses in self.map_inputs():
+            if not clouds:
+                out.append(None)
+                continue
+            xyz, _ = voxel_map(clouds, poses, voxel_size, device=b.device)
+            out.append(xyz if xyz.shape[1] else None)
+        self._map_cache = (sig, (out[0], out[1]))
+        return out[0], out[1]
+
+    def plot_data(self, draft: bool = False) -> dict:
+        """The layers of draw_trajectory's picture, as arrays:
+          scan_token / scan_agent / scan_key (n,) and scan_xy (n,2): the scans by timestep (stable), x / y of SE3_pred;
+          gt_xy (n,2): x / y of SE3_gt (NaN where the scan has none);
+          edge_type (E,) str and edge_xy (E,2,2) [[x_src, x_dst], [y_src, y_dst]]: the edges in insertion order;
+          full_map / key_map (2,M) float64 x / y of the voxel maps (None when draft or empty); agent_id."""
+        b = self.backend
+        toks = sorted(b.type, key=lambda t: t & 0xFFFF)
+        nan = np.full(2, np.nan)
+        d = dict(agent_id=int(b.agent_id),
+                 scan_token=np.array(toks, dtype=np.int64), scan_agent=np.array([t >> 16 for t in toks], dtype=np.int64),
+                 scan_key=np.array([b.type[t] == "full" for t in toks], dtype=bool),
+                 scan_xy=np.array([b.poses[t][:2, 3].double().numpy() for t in toks]).reshape(-1, 2),
+                 gt_xy=np.array([b.gt[t][:2, 3].double().numpy() if t in b.gt else nan for t in toks]).reshape(-1, 2))
+        es = [(e["type"], a, c) for (a, c), e in b.edges.items() if e["type"] in EDGE_STYLE]
+        d["edge_type"] = np.array([e[0] for e in es], dtype="<U4")
+        d["edge_xy"] = np.array([[[float(b.poses[a][0, 3]), float(b.poses[c][0, 3])], [float(b.poses[a][1, 3]), float(b.poses[c][1, 3])]]
+                                 for _, a, c in es], dtype=np.float64).reshape(-1, 2, 2)
+        d["full_map"] = d["key_map"] = None
+        if not draft:
+            full, key = self._maps(0.5)
+            d["full_map"] = None if full is None else full[:2].double().cpu().numpy()
+            d["key_map"] = None if key is None else key[:2].double().cpu().numpy()
+        return d
+
+    def draw_trajectory(self, file_name: str = "traj_jpg", draft: bool = False) -> None:
+        if not self.backend.result_maps:
+            return
+        self.render(self.plot_data(draft), self._path(file_name + ".map.jpg"), draft)
+
+    @staticmethod
+    def render(d: dict, path: str, draft: bool = False) -> None:
+        """plot_data's layers -> a picture (the reference's figure: dark face, equal axes, draft 10 x 10 in at the default
+        dpi, otherwise 20 x 20 in at 300 dpi)"""
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        fig = plt.figure(figsize=(10, 10), facecolor=PLOT_FACE_COLOR) if draft else \
+            plt.figure(figsize=(20, 20), dpi=300, facecolor=PLOT_FACE_COLOR)
+        try:
+            ax = plt.axes()
+            ax.axis("equal")
+            ax.set_facecolor(PLOT_FACE_COLOR)
+            for (x, y), a, key, (gx, gy) in zip(d["scan_xy"], d["scan_agent"], d["scan_key"], d["gt_xy"]):
+                if key:
+                    ax.plot(x, y, color=agent_color(int(a)), markersize=5, linestyle="", marker="o", markeredgewidth=1,
+                            markeredgecolor=agent_color_darker(int(a)), zorder=10)
+                else:
+                    ax.plot(x, y, color=agent_color(int(a)), markersize=5, linestyle="", marker=",", alpha=0.3, zorder=10)
+                if np.isfinite(gx):
+                    ax.scatter(gx, gy, marker=".", c="white", zorder=9)
+            for ty, (xs, ys) in zip(d["edge_type"], d["edge_xy"]):
+                color, alpha, z = EDGE_STYLE[str(ty)]
+                ax.plot(xs, ys, color=color, alpha=alpha, zorder=z)
+            if d.get("full_map") is not None:
+                ax.scatter(d["full_map"][0], d["full_map"][1], s=0.5, color=agent_color(d["agent_id"]), alpha=0.25, zorder=4)
+            if d.get("key_map") is not None:
+                ax.scatter(d["key_map"][0], d["key_map"][1], s=1, color=agent_color_darker(d["agent_id"]), alpha=0.5, zorder=5)
+            plt.tight_layout()
+            fig.savefig(path)
+        finally:
+            plt.close(fig)
+
+    def export_map(self, file_name: str = "map", voxel_size: float = 0.5) -> None:
+        """<file_name>.fullpoints.pcd and <file_name>.keypoints.pcd: the voxel maps (xyz) of the full clouds and of the key
+        points (a file for each map that has points)"""
+        if not self.backend.result_maps:
+            return
+        from .globalmap import write_pcd
+        full, key = self._maps(voxel_size)
+        if full is not None:
+            write_pcd(self._path(file_name + ".fullpoints.pcd"), full)
+        if key is not None:
+            write_pcd(self._path(file_name + ".keypoints.pcd"), key)
 
     def save_map(self, *a, **k) -> None:
         pass
@@ -129,9 +260,23 @@ class SlamSystem:
         """ScanPack.full_pcd (core.py:376): the scan in metres, (3,N) on the device"""
         return (point_cloud[:3].to(self.device, dtype=torch.float32) * self.coor_scale).contiguous()
 
-    def _backend_step(self, desc: torch.Tensor, point_cloud: torch.Tensor) -> EXIT_CODE:
+    @staticmethod
+    def _se3_gt(R, T) -> Optional[torch.Tensor]:
+        """PoseTool.SE3(R[0], T[0]) of the sensor data (core.py:379), on the host"""
+        if R is None or T is None:
+            return None
+        g = torch.eye(4)
+        g[:3, :3] = torch.as_tensor(R[0]).detach().to("cpu", torch.float32).reshape(3, 3)
+        g[:3, 3] = torch.as_tensor(T[0]).detach().to("cpu", torch.float32).reshape(3)
+        return g
+
+    def _backend_step(self, desc: torch.Tensor, point_cloud: torch.Tensor, R=None, T=None) -> EXIT_CODE:
         t0 = time.perf_counter()
         tok, code = self.backend.step(desc, self._full_pcd(point_cloud))
+        if self.backend.result_maps and tok in self.backend.type:
+            gt = self._se3_gt(R, T)
+            if gt is not None:
+                self.backend.gt[tok] = gt
         self.result_logger.record_perf("backend", time.perf_counter() - t0)      # odometer + mapping + loop_closure
         if code == ACPT and self.comm_module is not None:     # drop / dist leave step() before the upload (core.py:399-400)
             self.comm_module.send_message(caller=self.comm_id, callee=0, command="UPLOAD_SCAN",
@@ -143,12 +288,12 @@ class SlamSystem:
     @torch.no_grad()
     def step(self, sensor_data) -> EXIT_CODE:
         """sensor_data = [point_cloud (1,C,N) normalised, R, T, padding_mask (1,N), original_scan] (core.py:365)"""
-        point_cloud, padding_mask = sensor_data[0], sensor_data[3]
+        point_cloud, R, T, padding_mask = sensor_data[0], sensor_data[1], sensor_data[2], sensor_data[3]
         with torch.cuda.device(self.device):
             t0 = time.perf_counter()
             desc = self.extraction_thread.process(point_cloud=point_cloud, padding_mask=padding_mask)
             self.result_logger.record_perf("extract", time.perf_counter() - t0)   # enqueue time: the kernels run on
-            return self._backend_step(desc[0], point_cloud[0])
+            return self._backend_step(desc[0], point_cloud[0], R, T)
 
     def trajectory(self):
         """(tokens, SE3_pred (n,4,4)) of every scan of the graph, by token -- what recoder.py:76-97 writes out"""
@@ -197,7 +342,7 @@ class SlamSystem:
                         continue
                     (item, d) = it
                     d.record_stream(torch.cuda.current_stream(self.device))
-                    self._backend_step(d, item[1][0])
+                    self._backend_step(d, item[1][0], item[2], item[3])
 
         t1, t2 = threading.Thread(target=guard(extractor), name="dpm-extractor"), threading.Thread(target=guard(backend), name="dpm-backend")
         self._mt = (q_in, (t1, t2), errors)

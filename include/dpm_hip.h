@@ -511,6 +511,33 @@ int dpm_infomat_search_grids(const float *pcd, int N, const int32_t *src_frame, 
                              int n_pairs, const float *Rt, int rt_stride, double radius, float *out,
                              int out_stride, void *workspace, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- global map ------------ */
+
+/* ResultLogger.draw_trajectory's point-cloud map (system/modules/recoder.py:167-190): every scan's cloud moved by its
+ * SE3_pred, concatenated, open3d voxel_down_sample(vs).  Here: the voxel-centroid map of the union, computed in HBM
+ * with integer atomics (bit-reproducible, independent of arrival order), output in order of first appearance.
+ * A batch of scans: clouds (n_scans) device pointers to (3,N_i) fp32 channel-first clouds, offsets (n_scans+1) int64
+ * prefix sums of N_i (offsets[0] = 0, n_batch = offsets[n_scans]), poses (n_scans,12) [R row-major, T] fp32; the
+ * three arrays are device memory.  Batches may be fed one after another (base = global index of the batch's first
+ * point), so host-resident clouds can be streamed through a bounded staging buffer.  Sequence, per map of n_points:
+ *   init -> bounds (every batch) -> [caller reads the 256-byte workspace header: unsigned min[3], max[3]
+ *   (order-preserving images of fp32), non-finite coordinate count; computes min_b = min - vs/2 in fp64 and checks
+ *   that the extent fits 3 x 21 bits] -> insert (every batch, same order) -> finish -> [header word 8 = M voxels,
+ *   word 7 = keys out of range (must be 0), 64-bit words at byte 64/72 = runs flushed / CAS attempts] -> emit:
+ *   centroids (3,M) fp32, counts (M) int32.
+ * Limits: n_points < 2^31 and n_points * (vs * 2^32 + 2) < 2^62 (the 64-bit fixed-point sums cannot wrap).
+ * workspace: dpm_voxel_map_workspace_bytes(n_points) <= 51 bytes per point + 8 KB. */
+size_t dpm_voxel_map_workspace_bytes(long long n_points);
+int dpm_voxel_map_init(long long n_points, void *workspace, dpm_stream_t stream);
+int dpm_voxel_map_bounds(const float *const *clouds, const long long *offsets, const float *poses, int n_scans,
+                         long long n_batch, void *workspace, dpm_stream_t stream);
+int dpm_voxel_map_insert(const float *const *clouds, const long long *offsets, const float *poses, int n_scans,
+                         long long n_batch, long long base, long long n_points, double min_x, double min_y,
+                         double min_z, double voxel_size, void *workspace, dpm_stream_t stream);
+int dpm_voxel_map_finish(long long n_points, void *workspace, dpm_stream_t stream);
+int dpm_voxel_map_emit(const void *workspace, long long n_points, double min_x, double min_y, double min_z,
+                       double voxel_size, float *centroids, int32_t *counts, int M, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
