@@ -102,6 +102,10 @@ SIGNATURES = {
     "dpm_voxel_map_insert": (I, [P, P, P, I, LL, LL, LL, D, D, D, D, P, P]),
     "dpm_voxel_map_finish": (I, [LL, P, P]),
     "dpm_voxel_map_emit": (I, [P, LL, D, D, D, D, P, P, I, P]),
+    "dpm_reg_loss_pairs": (I, [P, P, I, I, I, D, P, P, P, P, P]),
+    "dpm_reg_loss_workspace_bytes": (c_size_t, [I, I, I, I]),
+    "dpm_reg_loss_forward": (I, [P, P, P, P, P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P, P]),
+    "dpm_reg_loss_backward": (I, [P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P, P]),
 }
 
 

@@ -45,6 +45,7 @@ SOURCES = {
     "voxel_sample.hip": [],
     "posegraph.hip": [],
     "voxel_map.hip": [],
+    "reg_loss.hip": [],
 }
 
 

@@ -1022,3 +1022,86 @@ def voxel_map_emit(ws: torch.Tensor, n_points: int, min_b, voxel_size: float, M:
                                               float(voxel_size), _ptr(out), _ptr(cnt), int(M), _stream(ws)),
                "dpm_voxel_map_emit")
     return out, cnt
+
+
+# ---- RegistrationLoss (training): csrc/reg_loss.hip ----------------------------------------------------------------------
+
+def _shape(t: torch.Tensor, want, name: str):
+    """the kernels index these tensors together: refuse any that disagrees with the shape the others define"""
+    if tuple(t.shape) != tuple(want):
+        raise ValueError(f"{name}: expected shape {tuple(want)}, got {tuple(t.shape)}")
+    return t
+
+
+def reg_loss_pairs(xyz_a: torch.Tensor, xyz_b: torch.Tensor, eps: float, neutral_counts: bool = False):
+    """xyz_a (B,3,M), xyz_b (B,3,N) fp32 -> nn_a (B,M), nn_b (B,N) int32 (make_pairs of both directions: the first nearest
+    neighbour where its squared distance is <= eps^2, else -1) [, neutral_a (B,M), neutral_b (B,N) int32: per row the entries
+    within eps other than the neighbour]."""
+    _chk(xyz_a, torch.float32, "xyz_a"), _chk(xyz_b, torch.float32, "xyz_b")
+    if xyz_a.dim() != 3 or xyz_b.dim() != 3:
+        raise ValueError(f"coordinates must be (B,3,M) / (B,3,N), got {tuple(xyz_a.shape)} / {tuple(xyz_b.shape)}")
+    B, _, M = xyz_a.shape
+    N = xyz_b.shape[2]
+    _shape(xyz_a, (B, 3, M), "xyz_a"), _shape(xyz_b, (B, 3, N), "xyz_b")
+    nn_a = torch.empty(B, M, device=xyz_a.device, dtype=torch.int32)
+    nn_b = torch.empty(B, N, device=xyz_a.device, dtype=torch.int32)
+    ne_a = torch.empty_like(nn_a) if neutral_counts else None
+    ne_b = torch.empty_like(nn_b) if neutral_counts else None
+    _lib.check(_lib.load().dpm_reg_loss_pairs(_ptr(xyz_a), _ptr(xyz_b), B, M, N, float(eps), _ptr(nn_a), _ptr(nn_b), _ptr(ne_a),
+                                              _ptr(ne_b), _stream(xyz_a)), "dpm_reg_loss_pairs")
+    return (nn_a, nn_b, ne_a, ne_b) if neutral_counts else (nn_a, nn_b)
+
+
+def reg_loss_forward(fea_a, fea_b, xyz_a, xyz_b, pad_a, pad_b, nn_a, nn_b, tau: float, eps: float, neutral: bool,
+                     argmax: bool = False):
+    """One feature pair (B,C,M) / (B,C,N) fp32 through both InfoNCE directions -> (loss 0-d, stats (8,), workspace[, argmax_a,
+    argmax_b]); the workspace is what reg_loss_backward reads.  pad_*: bool, True on padding.  Raises ValueError for C outside
+    {64, 128, 192, 256}."""
+    for t, n in ((fea_a, "fea_a"), (fea_b, "fea_b")):
+        _chk(t, torch.float32, n)
+    _chk(pad_a, torch.bool, "pad_a"), _chk(pad_b, torch.bool, "pad_b")
+    _chk(nn_a, torch.int32, "nn_a"), _chk(nn_b, torch.int32, "nn_b")
+    if neutral:
+        _chk(xyz_a, torch.float32, "xyz_a"), _chk(xyz_b, torch.float32, "xyz_b")
+    if fea_a.dim() != 3 or fea_b.dim() != 3:
+        raise ValueError(f"features must be (B,C,M) / (B,C,N), got {tuple(fea_a.shape)} / {tuple(fea_b.shape)}")
+    B, C, M = fea_a.shape
+    N = fea_b.shape[2]
+    _shape(fea_b, (B, C, N), "fea_b")
+    _shape(pad_a, (B, M), "pad_a"), _shape(pad_b, (B, N), "pad_b")
+    _shape(nn_a, (B, M), "nn_a"), _shape(nn_b, (B, N), "nn_b")
+    if neutral:
+        _shape(xyz_a, (B, 3, M), "xyz_a"), _shape(xyz_b, (B, 3, N), "xyz_b")
+    lib = _lib.load()
+    dev = fea_a.device
+    ws = torch.empty(lib.dpm_reg_loss_workspace_bytes(B, M, N, C), device=dev, dtype=torch.uint8)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    stats = torch.empty(8, device=dev, dtype=torch.float32)
+    am_a = torch.empty(B, M, device=dev, dtype=torch.int32) if argmax else None
+    am_b = torch.empty(B, N, device=dev, dtype=torch.int32) if argmax else None
+    _lib.check(lib.dpm_reg_loss_forward(_ptr(fea_a), _ptr(fea_b), _ptr(xyz_a) if neutral else None,
+                                        _ptr(xyz_b) if neutral else None, _ptr(pad_a), _ptr(pad_b), _ptr(nn_a), _ptr(nn_b), B, M,
+                                        N, C, float(tau), float(eps), int(neutral), _ptr(am_a), _ptr(am_b), _ptr(loss),
+                                        _ptr(stats), _ptr(ws), _stream(fea_a)), "dpm_reg_loss_forward")
+    return (loss, stats, ws, am_a, am_b) if argmax else (loss, stats, ws)
+
+
+def reg_loss_backward(xyz_a, xyz_b, nn_a, nn_b, shape, tau: float, eps: float, neutral: bool, grad_loss: torch.Tensor,
+                      stats: torch.Tensor, ws: torch.Tensor):
+    """Gradients (B,C,M), (B,C,N) of grad_loss (0-d fp32 on the device) x the loss reg_loss_forward returned with stats / ws."""
+    B, C, M, N = shape
+    _chk(grad_loss, torch.float32, "grad_loss"), _shape(grad_loss, (), "grad_loss")
+    _chk(nn_a, torch.int32, "nn_a"), _chk(nn_b, torch.int32, "nn_b")
+    _shape(nn_a, (B, M), "nn_a"), _shape(nn_b, (B, N), "nn_b")
+    if neutral:
+        _shape(xyz_a, (B, 3, M), "xyz_a"), _shape(xyz_b, (B, 3, N), "xyz_b")
+    _shape(stats, (8,), "stats")
+    if ws.numel() < _lib.load().dpm_reg_loss_workspace_bytes(B, M, N, C):
+        raise ValueError("reg_loss_backward: the workspace is smaller than this shape's forward needs")
+    ga = torch.empty(B, C, M, device=ws.device, dtype=torch.float32)
+    gb = torch.empty(B, C, N, device=ws.device, dtype=torch.float32)
+    _lib.check(_lib.load().dpm_reg_loss_backward(_ptr(xyz_a) if neutral else None, _ptr(xyz_b) if neutral else None, _ptr(nn_a),
+                                                 _ptr(nn_b), B, M, N, C, float(tau), float(eps), int(neutral), _ptr(grad_loss),
+                                                 _ptr(stats), _ptr(ws), _ptr(ga), _ptr(gb), _stream(ws)),
+               "dpm_reg_loss_backward")
+    return ga, gb

@@ -538,6 +538,32 @@ int dpm_voxel_map_finish(long long n_points, void *workspace, dpm_stream_t strea
 int dpm_voxel_map_emit(const void *workspace, long long n_points, double min_x, double min_y, double min_z,
                        double voxel_size, float *centroids, int32_t *counts, int M, dpm_stream_t stream);
 
+/* RegistrationLoss of the reference (network/loss.py) for training, without any (B,M,N) tensor (csrc/reg_loss.hip).
+ * Side a = src (M points), side b = dst (N points); coordinates (B,3,M) / (B,3,N), features (B,C,M) / (B,C,N) fp32
+ * contiguous, padding (B,M) / (B,N) bytes, nonzero on padding.
+ * pairs (make_pairs): nn_a[b,i] = first j minimising dist2 = (dx dx + dy dy) + dz dz (fp32, that order, no contraction) when
+ *   that minimum is <= (float)(eps * eps), else -1; nn_b the same from the b side.  neutral_a / neutral_b (may be NULL): per row
+ *   the number of entries with dist2 <= eps^2 other than the neighbour (the row sum of the reference's neutral mask).
+ * forward (pairing_loss of both directions, one feature pair): z = a^ b^T / tau with x^ = x / max(||x||, 1e-12); a row
+ *   counts when it is not padding and nn >= 0; its term is logsumexp_j z_ij - z_i,nn(i), the softmax over every column
+ *   (padding included) except, when `neutral` is set, the entries with dist2 <= eps^2 other than nn(i).  *loss = (mean_a +
+ *   mean_b) / 2, a direction without counted rows contributing 0; stats (8 floats): [loss, mean_a, mean_b, n_a, n_b, hits_a,
+ *   hits_b, 0], hits = counted rows whose argmax_j of the raw similarity (first on ties) is nn (neutral == 0 only).
+ *   argmax_a / argmax_b (B,M) / (B,N) (may be NULL; neutral == 0 only) receive those argmaxes.  workspace:
+ *   dpm_reg_loss_workspace_bytes(B,M,N,C); it holds what the backward reads and must stay intact until then.
+ * backward: grad_a (B,C,M), grad_b (B,C,N) of *grad_loss (device scalar) x loss, from the forward's workspace and stats.
+ * C in {64, 128, 192, 256}, else DPM_EUNSUPPORTED.  Deterministic (no float atomics). */
+int dpm_reg_loss_pairs(const float *xyz_a, const float *xyz_b, int B, int M, int N, double eps, int32_t *nn_a, int32_t *nn_b,
+                       int32_t *neutral_a, int32_t *neutral_b, dpm_stream_t stream);
+size_t dpm_reg_loss_workspace_bytes(int B, int M, int N, int C);
+int dpm_reg_loss_forward(const float *fea_a, const float *fea_b, const float *xyz_a, const float *xyz_b, const uint8_t *pad_a,
+                         const uint8_t *pad_b, const int32_t *nn_a, const int32_t *nn_b, int B, int M, int N, int C, double tau,
+                         double eps, int neutral, int32_t *argmax_a, int32_t *argmax_b, float *loss, float *stats,
+                         void *workspace, dpm_stream_t stream);
+int dpm_reg_loss_backward(const float *xyz_a, const float *xyz_b, const int32_t *nn_a, const int32_t *nn_b, int B, int M, int N,
+                          int C, double tau, double eps, int neutral, const float *grad_loss, const float *stats,
+                          const void *workspace, float *grad_a, float *grad_b, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
