@@ -106,6 +106,13 @@ SIGNATURES = {
     "dpm_reg_loss_workspace_bytes": (c_size_t, [I, I, I, I]),
     "dpm_reg_loss_forward": (I, [P, P, P, P, P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P, P]),
     "dpm_reg_loss_backward": (I, [P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P, P]),
+    "dpm_attention_train_workspace_bytes": (c_size_t, [I, I, I, I]),
+    "dpm_attention_train_forward": (I, [P, I, LL, P, I, LL, P, I, LL, P, I, LL, P, I, I, I, I, I, P, P]),
+    "dpm_attention_train_backward": (I, [P, I, LL, P, I, LL, P, I, LL, P, I, LL, P, P, I, LL, P, P, P, P, I, I, I, I, I, P, P]),
+    "dpm_offset_pairs_count": (I, [P, P, P, P, I, I, I, D, P, P, P]),
+    "dpm_offset_pairs_fill": (I, [P, P, P, P, I, I, I, D, P, P, P]),
+    "dpm_offset_pairs_gather": (I, [P, I, P, I, I, LL, I, P, P]),
+    "dpm_offset_pairs_segment_sum": (I, [P, I, P, P, LL, I, P, P]),
 }
 
 

@@ -46,6 +46,8 @@ SOURCES = {
     "posegraph.hip": [],
     "voxel_map.hip": [],
     "reg_loss.hip": [],
+    "attention_train.hip": [],
+    "offset_pairs.hip": [],
 }
 
 

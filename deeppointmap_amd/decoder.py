@@ -6,12 +6,14 @@ contracts:
      dst_padding_mask=None, num_sample=0.5) -> (R (3,3), T (3,1), conf (K,), rmse: float)`
      (decoder.py:91-127); 3-D inputs give the batched return shapes of the reference.
   * `loop_detection_forward(src (C,131,M), dst (C,131,N)) -> (C,)` (decoder.py:129-143).
-  * `forward` is training-only in the reference (decoder.py:34-38) and raises here as it does there.
+  * `forward(src_desc (B,131,M), dst_desc (B,131,N), src_padding_mask, dst_padding_mask, gt_Rt) -> [six tensors]`
+     (decoder.py:34-89) is the training forward; it needs `.train()` and raises in eval mode as the reference does.
 Padding masks ((B,M) / (B,N) bool, True = padding) are the key_padding_mask of every attention block and nothing else
 (descriptor_attention.py:33-42), as in the reference; no inference call site of the reference passes any
 (odometry.py:108-110, mapping.py:153-155, loop_closure.py:170-174,239-242).
 
-All arithmetic runs in libdpm_hip.so; the module is re-entrant (no per-call state on self), so
+All inference arithmetic runs in libdpm_hip.so (the training forward keeps its dense layers in torch under autograd, its
+attention cores and offset pairing in libdpm_hip.so); the module is re-entrant (no per-call state on self), so
 the three SLAM threads of the reference can share one instance (system/core.py:55-57).
 """
 from __future__ import annotations
@@ -21,6 +23,8 @@ import threading
 from typing import Dict, Tuple, Union
 
 import torch
+import torch.nn.functional as F
+from torch.utils.checkpoint import checkpoint
 
 from . import knobs, ops
 from .params import ParamTree, decoder_shapes
@@ -56,6 +60,9 @@ class Decoder(ParamTree):
         self._graphs: Dict[tuple, dict] = {}
         self._graph_lock = threading.Lock()
         self._stamp_params = None
+        # training forward: from this many stacked tokens (B * (M + N)) on, an attention layer's activations are recomputed in
+        # the backward rather than kept (sixteen (tokens, model_channel) tensors per layer: 256 MiB per layer at 16384 tokens)
+        self.train_checkpoint_rows = 8192
         self.eval()
 
     def __deepcopy__(self, memo):
@@ -281,9 +288,138 @@ class Decoder(ParamTree):
         return zp[:R], zp[R:]
 
     # -- public API ----------------------------------------------------------------------------
-    def forward(self, *a, **k):
+    def train(self, mode: bool = True):
+        """A real switch.  `.train()` selects the reference's registration training mode (model_pipeline.py's
+        `registration()`): every parameter whose name does not contain `loop` gets requires_grad = True, so `forward` ->
+        RegistrationLoss -> backward() fills their `.grad` and `torch.optim.*(decoder.parameters())` can step them; `loop_head`
+        stays frozen.  `.eval()` (what `__init__` ends in) turns requires_grad off again for all of them and drops the
+        weight-derived caches.  In-place optimiser steps bump the parameters' version counters, which both the derived-weight
+        cache (ops._derived) and the captured registration graphs (`_weights_stamp`) key on: inference after a step reads the
+        new weights."""
+        was = self.training
+        super().train(mode)
+        for name, p in self._flat.items():
+            p.requires_grad_(bool(mode) and "loop" not in name)
+        if was and not mode:
+            self.invalidate_caches()
+        return self
+
+    def _w(self, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(weight as (out, in), bias) of a Linear / Conv1d(k=1) for F.linear"""
+        w = self.p(key + ".weight")
+        return w.view(w.shape[0], w.shape[1]), self.p(key + ".bias")
+
+    def _train_layer(self, l: int, z, pos, B: int, M: int, N: int, ms, md):
+        """DescriptorAttentionLayer.forward (descriptor_attention.py:24-52) over the stacked rows [B*M source ; B*N target]:
+        the four attention cores are ops.attention_train (HIP, forward and backward); projections, LayerNorm and the MLP
+        are torch operations under autograd."""
+        E, R1 = self.model_channel, B * M
+        pre = f"descriptor_attention.{l}"
+        ln = lambda n, t: F.layer_norm(t, (E,), self.p(f"{pre}.{n}.weight"), self.p(f"{pre}.{n}.bias"))   # noqa: E731
+        zp = z + pos
+        qkv = F.linear(zp, self.p(pre + ".self_attn.in_proj_weight"), self.p(pre + ".self_attn.in_proj_bias"))
+        a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, M, M, HEADS, ms),
+                       ops.attention_train(qkv[R1:, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, N, N, HEADS, md)])
+        z1 = ln("norm1", zp + F.linear(a, *self._w(pre + ".self_attn.out_proj"))) + pos
+        qkv = F.linear(z1, self.p(pre + ".cross_attn.in_proj_weight"), self.p(pre + ".cross_attn.in_proj_bias"))
+        # both directions read the pre-update tensors (descriptor_attention.py:41-44)
+        a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, M, N, HEADS, md),
+                       ops.attention_train(qkv[R1:, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, N, M, HEADS, ms)])
+        z2 = ln("norm2", z1 + F.linear(a, *self._w(pre + ".cross_attn.out_proj")))
+        h = F.linear(F.relu(F.linear(z2, *self._w(pre + ".mlp.0"))), *self._w(pre + ".mlp.2"))
+        return ln("norm3", h + z2)
+
+    def forward(self, src_descriptor: torch.Tensor, dst_descriptor: torch.Tensor, src_padding_mask: torch.Tensor = None,
+                dst_padding_mask: torch.Tensor = None, gt_Rt: Tuple[torch.Tensor, torch.Tensor] = None):
+        """The reference's training forward (decoder.py:34-89), for a decoder in `.train()` mode on the GPU.
+
+        src_descriptor (B, in_channel + 3, M), dst_descriptor (B, in_channel + 3, N); padding masks (B, M) / (B, N) bool,
+        True = padding (None = no padding); gt_Rt = (R (B,3,3), T (B,3,1)), source -> target.  Returns the reference's list
+        `[src_pairing_fea (B,E,M), dst_pairing_fea (B,E,N), src_coarse_pairing_fea (B,C,M), dst_coarse_pairing_fea (B,C,N),
+        src_offset_res (K,3,1), dst_offset_res (K,3,1)]`, which `RegistrationLoss.forward` takes unchanged; K counts the
+        (batch, src, dst) triples of unpadded tokens within `eps_offset` after the ground-truth transform, listed in
+        torch.nonzero's order (K = 0 gives (0,3,1) residuals and zero gradients).
+
+        Differentiable with respect to every parameter the reference's autograd reaches (all but `loop_head`) and to the first
+        `in_channel` rows of both descriptors.  The three xyz rows get NO gradient (their `.grad` rows are zero): they are
+        sampled input points with no parameter upstream; the reference does propagate into them (through the offset
+        targets and the position embedding).
+
+        The attention cores and the offset pairing run in csrc/attention_train.hip and csrc/offset_pairs.hip in both
+        directions; no tensor of M x N elements exists in the forward, the saved state or the backward.  The dense layers
+        (projections, LayerNorm, MLPs, heads) are torch operations under autograd (DESIGN.md says what replacing them takes).
+        From `train_checkpoint_rows` stacked tokens (B * (M + N)) on, each attention layer is recomputed in the backward
+        instead of keeping its sixteen activation tensors (torch.utils.checkpoint: the same kernels on the same inputs,
+        identical bytes).  Raises AssertionError in eval mode and without gt_Rt, as the reference does; ValueError for
+        descriptors, masks or poses of the wrong shape and for a head width other than 32."""
         assert self.training, "forward is not available during inference!"
-        raise NotImplementedError("the training forward (decoder.py:40-89) is outside the inference hot path")
+        assert gt_Rt is not None, "gt_Rt must be provided during training"
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        C, E = self.in_channel, self.model_channel
+        if E // HEADS != ops.ATTENTION_TRAIN_HEAD_DIM or E % HEADS:
+            raise ValueError(f"Decoder.forward: model_channel {E} gives heads of width {E / HEADS:g}; the training attention "
+                             f"kernels support width {ops.ATTENTION_TRAIN_HEAD_DIM} only (model_channel "
+                             f"{ops.ATTENTION_TRAIN_HEAD_DIM * HEADS})")
+        for name, d in (("src_descriptor", src_descriptor), ("dst_descriptor", dst_descriptor)):
+            if d.dim() != 3 or d.shape[1] != C + 3:
+                raise ValueError(f"{name} must be (B, {C + 3}, tokens), got {tuple(d.shape)}")
+        src = src_descriptor.to(device=dev, dtype=torch.float32)
+        dst = dst_descriptor.to(device=dev, dtype=torch.float32)
+        B, _, M = src.shape
+        N = dst.shape[2]
+        if dst.shape[0] != B:
+            raise ValueError("src and dst batch sizes differ")
+
+        def as_mask(m, L, name):
+            if m is None:
+                return torch.zeros(B, L, dtype=torch.bool, device=dev)
+            if tuple(m.shape) != (B, L) or m.dtype != torch.bool:
+                raise ValueError(f"{name} must be a bool tensor of shape ({B}, {L})")
+            return m.to(dev).contiguous()
+        ps, pd = as_mask(src_padding_mask, M, "src_padding_mask"), as_mask(dst_padding_mask, N, "dst_padding_mask")
+        gt_R, gt_T = gt_Rt
+        if tuple(gt_R.shape) != (B, 3, 3) or tuple(gt_T.shape) != (B, 3, 1):
+            raise ValueError(f"gt_Rt must be ((B,3,3), (B,3,1)) with B = {B}, got {tuple(gt_R.shape)}, {tuple(gt_T.shape)}")
+        gt_R, gt_T = gt_R.detach().to(device=dev, dtype=torch.float32), gt_T.detach().to(device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            ms, md = ps.view(torch.uint8), pd.view(torch.uint8)
+            R1 = B * M
+            rows = torch.cat([src[:, :C].transpose(1, 2).reshape(R1, C), dst[:, :C].transpose(1, 2).reshape(B * N, C)])
+            xyz_s, xyz_d = src[:, C:].detach(), dst[:, C:].detach()                      # (B,3,M), (B,3,N)
+            xyz_rows = torch.cat([xyz_s.transpose(1, 2).reshape(R1, 3), xyz_d.transpose(1, 2).reshape(B * N, 3)])
+
+            def split(t, ch):   # stacked rows -> the reference's (B,ch,M), (B,ch,N)
+                return t[:R1].view(B, M, ch).transpose(1, 2), t[R1:].view(B, N, ch).transpose(1, 2)
+            # unified descriptor -> coarse pairing feature                                  (decoder.py:46-48)
+            coarse = F.linear(F.relu(F.linear(rows, *self._w("coarse_pairing_head.0"))), *self._w("coarse_pairing_head.2"))
+            # unified descriptor -> correlated descriptor                                   (decoder.py:145-162)
+            pos = ops.posemb(xyz_rows, self._dimt(dev), E)
+            z = F.linear(rows, *self._w("projection"))
+            recompute = B * (M + N) >= self.train_checkpoint_rows
+            for l in range(self.attention_layers):
+                if recompute:
+                    z = checkpoint(self._train_layer, l, z, pos, B, M, N, ms, md, use_reentrant=False)
+                else:
+                    z = self._train_layer(l, z, pos, B, M, N, ms, md)
+            # correlated descriptors -> similarity feature                                  (decoder.py:56-58)
+            sim = F.linear(F.relu(F.linear(z, *self._w("similarity_head.0"))), *self._w("similarity_head.2"))
+            # correlated descriptors -> offset                                              (decoder.py:60-86)
+            src_gt = (gt_R @ xyz_s + gt_T).contiguous()
+            pairs = ops.offset_pairs(src_gt, xyz_d.contiguous(), ps, pd, self.args.loss.eps_offset)
+            xs, xd = ops.offset_pair_rows(z[:R1], z[R1:], pairs, M, N)
+            bi, si, di = pairs[0].long().unbind(1)
+            K = bi.numel()
+            sp, dp = src_gt.transpose(1, 2)[bi, si], xyz_d.transpose(1, 2)[bi, di]         # (K,3) each, no gradient
+            src_gt_off = gt_R[bi].transpose(1, 2) @ (dp - sp).unsqueeze(2)
+            dst_gt_off = (sp - dp).unsqueeze(2)
+            X = torch.cat([torch.cat([xs, xd], dim=1), torch.cat([xd, xs], dim=1)])        # (2K, 2E): src -> dst rows, then dst -> src
+            h = F.linear(F.relu(F.linear(F.relu(F.linear(X, *self._w("offset_head.mlp.0"))), *self._w("offset_head.mlp.2"))),
+                         *self._w("offset_head.mlp.4"))
+            h = F.relu(h + F.linear(X, *self._w("offset_head.downsample")))
+            off = F.linear(h, *self._w("offset_head.head")).unsqueeze(2)                   # (2K,3,1)
+            return [*split(sim, E), *split(coarse, C), off[:K] - src_gt_off, off[K:] - dst_gt_off]
 
     @staticmethod
     def _num_pairs(num_sample, M: int, N: int) -> int:

@@ -1105,3 +1105,175 @@ def reg_loss_backward(xyz_a, xyz_b, nn_a, nn_b, shape, tau: float, eps: float, n
                                                  _ptr(stats), _ptr(ws), _ptr(ga), _ptr(gb), _stream(ws)),
                "dpm_reg_loss_backward")
     return ga, gb
+
+
+# ---- attention for training: csrc/attention_train.hip ----------------------------------------------------------------------
+
+ATTENTION_TRAIN_HEAD_DIM = 32   # the one head width dpm_attention_train_* implements (model_channel 256, 8 heads)
+
+
+def _attention_train_args(q, k, v, B: int, M: int, N: int, heads: int, key_mask):
+    for n, t, rows in (("q", q, B * M), ("k", k, B * N), ("v", v, B * N)):
+        _rows2d(t, n)
+        if t.shape[0] != rows:
+            raise ValueError(f"{n}: expected {rows} rows, got {t.shape[0]}")
+    E = q.shape[1]
+    if k.shape[1] != E or v.shape[1] != E or heads < 1 or E % heads:
+        raise ValueError(f"q / k / v must share a width divisible by heads = {heads}, got {q.shape[1]}, {k.shape[1]}, {v.shape[1]}")
+    if E // heads != ATTENTION_TRAIN_HEAD_DIM:
+        raise ValueError(f"attention_train: head width {E // heads} is not supported, only {ATTENTION_TRAIN_HEAD_DIM} "
+                         f"(model_channel {ATTENTION_TRAIN_HEAD_DIM * heads} at {heads} heads)")
+    if key_mask is not None:
+        _chk(key_mask, torch.uint8, "key_mask")
+        if tuple(key_mask.shape) != (B, N):
+            raise ValueError(f"key_mask must be ({B}, {N}), got {tuple(key_mask.shape)}")
+    return E
+
+
+def attention_train_forward(q, k, v, B: int, M: int, N: int, heads: int = 8, key_mask: Optional[torch.Tensor] = None):
+    """q (B*M,E) / k, v (B*N,E) row views -> (out (B*M,E), lse (B,heads,M)): the attention core and the log-sum-exp of every
+    score row over its unmasked keys, which is all the backward needs besides the operands."""
+    E = _attention_train_args(q, k, v, B, M, N, heads, key_mask)
+    out = torch.empty(B * M, E, device=q.device, dtype=torch.float32)
+    lse = torch.empty(B, heads, M, device=q.device, dtype=torch.float32)
+    _lib.check(_lib.load().dpm_attention_train_forward(_ptr(q), q.stride(0), M * q.stride(0), _ptr(k), k.stride(0), N * k.stride(0),
+                                                       _ptr(v), v.stride(0), N * v.stride(0), _ptr(out), E, M * E, _ptr(lse), B, M,
+                                                       N, heads, E // heads, _ptr(key_mask), _stream(q)),
+               "dpm_attention_train_forward")
+    return out, lse
+
+
+def attention_train_backward(q, k, v, out, lse, dout, B: int, M: int, N: int, heads: int = 8,
+                             key_mask: Optional[torch.Tensor] = None):
+    """-> (dq (B*M,E), dk (B*N,E), dv (B*N,E)) from the operands, the forward's out / lse and dout (B*M,E).  Deterministic."""
+    E = _attention_train_args(q, k, v, B, M, N, heads, key_mask)
+    _rows2d(out, "out"), _rows2d(dout, "dout")
+    _chk(lse, torch.float32, "lse")
+    _shape(out, (B * M, E), "out"), _shape(dout, (B * M, E), "dout"), _shape(lse, (B, heads, M), "lse")
+    lib = _lib.load()
+    dev = q.device
+    ws = torch.empty(lib.dpm_attention_train_workspace_bytes(B, M, N, heads), device=dev, dtype=torch.uint8)
+    dq = torch.empty(B * M, E, device=dev, dtype=torch.float32)
+    dk = torch.empty(B * N, E, device=dev, dtype=torch.float32)
+    dv = torch.empty(B * N, E, device=dev, dtype=torch.float32)
+    _lib.check(lib.dpm_attention_train_backward(_ptr(q), q.stride(0), M * q.stride(0), _ptr(k), k.stride(0), N * k.stride(0),
+                                                _ptr(v), v.stride(0), N * v.stride(0), _ptr(out), out.stride(0), M * out.stride(0),
+                                                _ptr(lse), _ptr(dout), dout.stride(0), M * dout.stride(0), _ptr(key_mask), _ptr(dq),
+                                                _ptr(dk), _ptr(dv), B, M, N, heads, E // heads, _ptr(ws), _stream(q)),
+               "dpm_attention_train_backward")
+    return dq, dk, dv
+
+
+class _AttentionTrain(torch.autograd.Function):
+    """Saved for the backward: the operands, out and lse -- no probability tensor."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B, M, N, heads, key_mask):
+        out, lse = attention_train_forward(q, k, v, B, M, N, heads, key_mask)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.mask, ctx.cfg = key_mask, (B, M, N, heads)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        if dout.stride(1) != 1 or dout.stride(0) % 4 or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        dq, dk, dv = attention_train_backward(q, k, v, out, lse, dout, *ctx.cfg, key_mask=ctx.mask)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, M: int, N: int, heads: int = 8,
+                    key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.attention for training: q (B*M,E) / k, v (B*N,E) fp32 row views (column slices of wider buffers allowed, rows 16-byte
+    aligned) -> (B*M,E), differentiable with respect to q, k and v.  key_mask (B,N) uint8, non-zero = padding key
+    (nn.MultiheadAttention's key_padding_mask); masked keys get exactly zero gradients.  Forward and backward run in
+    csrc/attention_train.hip in strips of the score matrix: no (B,heads,M,N) tensor exists, what is saved for the backward is
+    the output and one log-sum-exp per score row, and two runs give identical bytes.  Head width 32 only (ValueError
+    otherwise).  A sequence whose keys are all padding is a precondition violation: it yields NaN, as the reference does."""
+    return _AttentionTrain.apply(q, k, v, B, M, N, heads, key_mask)
+
+
+# ---- offset pairs of the training forward: csrc/offset_pairs.hip -----------------------------------------------------------
+
+def _offset_pairs_offsets(xa, xb, pa, pb, eps: float):
+    B, _, M = xa.shape
+    N = xb.shape[2]
+    counts = torch.empty(B * M, device=xa.device, dtype=torch.int32)
+    offsets = torch.empty(B * M + 1, device=xa.device, dtype=torch.int32)
+    _lib.check(_lib.load().dpm_offset_pairs_count(_ptr(xa), _ptr(xb), _ptr(pa), _ptr(pb), B, M, N, float(eps), _ptr(counts),
+                                                  _ptr(offsets), _stream(xa)), "dpm_offset_pairs_count")
+    return offsets
+
+
+def offset_pairs(xyz_a: torch.Tensor, xyz_b: torch.Tensor, pad_a: torch.Tensor, pad_b: torch.Tensor, eps: float):
+    """xyz_a (B,3,M), xyz_b (B,3,N) fp32, pad_* (B,M) / (B,N) bool (True = padding) -> (triples (K,3) int32, offsets_a (B*M+1),
+    offsets_b (B*N+1), perm_b (K,) int32): every (batch, a, b) with squared distance <= eps^2 between unpadded tokens in
+    torch.nonzero's order; offsets_a[r] .. offsets_a[r+1] are the pairs of a row r; perm_b lists the pairs stably sorted by b
+    row, offsets_b their ranges -- what offset_pair_rows' backward sums over.  One host synchronisation (K sizes the list)."""
+    _chk(xyz_a, torch.float32, "xyz_a"), _chk(xyz_b, torch.float32, "xyz_b")
+    _chk(pad_a, torch.bool, "pad_a"), _chk(pad_b, torch.bool, "pad_b")
+    if xyz_a.dim() != 3 or xyz_b.dim() != 3:
+        raise ValueError(f"coordinates must be (B,3,M) / (B,3,N), got {tuple(xyz_a.shape)} / {tuple(xyz_b.shape)}")
+    B, _, M = xyz_a.shape
+    N = xyz_b.shape[2]
+    _shape(xyz_a, (B, 3, M), "xyz_a"), _shape(xyz_b, (B, 3, N), "xyz_b")
+    _shape(pad_a, (B, M), "pad_a"), _shape(pad_b, (B, N), "pad_b")
+    off_a = _offset_pairs_offsets(xyz_a, xyz_b, pad_a, pad_b, eps)
+    off_b = _offset_pairs_offsets(xyz_b, xyz_a, pad_b, pad_a, eps)   # the distance is symmetric bit for bit: the same pairs
+    K = int(off_a[-1])
+    if K < 0:
+        raise ValueError("offset_pairs: more than 2^31 - 1 pairs")
+    triples = torch.empty(K, 3, device=xyz_a.device, dtype=torch.int32)
+    if K:
+        _lib.check(_lib.load().dpm_offset_pairs_fill(_ptr(xyz_a), _ptr(xyz_b), _ptr(pad_a), _ptr(pad_b), B, M, N, float(eps),
+                                                     _ptr(off_a), _ptr(triples), _stream(xyz_a)), "dpm_offset_pairs_fill")
+    key = triples[:, 0].long() * N + triples[:, 2].long()
+    perm_b = torch.sort(key, stable=True)[1].to(torch.int32)
+    return triples, off_a, off_b, perm_b
+
+
+def _segment_sum(g: torch.Tensor, offsets: torch.Tensor, perm: Optional[torch.Tensor], R: int) -> torch.Tensor:
+    E = g.shape[1]
+    out = torch.empty(R, E, device=g.device, dtype=torch.float32)
+    _lib.check(_lib.load().dpm_offset_pairs_segment_sum(_ptr(g) if g.numel() else None, max(g.stride(0), E), _ptr(offsets),
+                                                        _ptr(perm) if perm is not None and perm.numel() else None, R, E, _ptr(out),
+                                                        _stream(out)), "dpm_offset_pairs_segment_sum")
+    return out
+
+
+class _OffsetPairRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, triples, off_a, off_b, perm_b, M, N):
+        K, E = triples.shape[0], x.shape[1]
+        lib = _lib.load()
+        outs = []
+        for side, (t, rows) in enumerate(((x, M), (y, N))):
+            o = torch.empty(K, E, device=x.device, dtype=torch.float32)
+            _lib.check(lib.dpm_offset_pairs_gather(_ptr(t), t.stride(0), _ptr(triples), side, rows, K, E, _ptr(o), _stream(t)),
+                       "dpm_offset_pairs_gather")
+            outs.append(o)
+        ctx.save_for_backward(off_a, off_b, perm_b)
+        ctx.rows = (x.shape[0], y.shape[0])
+        return outs[0], outs[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ga, gb):
+        off_a, off_b, perm_b = ctx.saved_tensors
+        gx = _segment_sum(ga.contiguous(), off_a, None, ctx.rows[0])
+        gy = _segment_sum(gb.contiguous(), off_b, perm_b, ctx.rows[1])
+        return gx, gy, None, None, None, None, None, None
+
+
+def offset_pair_rows(x: torch.Tensor, y: torch.Tensor, pairs, M: int, N: int):
+    """x (B*M,E), y (B*N,E) fp32 rows, pairs = offset_pairs(...) -> (x rows of the pairs' a tokens (K,E), y rows of their b tokens
+    (K,E)), differentiable: the backward adds the K gradient rows back per token in a fixed order (no atomics)."""
+    _rows2d(x, "x"), _rows2d(y, "y")
+    triples, off_a, off_b, perm_b = pairs
+    if x.shape[1] != y.shape[1] or x.shape[1] % 4 or x.stride(0) % 4 or y.stride(0) % 4:
+        raise ValueError("offset_pair_rows: x and y must share a width that is a multiple of 4, rows 16-byte aligned")
+    if x.shape[0] + 1 != off_a.numel() or y.shape[0] + 1 != off_b.numel():
+        raise ValueError("offset_pair_rows: the pair list was made for other row counts")
+    return _OffsetPairRows.apply(x, y, triples, off_a, off_b, perm_b, M, N)

@@ -564,6 +564,44 @@ int dpm_reg_loss_backward(const float *xyz_a, const float *xyz_b, const int32_t 
                           int C, double tau, double eps, int neutral, const float *grad_loss, const float *stats,
                           const void *workspace, float *grad_a, float *grad_b, dpm_stream_t stream);
 
+/* Attention for training (csrc/attention_train.hip): the scaled-dot-product core of nn.MultiheadAttention
+ * (descriptor_attention.py:14-15, 33-44: softmax(Q_h K_h^T / sqrt(d)) V_h per head, dropout 0, key_padding_mask) with a
+ * backward, replacing autograd over the (B, heads, M, N) probability tensor.  Operands as in dpm_attention_masked: Q (B*M, E),
+ * K / V (B*N, E) row views with leading dims ld* and batch strides s* (floats; pointers 16-byte aligned, ld* and s* multiples
+ * of 4), key_mask (B,N) bytes, non-zero = padding key, NULL = none.  head_dim 32 only (else DPM_EUNSUPPORTED).
+ * forward: out (row view like Q) and lse (B, heads, M): log sum_n exp(score[m, n]) over the unmasked keys of each score row.
+ * backward: from Q, K, V, out, lse and dout (row view) -> dQ (B*M, E), dK, dV (B*N, E) contiguous; strips of the score matrix
+ *   are recomputed (P = exp(S - lse), dV = P^T dOut, dP = dOut V^T, dS = P (dP - rowsum(dOut out)) / sqrt(d), dQ = dS K,
+ *   dK = dS^T Q); masked keys get dK = dV = 0 exactly.  workspace: dpm_attention_train_workspace_bytes(B, M, N, heads).
+ * All products in fp32 on the matrix cores; no floating-point atomics: two runs give identical bytes.  A sequence whose keys
+ * are all padding yields NaN (as the reference). */
+size_t dpm_attention_train_workspace_bytes(int B, int M, int N, int heads);
+int dpm_attention_train_forward(const float *Q, int ldq, long long sq, const float *K, int ldk, long long sk, const float *V,
+                                int ldv, long long sv, float *out, int ldo, long long so, float *lse, int B, int M, int N,
+                                int heads, int head_dim, const uint8_t *key_mask, dpm_stream_t stream);
+int dpm_attention_train_backward(const float *Q, int ldq, long long sq, const float *K, int ldk, long long sk, const float *V,
+                                 int ldv, long long sv, const float *out, int ldo, long long so, const float *lse,
+                                 const float *dout, int ldd, long long sd, const uint8_t *key_mask, float *dQ, float *dK,
+                                 float *dV, int B, int M, int N, int heads, int head_dim, void *workspace, dpm_stream_t stream);
+
+/* Offset pairs of the decoder's training forward (decoder.py:62-83: the (B,M,N) distance matrix, its threshold mask and
+ * torch.nonzero) without that matrix (csrc/offset_pairs.hip).  xyz_a (B,3,M), xyz_b (B,3,N) fp32 contiguous, pad_* (B,M) / (B,N)
+ * bytes, non-zero = padding.  A pair (b, i, j) exists when neither token is padding and dist2 = (dx dx + dy dy) + dz dz (fp32,
+ * that order, no contraction) <= (float)(eps * eps).
+ * count: counts (B*M) pairs per a row and offsets (B*M + 1), their exclusive scan with the total K last (-1: beyond int32).
+ * fill: triples (K,3) int32 (b, i, j) in lexicographic order (torch.nonzero's), from the offsets of count.
+ * gather: out (K,E) = x[(b_k * rows + i_k or j_k)] (side 0: the a index, 1: the b index); x (B*rows, E) rows ldx apart.
+ * segment_sum: out (R,E) = per row r the sum of g[perm[k]] (perm NULL: g[k]) over k in [offsets[r], offsets[r+1]) in that
+ *   order (g rows ldg apart): the backward of gather, many pairs per token, in a fixed order without atomics. */
+int dpm_offset_pairs_count(const float *xyz_a, const float *xyz_b, const uint8_t *pad_a, const uint8_t *pad_b, int B, int M, int N,
+                           double eps, int32_t *counts, int32_t *offsets, dpm_stream_t stream);
+int dpm_offset_pairs_fill(const float *xyz_a, const float *xyz_b, const uint8_t *pad_a, const uint8_t *pad_b, int B, int M, int N,
+                          double eps, const int32_t *offsets, int32_t *triples, dpm_stream_t stream);
+int dpm_offset_pairs_gather(const float *x, int ldx, const int32_t *triples, int side, int rows, long long K, int E, float *out,
+                            dpm_stream_t stream);
+int dpm_offset_pairs_segment_sum(const float *g, int ldg, const int32_t *offsets, const int32_t *perm, long long R, int E,
+                                 float *out, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
