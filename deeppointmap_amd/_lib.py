@@ -113,6 +113,9 @@ SIGNATURES = {
     "dpm_offset_pairs_fill": (I, [P, P, P, P, I, I, I, D, P, P, P]),
     "dpm_offset_pairs_gather": (I, [P, I, P, I, I, LL, I, P, P]),
     "dpm_offset_pairs_segment_sum": (I, [P, I, P, P, LL, I, P, P]),
+    "dpm_group_train_forward": (I, [P, P, P, P, P, I, P, P, I, I, I, I, I, D, P, P, P]),
+    "dpm_group_train_workspace_bytes": (c_size_t, [I, I, I, I, I]),
+    "dpm_group_train_backward": (I, [P, P, P, P, P, I, P, I, I, I, I, I, D, P, P, P, P, P, P, P, P]),
 }
 
 

@@ -48,6 +48,7 @@ SOURCES = {
     "reg_loss.hip": [],
     "attention_train.hip": [],
     "offset_pairs.hip": [],
+    "group_train.hip": [],
 }
 
 

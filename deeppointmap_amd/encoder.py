@@ -4,7 +4,9 @@ Same constructor (`Encoder(args)`), same state-dict keys/shapes (params.encoder_
 call contract: `encoder(points (B,C>=3,N) f32, points_padding (B,N) bool) ->
 [coor (B,3,S), fea (B,out_channel,S), padding (B,S)]` (encoder.py:51-69).  Inputs may arrive on
 the CPU (ScanPack keeps CPU tensors, system/modules/pose_graph.py:43-45); they are staged to the
-module's GPU.  All arithmetic runs in libdpm_hip.so; there is no torch fallback.
+module's GPU.  All inference arithmetic runs in libdpm_hip.so; there is no torch fallback.  In `.train()` mode the same
+call is the reference's training forward: `fea` carries the autograd graph, the grouping layers run in csrc/group_train.hip in
+both directions and the dense layers are torch operations under autograd (`Encoder.train`, `Encoder._forward_train`).
 
 Internally everything is point-major fp32 with a per-frame valid length (valid points lead,
 exactly what the reference's FPS assumes, utils.py:255).
@@ -14,6 +16,8 @@ from __future__ import annotations
 from typing import List, Optional
 
 import torch
+import torch.nn.functional as F
+from torch.utils.checkpoint import checkpoint
 
 from . import ops
 from .params import ParamTree, encoder_shapes
@@ -48,6 +52,12 @@ class Encoder(ParamTree):
         # microseconds of work each but launches of the feature stream's dependent chain, and the geometry streams have slack
         self.presample_neighbours_from = None
         self._price_tail = 0   # measurement only (scripts/price_tail.py): extra evaluations of levels 3+ and the upsamplers
+        # training forward: from this many input points per call (B * N) on, every downsampling stage is recomputed in the
+        # backward instead of keeping the activations of its dense layers.  Measured (profiles/encoder_train_bench.md): a
+        # step at 8 x 16 384 points keeps 200 MiB, recomputation saves 68 MiB of them for +0.6 ms -- not worth a forward
+        # at the shipped sizes, so the threshold sits where the activations reach about 1.5 GiB
+        self.train_checkpoint_rows = 1 << 20
+        self._was_trained = False
         self.eval()
 
     # -- helpers -------------------------------------------------------------------------------
@@ -183,11 +193,21 @@ class Encoder(ParamTree):
         reference signature; used by the batched hot path): return instead the unified descriptor (B,out_channel+3,S) =
         [fea ; coor * descriptor_scale] that ExtractionThread.process builds from the triple (odometry.py:47-49).
         stop_level = i: run the downsampling levels below i and return the state (a dict) instead; resume = that state: run
-        the rest (same kernels in the same order: the two halves may sit on different HIP streams, pipeline.py)."""
+        the rest (same kernels in the same order: the two halves may sit on different HIP streams, pipeline.py).
+        In `.train()` mode: the training forward (`_forward_train`), `fea` attached to the autograd graph; the extra arguments
+        are inference-only and raise ValueError there."""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("deeppointmap_amd.Encoder runs on the GPU only: call .to('cuda') first "
                                "(there is no CPU fallback)")
+        if self.training:
+            for name, given in (("presampled", presampled is not None), ("descriptor_scale", descriptor_scale != 0.0),
+                                ("spare_frames", spare_frames != 0), ("stop_level", stop_level is not None),
+                                ("resume", resume is not None)):
+                if given:
+                    raise ValueError(f"Encoder.forward: `{name}` belongs to the inference pipeline and is not available in "
+                                     f".train() mode (call .eval() first)")
+            return self._forward_train(points, points_padding, trace)
         enc = self.encoder_cfg
         if resume is not None:
             samp = resume["samp"]
@@ -282,3 +302,134 @@ class Encoder(ParamTree):
             if descriptor_scale > 0:
                 return desc
         return [coor, feat, padding]
+
+    # -- training --------------------------------------------------------------------------------
+    def train(self, mode: bool = True):
+        """A real switch, like Decoder.train.  `.train()` selects the reference's registration training mode
+        (model_pipeline.py's `registration()` turns on every parameter whose name lacks `loop`: all of the encoder): every
+        parameter gets requires_grad = True and `forward` returns `fea` attached to the graph, so encoder -> decoder ->
+        RegistrationLoss -> backward() fills `.grad` of all 110 tensors.  `.eval()` (what `__init__` ends in) turns
+        requires_grad off again and drops the weight-derived caches; in-place optimiser steps bump the parameters' version
+        counters, which those caches key on, so inference after a step reads the new weights."""
+        super().train(mode)
+        for p in self._flat.values():
+            p.requires_grad_(bool(mode))
+        if mode:
+            self._was_trained = True
+        elif getattr(self, "_was_trained", False):
+            self._was_trained = False
+            self.invalidate_caches()
+        return self
+
+    def _w(self, key: str):
+        """(weight as (out, in), bias) of a Conv1d / Conv2d(k=1) for F.linear"""
+        w = self.p(key + ".weight")
+        return w.view(w.shape[0], w.shape[1]), self.p(key + ".bias")
+
+    def _mlp_ln_train(self, x, conv: str, ln: str, post=None):
+        """relu(LN(conv x) [+ post]) as torch operations under autograd (what ops.linear_layernorm evaluates)"""
+        y = F.layer_norm(F.linear(x, *self._w(conv)), (self.p(ln + ".weight").shape[0],), self.p(ln + ".weight"),
+                         self.p(ln + ".bias"))
+        return F.relu(y if post is None else y + post)
+
+    def _group_train(self, prefix: str, radius: float, xyz, fea, centers, idx, keep):
+        """SetAbstraction / LocalAggregation body: the projection under autograd, the rest in csrc/group_train.hip"""
+        W, bias = self._w(prefix + ".0")
+        Cin = fea.shape[2]
+        if W.shape[0] not in ops.GROUP_TRAIN_COUT or idx.shape[2] not in ops.GROUP_TRAIN_K:
+            raise ValueError(f"Encoder.forward (train mode): layer {prefix} has width {W.shape[0]} and {idx.shape[2]} "
+                             f"neighbours; the training kernels cover widths {ops.GROUP_TRAIN_COUT} and neighbour counts "
+                             f"{ops.GROUP_TRAIN_K}")
+        P = F.linear(fea, W[:, :Cin], bias)
+        slots = None if keep is None else []
+        out = ops.group_train(P, xyz, centers, idx, W[:, Cin:].contiguous(), self.p(prefix + ".1.ln.weight"),
+                              self.p(prefix + ".1.ln.bias"), radius, layer=prefix, keep_slots=slots)
+        if keep is not None:
+            keep[prefix + ".idx"], keep[prefix + ".winners"] = idx, ops.group_train_winners(idx, slots[0])
+        return out
+
+    def _train_stage(self, i: int, xyz, fea, new_xyz, gidx, lidx_list, keep):
+        """Stage i (pointnext.py:169-173): SetAbstraction, then its InvResMLP blocks"""
+        radii = self.encoder_cfg.radius_list[i]
+        pre = f"downsampler.{i}"
+        new_fea = self._group_train(pre + ".sa.mlp", radii[0], xyz, fea, new_xyz, gidx, keep)
+        for j in range(1, len(radii)):
+            q = f"{pre}.irm.{j - 1}"
+            t = self._group_train(q + ".la.mlp", radii[j], new_xyz, new_fea, new_xyz, lidx_list[j - 1], keep)
+            u = self._mlp_ln_train(t, q + ".pw_conv.0", q + ".pw_conv.1.ln")
+            new_fea = self._mlp_ln_train(u, q + ".pw_conv.3", q + ".pw_conv.4.ln", post=new_fea)
+        return new_fea
+
+    @staticmethod
+    def _interp_weights(xyz1, xyz2, len2):
+        """FeaturePropagation's 3-NN inverse-distance weights (pointnext.py:199-210) as a dense (B,N,S) matrix with three
+        non-zeros per row, made without gradient (coordinates have no parameter upstream): interpolation is then a bmm,
+        whose backward is a bmm again -- no scatter.  Padded coarse points are infinitely far (weight 0), as in
+        csrc/encoder_ops.hip."""
+        with torch.no_grad():
+            B, N, _ = xyz1.shape
+            S = xyz2.shape[1]
+            d = -2.0 * torch.bmm(xyz1, xyz2.transpose(1, 2))
+            d += (xyz1 ** 2).sum(-1).unsqueeze(2)
+            d += (xyz2 ** 2).sum(-1).unsqueeze(1)
+            pad = torch.arange(S, device=xyz2.device).unsqueeze(0) >= len2.unsqueeze(1)
+            d = d.masked_fill(pad.unsqueeze(1), float("inf"))
+            dist, nn = torch.topk(d, min(3, S), dim=-1, largest=False)
+            w = 1.0 / dist.clamp(min=1e-8)
+            w = w / w.sum(-1, keepdim=True)
+            return torch.zeros(B, N, S, device=xyz1.device, dtype=torch.float32).scatter_(2, nn, w)
+
+    def _forward_train(self, points: torch.Tensor, points_padding: torch.Tensor, trace: Optional[dict] = None):
+        """The reference's training forward (encoder.py:51-69 under autograd) -> [coor (B,3,S), fea (B,out_channel,S),
+        padding (B,S)], `fea` differentiable with respect to all 110 parameters.
+
+        Sampling, the neighbour queries and the level bookkeeping are the inference kernels under no_grad (geometry has no
+        parameter upstream).  Every grouping layer is ops.group_train (HIP forward and backward, no (B,S,K,C) tensor);
+        point_mlp0, the W_f projections, pw_conv and the upsampler MLPs with their LayerNorms are torch operations under
+        autograd, and the interpolation is a bmm with a weight matrix built without gradient.  Grad mode is enabled here,
+        whatever the caller's is.  From `train_checkpoint_rows` input points (B * N) on, each downsampling stage is
+        recomputed in the backward (torch.utils.checkpoint: the same kernels on the same inputs, identical bytes).
+        trace (a dict) receives, per grouping layer, `<layer>.idx` (B,S,K) and `<layer>.winners` (B,S,C): the neighbour
+        point that gave the maximum, -1 where the ReLU floor did, and per stage `downsampler.<i>.fps.new` / `.len`, the sampled
+        coordinates and valid counts (tracing turns the recomputation off).
+        Raises ValueError for configurations with a voxel sampler and for layer widths the kernels do not cover."""
+        if not self.all_fps:
+            raise ValueError("Encoder.forward (train mode): voxel samplers are inference-only; use 'fps' stages for training")
+        enc, dev = self.encoder_cfg, self.device
+        with torch.no_grad():
+            samp = self.presample(points, points_padding)
+            knn = samp["knn"] if "knn" in samp and self.presample_neighbours else self._neighbour_queries(samp)
+        keep = trace   # tracing keeps the winners of every grouping layer
+        with torch.enable_grad(), torch.cuda.device(dev):
+            pts, xyz, lengths = samp["pts"], samp["xyz"], samp["lengths"]
+            x0 = xyz if self.in_channel == 3 else pts[:, :self.in_channel].transpose(1, 2).contiguous()
+            fea = F.linear(x0, *self._w("point_mlp0"))
+            recompute = keep is None and xyz.shape[0] * xyz.shape[1] >= self.train_checkpoint_rows
+            levels = [(xyz, fea, lengths)]
+            for i in range(len(enc.npoint)):
+                radii, ks = enc.radius_list[i], enc.nsample_list[i]
+                new_xyz, new_len = samp[f"xyz{i}"], samp[f"len{i}"]
+                lidx = [knn[("la", i, (float(radii[j]), int(ks[j])))] for j in range(1, len(radii))]
+                if recompute:
+                    new_fea = checkpoint(self._train_stage, i, xyz, fea, new_xyz, knn[("sa", i)], lidx, None, use_reentrant=False)
+                else:
+                    new_fea = self._train_stage(i, xyz, fea, new_xyz, knn[("sa", i)], lidx, keep)
+                if keep is not None:
+                    keep[f"downsampler.{i}.fps.new"], keep[f"downsampler.{i}.len"] = new_xyz, new_len
+                levels.append((new_xyz, new_fea, new_len))
+                xyz, fea = new_xyz, new_fea
+            L = self.downsample_layers
+            for i in range(self.upsample_layers):
+                xyz1, fea1, len1 = levels[L - i - 1]
+                xyz2, fea2, len2 = levels[-1]
+                q = f"upsampler.{i}"
+                if xyz2.shape[1] == 1:   # pointnext.py:194-196
+                    up = fea2.expand(-1, xyz1.shape[1], -1)
+                else:
+                    up = torch.bmm(self._interp_weights(xyz1, xyz2, len2), fea2)
+                x = self._mlp_ln_train(torch.cat([fea1, up], dim=2), q + ".mlp.0", q + ".mlp.1.ln")
+                x = self._mlp_ln_train(x, q + ".mlp.3", q + ".mlp.4.ln")
+                levels.append((xyz1, x, len1))
+            xyz, fea, lengths = levels[-1]
+            coor, _, padding, _ = ops.emit_descriptors(xyz, fea.detach().contiguous(), lengths)
+            return [coor, fea.transpose(1, 2), padding]

@@ -1277,3 +1277,100 @@ def offset_pair_rows(x: torch.Tensor, y: torch.Tensor, pairs, M: int, N: int):
     if x.shape[0] + 1 != off_a.numel() or y.shape[0] + 1 != off_b.numel():
         raise ValueError("offset_pair_rows: the pair list was made for other row counts")
     return _OffsetPairRows.apply(x, y, triples, off_a, off_b, perm_b, M, N)
+
+
+# ---- the encoder's grouping layer for training: csrc/group_train.hip -------------------------------------------------------
+
+GROUP_TRAIN_COUT = (32, 64, 128, 256, 512)   # the widths and neighbour counts dpm_group_train_* implements: every shipped layer
+GROUP_TRAIN_K = (16, 32)
+GROUP_TRAIN_NO_WINNER = 255                  # slot value where no neighbour exceeds the ReLU floor
+
+
+def _group_train_args(P, xyz, centers, idx, W_rel, gamma, layer: str):
+    for n, t in (("P", P), ("xyz", xyz), ("centers", centers), ("W_rel", W_rel), ("gamma", gamma)):
+        _chk(t, torch.float32, n)
+    _chk(idx, torch.int32, "idx")
+    if P.dim() != 3 or idx.dim() != 3:
+        raise ValueError("group_train: P must be (B,N,Cout) and idx (B,S,K)")
+    B, N, Cout = P.shape
+    S, K = idx.shape[1], idx.shape[2]
+    if Cout not in GROUP_TRAIN_COUT or K not in GROUP_TRAIN_K:
+        raise ValueError(f"group_train: layer {layer or '<unnamed>'} has width {Cout} and {K} neighbours; the training kernels cover "
+                         f"widths {GROUP_TRAIN_COUT} and neighbour counts {GROUP_TRAIN_K}")
+    _shape(xyz, (B, N, 3), "xyz"), _shape(centers, (B, S, 3), "centers"), _shape(W_rel, (Cout, 3), "W_rel")
+    _shape(gamma, (Cout,), "gamma")
+    if idx.shape[0] != B:
+        raise ValueError(f"idx must be ({B}, S, K), got {tuple(idx.shape)}")
+    return B, N, S, K, Cout
+
+
+def group_train_forward(P, xyz, centers, idx, W_rel, gamma, beta, radius: float, layer: str = ""):
+    """P (B,N,Cout) projected point rows, xyz (B,N,3), centers (B,S,3), idx (B,S,K) int32, W_rel (Cout,3) ->
+    (out (B,S,Cout), slots (B,S,Cout) uint8): dpm_group_gather_ln_max's result and, per channel, the neighbour slot k that
+    gave the maximum (GROUP_TRAIN_NO_WINNER where the ReLU floor did) -- all the backward needs besides the operands."""
+    B, N, S, K, Cout = _group_train_args(P, xyz, centers, idx, W_rel, gamma, layer)
+    _chk(beta, torch.float32, "beta"), _shape(beta, (Cout,), "beta")
+    out = torch.empty(B, S, Cout, device=P.device, dtype=torch.float32)
+    slots = torch.empty(B, S, Cout, device=P.device, dtype=torch.uint8)
+    _lib.check(_lib.load().dpm_group_train_forward(_ptr(P), _ptr(xyz), _ptr(centers), _ptr(idx), _ptr(W_rel), 3, _ptr(gamma),
+                                                   _ptr(beta), B, N, S, K, Cout, float(radius), _ptr(out), _ptr(slots),
+                                                   _stream(P)), "dpm_group_train_forward")
+    return out, slots
+
+
+def group_train_backward(P, xyz, centers, idx, W_rel, gamma, radius: float, dout, slots, layer: str = ""):
+    """-> (dP (B,N,Cout), dW_rel (Cout,3), dgamma (Cout), dbeta (Cout)) from the operands, the forward's slots and dout
+    (B,S,Cout).  Deterministic; rows of dP that no winning neighbour names are exact zeros."""
+    B, N, S, K, Cout = _group_train_args(P, xyz, centers, idx, W_rel, gamma, layer)
+    _chk(dout, torch.float32, "dout"), _chk(slots, torch.uint8, "slots")
+    _shape(dout, (B, S, Cout), "dout"), _shape(slots, (B, S, Cout), "slots")
+    lib, dev = _lib.load(), P.device
+    ws = torch.empty(lib.dpm_group_train_workspace_bytes(B, N, S, K, Cout), device=dev, dtype=torch.uint8)
+    dP = torch.empty(B, N, Cout, device=dev, dtype=torch.float32)
+    dW = torch.empty(Cout, 3, device=dev, dtype=torch.float32)
+    dgamma = torch.empty(Cout, device=dev, dtype=torch.float32)
+    dbeta = torch.empty(Cout, device=dev, dtype=torch.float32)
+    _lib.check(lib.dpm_group_train_backward(_ptr(P), _ptr(xyz), _ptr(centers), _ptr(idx), _ptr(W_rel), 3, _ptr(gamma), B, N, S, K,
+                                            Cout, float(radius), _ptr(dout), _ptr(slots), _ptr(dP), _ptr(dW), _ptr(dgamma),
+                                            _ptr(dbeta), _ptr(ws), _stream(P)), "dpm_group_train_backward")
+    return dP, dW, dgamma, dbeta
+
+
+class _GroupTrain(torch.autograd.Function):
+    """Saved for the backward: P, the (small) geometry and layer tensors and one byte per output element -- no (B,S,K,Cout) tensor."""
+
+    @staticmethod
+    def forward(ctx, P, W_rel, gamma, beta, xyz, centers, idx, radius, layer, keep):
+        out, slots = group_train_forward(P, xyz, centers, idx, W_rel, gamma, beta, radius, layer)
+        ctx.save_for_backward(P, W_rel, gamma, xyz, centers, idx, slots)
+        ctx.cfg = (float(radius), layer)
+        if keep is not None:
+            keep.append(slots)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        P, W_rel, gamma, xyz, centers, idx, slots = ctx.saved_tensors
+        radius, layer = ctx.cfg
+        dP, dW, dgamma, dbeta = group_train_backward(P, xyz, centers, idx, W_rel, gamma, radius, dout.contiguous(), slots, layer)
+        return dP, dW, dgamma, dbeta, None, None, None, None, None, None
+
+
+def group_train(P: torch.Tensor, xyz: torch.Tensor, centers: torch.Tensor, idx: torch.Tensor, W_rel: torch.Tensor,
+                gamma: torch.Tensor, beta: torch.Tensor, radius: float, layer: str = "", keep_slots: Optional[list] = None):
+    """The grouping layer for training: out[b,s,c] = max_k relu(LN_c(P[b, idx[b,s,k]] + W_rel (xyz[idx] - centre) / radius)),
+    differentiable with respect to P, W_rel (Cout,3), gamma and beta (LayerNorm eps 1e-5, biased variance); the geometry gets
+    no gradient.  P = fea W_f^T + b is the caller's, under autograd.  Forward and backward run in csrc/group_train.hip; what is
+    saved is P and a byte per output element, and two runs give identical bytes.  ValueError (naming `layer`) for a width
+    outside GROUP_TRAIN_COUT or a neighbour count outside GROUP_TRAIN_K.  keep_slots: a list that receives the winning slots
+    (group_train_winners turns them into point indices)."""
+    return _GroupTrain.apply(P, W_rel, gamma, beta, xyz, centers, idx, radius, layer, keep_slots)
+
+
+def group_train_winners(idx: torch.Tensor, slots: torch.Tensor) -> torch.Tensor:
+    """idx (B,S,K) int32, slots (B,S,Cout) uint8 -> (B,S,Cout) int64: the POINT idx[b,s,slot] that wins channel c of centre s,
+    -1 where none does (the ReLU floor)."""
+    live = slots != GROUP_TRAIN_NO_WINNER
+    pts = torch.gather(idx.long(), 2, slots.long().clamp(max=idx.shape[2] - 1))
+    return torch.where(live, pts, torch.full_like(pts, -1))

@@ -602,6 +602,27 @@ int dpm_offset_pairs_gather(const float *x, int ldx, const int32_t *triples, int
 int dpm_offset_pairs_segment_sum(const float *g, int ldg, const int32_t *offsets, const int32_t *perm, long long R, int E,
                                  float *out, dpm_stream_t stream);
 
+/* The grouping layer for training (csrc/group_train.hip): SetAbstraction / LocalAggregation's
+ * gather -> [fea ; rel] -> Conv2d -> LayerNorm -> ReLU -> max over the K neighbours (pointnext.py:52-61, 97-107) with a
+ * backward, replacing autograd over the (B, Cout, K, S) activations of build_mlp.  Same contract as dpm_group_gather_ln_max:
+ * P (B,N,Cout) = fea W_f^T + b made by the caller, W_rel (Cout rows, ldw_rel apart, 3 used), idx clamped to [0, N).
+ * forward: out (B,S,Cout) and slots (B,S,Cout) bytes: the k whose row gave the maximum (the smallest on ties), 255 where no
+ *   row exceeds the ReLU floor (out = 0, no gradient).
+ * backward: from dout (B,S,Cout) and the forward's slots -> dP (B,N,Cout) (rows nobody gathered are exact zeros), dW_rel
+ *   (Cout,3) contiguous, dgamma, dbeta (Cout).  The pre-norm rows and their statistics are recomputed; the rows are regrouped
+ *   by gathered point (a counting sort of idx, integer atomics only) and every dP row has one writer that adds in (s, k)
+ *   order; the weight gradients are per-wave partials added in wave order: two runs give identical bytes.
+ *   workspace: dpm_group_train_workspace_bytes(B,N,S,K,Cout), 16-byte aligned.
+ * Cout in {32,64,128,256,512} and K in {16,32}, else DPM_EUNSUPPORTED (workspace_bytes: 0). */
+int dpm_group_train_forward(const float *P, const float *xyz, const float *centers, const int32_t *idx, const float *W_rel,
+                            int ldw_rel, const float *gamma, const float *beta, int B, int N, int S, int K, int Cout,
+                            double radius, float *out, uint8_t *slots, dpm_stream_t stream);
+size_t dpm_group_train_workspace_bytes(int B, int N, int S, int K, int Cout);
+int dpm_group_train_backward(const float *P, const float *xyz, const float *centers, const int32_t *idx, const float *W_rel,
+                             int ldw_rel, const float *gamma, int B, int N, int S, int K, int Cout, double radius,
+                             const float *dout, const uint8_t *slots, float *dP, float *dW_rel, float *dgamma, float *dbeta,
+                             void *workspace, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
