@@ -116,6 +116,10 @@ SIGNATURES = {
     "dpm_group_train_forward": (I, [P, P, P, P, P, I, P, P, I, I, I, I, I, D, P, P, P]),
     "dpm_group_train_workspace_bytes": (c_size_t, [I, I, I, I, I]),
     "dpm_group_train_backward": (I, [P, P, P, P, P, I, P, I, I, I, I, I, D, P, P, P, P, P, P, P, P]),
+    "dpm_loop_pool_workspace_bytes": (c_size_t, [I, I, I]),
+    "dpm_loop_pool_forward": (I, [P, I, P, P, I, I, I, P, P, P]),
+    "dpm_loop_pool_backward": (I, [P, I, P, P, P, I, I, I, P, P, P, P]),
+    "dpm_loop_bce_forward": (I, [P, P, I, P, P, P, P]),
 }
 
 

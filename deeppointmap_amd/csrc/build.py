@@ -49,6 +49,7 @@ SOURCES = {
     "attention_train.hip": [],
     "offset_pairs.hip": [],
     "group_train.hip": [],
+    "loop_head_train.hip": [],
 }
 
 

@@ -5,7 +5,8 @@ contracts:
   * `registration_forward(src_desc (131,M), dst_desc (131,N), src_padding_mask=None,
      dst_padding_mask=None, num_sample=0.5) -> (R (3,3), T (3,1), conf (K,), rmse: float)`
      (decoder.py:91-127); 3-D inputs give the batched return shapes of the reference.
-  * `loop_detection_forward(src (C,131,M), dst (C,131,N)) -> (C,)` (decoder.py:129-143).
+  * `loop_detection_forward(src (C,131,M), dst (C,131,N)) -> (C,)` (decoder.py:129-143); in `.train()` at train stage
+     "loop_detection" (`set_train_stage`) it is the reference's second training stage: the result carries the loop head's graph.
   * `forward(src_desc (B,131,M), dst_desc (B,131,N), src_padding_mask, dst_padding_mask, gt_Rt) -> [six tensors]`
      (decoder.py:34-89) is the training forward; it needs `.train()` and raises in eval mode as the reference does.
 Padding masks ((B,M) / (B,N) bool, True = padding) are the key_padding_mask of every attention block and nothing else
@@ -30,6 +31,7 @@ from . import knobs, ops
 from .params import ParamTree, decoder_shapes
 
 HEADS = 8
+TRAIN_STAGES = ("registration", "loop_detection")
 
 
 class Decoder(ParamTree):
@@ -63,6 +65,7 @@ class Decoder(ParamTree):
         # training forward: from this many stacked tokens (B * (M + N)) on, an attention layer's activations are recomputed in
         # the backward rather than kept (sixteen (tokens, model_channel) tensors per layer: 256 MiB per layer at 16384 tokens)
         self.train_checkpoint_rows = 8192
+        self.train_stage = "registration"   # what `.train()` trains: set_train_stage
         self.eval()
 
     def __deepcopy__(self, memo):
@@ -289,19 +292,33 @@ class Decoder(ParamTree):
 
     # -- public API ----------------------------------------------------------------------------
     def train(self, mode: bool = True):
-        """A real switch.  `.train()` selects the reference's registration training mode (model_pipeline.py's
-        `registration()`): every parameter whose name does not contain `loop` gets requires_grad = True, so `forward` ->
-        RegistrationLoss -> backward() fills their `.grad` and `torch.optim.*(decoder.parameters())` can step them; `loop_head`
-        stays frozen.  `.eval()` (what `__init__` ends in) turns requires_grad off again for all of them and drops the
-        weight-derived caches.  In-place optimiser steps bump the parameters' version counters, which both the derived-weight
-        cache (ops._derived) and the captured registration graphs (`_weights_stamp`) key on: inference after a step reads the
-        new weights."""
+        """A real switch.  `.train()` selects the training mode of `self.train_stage`.  "registration" (the default; the
+        reference's model_pipeline.py `registration()`): every parameter whose name does not contain `loop` gets
+        requires_grad = True, so `forward` -> RegistrationLoss -> backward() fills their `.grad` and
+        `torch.optim.*(decoder.parameters())` can step them; `loop_head` stays frozen.  "loop_detection" (`loop_detection()`
+        there): exactly the eight `loop_head.*` tensors get requires_grad = True and `loop_detection_forward` returns a
+        probability attached to the graph; everything else is frozen.  `.eval()` (what `__init__` ends in) turns requires_grad
+        off again for all of them and drops the weight-derived caches.  In-place optimiser steps bump the parameters' version
+        counters, which both the derived-weight cache (ops._derived) and the captured registration graphs (`_weights_stamp`)
+        key on: inference after a step reads the new weights."""
         was = self.training
         super().train(mode)
+        loop = getattr(self, "train_stage", "registration") == "loop_detection"
         for name, p in self._flat.items():
-            p.requires_grad_(bool(mode) and "loop" not in name)
+            p.requires_grad_(bool(mode) and (("loop" in name) == loop))
         if was and not mode:
             self.invalidate_caches()
+        return self
+
+    def set_train_stage(self, stage: str = "registration"):
+        """Which of the reference's two training stages `.train()` selects (pipeline/modules/trainer.py runs them in turn):
+        "registration" or "loop_detection".  Kept in `self.train_stage` across `.train()` / `.eval()`; applied at once if the
+        module is training.  Returns self.  ValueError for any other name."""
+        if stage not in TRAIN_STAGES:
+            raise ValueError(f"train stage must be one of {TRAIN_STAGES}, got {stage!r}")
+        self.train_stage = stage
+        if self.training:
+            self.train(True)
         return self
 
     def _w(self, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -672,22 +689,43 @@ class Decoder(ParamTree):
             return R, T, cf, rmse
         return R.unsqueeze(0), T.unsqueeze(0), cf.unsqueeze(0), [rmse]
 
-    @torch.no_grad()
     def loop_detection_forward(self, src_descriptor: torch.Tensor, dst_descriptor: torch.Tensor,
                                src_padding_mask=None, dst_padding_mask=None) -> torch.Tensor:
+        """(C,131,M), (C,131,N) -> loop probabilities (C,)   (decoder.py:129-143).
+
+        Inference everywhere but in one situation: a decoder in `.train()` mode at stage "loop_detection"
+        (`set_train_stage`), called with grad mode enabled, returns the probabilities attached to the autograd graph of the
+        eight `loop_head.*` parameters -- the reference's second training stage (model_pipeline.py:136-181).  The attention
+        trunk is frozen there and runs on the inference kernels without a graph; the head's token-sized layer is
+        ops.loop_pool (csrc/loop_head_train.hip, forward and backward), its (C, 2 E)-sized layers are torch operations under
+        autograd.  The descriptors get NO gradient in that mode: nothing upstream of the head is trainable in this stage."""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
         if src_descriptor.ndim == 2 and dst_descriptor.ndim == 2:
             src_descriptor, dst_descriptor = src_descriptor.unsqueeze(0), dst_descriptor.unsqueeze(0)
         E = self.model_channel
-        with torch.cuda.device(dev):
+        train_head = self.training and self.train_stage == "loop_detection" and torch.is_grad_enabled()
+        with torch.no_grad(), torch.cuda.device(dev):
             x, _, y, _, B, M, N = self._descriptor_attention_forward(src_descriptor, dst_descriptor,
                                                                      src_padding_mask, dst_padding_mask)
-            fx = self._lin("loop_head.mlp.2", self._lin("loop_head.mlp.0", x, ops.ACT_RELU))
-            fy = self._lin("loop_head.mlp.2", self._lin("loop_head.mlp.0", y, ops.ACT_RELU))
-            cat = torch.empty(B, 2 * E, device=dev, dtype=torch.float32)
-            ops.mean_rows(fx.view(B, M, E), cat[:, :E])
-            ops.mean_rows(fy.view(B, N, E), cat[:, E:])
-            h = self._lin("loop_head.projection.0", cat, ops.ACT_RELU)
-            return self._lin("loop_head.projection.2", h, ops.ACT_SIGMOID).flatten()
+            if not train_head:
+                fx = self._lin("loop_head.mlp.2", self._lin("loop_head.mlp.0", x, ops.ACT_RELU))
+                fy = self._lin("loop_head.mlp.2", self._lin("loop_head.mlp.0", y, ops.ACT_RELU))
+                cat = torch.empty(B, 2 * E, device=dev, dtype=torch.float32)
+                ops.mean_rows(fx.view(B, M, E), cat[:, :E])
+                ops.mean_rows(fy.view(B, N, E), cat[:, E:])
+                h = self._lin("loop_head.projection.0", cat, ops.ACT_RELU)
+                return self._lin("loop_head.projection.2", h, ops.ACT_SIGMOID).flatten()
+        with torch.cuda.device(dev):
+            return self._loop_head_train(x, y, B, M, N)
+
+    def _loop_head_train(self, x: torch.Tensor, y: torch.Tensor, B: int, M: int, N: int) -> torch.Tensor:
+        """OverlapHead (heads.py:60-69) under autograd on correlated features x (B*M,E), y (B*N,E) that carry no graph: the mean
+        over the tokens (padding included, heads.py:65-66) of mlp.0 + ReLU is ops.loop_pool, then mlp.2 acts on the means --
+        the second convolution is affine and commutes with the mean -- and the projection on (B, 2 E) rows"""
+        W1, b1 = self._w("loop_head.mlp.0")
+        m = torch.cat([ops.loop_pool(x, B, M, W1, b1), ops.loop_pool(y, B, N, W1, b1)])      # (2B, E)
+        f = F.linear(m, *self._w("loop_head.mlp.2"))
+        h = F.relu(F.linear(torch.cat([f[:B], f[B:]], dim=1), *self._w("loop_head.projection.0")))
+        return torch.sigmoid(F.linear(h, *self._w("loop_head.projection.2"))).flatten()

@@ -58,6 +58,7 @@ class Encoder(ParamTree):
         # at the shipped sizes, so the threshold sits where the activations reach about 1.5 GiB
         self.train_checkpoint_rows = 1 << 20
         self._was_trained = False
+        self.train_stage = "registration"   # what `.train()` trains: set_train_stage
         self.eval()
 
     # -- helpers -------------------------------------------------------------------------------
@@ -195,12 +196,13 @@ class Encoder(ParamTree):
         stop_level = i: run the downsampling levels below i and return the state (a dict) instead; resume = that state: run
         the rest (same kernels in the same order: the two halves may sit on different HIP streams, pipeline.py).
         In `.train()` mode: the training forward (`_forward_train`), `fea` attached to the autograd graph; the extra arguments
-        are inference-only and raise ValueError there."""
+        are inference-only and raise ValueError there.  At train stage "loop_detection" (`set_train_stage`) the encoder is
+        frozen and `.train()` changes nothing here: this inference forward runs, with all its arguments."""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("deeppointmap_amd.Encoder runs on the GPU only: call .to('cuda') first "
                                "(there is no CPU fallback)")
-        if self.training:
+        if self.training and self.train_stage != "loop_detection":
             for name, given in (("presampled", presampled is not None), ("descriptor_scale", descriptor_scale != 0.0),
                                 ("spare_frames", spare_frames != 0), ("stop_level", stop_level is not None),
                                 ("resume", resume is not None)):
@@ -310,15 +312,30 @@ class Encoder(ParamTree):
         parameter gets requires_grad = True and `forward` returns `fea` attached to the graph, so encoder -> decoder ->
         RegistrationLoss -> backward() fills `.grad` of all 110 tensors.  `.eval()` (what `__init__` ends in) turns
         requires_grad off again and drops the weight-derived caches; in-place optimiser steps bump the parameters' version
-        counters, which those caches key on, so inference after a step reads the new weights."""
+        counters, which those caches key on, so inference after a step reads the new weights.
+        At train stage "loop_detection" (`set_train_stage`; model_pipeline.py's `loop_detection()` freezes every parameter
+        whose name lacks `loop`: all of the encoder) `.train()` leaves every parameter frozen and `forward` stays the
+        inference forward: the same bytes as in `.eval()`, at inference cost."""
         super().train(mode)
+        on = bool(mode) and getattr(self, "train_stage", "registration") != "loop_detection"
         for p in self._flat.values():
-            p.requires_grad_(bool(mode))
+            p.requires_grad_(on)
         if mode:
             self._was_trained = True
         elif getattr(self, "_was_trained", False):
             self._was_trained = False
             self.invalidate_caches()
+        return self
+
+    def set_train_stage(self, stage: str = "registration"):
+        """Which of the reference's two training stages `.train()` selects: "registration" or "loop_detection" (see
+        `train`).  Kept in `self.train_stage` across `.train()` / `.eval()`; applied at once if the module is training.
+        Returns self.  ValueError for any other name."""
+        if stage not in ("registration", "loop_detection"):
+            raise ValueError(f"train stage must be 'registration' or 'loop_detection', got {stage!r}")
+        self.train_stage = stage
+        if self.training:
+            self.train(True)
         return self
 
     def _w(self, key: str):

@@ -1,4 +1,5 @@
-"""RegistrationLoss of the reference (network/loss.py) for training on the MI355X.
+"""The training objectives of the reference for the MI355X: RegistrationLoss (network/loss.py) and the loop-detection
+stage's binary cross-entropy with its metrics (pipeline/modules/model_pipeline.py:156-181, LoopDetectionLoss below).
 
 The pairing terms run in csrc/reg_loss.hip: nearest neighbours, the InfoNCE forward of both directions and its analytic
 backward, in strips of the similarity matrix that are recomputed rather than stored, so no (B, S, D) tensor exists in memory.
@@ -158,3 +159,43 @@ class RegistrationLoss(nn.Module):
         _, stats, _ = ops.reg_loss_forward(a, b, None, None, pad_a, pad_b, nn_a, nn_b, 1.0, 0.0, False)
         s = stats.tolist()
         return _top1(s[5], s[3])
+
+
+class LoopDetectionLoss(nn.Module):
+    """The objective of the reference's loop-detection stage (pipeline/modules/model_pipeline.py:156-181).
+
+    forward(loop_pred (B,), src_T (B,3,1), dst_T (B,3,1)) -> (loss, metric_dict): a pair is a loop (label 1) when its two
+    frames are at most `args.train.loop_detection.distance` apart, ||src_T - dst_T||_2 computed in fp32; loss is
+    F.binary_cross_entropy(loop_pred, label), a 0-d tensor differentiable with respect to loop_pred (ops.loop_bce: loss,
+    gradient seed and counts in one launch).  metric_dict holds Python floats under the reference's keys, from ONE
+    device-to-host copy: `loss_loop`; `loop_precision`, which there is the share of pairs with prediction == label (the name is
+    kept); `loop_recall`, 1.0 when no pair is a loop; `loop_false_positive`, 0.0 when every pair is one.  The prediction is
+    loop_pred > 0.5."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.distance = float(args.train.loop_detection.distance)
+
+    def forward(self, loop_pred: Tensor, src_T: Tensor, dst_T: Tensor):
+        if loop_pred.dim() != 1 or loop_pred.numel() < 1:
+            raise ValueError(f"loop_pred must be (B,) with B >= 1, got {tuple(loop_pred.shape)}")
+        B = loop_pred.numel()
+        for name, t in (("src_T", src_T), ("dst_T", dst_T)):
+            if tuple(t.shape) != (B, 3, 1):
+                raise ValueError(f"{name}: expected shape ({B}, 3, 1), got {tuple(t.shape)}")
+        dev = loop_pred.device
+        dis = torch.norm((_f32(src_T).to(dev) - _f32(dst_T).to(dev)).squeeze(-1), p=2, dim=-1)
+        loop_gt = (dis <= self.distance).float()
+        pred = loop_pred if loop_pred.dtype == torch.float32 else loop_pred.float()
+        loss, stats = ops.loop_bce(pred, loop_gt)
+        s = stats.tolist()
+        n_pos, n_neg, n_equal, true_pos, false_pos = s[1:6]
+        ratio = lambda a, b: float(np.float32(a) / np.float32(b))   # noqa: E731  (the reference divides fp32 tensors)
+        metric_dict = {
+            "loss_loop": s[0],
+            "loop_precision": ratio(n_equal, B),
+            "loop_recall": ratio(true_pos, n_pos) if n_pos > 0 else 1.0,
+            "loop_false_positive": ratio(false_pos, n_neg) if n_neg > 0 else 0.0,
+        }
+        return loss, metric_dict

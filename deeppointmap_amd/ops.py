@@ -1374,3 +1374,107 @@ def group_train_winners(idx: torch.Tensor, slots: torch.Tensor) -> torch.Tensor:
     live = slots != GROUP_TRAIN_NO_WINNER
     pts = torch.gather(idx.long(), 2, slots.long().clamp(max=idx.shape[2] - 1))
     return torch.where(live, pts, torch.full_like(pts, -1))
+
+
+# ---- the loop head for training: csrc/loop_head_train.hip ------------------------------------------------------------------
+
+LOOP_POOL_CHANNELS = 256   # the one width dpm_loop_pool_* implements (model_channel of every shipped config)
+
+
+def _loop_pool_args(x, B: int, L: int, W1, b1):
+    _rows2d(x, "x")
+    E = x.shape[1]
+    if E != LOOP_POOL_CHANNELS:
+        raise ValueError(f"loop_pool: width {E} is not supported, only {LOOP_POOL_CHANNELS} (model_channel)")
+    if B < 1 or L < 1:
+        raise ValueError(f"loop_pool: needs B >= 1 sequences of L >= 1 tokens, got B = {B}, L = {L}")
+    if x.shape[0] != B * L:
+        raise ValueError(f"x: expected {B * L} rows (B * L), got {x.shape[0]}")
+    _chk(W1, torch.float32, "W1"), _chk(b1, torch.float32, "b1")
+    _shape(W1, (E, E), "W1"), _shape(b1, (E,), "b1")
+    return E
+
+
+def loop_pool_forward(x: torch.Tensor, B: int, L: int, W1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
+    """x (B*L, E) fp32 row view, W1 (E,E), b1 (E) -> m (B,E) = mean over the L tokens of relu(x W1^T + b1)."""
+    E = _loop_pool_args(x, B, L, W1, b1)
+    lib = _lib.load()
+    ws = torch.empty(lib.dpm_loop_pool_workspace_bytes(B, L, E), device=x.device, dtype=torch.uint8)
+    m = torch.empty(B, E, device=x.device, dtype=torch.float32)
+    _lib.check(lib.dpm_loop_pool_forward(_ptr(x), x.stride(0), _ptr(W1), _ptr(b1), B, L, E, _ptr(m), _ptr(ws), _stream(x)),
+               "dpm_loop_pool_forward")
+    return m
+
+
+def loop_pool_backward(x: torch.Tensor, B: int, L: int, W1: torch.Tensor, b1: torch.Tensor, g: torch.Tensor):
+    """-> (dW1 (E,E), db1 (E)) from g = dL/dm (B,E) and the forward's operands.  Deterministic; x gets no gradient."""
+    E = _loop_pool_args(x, B, L, W1, b1)
+    _chk(g, torch.float32, "g"), _shape(g, (B, E), "g")
+    lib = _lib.load()
+    ws = torch.empty(lib.dpm_loop_pool_workspace_bytes(B, L, E), device=x.device, dtype=torch.uint8)
+    dW1 = torch.empty(E, E, device=x.device, dtype=torch.float32)
+    db1 = torch.empty(E, device=x.device, dtype=torch.float32)
+    _lib.check(lib.dpm_loop_pool_backward(_ptr(x), x.stride(0), _ptr(W1), _ptr(b1), _ptr(g), B, L, E, _ptr(dW1), _ptr(db1),
+                                          _ptr(ws), _stream(x)), "dpm_loop_pool_backward")
+    return dW1, db1
+
+
+class _LoopPool(torch.autograd.Function):
+    """Saved for the backward: x, W1, b1 -- nothing of B * L * E elements besides the input itself."""
+
+    @staticmethod
+    def forward(ctx, x, B, L, W1, b1):
+        W1c, b1c = W1.detach().contiguous(), b1.detach().contiguous()
+        m = loop_pool_forward(x, B, L, W1c, b1c)
+        ctx.save_for_backward(x, W1c, b1c)
+        ctx.cfg = (B, L)
+        return m
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, W1, b1 = ctx.saved_tensors
+        dW1, db1 = loop_pool_backward(x, *ctx.cfg, W1, b1, g.contiguous())
+        return None, None, None, dW1, db1
+
+
+def loop_pool(x: torch.Tensor, B: int, L: int, W1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
+    """mean over the tokens of relu(x W1^T + b1): x (B*L, E) fp32 row view (a column slice of a wider buffer is allowed, rows
+    16-byte aligned), W1 (E,E), b1 (E) -> (B,E), differentiable with respect to W1 and b1 ONLY -- x is the output of a frozen
+    trunk and gets no gradient.  The mean runs over all L tokens.  Forward and backward run in csrc/loop_head_train.hip: the
+    (B*L, E) pre-activation exists in neither direction, the backward recomputes it with the forward's instruction sequence
+    (the same ReLU mask, bit for bit), and two runs give identical bytes.  E = 256 only (ValueError otherwise)."""
+    return _LoopPool.apply(x, B, L, W1, b1)
+
+
+class _LoopBce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        p, y = pred.detach().contiguous(), target.detach().contiguous()
+        dev = p.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        stats = torch.empty(8, device=dev, dtype=torch.float32)
+        unit = torch.empty_like(p)
+        _lib.check(_lib.load().dpm_loop_bce_forward(_ptr(p), _ptr(y), p.numel(), _ptr(loss), _ptr(stats), _ptr(unit), _stream(p)),
+                   "dpm_loop_bce_forward")
+        ctx.save_for_backward(unit)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        unit, = ctx.saved_tensors
+        return grad_loss * unit, None
+
+
+def loop_bce(pred: torch.Tensor, target: torch.Tensor):
+    """F.binary_cross_entropy(pred, target) of (B,) fp32 probabilities and 0 / 1 labels (mean reduction, both logarithms clamped
+    at -100) -> (loss 0-d, stats (8,)), one launch: stats = [loss, n_pos, n_neg, n_equal, true_pos, false_pos, 0, 0] with the
+    prediction `pred > 0.5` (model_pipeline.py:160-173).  loss is differentiable with respect to pred, by torch's formula
+    grad (p - t) / max(p (1 - p), 1e-12) / B; stats is not differentiable."""
+    _chk(pred.detach(), torch.float32, "pred"), _chk(target.detach(), torch.float32, "target")
+    if pred.dim() != 1 or pred.numel() < 1:
+        raise ValueError(f"pred must be (B,) with B >= 1, got {tuple(pred.shape)}")
+    _shape(target, pred.shape, "target")
+    return _LoopBce.apply(pred, target)

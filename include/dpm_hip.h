@@ -623,6 +623,28 @@ int dpm_group_train_backward(const float *P, const float *xyz, const float *cent
                              const float *dout, const uint8_t *slots, float *dP, float *dW_rel, float *dgamma, float *dbeta,
                              void *workspace, dpm_stream_t stream);
 
+/* The loop head for training (csrc/loop_head_train.hip; network/decoder/heads.py:45-69 OverlapHead under
+ * pipeline/modules/model_pipeline.py:156-181, the reference's loop-detection stage: everything but the head is frozen).
+ * loop_pool: x (B*L, E) token rows, ldx floats apart (16-byte aligned, ldx a multiple of 4), W1 (E,E) row-major, b1 (E) ->
+ *   m (B,E), m[b,c] = (1/L) sum_l relu(x[b,l,:] . W1[c,:] + b1[c]): OverlapHead.mlp's first convolution, its ReLU and the mean
+ *   over ALL L tokens (padding included, as torch.mean(dim=-1) there); the second convolution is affine and commutes with the
+ *   mean, so it acts on m.  backward: from g = dL/dm (B,E) -> dW1 (E,E), db1 (E); the ReLU mask is recomputed with the
+ *   forward's instruction sequence (same bits), x gets no gradient.  Neither direction writes a (B*L, E) tensor.
+ *   workspace: dpm_loop_pool_workspace_bytes(B, L, E) for either call (per-tile column sums forward, a fixed number of
+ *   partial dW1 backward); E = 256 only, else DPM_EUNSUPPORTED (workspace_bytes: 0).
+ * loop_bce: pred, target (B,) -> *loss = mean(-(t max(log p, -100) + (1 - t) max(log(1 - p), -100))) (F.binary_cross_entropy,
+ *   model_pipeline.py:158), stats (8) = [loss, n_pos, n_neg, n_equal, true_pos, false_pos, 0, 0] with the prediction p > 0.5
+ *   (model_pipeline.py:160-173) and dpred_unit (B,) = (p - t) / max(p (1 - p), 1e-12) / B, the gradient of the loss: the
+ *   backward is a product with it, there is no dpm_loop_bce_backward.
+ * All products in fp32 on the matrix cores, no floating-point atomics: two runs give identical bytes. */
+size_t dpm_loop_pool_workspace_bytes(int B, int L, int E);
+int dpm_loop_pool_forward(const float *x, int ldx, const float *W1, const float *b1, int B, int L, int E, float *m,
+                          void *workspace, dpm_stream_t stream);
+int dpm_loop_pool_backward(const float *x, int ldx, const float *W1, const float *b1, const float *g, int B, int L, int E,
+                           float *dW1, float *db1, void *workspace, dpm_stream_t stream);
+int dpm_loop_bce_forward(const float *pred, const float *target, int B, float *loss, float *stats, float *dpred_unit,
+                         dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
