@@ -120,6 +120,10 @@ SIGNATURES = {
     "dpm_loop_pool_forward": (I, [P, I, P, P, I, I, I, P, P, P]),
     "dpm_loop_pool_backward": (I, [P, I, P, P, P, I, I, I, P, P, P, P]),
     "dpm_loop_bce_forward": (I, [P, P, I, P, P, P, P]),
+    "dpm_dense_train_workspace_bytes": (c_size_t, [LL, I, I]),
+    "dpm_dense_train_forward": (I, [P, I, P, I, P, P, P, P, P, LL, I, I, I, P, P, P, P]),
+    "dpm_dense_train_backward_rows": (I, [P, P, P, P, P, LL, I, I, P, P, P, P, P, P]),
+    "dpm_dense_train_backward_gemm": (I, [P, P, I, P, I, LL, I, I, P, P, P, P, P]),
 }
 
 

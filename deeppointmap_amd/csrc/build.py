@@ -50,6 +50,7 @@ SOURCES = {
     "offset_pairs.hip": [],
     "group_train.hip": [],
     "loop_head_train.hip": [],
+    "dense_train.hip": [],
 }
 
 

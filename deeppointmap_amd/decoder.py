@@ -13,8 +13,8 @@ Padding masks ((B,M) / (B,N) bool, True = padding) are the key_padding_mask of e
 (descriptor_attention.py:33-42), as in the reference; no inference call site of the reference passes any
 (odometry.py:108-110, mapping.py:153-155, loop_closure.py:170-174,239-242).
 
-All inference arithmetic runs in libdpm_hip.so (the training forward keeps its dense layers in torch under autograd, its
-attention cores and offset pairing in libdpm_hip.so); the module is re-entrant (no per-call state on self), so
+All inference arithmetic runs in libdpm_hip.so (the training forward keeps its dense layers in torch under autograd unless
+`set_train_dense("hip")` moves them to csrc/dense_train.hip, its attention cores and offset pairing in libdpm_hip.so); the module is re-entrant (no per-call state on self), so
 the three SLAM threads of the reference can share one instance (system/core.py:55-57).
 """
 from __future__ import annotations
@@ -32,6 +32,7 @@ from .params import ParamTree, decoder_shapes
 
 HEADS = 8
 TRAIN_STAGES = ("registration", "loop_detection")
+TRAIN_DENSE = ("torch", "hip")
 
 
 class Decoder(ParamTree):
@@ -66,6 +67,7 @@ class Decoder(ParamTree):
         # the backward rather than kept (sixteen (tokens, model_channel) tensors per layer: 256 MiB per layer at 16384 tokens)
         self.train_checkpoint_rows = 8192
         self.train_stage = "registration"   # what `.train()` trains: set_train_stage
+        self.train_dense = "torch"          # who evaluates the training forward's dense layers: set_train_dense
         self.eval()
 
     def __deepcopy__(self, memo):
@@ -321,6 +323,16 @@ class Decoder(ParamTree):
             self.train(True)
         return self
 
+    def set_train_dense(self, mode: str = "torch"):
+        """Who evaluates the dense layers (projections, LayerNorms, MLPs, heads) of the training forward: "torch" (the default:
+        F.linear / F.layer_norm / F.relu under autograd) or "hip" (ops.dense_linear_train / ops.dense_linear_ln_train,
+        csrc/dense_train.hip: exact fp32 products, every sum in one order, so a whole step gives identical bytes twice).  Kept in
+        `self.train_dense` across `.train()` / `.eval()` and copy.deepcopy.  Returns self.  ValueError for any other name."""
+        if mode not in TRAIN_DENSE:
+            raise ValueError(f"train_dense must be one of {TRAIN_DENSE}, got {mode!r}")
+        self.train_dense = mode
+        return self
+
     def _w(self, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
         """(weight as (out, in), bias) of a Linear / Conv1d(k=1) for F.linear"""
         w = self.p(key + ".weight")
@@ -332,6 +344,8 @@ class Decoder(ParamTree):
         are torch operations under autograd."""
         E, R1 = self.model_channel, B * M
         pre = f"descriptor_attention.{l}"
+        if self.train_dense == "hip":
+            return self._train_layer_hip(l, z, pos, B, M, N, ms, md)
         ln = lambda n, t: F.layer_norm(t, (E,), self.p(f"{pre}.{n}.weight"), self.p(f"{pre}.{n}.bias"))   # noqa: E731
         zp = z + pos
         qkv = F.linear(zp, self.p(pre + ".self_attn.in_proj_weight"), self.p(pre + ".self_attn.in_proj_bias"))
@@ -345,6 +359,31 @@ class Decoder(ParamTree):
         z2 = ln("norm2", z1 + F.linear(a, *self._w(pre + ".cross_attn.out_proj")))
         h = F.linear(F.relu(F.linear(z2, *self._w(pre + ".mlp.0"))), *self._w(pre + ".mlp.2"))
         return ln("norm3", h + z2)
+
+    def _train_layer_hip(self, l: int, z, pos, B: int, M: int, N: int, ms, md):
+        """`_train_layer` with every dense layer in csrc/dense_train.hip: the in-projections are plain products, each
+        out-projection carries its residual, LayerNorm and (norm1) the position embedding of the next block, mlp.2 carries the
+        residual and norm3"""
+        E, R1 = self.model_channel, B * M
+        pre = f"descriptor_attention.{l}"
+        nrm = lambda n: (self.p(f"{pre}.{n}.weight"), self.p(f"{pre}.{n}.bias"))   # noqa: E731
+        zp = z + pos
+        qkv = ops.dense_linear_train(zp, self.p(pre + ".self_attn.in_proj_weight"), self.p(pre + ".self_attn.in_proj_bias"))
+        a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, M, M, HEADS, ms),
+                       ops.attention_train(qkv[R1:, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, N, N, HEADS, md)])
+        z1 = ops.dense_linear_ln_train(a, *self._w(pre + ".self_attn.out_proj"), *nrm("norm1"), residual=zp, post=pos)
+        qkv = ops.dense_linear_train(z1, self.p(pre + ".cross_attn.in_proj_weight"), self.p(pre + ".cross_attn.in_proj_bias"))
+        a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, M, N, HEADS, md),
+                       ops.attention_train(qkv[R1:, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, N, M, HEADS, ms)])
+        z2 = ops.dense_linear_ln_train(a, *self._w(pre + ".cross_attn.out_proj"), *nrm("norm2"), residual=z1)
+        u = ops.dense_linear_train(z2, *self._w(pre + ".mlp.0"), act=ops.ACT_RELU)
+        return ops.dense_linear_ln_train(u, *self._w(pre + ".mlp.2"), *nrm("norm3"), residual=z2)
+
+    def _dense2(self, x, first: str, second: str):
+        """second(relu(first(x))): a two-layer head, by whoever `train_dense` names"""
+        if self.train_dense == "hip":
+            return ops.dense_linear_train(ops.dense_linear_train(x, *self._w(first), act=ops.ACT_RELU), *self._w(second))
+        return F.linear(F.relu(F.linear(x, *self._w(first))), *self._w(second))
 
     def forward(self, src_descriptor: torch.Tensor, dst_descriptor: torch.Tensor, src_padding_mask: torch.Tensor = None,
                 dst_padding_mask: torch.Tensor = None, gt_Rt: Tuple[torch.Tensor, torch.Tensor] = None):
@@ -364,7 +403,8 @@ class Decoder(ParamTree):
 
         The attention cores and the offset pairing run in csrc/attention_train.hip and csrc/offset_pairs.hip in both
         directions; no tensor of M x N elements exists in the forward, the saved state or the backward.  The dense layers
-        (projections, LayerNorm, MLPs, heads) are torch operations under autograd (DESIGN.md says what replacing them takes).
+        (projections, LayerNorm, MLPs, heads) are torch operations under autograd, or, after `set_train_dense("hip")`,
+        ops.dense_linear_train / ops.dense_linear_ln_train (csrc/dense_train.hip) in both directions.
         From `train_checkpoint_rows` stacked tokens (B * (M + N)) on, each attention layer is recomputed in the backward
         instead of keeping its sixteen activation tensors (torch.utils.checkpoint: the same kernels on the same inputs,
         identical bytes).  Raises AssertionError in eval mode and without gt_Rt, as the reference does; ValueError for
@@ -410,10 +450,11 @@ class Decoder(ParamTree):
             def split(t, ch):   # stacked rows -> the reference's (B,ch,M), (B,ch,N)
                 return t[:R1].view(B, M, ch).transpose(1, 2), t[R1:].view(B, N, ch).transpose(1, 2)
             # unified descriptor -> coarse pairing feature                                  (decoder.py:46-48)
-            coarse = F.linear(F.relu(F.linear(rows, *self._w("coarse_pairing_head.0"))), *self._w("coarse_pairing_head.2"))
+            hip = self.train_dense == "hip"
+            coarse = self._dense2(rows, "coarse_pairing_head.0", "coarse_pairing_head.2")
             # unified descriptor -> correlated descriptor                                   (decoder.py:145-162)
             pos = ops.posemb(xyz_rows, self._dimt(dev), E)
-            z = F.linear(rows, *self._w("projection"))
+            z = ops.dense_linear_train(rows, *self._w("projection")) if hip else F.linear(rows, *self._w("projection"))
             recompute = B * (M + N) >= self.train_checkpoint_rows
             for l in range(self.attention_layers):
                 if recompute:
@@ -421,7 +462,7 @@ class Decoder(ParamTree):
                 else:
                     z = self._train_layer(l, z, pos, B, M, N, ms, md)
             # correlated descriptors -> similarity feature                                  (decoder.py:56-58)
-            sim = F.linear(F.relu(F.linear(z, *self._w("similarity_head.0"))), *self._w("similarity_head.2"))
+            sim = self._dense2(z, "similarity_head.0", "similarity_head.2")
             # correlated descriptors -> offset                                              (decoder.py:60-86)
             src_gt = (gt_R @ xyz_s + gt_T).contiguous()
             pairs = ops.offset_pairs(src_gt, xyz_d.contiguous(), ps, pd, self.args.loss.eps_offset)
@@ -432,10 +473,17 @@ class Decoder(ParamTree):
             src_gt_off = gt_R[bi].transpose(1, 2) @ (dp - sp).unsqueeze(2)
             dst_gt_off = (sp - dp).unsqueeze(2)
             X = torch.cat([torch.cat([xs, xd], dim=1), torch.cat([xd, xs], dim=1)])        # (2K, 2E): src -> dst rows, then dst -> src
-            h = F.linear(F.relu(F.linear(F.relu(F.linear(X, *self._w("offset_head.mlp.0"))), *self._w("offset_head.mlp.2"))),
-                         *self._w("offset_head.mlp.4"))
-            h = F.relu(h + F.linear(X, *self._w("offset_head.downsample")))
-            off = F.linear(h, *self._w("offset_head.head")).unsqueeze(2)                   # (2K,3,1)
+            if hip:   # the skip connection is the residual of mlp.4, the ReLU after the sum its activation
+                h = ops.dense_linear_train(ops.dense_linear_train(X, *self._w("offset_head.mlp.0"), act=ops.ACT_RELU),
+                                           *self._w("offset_head.mlp.2"), act=ops.ACT_RELU)
+                h = ops.dense_linear_train(h, *self._w("offset_head.mlp.4"), act=ops.ACT_RELU,
+                                           residual=ops.dense_linear_train(X, *self._w("offset_head.downsample")))
+                off = ops.dense_linear_train(h, *self._w("offset_head.head")).unsqueeze(2)  # (2K,3,1)
+            else:
+                h = F.linear(F.relu(F.linear(F.relu(F.linear(X, *self._w("offset_head.mlp.0"))), *self._w("offset_head.mlp.2"))),
+                             *self._w("offset_head.mlp.4"))
+                h = F.relu(h + F.linear(X, *self._w("offset_head.downsample")))
+                off = F.linear(h, *self._w("offset_head.head")).unsqueeze(2)               # (2K,3,1)
             return [*split(sim, E), *split(coarse, C), off[:K] - src_gt_off, off[K:] - dst_gt_off]
 
     @staticmethod

@@ -6,7 +6,8 @@ call contract: `encoder(points (B,C>=3,N) f32, points_padding (B,N) bool) ->
 the CPU (ScanPack keeps CPU tensors, system/modules/pose_graph.py:43-45); they are staged to the
 module's GPU.  All inference arithmetic runs in libdpm_hip.so; there is no torch fallback.  In `.train()` mode the same
 call is the reference's training forward: `fea` carries the autograd graph, the grouping layers run in csrc/group_train.hip in
-both directions and the dense layers are torch operations under autograd (`Encoder.train`, `Encoder._forward_train`).
+both directions and the dense layers are torch operations under autograd or, after `set_train_dense("hip")`, the kernels of
+csrc/dense_train.hip (`Encoder.train`, `Encoder._forward_train`).
 
 Internally everything is point-major fp32 with a per-frame valid length (valid points lead,
 exactly what the reference's FPS assumes, utils.py:255).
@@ -59,6 +60,7 @@ class Encoder(ParamTree):
         self.train_checkpoint_rows = 1 << 20
         self._was_trained = False
         self.train_stage = "registration"   # what `.train()` trains: set_train_stage
+        self.train_dense = "torch"          # who evaluates the training forward's dense layers: set_train_dense
         self.eval()
 
     # -- helpers -------------------------------------------------------------------------------
@@ -338,13 +340,30 @@ class Encoder(ParamTree):
             self.train(True)
         return self
 
+    def set_train_dense(self, mode: str = "torch"):
+        """Who evaluates the dense layers of the training forward (point_mlp0, the W_f projections, pw_conv and the upsampler MLPs
+        with their LayerNorms): "torch" (the default: F.linear / F.layer_norm / F.relu under autograd) or "hip"
+        (ops.dense_linear_train / ops.dense_linear_ln_train, csrc/dense_train.hip).  Kept in `self.train_dense` across `.train()`
+        / `.eval()` and copy.deepcopy.  Returns self.  ValueError for any other name."""
+        if mode not in ("torch", "hip"):
+            raise ValueError(f"train_dense must be 'torch' or 'hip', got {mode!r}")
+        self.train_dense = mode
+        return self
+
+    def _linear_train(self, x, W, bias):
+        return ops.dense_linear_train(x, W, bias) if self.train_dense == "hip" else F.linear(x, W, bias)
+
     def _w(self, key: str):
         """(weight as (out, in), bias) of a Conv1d / Conv2d(k=1) for F.linear"""
         w = self.p(key + ".weight")
         return w.view(w.shape[0], w.shape[1]), self.p(key + ".bias")
 
     def _mlp_ln_train(self, x, conv: str, ln: str, post=None):
-        """relu(LN(conv x) [+ post]) as torch operations under autograd (what ops.linear_layernorm evaluates)"""
+        """relu(LN(conv x) [+ post]) as torch operations under autograd (what ops.linear_layernorm evaluates), or as ONE
+        ops.dense_linear_ln_train (train_dense "hip")"""
+        if self.train_dense == "hip":
+            return ops.dense_linear_ln_train(x, *self._w(conv), self.p(ln + ".weight"), self.p(ln + ".bias"), post=post,
+                                             act=ops.ACT_RELU)
         y = F.layer_norm(F.linear(x, *self._w(conv)), (self.p(ln + ".weight").shape[0],), self.p(ln + ".weight"),
                          self.p(ln + ".bias"))
         return F.relu(y if post is None else y + post)
@@ -357,7 +376,7 @@ class Encoder(ParamTree):
             raise ValueError(f"Encoder.forward (train mode): layer {prefix} has width {W.shape[0]} and {idx.shape[2]} "
                              f"neighbours; the training kernels cover widths {ops.GROUP_TRAIN_COUT} and neighbour counts "
                              f"{ops.GROUP_TRAIN_K}")
-        P = F.linear(fea, W[:, :Cin], bias)
+        P = self._linear_train(fea, W[:, :Cin], bias)
         slots = None if keep is None else []
         out = ops.group_train(P, xyz, centers, idx, W[:, Cin:].contiguous(), self.p(prefix + ".1.ln.weight"),
                               self.p(prefix + ".1.ln.bias"), radius, layer=prefix, keep_slots=slots)
@@ -420,7 +439,7 @@ class Encoder(ParamTree):
         with torch.enable_grad(), torch.cuda.device(dev):
             pts, xyz, lengths = samp["pts"], samp["xyz"], samp["lengths"]
             x0 = xyz if self.in_channel == 3 else pts[:, :self.in_channel].transpose(1, 2).contiguous()
-            fea = F.linear(x0, *self._w("point_mlp0"))
+            fea = self._linear_train(x0, *self._w("point_mlp0"))
             recompute = keep is None and xyz.shape[0] * xyz.shape[1] >= self.train_checkpoint_rows
             levels = [(xyz, fea, lengths)]
             for i in range(len(enc.npoint)):

@@ -1478,3 +1478,182 @@ def loop_bce(pred: torch.Tensor, target: torch.Tensor):
         raise ValueError(f"pred must be (B,) with B >= 1, got {tuple(pred.shape)}")
     _shape(target, pred.shape, "target")
     return _LoopBce.apply(pred, target)
+
+
+# ---- the dense layers for training (csrc/dense_train.hip) ----------------------------------------------------------------------
+
+def _dense_check(t, shape, name: str) -> None:
+    """shape (None = any leading dimensions, then the given ones) and dtype -> ValueError"""
+    ok = isinstance(t, torch.Tensor) and t.dim() >= len(shape) and all(
+        w is None or w == g for w, g in zip(shape, t.shape[t.dim() - len(shape):])) and (shape[0] is None or t.dim() == len(shape))
+    if not ok:
+        want = ", ".join("..." if w is None else str(w) for w in shape)
+        raise ValueError(f"{name}: expected ({want}), got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: expected torch.float32, got {t.dtype}")
+
+
+def _dense_rows(t: torch.Tensor, cols: int, name: str) -> torch.Tensor:
+    """(..., cols) fp32 on the GPU -> a (rows, cols) view with last-dimension stride 1 (a copy only where no such view exists)"""
+    if not t.is_cuda:
+        raise _lib.DpmError(f"{name}: expected a tensor on the GPU, got {t.device} (no CPU fallback)")
+    t = t.detach().reshape(-1, cols)
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < cols):
+        t = t.contiguous()
+    return t
+
+
+def _dense_ld(t: torch.Tensor) -> int:
+    return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
+
+
+def _dense_args(x, W, bias, residual, gamma, beta, post, act: int, what: str):
+    if act not in (ACT_NONE, ACT_RELU):
+        raise ValueError(f"{what}: act must be ACT_NONE or ACT_RELU, got {act}")
+    if not isinstance(W, torch.Tensor) or W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+        raise ValueError(f"{what}: W must be (Cout >= 1, Cin >= 1), got {tuple(W.shape) if isinstance(W, torch.Tensor) else type(W)}")
+    Cout, Cin = W.shape
+    _dense_check(W, (Cout, Cin), "W")
+    _dense_check(x, (None, Cin), "x")
+    lead = tuple(x.shape[:-1])
+    for t, name in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _dense_check(t, (Cout,), name)
+    for t, name in ((residual, "residual"), (post, "post")):
+        if t is not None:
+            _dense_check(t, lead + (Cout,), name)
+    for t, name in ((W, "W"), (bias, "bias"), (gamma, "gamma"), (beta, "beta"), (residual, "residual"), (post, "post")):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{what}: x on {x.device}, {name} on {t.device}")
+    vec = lambda t, name: None if t is None else _dense_rows(t, Cout, name).reshape(Cout).contiguous()   # noqa: E731
+    rows = lambda t, name: None if t is None else _dense_rows(t, Cout, name).contiguous()                # noqa: E731
+    return (_dense_rows(x, Cin, "x"), _dense_rows(W, Cin, "W"), vec(bias, "bias"), rows(residual, "residual"), vec(gamma, "gamma"),
+            vec(beta, "beta"), rows(post, "post"), lead)
+
+
+def _dense_ws(lib, R: int, Cin: int, Cout: int, dev) -> torch.Tensor:
+    return torch.empty(lib.dpm_dense_train_workspace_bytes(R, Cin, Cout), device=dev, dtype=torch.uint8)
+
+
+def _dense_backward_gemm(dh, x, W, need_x: bool, need_W: bool, need_b: bool):
+    """dh (R, Cout) contiguous -> (dx (R, Cin) | None, dW (Cout, Cin) | None, dbias (Cout) | None)"""
+    R, (Cout, Cin) = x.shape[0], W.shape
+    lib, dev = _lib.load(), dh.device
+    dx = torch.empty(R, Cin, device=dev, dtype=torch.float32) if need_x else None
+    dW = torch.empty(Cout, Cin, device=dev, dtype=torch.float32) if (need_W or need_b) else None
+    db = torch.empty(Cout, device=dev, dtype=torch.float32) if need_b else None
+    if dx is not None or dW is not None:
+        ws = _dense_ws(lib, R, Cin, Cout, dev) if dW is not None else None
+        _lib.check(lib.dpm_dense_train_backward_gemm(_ptr(dh), _ptr(x), _dense_ld(x), _ptr(W), _dense_ld(W), R, Cin, Cout, _ptr(dx),
+                                                     _ptr(dW), _ptr(db), _ptr(ws), _stream(dh)), "dpm_dense_train_backward_gemm")
+    return dx, (dW if need_W else None), db
+
+
+def _dense_forward(x, W, bias, gamma, beta, residual, post, act: int):
+    """-> (out, h, stats, (the row views of x and W and the contiguous gamma the kernels read))"""
+    normed = gamma is not None
+    if normed != (beta is not None) or (post is not None and not normed):
+        raise ValueError("dense_train_forward: gamma and beta come together, post needs them")
+    xv, Wv, bv, rv, gv, bev, pv, lead = _dense_args(x, W, bias, residual, gamma, beta, post, act, "dense_train_forward")
+    R, (Cout, Cin) = xv.shape[0], Wv.shape
+    dev = xv.device
+    out = torch.empty(R, Cout, device=dev, dtype=torch.float32)
+    h = torch.empty(R, Cout, device=dev, dtype=torch.float32) if normed else None
+    stats = torch.empty(R, 2, device=dev, dtype=torch.float32) if normed else None
+    _lib.check(_lib.load().dpm_dense_train_forward(_ptr(xv), _dense_ld(xv), _ptr(Wv), _dense_ld(Wv), _ptr(bv), _ptr(rv), _ptr(gv),
+                                                   _ptr(bev), _ptr(pv), R, Cin, Cout, act, _ptr(out), _ptr(h), _ptr(stats),
+                                                   _stream(xv)), "dpm_dense_train_forward")
+    return out.view(lead + (Cout,)), h, stats, (xv, Wv, gv)
+
+
+def dense_train_forward(x, W, bias=None, gamma=None, beta=None, residual=None, post=None, act: int = ACT_NONE):
+    """The forward of both forms without a graph -> (out (..., Cout), h (R, Cout), stats (R, 2)); normed when gamma is given, else
+    h and stats are None.  h = x W^T + bias + residual: the same bits in both forms.  stats = (mean, rstd) per row."""
+    return _dense_forward(x, W, bias, gamma, beta, residual, post, act)[:3]
+
+
+class _DenseLinear(torch.autograd.Function):
+    """Saved for the backward: x, W and, with ReLU, the output (its sign is the mask)."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, residual, act):
+        out, _, _, (xv, Wv, _) = _dense_forward(x, W, bias, None, None, residual, None, act)
+        ctx.save_for_backward(xv, Wv, out.view(xv.shape[0], Wv.shape[0]) if act == ACT_RELU else None)
+        ctx.cfg = (act, tuple(x.shape), tuple(W.shape), tuple(out.shape))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        xv, Wv, out = ctx.saved_tensors
+        act, xshape, wshape, oshape = ctx.cfg
+        need_x, need_W, need_b, need_r = ctx.needs_input_grad[:4]
+        R, Cout = xv.shape[0], Wv.shape[0]
+        g = dy.reshape(R, Cout).contiguous()
+        if act == ACT_RELU:
+            gm = torch.empty_like(g)
+            _lib.check(_lib.load().dpm_dense_train_backward_rows(_ptr(g), _ptr(out), None, None, None, R, Cout, act, _ptr(gm), None, None,
+                                                                 None, None, _stream(g)), "dpm_dense_train_backward_rows")
+            g = gm
+        dx, dW, db = _dense_backward_gemm(g, xv, Wv, need_x, need_W, need_b)
+        return (None if dx is None else dx.view(xshape), None if dW is None else dW.view(wshape), db,
+                g.view(oshape) if need_r else None, None)
+
+
+def dense_linear_train(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                       act: int = ACT_NONE) -> torch.Tensor:
+    """act(x W^T + bias + residual) with a backward, both in csrc/dense_train.hip: x (..., Cin) fp32 (a column slice of a wider
+    buffer is used in place), W (Cout, Cin) (a column slice likewise: any row stride, any alignment), bias (Cout), residual
+    (..., Cout), act ACT_NONE or ACT_RELU -> (..., Cout).  Differentiable with respect to x, W, bias and residual; each gradient is
+    computed only when it is needed.  Exact fp32 products, every sum in one order: two runs give identical bytes.  Operands whose
+    last-dimension stride is not 1 are copied.  ValueError for shape or dtype mismatches."""
+    return _DenseLinear.apply(x, W, bias, residual, act)
+
+
+class _DenseLinearLN(torch.autograd.Function):
+    """Saved for the backward: x, W, gamma, the pre-norm rows h, (mean, rstd) per row and, with ReLU, the output."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, gamma, beta, residual, post, act):
+        if gamma is None or beta is None:
+            raise ValueError("dense_linear_ln_train: gamma and beta are required")
+        out, h, stats, (xv, Wv, gv) = _dense_forward(x, W, bias, gamma, beta, residual, post, act)
+        ctx.save_for_backward(xv, Wv, gv, h, stats, out.view(xv.shape[0], Wv.shape[0]) if act == ACT_RELU else None)
+        ctx.cfg = (act, tuple(x.shape), tuple(W.shape), tuple(out.shape))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        xv, Wv, gv, h, stats, out = ctx.saved_tensors
+        act, xshape, wshape, oshape = ctx.cfg
+        need_x, need_W, need_b, need_g, need_be, need_r, need_p = ctx.needs_input_grad[:7]
+        R, (Cout, Cin) = xv.shape[0], Wv.shape
+        lib, dev = _lib.load(), xv.device
+        dy = dy.reshape(R, Cout).contiguous()
+        if act == ACT_NONE and need_p:
+            g = None                      # d post is dy itself
+        else:
+            g = torch.empty_like(dy) if need_p else None
+        dh = torch.empty_like(dy)
+        affine = need_g or need_be
+        dgamma = torch.empty(Cout, device=dev, dtype=torch.float32) if affine else None
+        dbeta = torch.empty(Cout, device=dev, dtype=torch.float32) if affine else None
+        ws = _dense_ws(lib, R, Cin, Cout, dev) if affine else None
+        _lib.check(lib.dpm_dense_train_backward_rows(_ptr(dy), _ptr(out), _ptr(h), _ptr(stats), _ptr(gv), R, Cout, act, _ptr(g), _ptr(dh),
+                                                     _ptr(dgamma), _ptr(dbeta), _ptr(ws), _stream(dy)), "dpm_dense_train_backward_rows")
+        dx, dW, db = _dense_backward_gemm(dh, xv, Wv, need_x, need_W, need_b)
+        dpost = None if not need_p else (dy if g is None else g).view(oshape)
+        return (None if dx is None else dx.view(xshape), None if dW is None else dW.view(wshape), db,
+                dgamma if need_g else None, dbeta if need_be else None, dh.view(oshape) if need_r else None, dpost, None)
+
+
+def dense_linear_ln_train(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
+                          residual: Optional[torch.Tensor] = None, post: Optional[torch.Tensor] = None,
+                          act: int = ACT_NONE) -> torch.Tensor:
+    """act(LN(x W^T + bias + residual) * gamma + beta + post) (eps 1e-5, biased variance) with a backward, both in
+    csrc/dense_train.hip; operands as for dense_linear_train, gamma, beta (Cout), post (..., Cout).  Differentiable with respect to
+    x, W, bias, gamma, beta, residual and post; each gradient is computed only when it is needed.  Widths 32, 64, 128, 256 normalise
+    in the product kernel's epilogue, other widths in a row kernel after it; the pre-norm rows are the bits dense_linear_train gives
+    for the same operands either way.  Two runs give identical bytes.  ValueError for shape or dtype mismatches."""
+    return _DenseLinearLN.apply(x, W, bias, gamma, beta, residual, post, act)

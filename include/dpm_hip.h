@@ -645,6 +645,37 @@ int dpm_loop_pool_backward(const float *x, int ldx, const float *W1, const float
 int dpm_loop_bce_forward(const float *pred, const float *target, int B, float *loss, float *stats, float *dpred_unit,
                          dpm_stream_t stream);
 
+/* The dense layers for training (csrc/dense_train.hip): build_mlp's Conv -> LayerNorm -> ReLU (network/encoder/utils.py:358-413),
+ * the projections, LayerNorms and MLP of DescriptorAttentionLayer (network/decoder/descriptor_attention.py:16-48) and the heads
+ * (network/decoder/heads.py), replacing F.linear / F.layer_norm / F.relu under autograd.  One primitive in two forms:
+ *   plain  (gamma NULL):  out = act(x W^T + bias + residual)
+ *   normed (gamma given): h = x W^T + bias + residual;  out = act(LN(h) * gamma + beta + post)   (eps 1e-5, biased variance)
+ * x (R, Cin) rows ldx >= Cin floats apart, W (Cout, Cin) rows ldw >= Cin apart (any alignment: rows that are not 16-byte aligned
+ * are read with scalar loads), bias (Cout) or NULL, residual / post (R, Cout) contiguous or NULL, act DPM_ACT_NONE or
+ * DPM_ACT_RELU; out, h (R, Cout) and stats (R, 2) = (mean, rstd) per row are contiguous.  Any R >= 0, Cin, Cout >= 1.
+ * forward: writes out and, normed, h and stats -- all the backward needs besides x, W and gamma (the ReLU mask is out > 0).
+ *   Every h element is one k-ascending fp32 accumulator chain from zero, + bias, + residual: the same bits in both forms.
+ * backward_rows: from dy (R, Cout) -> g = dy . [out > 0] (d post; for the plain form also d residual and the dh of the GEMMs; g
+ *   may be NULL in the normed form), and normed: dh = rstd (dn - mean(dn) - xhat mean(dn xhat)) with dn = gamma g, xhat =
+ *   (h - mean) rstd (d residual), dgamma = sum_rows g xhat, dbeta = sum_rows g (both or neither; they need workspace).
+ *   out may be NULL for DPM_ACT_NONE.
+ * backward_gemm: from dh -> dx (R, Cin) = dh W, dW (Cout, Cin) = dh^T x, dbias (Cout) = column sums of dh, all contiguous;
+ *   each may be NULL and is skipped then (dbias needs dW).  The rows are cut into at most 32 slices of 64-row tiles whose
+ *   partial dW are added in slice order.
+ * R = 0 launches no kernel and zeroes dW, dbias, dgamma, dbeta.  workspace: dpm_dense_train_workspace_bytes(R, Cin, Cout) for
+ * either backward call (host function: at most 32 (Cout Cin + Cout) + 256 x 2 Cout floats, constant in R beyond 32 tiles of 64 rows;
+ * 0 for an invalid shape).
+ * All products in fp32 on the matrix cores, no floating-point atomics, every sum in one order: two runs give identical bytes. */
+size_t dpm_dense_train_workspace_bytes(long long R, int Cin, int Cout);
+int dpm_dense_train_forward(const float *x, int ldx, const float *W, int ldw, const float *bias, const float *residual,
+                            const float *gamma, const float *beta, const float *post, long long R, int Cin, int Cout, int act,
+                            float *out, float *h, float *stats, dpm_stream_t stream);
+int dpm_dense_train_backward_rows(const float *dy, const float *out, const float *h, const float *stats, const float *gamma,
+                                  long long R, int Cout, int act, float *g, float *dh, float *dgamma, float *dbeta,
+                                  void *workspace, dpm_stream_t stream);
+int dpm_dense_train_backward_gemm(const float *dh, const float *x, int ldx, const float *W, int ldw, long long R, int Cin,
+                                  int Cout, float *dx, float *dW, float *dbias, void *workspace, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
