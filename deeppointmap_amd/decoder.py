@@ -31,8 +31,6 @@ from . import knobs, ops
 from .params import ParamTree, decoder_shapes
 
 HEADS = 8
-TRAIN_STAGES = ("registration", "loop_detection")
-TRAIN_DENSE = ("torch", "hip")
 
 
 class Decoder(ParamTree):
@@ -66,8 +64,6 @@ class Decoder(ParamTree):
         # training forward: from this many stacked tokens (B * (M + N)) on, an attention layer's activations are recomputed in
         # the backward rather than kept (sixteen (tokens, model_channel) tensors per layer: 256 MiB per layer at 16384 tokens)
         self.train_checkpoint_rows = 8192
-        self.train_stage = "registration"   # what `.train()` trains: set_train_stage
-        self.train_dense = "torch"          # who evaluates the training forward's dense layers: set_train_dense
         self.eval()
 
     def __deepcopy__(self, memo):
@@ -305,85 +301,37 @@ class Decoder(ParamTree):
         key on: inference after a step reads the new weights."""
         was = self.training
         super().train(mode)
-        loop = getattr(self, "train_stage", "registration") == "loop_detection"
+        loop = self.train_stage == "loop_detection"
         for name, p in self._flat.items():
             p.requires_grad_(bool(mode) and (("loop" in name) == loop))
         if was and not mode:
             self.invalidate_caches()
         return self
 
-    def set_train_stage(self, stage: str = "registration"):
-        """Which of the reference's two training stages `.train()` selects (pipeline/modules/trainer.py runs them in turn):
-        "registration" or "loop_detection".  Kept in `self.train_stage` across `.train()` / `.eval()`; applied at once if the
-        module is training.  Returns self.  ValueError for any other name."""
-        if stage not in TRAIN_STAGES:
-            raise ValueError(f"train stage must be one of {TRAIN_STAGES}, got {stage!r}")
-        self.train_stage = stage
-        if self.training:
-            self.train(True)
-        return self
-
-    def set_train_dense(self, mode: str = "torch"):
-        """Who evaluates the dense layers (projections, LayerNorms, MLPs, heads) of the training forward: "torch" (the default:
-        F.linear / F.layer_norm / F.relu under autograd) or "hip" (ops.dense_linear_train / ops.dense_linear_ln_train,
-        csrc/dense_train.hip: exact fp32 products, every sum in one order, so a whole step gives identical bytes twice).  Kept in
-        `self.train_dense` across `.train()` / `.eval()` and copy.deepcopy.  Returns self.  ValueError for any other name."""
-        if mode not in TRAIN_DENSE:
-            raise ValueError(f"train_dense must be one of {TRAIN_DENSE}, got {mode!r}")
-        self.train_dense = mode
-        return self
-
-    def _w(self, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(weight as (out, in), bias) of a Linear / Conv1d(k=1) for F.linear"""
-        w = self.p(key + ".weight")
-        return w.view(w.shape[0], w.shape[1]), self.p(key + ".bias")
-
     def _train_layer(self, l: int, z, pos, B: int, M: int, N: int, ms, md):
         """DescriptorAttentionLayer.forward (descriptor_attention.py:24-52) over the stacked rows [B*M source ; B*N target]:
-        the four attention cores are ops.attention_train (HIP, forward and backward); projections, LayerNorm and the MLP
-        are torch operations under autograd."""
-        E, R1 = self.model_channel, B * M
-        pre = f"descriptor_attention.{l}"
-        if self.train_dense == "hip":
-            return self._train_layer_hip(l, z, pos, B, M, N, ms, md)
-        ln = lambda n, t: F.layer_norm(t, (E,), self.p(f"{pre}.{n}.weight"), self.p(f"{pre}.{n}.bias"))   # noqa: E731
-        zp = z + pos
-        qkv = F.linear(zp, self.p(pre + ".self_attn.in_proj_weight"), self.p(pre + ".self_attn.in_proj_bias"))
-        a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, M, M, HEADS, ms),
-                       ops.attention_train(qkv[R1:, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, N, N, HEADS, md)])
-        z1 = ln("norm1", zp + F.linear(a, *self._w(pre + ".self_attn.out_proj"))) + pos
-        qkv = F.linear(z1, self.p(pre + ".cross_attn.in_proj_weight"), self.p(pre + ".cross_attn.in_proj_bias"))
-        # both directions read the pre-update tensors (descriptor_attention.py:41-44)
-        a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, M, N, HEADS, md),
-                       ops.attention_train(qkv[R1:, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, N, M, HEADS, ms)])
-        z2 = ln("norm2", z1 + F.linear(a, *self._w(pre + ".cross_attn.out_proj")))
-        h = F.linear(F.relu(F.linear(z2, *self._w(pre + ".mlp.0"))), *self._w(pre + ".mlp.2"))
-        return ln("norm3", h + z2)
-
-    def _train_layer_hip(self, l: int, z, pos, B: int, M: int, N: int, ms, md):
-        """`_train_layer` with every dense layer in csrc/dense_train.hip: the in-projections are plain products, each
-        out-projection carries its residual, LayerNorm and (norm1) the position embedding of the next block, mlp.2 carries the
-        residual and norm3"""
+        the four attention cores are ops.attention_train (HIP, forward and backward); the dense layers go through `_dense` /
+        `_dense_ln`: the in-projections are plain products, each out-projection carries its residual, LayerNorm and (norm1) the
+        position embedding of the next block, mlp.2 carries the residual and norm3."""
         E, R1 = self.model_channel, B * M
         pre = f"descriptor_attention.{l}"
         nrm = lambda n: (self.p(f"{pre}.{n}.weight"), self.p(f"{pre}.{n}.bias"))   # noqa: E731
         zp = z + pos
-        qkv = ops.dense_linear_train(zp, self.p(pre + ".self_attn.in_proj_weight"), self.p(pre + ".self_attn.in_proj_bias"))
+        qkv = self._dense(zp, self.p(pre + ".self_attn.in_proj_weight"), self.p(pre + ".self_attn.in_proj_bias"))
         a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, M, M, HEADS, ms),
                        ops.attention_train(qkv[R1:, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, N, N, HEADS, md)])
-        z1 = ops.dense_linear_ln_train(a, *self._w(pre + ".self_attn.out_proj"), *nrm("norm1"), residual=zp, post=pos)
-        qkv = ops.dense_linear_train(z1, self.p(pre + ".cross_attn.in_proj_weight"), self.p(pre + ".cross_attn.in_proj_bias"))
+        z1 = self._dense_ln(a, *self._w(pre + ".self_attn.out_proj"), *nrm("norm1"), residual=zp, post=pos)
+        qkv = self._dense(z1, self.p(pre + ".cross_attn.in_proj_weight"), self.p(pre + ".cross_attn.in_proj_bias"))
+        # both directions read the pre-update tensors (descriptor_attention.py:41-44)
         a = torch.cat([ops.attention_train(qkv[:R1, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, M, N, HEADS, md),
                        ops.attention_train(qkv[R1:, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, N, M, HEADS, ms)])
-        z2 = ops.dense_linear_ln_train(a, *self._w(pre + ".cross_attn.out_proj"), *nrm("norm2"), residual=z1)
-        u = ops.dense_linear_train(z2, *self._w(pre + ".mlp.0"), act=ops.ACT_RELU)
-        return ops.dense_linear_ln_train(u, *self._w(pre + ".mlp.2"), *nrm("norm3"), residual=z2)
+        z2 = self._dense_ln(a, *self._w(pre + ".cross_attn.out_proj"), *nrm("norm2"), residual=z1)
+        u = self._dense(z2, *self._w(pre + ".mlp.0"), act=ops.ACT_RELU)
+        return self._dense_ln(u, *self._w(pre + ".mlp.2"), *nrm("norm3"), residual=z2)
 
     def _dense2(self, x, first: str, second: str):
-        """second(relu(first(x))): a two-layer head, by whoever `train_dense` names"""
-        if self.train_dense == "hip":
-            return ops.dense_linear_train(ops.dense_linear_train(x, *self._w(first), act=ops.ACT_RELU), *self._w(second))
-        return F.linear(F.relu(F.linear(x, *self._w(first))), *self._w(second))
+        """second(relu(first(x))): a two-layer head"""
+        return self._dense(self._dense(x, *self._w(first), act=ops.ACT_RELU), *self._w(second))
 
     def forward(self, src_descriptor: torch.Tensor, dst_descriptor: torch.Tensor, src_padding_mask: torch.Tensor = None,
                 dst_padding_mask: torch.Tensor = None, gt_Rt: Tuple[torch.Tensor, torch.Tensor] = None):
@@ -411,9 +359,7 @@ class Decoder(ParamTree):
         descriptors, masks or poses of the wrong shape and for a head width other than 32."""
         assert self.training, "forward is not available during inference!"
         assert gt_Rt is not None, "gt_Rt must be provided during training"
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        dev = self._require_gpu()
         C, E = self.in_channel, self.model_channel
         if E // HEADS != ops.ATTENTION_TRAIN_HEAD_DIM or E % HEADS:
             raise ValueError(f"Decoder.forward: model_channel {E} gives heads of width {E / HEADS:g}; the training attention "
@@ -450,11 +396,10 @@ class Decoder(ParamTree):
             def split(t, ch):   # stacked rows -> the reference's (B,ch,M), (B,ch,N)
                 return t[:R1].view(B, M, ch).transpose(1, 2), t[R1:].view(B, N, ch).transpose(1, 2)
             # unified descriptor -> coarse pairing feature                                  (decoder.py:46-48)
-            hip = self.train_dense == "hip"
             coarse = self._dense2(rows, "coarse_pairing_head.0", "coarse_pairing_head.2")
             # unified descriptor -> correlated descriptor                                   (decoder.py:145-162)
             pos = ops.posemb(xyz_rows, self._dimt(dev), E)
-            z = ops.dense_linear_train(rows, *self._w("projection")) if hip else F.linear(rows, *self._w("projection"))
+            z = self._dense(rows, *self._w("projection"))
             recompute = B * (M + N) >= self.train_checkpoint_rows
             for l in range(self.attention_layers):
                 if recompute:
@@ -473,17 +418,12 @@ class Decoder(ParamTree):
             src_gt_off = gt_R[bi].transpose(1, 2) @ (dp - sp).unsqueeze(2)
             dst_gt_off = (sp - dp).unsqueeze(2)
             X = torch.cat([torch.cat([xs, xd], dim=1), torch.cat([xd, xs], dim=1)])        # (2K, 2E): src -> dst rows, then dst -> src
-            if hip:   # the skip connection is the residual of mlp.4, the ReLU after the sum its activation
-                h = ops.dense_linear_train(ops.dense_linear_train(X, *self._w("offset_head.mlp.0"), act=ops.ACT_RELU),
-                                           *self._w("offset_head.mlp.2"), act=ops.ACT_RELU)
-                h = ops.dense_linear_train(h, *self._w("offset_head.mlp.4"), act=ops.ACT_RELU,
-                                           residual=ops.dense_linear_train(X, *self._w("offset_head.downsample")))
-                off = ops.dense_linear_train(h, *self._w("offset_head.head")).unsqueeze(2)  # (2K,3,1)
-            else:
-                h = F.linear(F.relu(F.linear(F.relu(F.linear(X, *self._w("offset_head.mlp.0"))), *self._w("offset_head.mlp.2"))),
-                             *self._w("offset_head.mlp.4"))
-                h = F.relu(h + F.linear(X, *self._w("offset_head.downsample")))
-                off = F.linear(h, *self._w("offset_head.head")).unsqueeze(2)               # (2K,3,1)
+            # the skip connection is the residual of mlp.4, the ReLU after the sum its activation
+            h = self._dense(self._dense(X, *self._w("offset_head.mlp.0"), act=ops.ACT_RELU),
+                            *self._w("offset_head.mlp.2"), act=ops.ACT_RELU)
+            h = self._dense(h, *self._w("offset_head.mlp.4"), act=ops.ACT_RELU,
+                            residual=self._dense(X, *self._w("offset_head.downsample")))
+            off = self._dense(h, *self._w("offset_head.head")).unsqueeze(2)                # (2K,3,1)
             return [*split(sim, E), *split(coarse, C), off[:K] - src_gt_off, off[K:] - dst_gt_off]
 
     @staticmethod
@@ -559,9 +499,7 @@ class Decoder(ParamTree):
         """B independent pairs in one pass (not in the reference API; used by the frame-sharded hot path).
         -> result (B, 20+2k) on the device: per pair R(9) T(3) rmse n_corr n_inlier iters conf30 ..., then the
         inlier confidences.  No host synchronisation."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        dev = self._require_gpu()
         with torch.cuda.device(dev):
             return self._register(src_descriptor, dst_descriptor, num_sample, header_out)
 
@@ -573,9 +511,7 @@ class Decoder(ParamTree):
         (src_frame[p], dst_frame[p]) (int32 device tensors).  The per-frame part of the decoder (projection, position
         embedding, first self-attention block) runs once per frame instead of once per pair side; results are
         bit-identical to registration_forward_batch(descriptors[src_frame], descriptors[dst_frame])."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        dev = self._require_gpu()
         with torch.cuda.device(dev):
             pairs = (src_frame, dst_frame) if order is None else (src_frame, dst_frame, order)
             return self._register(descriptors, None, num_sample, header_out, pairs=pairs)
@@ -644,9 +580,7 @@ class Decoder(ParamTree):
         like the others (they are not captured again behind the caller's back: call this again).  `copies` > 1 captures that many
         instances per shape (each with its own static buffers): threads that ask for the same shape at the same time then replay
         different instances side by side on the device instead of queueing behind one."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        dev = self._require_gpu()
         if threading.active_count() > 1:
             raise RuntimeError("capture_registration_graphs must run before the process starts its worker threads")
         n = 0
@@ -688,9 +622,7 @@ class Decoder(ParamTree):
     def registration_forward(self, src_descriptor: torch.Tensor, dst_descriptor: torch.Tensor,
                              src_padding_mask=None, dst_padding_mask=None,
                              num_sample: Union[int, float] = 0.5, trace: dict = None, header_out: torch.Tensor = None):
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        dev = self._require_gpu()
         batch = not (src_descriptor.ndim == 2 and dst_descriptor.ndim == 2)
         if not batch:
             src_descriptor, dst_descriptor = src_descriptor.unsqueeze(0), dst_descriptor.unsqueeze(0)
@@ -747,9 +679,7 @@ class Decoder(ParamTree):
         trunk is frozen there and runs on the inference kernels without a graph; the head's token-sized layer is
         ops.loop_pool (csrc/loop_head_train.hip, forward and backward), its (C, 2 E)-sized layers are torch operations under
         autograd.  The descriptors get NO gradient in that mode: nothing upstream of the head is trainable in this stage."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Decoder runs on the GPU only (there is no CPU fallback)")
+        dev = self._require_gpu()
         if src_descriptor.ndim == 2 and dst_descriptor.ndim == 2:
             src_descriptor, dst_descriptor = src_descriptor.unsqueeze(0), dst_descriptor.unsqueeze(0)
         E = self.model_channel

@@ -17,7 +17,6 @@ from __future__ import annotations
 from typing import List, Optional
 
 import torch
-import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
 from . import ops
@@ -59,8 +58,6 @@ class Encoder(ParamTree):
         # at the shipped sizes, so the threshold sits where the activations reach about 1.5 GiB
         self.train_checkpoint_rows = 1 << 20
         self._was_trained = False
-        self.train_stage = "registration"   # what `.train()` trains: set_train_stage
-        self.train_dense = "torch"          # who evaluates the training forward's dense layers: set_train_dense
         self.eval()
 
     # -- helpers -------------------------------------------------------------------------------
@@ -119,10 +116,7 @@ class Encoder(ParamTree):
         Pass the result to forward(..., presampled=...).  `levels` limits the pass to the first FPS levels (the
         remaining, much shorter ones then run inside forward) -- a knob for balancing pipeline stages.
         `sampled0` = (idx, new_xyz, new_lengths) of the first level when the caller sampled it already."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Encoder runs on the GPU only: call .to('cuda') first "
-                               "(there is no CPU fallback)")
+        dev = self._require_gpu()
         with torch.cuda.device(dev):
             pts = points.to(device=dev, dtype=torch.float32).contiguous()
             pad = points_padding.to(device=dev).contiguous()
@@ -200,10 +194,7 @@ class Encoder(ParamTree):
         In `.train()` mode: the training forward (`_forward_train`), `fea` attached to the autograd graph; the extra arguments
         are inference-only and raise ValueError there.  At train stage "loop_detection" (`set_train_stage`) the encoder is
         frozen and `.train()` changes nothing here: this inference forward runs, with all its arguments."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("deeppointmap_amd.Encoder runs on the GPU only: call .to('cuda') first "
-                               "(there is no CPU fallback)")
+        dev = self._require_gpu()
         if self.training and self.train_stage != "loop_detection":
             for name, given in (("presampled", presampled is not None), ("descriptor_scale", descriptor_scale != 0.0),
                                 ("spare_frames", spare_frames != 0), ("stop_level", stop_level is not None),
@@ -319,7 +310,7 @@ class Encoder(ParamTree):
         whose name lacks `loop`: all of the encoder) `.train()` leaves every parameter frozen and `forward` stays the
         inference forward: the same bytes as in `.eval()`, at inference cost."""
         super().train(mode)
-        on = bool(mode) and getattr(self, "train_stage", "registration") != "loop_detection"
+        on = bool(mode) and self.train_stage != "loop_detection"
         for p in self._flat.values():
             p.requires_grad_(on)
         if mode:
@@ -329,44 +320,9 @@ class Encoder(ParamTree):
             self.invalidate_caches()
         return self
 
-    def set_train_stage(self, stage: str = "registration"):
-        """Which of the reference's two training stages `.train()` selects: "registration" or "loop_detection" (see
-        `train`).  Kept in `self.train_stage` across `.train()` / `.eval()`; applied at once if the module is training.
-        Returns self.  ValueError for any other name."""
-        if stage not in ("registration", "loop_detection"):
-            raise ValueError(f"train stage must be 'registration' or 'loop_detection', got {stage!r}")
-        self.train_stage = stage
-        if self.training:
-            self.train(True)
-        return self
-
-    def set_train_dense(self, mode: str = "torch"):
-        """Who evaluates the dense layers of the training forward (point_mlp0, the W_f projections, pw_conv and the upsampler MLPs
-        with their LayerNorms): "torch" (the default: F.linear / F.layer_norm / F.relu under autograd) or "hip"
-        (ops.dense_linear_train / ops.dense_linear_ln_train, csrc/dense_train.hip).  Kept in `self.train_dense` across `.train()`
-        / `.eval()` and copy.deepcopy.  Returns self.  ValueError for any other name."""
-        if mode not in ("torch", "hip"):
-            raise ValueError(f"train_dense must be 'torch' or 'hip', got {mode!r}")
-        self.train_dense = mode
-        return self
-
-    def _linear_train(self, x, W, bias):
-        return ops.dense_linear_train(x, W, bias) if self.train_dense == "hip" else F.linear(x, W, bias)
-
-    def _w(self, key: str):
-        """(weight as (out, in), bias) of a Conv1d / Conv2d(k=1) for F.linear"""
-        w = self.p(key + ".weight")
-        return w.view(w.shape[0], w.shape[1]), self.p(key + ".bias")
-
     def _mlp_ln_train(self, x, conv: str, ln: str, post=None):
-        """relu(LN(conv x) [+ post]) as torch operations under autograd (what ops.linear_layernorm evaluates), or as ONE
-        ops.dense_linear_ln_train (train_dense "hip")"""
-        if self.train_dense == "hip":
-            return ops.dense_linear_ln_train(x, *self._w(conv), self.p(ln + ".weight"), self.p(ln + ".bias"), post=post,
-                                             act=ops.ACT_RELU)
-        y = F.layer_norm(F.linear(x, *self._w(conv)), (self.p(ln + ".weight").shape[0],), self.p(ln + ".weight"),
-                         self.p(ln + ".bias"))
-        return F.relu(y if post is None else y + post)
+        """relu(LN(conv x) [+ post]): what ops.linear_layernorm evaluates, under autograd"""
+        return self._dense_ln(x, *self._w(conv), self.p(ln + ".weight"), self.p(ln + ".bias"), post=post, act=ops.ACT_RELU)
 
     def _group_train(self, prefix: str, radius: float, xyz, fea, centers, idx, keep):
         """SetAbstraction / LocalAggregation body: the projection under autograd, the rest in csrc/group_train.hip"""
@@ -376,7 +332,7 @@ class Encoder(ParamTree):
             raise ValueError(f"Encoder.forward (train mode): layer {prefix} has width {W.shape[0]} and {idx.shape[2]} "
                              f"neighbours; the training kernels cover widths {ops.GROUP_TRAIN_COUT} and neighbour counts "
                              f"{ops.GROUP_TRAIN_K}")
-        P = self._linear_train(fea, W[:, :Cin], bias)
+        P = self._dense(fea, W[:, :Cin], bias)
         slots = None if keep is None else []
         out = ops.group_train(P, xyz, centers, idx, W[:, Cin:].contiguous(), self.p(prefix + ".1.ln.weight"),
                               self.p(prefix + ".1.ln.bias"), radius, layer=prefix, keep_slots=slots)
@@ -439,7 +395,7 @@ class Encoder(ParamTree):
         with torch.enable_grad(), torch.cuda.device(dev):
             pts, xyz, lengths = samp["pts"], samp["xyz"], samp["lengths"]
             x0 = xyz if self.in_channel == 3 else pts[:, :self.in_channel].transpose(1, 2).contiguous()
-            fea = self._linear_train(x0, *self._w("point_mlp0"))
+            fea = self._dense(x0, *self._w("point_mlp0"))
             recompute = keep is None and xyz.shape[0] * xyz.shape[1] >= self.train_checkpoint_rows
             levels = [(xyz, fea, lengths)]
             for i in range(len(enc.npoint)):

@@ -11,10 +11,16 @@ and verified by loading them with strict=True into the reference modules
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict
+from typing import Dict, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+
+TRAIN_STAGES = ("registration", "loop_detection")
+TRAIN_DENSE = ("torch", "hip")
 
 Shapes = "OrderedDict[str, Tuple[int, ...]]"
 
@@ -102,6 +108,8 @@ class ParamTree(nn.Module):
         super().__init__()
         self._flat: Dict[str, nn.Parameter] = {}
         self._epoch = 0   # bumped whenever parameter storage may have moved (load_state_dict, .to(), invalidate_caches)
+        self.train_stage = "registration"   # what `.train()` trains: set_train_stage
+        self.train_dense = "torch"          # who evaluates the training forward's dense layers: set_train_dense
         for key, shape in (shapes or {}).items():
             self._add(key, shape)
 
@@ -121,7 +129,6 @@ class ParamTree(nn.Module):
     def invalidate_caches(self) -> None:
         """Drop the tensors the kernels derived from these weights (folded point_mlp0, packed feature columns ...).
         Automatic on load_state_dict(); needed by hand only after in-place edits through `.data`."""
-        from . import ops
         ops.invalidate_derived()
         self._epoch += 1
 
@@ -139,6 +146,63 @@ class ParamTree(nn.Module):
     def flat(self) -> Dict[str, torch.Tensor]:
         """{key: tensor} view of the live parameters (what the oracle calls `sd`)."""
         return dict(self._flat)
+
+    def _require_gpu(self) -> torch.device:
+        """the device of the parameters; RuntimeError unless that is a GPU"""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"deeppointmap_amd.{type(self).__name__} runs on the GPU only: call .to('cuda') first "
+                               f"(there is no CPU fallback)")
+        return dev
+
+    # -- training switches and the dense layers of the training forwards -----------------------------
+    def set_train_stage(self, stage: str = "registration"):
+        """Which of the reference's two training stages `.train()` selects (pipeline/modules/trainer.py runs them in turn):
+        "registration" or "loop_detection" (see the module's `train`).  Kept in `self.train_stage` across `.train()` /
+        `.eval()`; applied at once if the module is training.  Returns self.  ValueError for any other name."""
+        if stage not in TRAIN_STAGES:
+            raise ValueError(f"train stage must be one of {TRAIN_STAGES}, got {stage!r}")
+        self.train_stage = stage
+        if self.training:
+            self.train(True)
+        return self
+
+    def set_train_dense(self, mode: str = "torch"):
+        """Who evaluates the dense layers (projections, LayerNorms, MLPs, heads) of the training forward: "torch" (the default:
+        F.linear / F.layer_norm / F.relu under autograd) or "hip" (ops.dense_linear_train / ops.dense_linear_ln_train,
+        csrc/dense_train.hip: exact fp32 products, every sum in one order, so a whole step gives identical bytes twice).  Both
+        modes run the same layer code: `_dense` and `_dense_ln` are the one place that looks at the switch.  Kept in
+        `self.train_dense` across `.train()` / `.eval()` and copy.deepcopy.  Returns self.  ValueError for any other name."""
+        if mode not in TRAIN_DENSE:
+            raise ValueError(f"train_dense must be one of {TRAIN_DENSE}, got {mode!r}")
+        self.train_dense = mode
+        return self
+
+    def _w(self, key: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(weight as (out, in), bias) of a Linear / Conv1d / Conv2d(k=1) for `_dense`"""
+        w = self.p(key + ".weight")
+        return w.view(w.shape[0], w.shape[1]), self.p(key + ".bias")
+
+    def _dense(self, x, W, b, act: int = ops.ACT_NONE, residual=None):
+        """act(x W^T + b + residual), act ACT_NONE or ACT_RELU, by whoever `train_dense` names"""
+        if self.train_dense == "hip":
+            return ops.dense_linear_train(x, W, b, residual=residual, act=act)
+        y = F.linear(x, W, b)
+        if residual is not None:
+            y = y + residual
+        return F.relu(y) if act == ops.ACT_RELU else y
+
+    def _dense_ln(self, x, W, b, gamma, beta, residual=None, post=None, act: int = ops.ACT_NONE):
+        """act(LN(x W^T + b + residual) gamma + beta + post), the LayerNorm over the output width"""
+        if self.train_dense == "hip":
+            return ops.dense_linear_ln_train(x, W, b, gamma, beta, residual=residual, post=post, act=act)
+        y = F.linear(x, W, b)
+        if residual is not None:
+            y = y + residual
+        y = F.layer_norm(y, (W.shape[0],), gamma, beta)
+        if post is not None:
+            y = y + post
+        return F.relu(y) if act == ops.ACT_RELU else y
 
 
 class _Node(nn.Module):

@@ -122,3 +122,40 @@ def test_set_train_dense_switch(cfg_full):
                 m.set_train_dense(name)
         assert m.train_dense == "hip"
         assert m.set_train_dense("torch") is m and m.train_dense == "torch" and m.set_train_dense().train_dense == "torch"
+
+
+def test_torch_body_of_the_dispatch_is_the_literal_expression():
+    """ParamTree._dense / _dense_ln in "torch" mode ARE the inline expressions the training forwards used to spell out: equal bytes
+    for the outputs and for every input gradient under a fixed dy (CPU, fp32, R = 5, Cin = 8, Cout = 4)"""
+    from deeppointmap_amd import ops
+    from deeppointmap_amd.params import ParamTree
+    m = ParamTree()
+    assert m.train_dense == "torch"
+    g = torch.Generator().manual_seed(5)
+    t = dict(x=torch.randn(5, 8, generator=g), W=torch.randn(4, 8, generator=g), b=torch.randn(4, generator=g),
+             gamma=torch.randn(4, generator=g), beta=torch.randn(4, generator=g), residual=torch.randn(5, 4, generator=g),
+             post=torch.randn(5, 4, generator=g))
+    dy = torch.randn(5, 4, generator=g)
+    ln = lambda y, a: F.layer_norm(y, (4,), a["gamma"], a["beta"])   # noqa: E731
+    forms = [
+        ("x W b", lambda a: m._dense(a["x"], a["W"], a["b"]), lambda a: F.linear(a["x"], a["W"], a["b"])),
+        ("x W b residual", lambda a: m._dense(a["x"], a["W"], a["b"], act=ops.ACT_RELU, residual=a["residual"]),
+         lambda a: F.relu(F.linear(a["x"], a["W"], a["b"]) + a["residual"])),
+        ("x W", lambda a: m._dense(a["x"], a["W"], None), lambda a: F.linear(a["x"], a["W"])),
+        ("x W b gamma beta residual post",
+         lambda a: m._dense_ln(a["x"], a["W"], a["b"], a["gamma"], a["beta"], residual=a["residual"], post=a["post"]),
+         lambda a: ln(F.linear(a["x"], a["W"], a["b"]) + a["residual"], a) + a["post"]),
+        ("x W b gamma beta post", lambda a: m._dense_ln(a["x"], a["W"], a["b"], a["gamma"], a["beta"], post=a["post"], act=ops.ACT_RELU),
+         lambda a: F.relu(ln(F.linear(a["x"], a["W"], a["b"]), a) + a["post"])),
+        ("x W b gamma beta", lambda a: m._dense_ln(a["x"], a["W"], a["b"], a["gamma"], a["beta"]),
+         lambda a: ln(F.linear(a["x"], a["W"], a["b"]), a)),
+    ]
+    for names, got_f, want_f in forms:
+        with torch.enable_grad():
+            a = {k: t[k].clone().requires_grad_(True) for k in names.split()}
+            b = {k: t[k].clone().requires_grad_(True) for k in names.split()}
+            got, want = got_f(a), want_f(b)
+            gg, gw = torch.autograd.grad(got, list(a.values()), dy), torch.autograd.grad(want, list(b.values()), dy)
+        assert torch.equal(got, want), names
+        for k, u, v in zip(a, gg, gw):
+            assert torch.equal(u, v), (names, k)
