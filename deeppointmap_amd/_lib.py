@@ -90,6 +90,13 @@ SIGNATURES = {
     "dpm_point_normals": (I, [P, I, D, P, P, P]),
     "dpm_lowpass_similarity": (I, [P, P, I, I, I, P, P]),
     "dpm_stat_filter": (I, [P, I, D, I, D, P, P, P, P, P, P]),
+    "dpm_augment_workspace_bytes": (c_size_t, [I, LL]),
+    "dpm_ground_filter": (I, [P, P, P, I, I, I, D, D, I, P, P, P, P, P]),
+    "dpm_voxel_select": (I, [P, P, P, I, D, I, LL, P, P, P, P, P]),
+    "dpm_mask_select": (I, [P, P, P, I, I, D, D, P, D, P, I, P, P, P, P, P]),
+    "dpm_points_affine": (I, [P, P, I, I, P, P, P]),
+    "dpm_gather_points": (I, [P, P, P, I, P, I, I, P, P, P, P]),
+    "dpm_pack_frames": (I, [P, P, P, I, I, P, P, P, P]),
     "dpm_map_tile": (I, [P, P, P, P, I, I, I, P, P]),
     "dpm_infomat_workspace_bytes": (c_size_t, [I, I, I]),
     "dpm_information_matrix": (I, [P, I, P, I, P, D, P, P, P]),

@@ -51,6 +51,7 @@ SOURCES = {
     "group_train.hip": [],
     "loop_head_train.hip": [],
     "dense_train.hip": [],
+    "augment.hip": [],
 }
 
 

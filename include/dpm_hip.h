@@ -476,6 +476,61 @@ int dpm_lowpass_similarity(const float *normals, const int32_t *idx, int N, int 
 int dpm_stat_filter(const float *stat, int N, double k_std, int mode, double ratio, const float *xyz_in,
                     const int32_t *idx_in, float *xyz_out, int32_t *idx_out, int32_t *n_out, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- training transforms --- */
+
+/* The transforms only training configs use (dataloader/transforms.py).  ONE RULE: a frame is a fixed-capacity buffer
+ * plus a count in DEVICE memory -- xyz (capacity,3) fp32, idx (capacity,) int32 [original indices, NULL-able: positions],
+ * count (1,) int32.  Every entry reads the count through its pointer, sizes its grid by the capacity and writes the new
+ * count to device memory; rows at and past the count are never read.  Selections are stable, ordered compactions; outputs
+ * must not alias inputs.  Two runs give identical bytes.  workspace: dpm_augment_workspace_bytes(capacity, cells) with
+ * cells = img_len*img_width (ground filter), max_cells (voxel select) or 0 (mask select).
+ *
+ * dpm_ground_filter: GroundFilter (transforms.py:174-227).  Cell = int32(x / grid_width + img_len / 2) in float32,
+ *   truncated towards zero (so (-1, 0) lands in row 0 and is kept; columns alike); points outside the image and cells
+ *   with fewer than 3 points are dropped; a cell with zmax - zmin > ground_height (float32) keeps all its points,
+ *   any other cell keeps one representative when preserve_sparse_ground.  ground_height <= 0 is the identity.
+ *   ORDER AND REPRESENTATIVE ARE DEFINED HERE, not by the reference, whose unstable np.argsort over cell ids leaves the
+ *   in-cell order -- and with it the representative -- to the numpy build: kept points come in ascending input position,
+ *   and a sparse cell's representative is its point with the lowest input position.  The SETS (non-ground points, sparse
+ *   cells) equal the reference's.
+ * dpm_voxel_select: VoxelSample (transforms.py:322-356), retention 0 = 'first' (the bytes of dpm_preprocess_scan with
+ *   the crop and the normalisation off), 1 = 'center' (per voxel the point nearest the voxel centre, distance in fp64
+ *   as the reference's int32 * python float promotes, equal distances to the lower position).  Output in ascending
+ *   voxel id.  status[0] = number kept (usable as the new count), status[1] = 1 when the grid exceeded max_cells
+ *   (nothing kept then).  An empty frame stays empty.
+ * dpm_mask_select: keep = distance crop (DistanceSample, transforms.py:387-397; use_distance) AND u[i] >= drop_ratio in
+ *   float32 (RandomDrop, transforms.py:429-434; u NULL = off, u has `capacity` entries) AND outside every occlusion wedge
+ *   (RandomShield, transforms.py:447-474): wedges = n_wedges x (start, end, wraps, dis_threshold) floats in HOST memory,
+ *   at most 16; azimuth = atan2(y, x) * 180 / pi and distance = |xyz| in float32; a point goes when start <= azimuth <= end
+ *   (wraps: azimuth >= start OR azimuth <= end, end already reduced by 360) AND distance >= dis_threshold.
+ * dpm_points_affine: in place on the first count rows.  mode 0: R x + T, params = R row-major (9) then T (3)
+ *   (RandomRT, transforms.py:529); mode 1: x += jitter (capacity,3) (RandomPosJitter, transforms.py:561-563); mode 2:
+ *   x / params[0], a true division (CoordinatesNormalization, transforms.py:406); mode 3: VerticalCorrect
+ *   (transforms.py:300-319), params = (sin, cos) of the angle: per point the rotation about normalize(x cross z) built in
+ *   fp64 and rounded to float32 before it multiplies the point.  A point on the z axis becomes NaN, as in the reference.
+ * dpm_gather_points: out[j] = in[sel[j]] (RandomShuffle, RandomSample, FarthestPointSample: transforms.py:359-384,
+ *   410-420).  limit < 0: all min(count, n_sel) rows; limit >= 0: a frame of at most `limit` points is copied unchanged,
+ *   a longer one keeps min(limit, n_sel) rows.  A selector outside [0, count) gives a zero row with index -1.
+ * dpm_pack_frames: ToTensor(padding_to) + map_collate_fn (transforms.py:69-98, body.py:155-161) for S frames given as
+ *   HOST arrays of device pointers: points (S,3,padding_to) channel-first with zero fill, padding (S,padding_to) bytes
+ *   (1 past a frame's count), status (S,2) = (count, 1 when count > padding_to; that frame's rows are zero). */
+size_t dpm_augment_workspace_bytes(int capacity, long long cells);
+int dpm_ground_filter(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, int img_len,
+                      int img_width, double grid_width, double ground_height, int preserve_sparse_ground, float *out_xyz,
+                      int32_t *out_idx, int32_t *out_count, void *workspace, dpm_stream_t stream);
+int dpm_voxel_select(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, double voxel_size,
+                     int retention, long long max_cells, float *out_xyz, int32_t *out_idx, int32_t *status,
+                     void *workspace, dpm_stream_t stream);
+int dpm_mask_select(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, int use_distance,
+                    double min_dis, double max_dis, const float *u, double drop_ratio, const float *wedges, int n_wedges,
+                    float *out_xyz, int32_t *out_idx, int32_t *out_count, void *workspace, dpm_stream_t stream);
+int dpm_points_affine(float *xyz, const int32_t *count, int capacity, int mode, const double *params,
+                      const float *jitter, dpm_stream_t stream);
+int dpm_gather_points(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, const int32_t *sel,
+                      int n_sel, int limit, float *out_xyz, int32_t *out_idx, int32_t *out_count, dpm_stream_t stream);
+int dpm_pack_frames(const float *const *xyz, const int32_t *const *counts, const int32_t *capacities, int S,
+                    int padding_to, float *points, unsigned char *padding, int32_t *status, dpm_stream_t stream);
+
 /* ---------------------------------------------------------------- map tiles ------------- */
 
 /* PoseGraph.__global_mapping + centring of global_map_query_graph (system/modules/pose_graph.py:373-409,
