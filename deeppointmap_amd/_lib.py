@@ -131,6 +131,11 @@ SIGNATURES = {
     "dpm_dense_train_forward": (I, [P, I, P, I, P, P, P, P, P, LL, I, I, I, P, P, P, P]),
     "dpm_dense_train_backward_rows": (I, [P, P, P, P, P, LL, I, I, P, P, P, P, P, P]),
     "dpm_dense_train_backward_gemm": (I, [P, P, I, P, I, LL, I, I, P, P, P, P, P]),
+    "dpm_map_poses": (I, [P, P, P, P, P, I, I, I, P, P, P]),
+    "dpm_map_assemble_fwd": (I, [P, P, P, P, P, I, I, I, I, I, D, P, P, P, P, P, P, P]),
+    "dpm_map_assemble_bwd": (I, [P, P, I, I, I, I, I, P, P]),
+    "dpm_optim_chunk": (I, []),
+    "dpm_optim_step": (I, [I, P, P, I, D, D, D, D, D, D, D, D, I, I, P]),
 }
 
 

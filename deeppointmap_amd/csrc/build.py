@@ -52,6 +52,8 @@ SOURCES = {
     "loop_head_train.hip": [],
     "dense_train.hip": [],
     "augment.hip": [],
+    "map_assemble.hip": [],
+    "optim.hip": [],
 }
 
 

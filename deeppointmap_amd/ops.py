@@ -1657,3 +1657,94 @@ def dense_linear_ln_train(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch
     in the product kernel's epilogue, other widths in a row kernel after it; the pre-norm rows are the bits dense_linear_train gives
     for the same operands either way.  Two runs give identical bytes.  ValueError for shape or dtype mismatches."""
     return _DenseLinearLN.apply(x, W, bias, gamma, beta, residual, post, act)
+
+
+# ---- the map assembly of the registration training step (csrc/map_assemble.hip) -------------------------------------------------
+def _map_split(F: int, S: int, S1: int, what: str) -> int:
+    if S < 2 or not 1 <= S1 < S or F < S or F % S:
+        raise ValueError(f"{what}: needs F = B * S frames with S >= 2 and 1 <= S1 < S, got F = {F}, S = {S}, S1 = {S1}")
+    return F // S
+
+
+def map_poses(R: torch.Tensor, T: torch.Tensor, calib: torch.Tensor, icp: torch.Tensor, has_icp: torch.Tensor, S: int, S1: int):
+    """R (F,3,3), T (F,3,1), calib (F,4,4) fp32: the global poses and calibrations of F = B * S frames; icp (F+B,16) fp32,
+    has_icp (F+B,) uint8: the refined poses the host found (train_pipeline.icp_table) -> rel (F,12), gt (B,12), rows [R | T]
+    (3x4): frame (b,s) into its map's first frame (frame 0 for s < S1, frame S1 otherwise; those two get the exact identity)
+    and map b's source-first into its target-first.  With has_icp: d_calib @ icp @ inverse(s_calib); otherwise
+    rt_global_to_relative.  One launch, no host round trip.  A singular calib is not supported (Inf / NaN)."""
+    for t, name in ((R, "R"), (T, "T"), (calib, "calib"), (icp, "icp")):
+        _chk(t, torch.float32, name)
+    _chk(has_icp, torch.uint8, "has_icp")
+    F = R.shape[0]
+    B = _map_split(F, S, S1, "map_poses")
+    _shape(R, (F, 3, 3), "R"), _shape(T, (F, 3, 1), "T"), _shape(calib, (F, 4, 4), "calib")
+    _shape(icp, (F + B, 16), "icp"), _shape(has_icp, (F + B,), "has_icp")
+    rel = torch.empty(F, 12, device=R.device, dtype=torch.float32)
+    gt = torch.empty(B, 12, device=R.device, dtype=torch.float32)
+    _lib.check(_lib.load().dpm_map_poses(_ptr(R), _ptr(T), _ptr(calib), _ptr(icp), _ptr(has_icp), B, S, S1, _ptr(rel), _ptr(gt),
+                                         _stream(R)), "dpm_map_poses")
+    return rel, gt
+
+
+def map_assemble_forward(coor, fea, mask, rel, gt, S: int, S1: int, coor_scale: float):
+    for t, name in ((coor, "coor"), (fea, "fea"), (rel, "rel"), (gt, "gt")):
+        _chk(t, torch.float32, name)
+    m = _chk(mask.view(torch.uint8) if mask.dtype == torch.bool else mask, torch.uint8, "mask")   # same bytes
+    F, C, N = fea.shape
+    B = _map_split(F, S, S1, "map_assemble")
+    _shape(coor, (F, 3, N), "coor"), _shape(m, (F, N), "mask"), _shape(rel, (F, 12), "rel"), _shape(gt, (B, 12), "gt")
+    if N < 1 or C < 1:
+        raise ValueError(f"map_assemble: needs N >= 1 points and C >= 1 channels, got N = {N}, C = {C}")
+    dev, S2 = fea.device, S - S1
+    new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)   # noqa: E731
+    src_desc, dst_desc = new(B, C + 3, S1 * N), new(B, C + 3, S2 * N)
+    src_mask, dst_mask = new(B, S1 * N, dtype=torch.uint8), new(B, S2 * N, dtype=torch.uint8)
+    src_global, dst_global = new(B, 3, S1 * N), new(B, 3, S2 * N)
+    _lib.check(_lib.load().dpm_map_assemble_fwd(_ptr(coor), _ptr(fea), _ptr(m), _ptr(rel), _ptr(gt), B, S, S1, N, C,
+                                                float(coor_scale), _ptr(src_desc), _ptr(dst_desc), _ptr(src_mask), _ptr(dst_mask),
+                                                _ptr(src_global), _ptr(dst_global), _stream(fea)), "dpm_map_assemble_fwd")
+    return src_desc, dst_desc, src_mask.view(torch.bool), dst_mask.view(torch.bool), src_global, dst_global
+
+
+def map_assemble_backward(d_src_desc, d_dst_desc, F: int, C: int, N: int, S: int, S1: int) -> torch.Tensor:
+    """dfea (F,C,N) from the gradients of the two descriptors (either may be None: zeros); a gather, exact and repeatable"""
+    B = _map_split(F, S, S1, "map_assemble")
+    ref = d_src_desc if d_src_desc is not None else d_dst_desc
+    if ref is None:
+        raise ValueError("map_assemble_backward: no gradient given")
+    for t, name, Sx in ((d_src_desc, "d_src_desc", S1), (d_dst_desc, "d_dst_desc", S - S1)):
+        if t is not None:
+            _chk(t, torch.float32, name), _shape(t, (B, C + 3, Sx * N), name)
+    dfea = torch.empty(F, C, N, device=ref.device, dtype=torch.float32)
+    _lib.check(_lib.load().dpm_map_assemble_bwd(_ptr(d_src_desc), _ptr(d_dst_desc), B, S, S1, N, C, _ptr(dfea), _stream(ref)),
+               "dpm_map_assemble_bwd")
+    return dfea
+
+
+class _MapAssemble(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fea, coor, mask, rel, gt, S, S1, coor_scale):
+        outs = map_assemble_forward(coor, fea.detach().contiguous(), mask, rel, gt, S, S1, coor_scale)
+        ctx.cfg = (*fea.shape, S, S1)
+        ctx.mark_non_differentiable(*outs[2:])
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_src, d_dst, *_):
+        F, C, N, S, S1 = ctx.cfg
+        dfea = map_assemble_backward(None if d_src is None else d_src.contiguous(), None if d_dst is None else d_dst.contiguous(),
+                                     F, C, N, S, S1)
+        return dfea, None, None, None, None, None, None, None
+
+
+def map_assemble(coor: torch.Tensor, fea: torch.Tensor, mask: torch.Tensor, rel: torch.Tensor, gt: torch.Tensor, S: int, S1: int,
+                 coor_scale: float):
+    """model_pipeline.py:40-104 after the poses: coor (F,3,N) unscaled, fea (F,C,N), mask (F,N) bool of F = B * S encoded frames,
+    rel (F,12), gt (B,12) from map_poses -> (src_desc (B,C+3,S1*N), dst_desc (B,C+3,S2*N), src_mask (B,S1*N), dst_mask (B,S2*N),
+    src_global (B,3,S1*N), dst_global (B,3,S2*N)), S2 = S - S1: what the decoder and the criterion take.  Token s*N + n of a
+    map is point n of its frame s; feature rows first, then xyz = rel_R @ (coor * coor_scale) + rel_T (a map's first frame:
+    coor * coor_scale and nothing else); src_global = gt_R @ src_xyz + gt_T.  One launch forward, one backward.
+    Differentiable with respect to fea ONLY: the xyz rows and coor get no gradient (the decoder's rule), and the
+    backward is a gather of the two descriptor gradients' feature rows -- exact, identical bytes on every run."""
+    return _MapAssemble.apply(fea, coor, mask, rel, gt, S, S1, coor_scale)

@@ -731,6 +731,50 @@ int dpm_dense_train_backward_rows(const float *dy, const float *out, const float
 int dpm_dense_train_backward_gemm(const float *dh, const float *x, int ldx, const float *W, int ldw, long long R, int Cin,
                                   int Cout, float *dx, float *dW, float *dbias, void *workspace, dpm_stream_t stream);
 
+/* The map assembly of the registration training step (csrc/map_assemble.hip; pipeline/modules/model_pipeline.py:62-104 and
+ * _get_accurate_RT, :199-272).  F = B * S encoded frames, map b = frames [b S, (b+1) S): its first S1 frames are the source map,
+ * the other S2 = S - S1 the target map.  1 <= S1 < S, B * S <= 65535, any N, C >= 1.  A pose is 12 floats [R | T], 3x4 row-major.
+ * map_poses (model_pipeline.py:70-94, 234-266; utils/pose.py:6-10): R (F,3,3), T (F,3,1), calib (F,4,4) the batch's global
+ *   poses and calibrations; icp (F+B,16), has_icp (F+B,) bytes: the refined pose of an entry where the host found one
+ *   (get_SE3_from_dict, model_pipeline.py:285-298, already `.float()`).  Entry f < F is frame f into the first frame of its map
+ *   (frame 0 for s < S1, frame S1 otherwise), entry F + b is map b's source-first into its target-first.  -> rel (F,12), gt
+ *   (B,12): with has_icp rows [:3] of d_calib @ icp @ inverse(s_calib) (fp32; the 4x4 inverse is a Gauss-Jordan elimination with
+ *   partial pivoting), otherwise Rc^T Ro | Rc^T (To - Tc).  The two first frames of a map get the exact identity.  A singular
+ *   calib is NOT supported: it gives Inf / NaN where the reference's `except` would take the global poses.
+ * map_assemble_fwd (model_pipeline.py:40, 84, 95-104, 110-111): coor (F,3,N) unscaled, fea (F,C,N), mask (F,N) bytes ->
+ *   src_desc (B, C+3, S1 N), dst_desc (B, C+3, S2 N): C feature rows, then xyz (torch.cat([fea, coor], 1)); src_mask (B, S1 N),
+ *   dst_mask (B, S2 N); src_global (B,3,S1 N) = gt_R src_xyz + gt_T; dst_global (B,3,S2 N) = dst_xyz.  Token s' N + n of map b
+ *   is point n of the map's frame s' (transpose(1,2).reshape).  Feature rows and masks are copies; xyz of a map's first frame is
+ *   coor * (float)coor_scale and nothing else, of the others fma(r2, z, fma(r1, y, r0 * x)) + t per row of rel.
+ * map_assemble_bwd: dfea (F,C,N) gathered from the two descriptor gradients (either may be NULL: zeros); the xyz rows and
+ *   coor get no gradient.  A gather: exact, identical bytes on every run.
+ * Rows are moved as float4 when N % 4 == 0 and the bases are 16-byte aligned, else by scalar accesses (decided per launch). */
+int dpm_map_poses(const float *R, const float *T, const float *calib, const float *icp, const uint8_t *has_icp, int B, int S,
+                  int S1, float *rel, float *gt, dpm_stream_t stream);
+int dpm_map_assemble_fwd(const float *coor, const float *fea, const uint8_t *mask, const float *rel, const float *gt, int B, int S,
+                         int S1, int N, int C, double coor_scale, float *src_desc, float *dst_desc, uint8_t *src_mask,
+                         uint8_t *dst_mask, float *src_global, float *dst_global, dpm_stream_t stream);
+int dpm_map_assemble_bwd(const float *d_src_desc, const float *d_dst_desc, int B, int S, int S1, int N, int C, float *dfea,
+                         dpm_stream_t stream);
+
+/* The optimiser step of a parameter group in one launch (csrc/optim.hip; the reference builds torch.optim.AdamW / Adam / SGD in
+ * pipeline/modules/utils.py:86-100 and steps them in pipeline/modules/trainer.py:176-178).  tensors (T,5) int64 device table
+ * [param, grad, state0, state1, numel] of fp32 arrays (state0 = exp_avg or momentum_buffer, state1 = exp_avg_sq; unused ones 0),
+ * chunks (n_chunks,2) int32 device table [tensor, chunk]: one block per row updates elements [chunk * dpm_optim_chunk(),
+ * min(numel, (chunk + 1) * dpm_optim_chunk())) of that tensor, so every element of the group must be covered by exactly one row.
+ * torch's single-tensor rule in fp32: AdamW p *= 1 - lr wd; Adam and SGD g += wd p; m, v moving averages; p -= lr / (1 - beta1^step)
+ * m / (sqrt(v) / sqrt(1 - beta2^step) + eps); SGD with momentum, dampening, nesterov; `first` (SGD): the momentum buffers are
+ * being created (buf = g).  `step` (Adam, AdamW) is the step count AFTER this update, >= 1, the same for every tensor of the
+ * call.  A tensor whose addresses are all 16-byte aligned moves as float4, any other by scalar accesses; the result does not
+ * depend on the chunking.  n_chunks = 0 launches nothing. */
+#define DPM_OPTIM_ADAMW 0
+#define DPM_OPTIM_ADAM 1
+#define DPM_OPTIM_SGD 2
+int dpm_optim_chunk(void);
+int dpm_optim_step(int algo, const long long *tensors, const int32_t *chunks, int n_chunks, double lr, double beta1, double beta2,
+                   double eps, double weight_decay, double step, double momentum, double dampening, int nesterov, int first,
+                   dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
