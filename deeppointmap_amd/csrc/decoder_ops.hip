@@ -39,12 +39,7 @@ __global__ __launch_bounds__(256) void posemb_kernel(const float *__restrict__ x
 // ------------------------------------------------------------------------------------------
 constexpr int HD = 32;
 constexpr float LOG2E = 1.44269504088896340736f;
-// workgroups of 128 queries a launch must have for the 32-queries-per-wave form (QT = 2); 0 = never.  Round 5: with P V on the
-// bf16 pipe that form holds 204 registers (two waves per SIMD) against 128 at QT = 1; it is as fast alone (67.4 against 66.5 us at
-// 128 sequences) and costs the pipelined step what the P V change wins (4.16 / 4.18 against 4.10 / 4.10 ms): never.
-#ifndef DPM_ATT_WIDE_MIN
-#define DPM_ATT_WIDE_MIN 0
-#endif
+// the eight-wave workgroups of the attention kernel and the query count they start at (attention_launch says why)
 #ifndef DPM_ATT_BLOCK8
 #define DPM_ATT_BLOCK8 1
 #endif
@@ -98,33 +93,28 @@ __device__ __forceinline__ float rows4_sum(float v) {
 // probabilities never leave the registers (no LDS round trip to re-shape P), a lane owns ONE query -- its running
 // max / sum are scalars, the max needs two lane swaps instead of a 16-lane reduction, the row sum meets once at the
 // end -- and it ends up with 2 x 4 consecutive output channels of that query: two 16-byte stores.
-// QT = query groups of 16 per wave: with two, every K / V fragment read from LDS feeds two MFMAs and a block covers
-// 128 queries, so the fetch of the first K / V tile (a block lives for only N / 64 tiles) is paid half as often.
+// QT = query groups of 16 per wave, a constant of 1: a workgroup covers 16 NWV queries.  The form with two (every K / V fragment
+// read from LDS feeding two MFMAs) held 204 registers against 128, was as fast alone and slower in the pipelined step
+// (docs/r05_measured_not_kept.md), and is no longer built; the kernel keeps its [QT] arrays and loops because written without
+// them it compiles to other instructions (profiles/csrc_prune_isa.md).
 // MASK: key_mask (batch, N) bytes, non-zero = the key is padding (nn.MultiheadAttention's key_padding_mask): its score is
 // -inf like a key beyond N.  A sequence whose keys are ALL masked gives NaN rows, as in the reference.
 // SPLIT: few queries against many keys (a scan's 256 tokens attending a 4096-token map tile: 32 blocks walking 64 key
 // tiles each).  The keys are cut into `nsplit` ranges of whole tiles, gridDim.x = query tiles x nsplit; a block writes its
 // range's UNNORMALISED output rows (relative to its own running max) into part_o (nsplit, B, M, heads*HD) and
 // (max, sum) into part_ml (nsplit, B, heads, M, 2); attention_merge_kernel rescales and adds the ranges.
-template <bool VEC, int QT, bool MASK = false, bool SPLIT = false, int NWV = 4, bool PRE = false>
-#ifndef DPM_ATT_WAVES
-#define DPM_ATT_WAVES 0
-#endif
-#if DPM_ATT_WAVES
-#define DPM_ATT_OCC __attribute__((amdgpu_waves_per_eu(DPM_ATT_WAVES, DPM_ATT_WAVES)))
-#else
-#define DPM_ATT_OCC
-#endif
-__global__ __launch_bounds__(64 * NWV) DPM_ATT_OCC void attention_kernel(const float *__restrict__ Q, int ldq, long long sq,
-                                                        const float *__restrict__ Kp, int ldk, long long sk,
-                                                        const float *__restrict__ V, int ldv, long long sv,
-                                                        float *__restrict__ O, int ldo, long long so, int M,
-                                                        int N, float scale, int kv_shift,
-                                                        const uint8_t *__restrict__ key_mask = nullptr, int nsplit = 1,
-                                                        float *__restrict__ part_o = nullptr,
-                                                        float *__restrict__ part_ml = nullptr,
-                                                        const int32_t *__restrict__ seq = nullptr,
-                                                        const uint16_t *__restrict__ kvp = nullptr) {
+template <bool VEC, bool MASK = false, bool SPLIT = false, int NWV = 4, bool PRE = false>
+__global__ __launch_bounds__(64 * NWV) void attention_kernel(const float *__restrict__ Q, int ldq, long long sq,
+                                                             const float *__restrict__ Kp, int ldk, long long sk,
+                                                             const float *__restrict__ V, int ldv, long long sv,
+                                                             float *__restrict__ O, int ldo, long long so, int M,
+                                                             int N, float scale, int kv_shift,
+                                                             const uint8_t *__restrict__ key_mask = nullptr, int nsplit = 1,
+                                                             float *__restrict__ part_o = nullptr,
+                                                             float *__restrict__ part_ml = nullptr,
+                                                             const int32_t *__restrict__ seq = nullptr,
+                                                             const uint16_t *__restrict__ kvp = nullptr) {
+    constexpr int QT = 1;                  // query groups of 16 per wave
     // PRE (round 5): the keys and values arrive as the bf16 planes this kernel would otherwise make of them, one 24 KB image
     // per (stored sequence, head, 64-key tile) in exactly the layout of Ks3 | Vt3 below -- written once by the q | k | v
     // projection's epilogue (gemm_b3.hip, KvPlanes) instead of being split by every query block that reads the tile: staging is
@@ -267,7 +257,7 @@ __global__ __launch_bounds__(64 * NWV) DPM_ATT_OCC void attention_kernel(const f
                     ka[jj][pl] = *reinterpret_cast<const bf16x8 *>(&Ks3[pl][(jp + jj) * 16 + (lane & 15)][b3_col(lane & 15, 8 * g)]);
 #define DPM_S3(PK, PQ)                                                                                              \
     _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) _Pragma("unroll") for (int u = 0; u < QT; ++u)                \
-        sacc[u][jp + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[jj][PK], qb[u][PQ], sacc[u][jp + jj], 0, 0, 0), mfma_pace()
+        sacc[u][jp + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[jj][PK], qb[u][PQ], sacc[u][jp + jj], 0, 0, 0)
             DPM_S3(1, 1);
             DPM_S3(2, 0);
             DPM_S3(0, 2);
@@ -344,7 +334,7 @@ __global__ __launch_bounds__(64 * NWV) DPM_ATT_OCC void attention_kernel(const f
                 }
 #define DPM_PV3(PVQ, PPQ)                                                                                           \
     _Pragma("unroll") for (int jd = 0; jd < 2; ++jd) _Pragma("unroll") for (int u = 0; u < QT; ++u)                \
-        oacc[u][jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[jd][PVQ], pb[u][PPQ], oacc[u][jd], 0, 0, 0), mfma_pace()
+        oacc[u][jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[jd][PVQ], pb[u][PPQ], oacc[u][jd], 0, 0, 0)
             DPM_PV3(1, 1);
             DPM_PV3(2, 0);
             DPM_PV3(0, 2);
@@ -1390,42 +1380,31 @@ static int attention_launch(const float *Q, int ldq, long long sq, const float *
     const bool vec = ldk % 4 == 0 && ldv % 4 == 0 && sk % 4 == 0 && sv % 4 == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)V & 15) == 0 &&
                      ldo % 4 == 0 && so % 4 == 0 && ((uintptr_t)out & 15) == 0;  // 16-byte K / V loads and output stores
     const float scale = (float)(1.0 / sqrt((double)head_dim));
-    // 32 queries per wave when the query count fills such blocks and there are enough of them for the chip
-    const bool wide = DPM_ATT_WIDE_MIN > 0 && M % 128 == 0 && (long long)(M / 128) * heads * B >= DPM_ATT_WIDE_MIN;
-#define DPM_ATT(V, QT)                                                                                                  \
-    hipLaunchKernelGGL((attention_kernel<V, QT>), dim3(dpm_cdiv(M, 64 * QT), heads, B), dim3(256), (size_t)dpm_knob("DPM_ATT_LDS_PAD", 0), (hipStream_t)stream, \
-                       Q, ldq, sq, K, ldk, sk, V_, ldv, sv, out, ldo, so, M, N, scale, kv_shift, nullptr, 1, nullptr,     \
+#define DPM_ATT(VEC)                                                                                                    \
+    hipLaunchKernelGGL((attention_kernel<VEC>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), (size_t)dpm_knob("DPM_ATT_LDS_PAD", 0), (hipStream_t)stream, \
+                       Q, ldq, sq, K, ldk, sk, V, ldv, sv, out, ldo, so, M, N, scale, kv_shift, nullptr, 1, nullptr,      \
                        nullptr, seq)
-    const float *V_ = V;
     if (key_mask) {
         if (vec)
-            hipLaunchKernelGGL((attention_kernel<true, 1, true>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), 0, (hipStream_t)stream,
+            hipLaunchKernelGGL((attention_kernel<true, true>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), 0, (hipStream_t)stream,
                                Q, ldq, sq, K, ldk, sk, V, ldv, sv, out, ldo, so, M, N, scale, kv_shift, key_mask);
         else
-            hipLaunchKernelGGL((attention_kernel<false, 1, true>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), 0, (hipStream_t)stream,
+            hipLaunchKernelGGL((attention_kernel<false, true>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), 0, (hipStream_t)stream,
                                Q, ldq, sq, K, ldk, sk, V, ldv, sv, out, ldo, so, M, N, scale, kv_shift, key_mask);
         return dpm_launch_status();
     }
-#ifndef DPM_ATT_BLOCK8
-#define DPM_ATT_BLOCK8 1
-#endif
-#ifndef DPM_ATT_BLOCK8_MIN_M
-#define DPM_ATT_BLOCK8_MIN_M 1024
-#endif
     // Eight waves per workgroup (128 queries): a K / V tile is fetched, split and staged once per 128 queries instead of 64.
     // Alone it wins at every size (128 x 256 x 256: 65.4 -> 61.0 us; 2 x 4096 x 4096: 264 -> 233 us); in the pipelined step,
     // where the 256-token sequences run between the other stages' workgroups, 512-thread workgroups find their place later
     // and the step is 1.6 % LONGER (4.04 / 4.03 / 4.05 -> 4.09 / 4.12 / 4.11 ms).  So: map-sized query sets only (the
     // rank-0 registrations against a map tile run alone on their stream).
-    if (DPM_ATT_BLOCK8 && vec && !wide && M % 128 == 0 && M >= DPM_ATT_BLOCK8_MIN_M) {
-        hipLaunchKernelGGL((attention_kernel<true, 1, false, false, 8>), dim3(M / 128, heads, B), dim3(512), 0, (hipStream_t)stream,
+    if (DPM_ATT_BLOCK8 && vec && M % 128 == 0 && M >= DPM_ATT_BLOCK8_MIN_M) {
+        hipLaunchKernelGGL((attention_kernel<true, false, false, 8>), dim3(M / 128, heads, B), dim3(512), 0, (hipStream_t)stream,
                            Q, ldq, sq, K, ldk, sk, V, ldv, sv, out, ldo, so, M, N, scale, kv_shift, nullptr, 1, nullptr, nullptr, seq);
         return dpm_launch_status();
     }
-    if (vec && wide) DPM_ATT(true, 2);
-    else if (vec) DPM_ATT(true, 1);
-    else if (wide) DPM_ATT(false, 2);
-    else DPM_ATT(false, 1);
+    if (vec) DPM_ATT(true);
+    else DPM_ATT(false);
 #undef DPM_ATT
     return dpm_launch_status();
 }
@@ -1469,10 +1448,10 @@ extern "C" int dpm_attention_planes(const float *Q, int ldq, long long sq, const
     hipStream_t st = (hipStream_t)stream;
     const uint16_t *kvp = (const uint16_t *)kv_planes;
     if (DPM_ATT_BLOCK8 && M % 128 == 0 && M >= DPM_ATT_BLOCK8_MIN_M)
-        hipLaunchKernelGGL((attention_kernel<true, 1, false, false, 8, true>), dim3(M / 128, heads, B), dim3(512), 0, st, Q, ldq, sq, Q, 0,
+        hipLaunchKernelGGL((attention_kernel<true, false, false, 8, true>), dim3(M / 128, heads, B), dim3(512), 0, st, Q, ldq, sq, Q, 0,
                            0LL, Q, 0, 0LL, out, ldo, so, M, N, scale, kv_shift, nullptr, 1, nullptr, nullptr, seq_index, kvp);
     else
-        hipLaunchKernelGGL((attention_kernel<true, 1, false, false, 4, true>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), 0, st, Q, ldq, sq,
+        hipLaunchKernelGGL((attention_kernel<true, false, false, 4, true>), dim3(dpm_cdiv(M, 64), heads, B), dim3(256), 0, st, Q, ldq, sq,
                            Q, 0, 0LL, Q, 0, 0LL, out, ldo, so, M, N, scale, kv_shift, nullptr, 1, nullptr, nullptr, seq_index, kvp);
     return dpm_launch_status();
 }
@@ -1502,10 +1481,10 @@ extern "C" int dpm_attention_split(const float *Q, int ldq, long long sq, const 
     const float scale = (float)(1.0 / sqrt((double)head_dim));
     const dim3 grid(dpm_cdiv(M, 64) * nsplit, heads, B);
     if (vec)
-        hipLaunchKernelGGL((attention_kernel<true, 1, false, true>), grid, dim3(256), 0, st, Q, ldq, sq, K, ldk, sk, V, ldv, sv,
+        hipLaunchKernelGGL((attention_kernel<true, false, true>), grid, dim3(256), 0, st, Q, ldq, sq, K, ldk, sk, V, ldv, sv,
                            out, ldo, so, M, N, scale, kv_shift, nullptr, nsplit, part_o, part_ml);
     else
-        hipLaunchKernelGGL((attention_kernel<false, 1, false, true>), grid, dim3(256), 0, st, Q, ldq, sq, K, ldk, sk, V, ldv, sv,
+        hipLaunchKernelGGL((attention_kernel<false, false, true>), grid, dim3(256), 0, st, Q, ldq, sq, K, ldk, sk, V, ldv, sv,
                            out, ldo, so, M, N, scale, kv_shift, nullptr, nsplit, part_o, part_ml);
     hipLaunchKernelGGL(attention_merge_kernel, dim3(dpm_cdiv((long long)B * M * heads * HD, 256)), dim3(256), 0, st, part_o, part_ml,
                        nsplit, B, M, heads, out, ldo, so);

@@ -45,34 +45,6 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-// Issue priority of the kernels that are bound by vector-ALU issue (neighbour searches, gather + LayerNorm kernels, the
-// NN-1 search): inside the stream pipeline they share every SIMD with matrix-pipe kernels and the sampling chains.
-// -DDPM_VALU_PRIO=n builds a library whose VALU-bound kernels run at wave priority n (A/B measurements; 0 = default).
-#ifndef DPM_VALU_PRIO
-#define DPM_VALU_PRIO 0
-#endif
-__device__ __forceinline__ void valu_bound_priority() {
-    if (DPM_VALU_PRIO) __builtin_amdgcn_s_setprio(DPM_VALU_PRIO);
-}
-
-// Pacing of matrix instructions (experiment of round 4, profiles/r04_corun.md): a wave whose NEXT instruction is an MFMA
-// while the matrix pipe is busy waits AT the SIMD's vector issue port and keeps every other wave's vector instructions
-// out (scripts/micro/corun_pure.hip: a matrix-only and a vector-only wave on one SIMD take the SUM of their times; with
-// the matrix wave idling after each MFMA the vector wave's work disappears in the gaps).  -DDPM_MFMA_PACE=n makes the
-// dense kernels idle n wait states (4 cycles each) after every matrix instruction.  0 = shipped.
-#ifndef DPM_MFMA_PACE
-#define DPM_MFMA_PACE 0
-#endif
-__device__ __forceinline__ void mfma_pace() {
-#if DPM_MFMA_PACE > 0
-#pragma unroll
-    for (int left = DPM_MFMA_PACE; left > 0; left -= 16) {
-        if (left >= 16) asm volatile("s_nop 15");
-        else asm volatile("s_nop %0" ::"n"((DPM_MFMA_PACE - 1) & 15));
-    }
-#endif
-}
-
 // ---- exact three-way bf16 split of an fp32 value (csrc/gemm_b3.hip says what it is for): x = hi + mid + lo, each term a
 // truncation to the top 16 bits of a float, each remainder exact.  hi / mid come back masked, lo unmasked (its truncation
 // happens where the term is stored: pack2 / a 16-bit store of the upper half).

@@ -232,35 +232,9 @@ __global__ __launch_bounds__(FB) void fps_bucket_sort_kernel(const float *__rest
 // parallel, each wave working only on its OWN buckets -- no work list, no atomics, and one barrier per round
 // (the cross-wave arg-max exchange, double-buffered by round parity).
 // ------------------------------------------------------------------------------------------
-// REGCL (experiment of round 6, -DDPM_FPS_REGCL=1; profiles/r06_fps.md): the running `closest` of the wave's 64 buckets in 64 registers
-// per lane (bucket slot l of the wave = register l, wave-uniform index) instead of the workspace array: one global load per touched
-// bucket instead of two, no store.
-#ifndef DPM_FPS_REGCL
-#define DPM_FPS_REGCL 0
-#endif
-// DPM_FPS_NT (round 6, profiles/r06_step_model.md): the rounds' re-reads of the frame state with the non-temporal cache policy.  A frame's
-// state is 1.3 MB, sixteen frames share an XCD's 4 MB L2 while two launches are in flight, and the rounds stream through all of it
-// every few tens of microseconds: with the default policy they keep evicting what the feature and registration kernels re-use.
-//   bit 0: the point loads (16 B x 64 per touched bucket), bit 1: the `closest` loads and stores.
-#ifndef DPM_FPS_NT
-#define DPM_FPS_NT 0
-#endif
-#ifndef DPM_FPS_XBCAST
-#define DPM_FPS_XBCAST 0
-#endif
-typedef float fps_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 fps_load_point(const float4 *p) {
-    if (DPM_FPS_NT & 1) {
-        const fps_f4 v = __builtin_nontemporal_load((const fps_f4 *)p);
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *p;
-}
-__device__ __forceinline__ float fps_load_closest(const float *p) { return (DPM_FPS_NT & 2) ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void fps_store_closest(float *p, float v) {
-    if (DPM_FPS_NT & 2) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+// a point of the sorted frame.  It stays a function on purpose: written as a plain `pts[q]` in the round loop the compiler swaps
+// the operands of two additions of the distance that follows (profiles/csrc_prune_isa.md), and the rounds' code was to stay as it is
+__device__ __forceinline__ float4 fps_load_point(const float4 *p) { return *p; }
 
 // Timing-only ablations of a round (-DDPM_FPS_ABLATE=bits, WRONG RESULTS; profiles/r06_step_model.md asks which part of a round the
 // kernels next to it pay for): bit 0 = no bucket updates (no global loads / stores, no per-bucket arg-max), bit 1 = no exchange (no
@@ -268,7 +242,7 @@ __device__ __forceinline__ void fps_store_closest(float *p, float v) {
 // after the previous one, so that all variants keep their workgroups resident equally long.
 // Both are kernel arguments of the EXPERIMENT instantiation only (run-time values of -DDPM_EXPERIMENT builds: DPM_FPS_ABLATE, DPM_FPS_PACE in
 // the environment); the shipped instantiation has them folded to 0.
-template <bool REGCL, bool EXP = false>
+template <bool EXP = false>
 __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict__ xyz_all,
                                                         const int32_t *__restrict__ lengths, int N, int K,
                                                         const float4 *__restrict__ pts_all,
@@ -287,14 +261,8 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
         if (x < 0 || x >= exp_xcds) return;
         frame = (int)(blockIdx.x >> 3) * exp_xcds + x;
     }
-#ifdef DPM_FPS_PRIO   // wave priority of the sampling waves (A/B builds; round 3 and round 6 measured no effect on the rounds)
-    __builtin_amdgcn_s_setprio(DPM_FPS_PRIO);
-#endif
     constexpr int NW = FB / 64;
-#ifndef DPM_FPS_OB
-#define DPM_FPS_OB 2048
-#endif
-    constexpr int OB = DPM_FPS_OB;  // picks buffered in LDS between flushes to global memory
+    constexpr int OB = 2048;  // picks buffered in LDS between flushes to global memory
     // per-wave bests, double-buffered by round parity: [parity][value, index bits, x, y, z][wave] in ONE block, so
     // a wave's five fields are one address plus immediate offsets
     __shared__ float s_ex[2][5][NW];
@@ -330,23 +298,6 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
         x1 = wave_max_dpp(x1), y1 = wave_max_dpp(y1), z1 = wave_max_dpp(z1);
         if (lane == l) bx0 = x0, by0 = y0, bz0 = z0, bx1 = x1, by1 = y1, bz1 = z1;
     }
-    // two 32-wide register vectors (a C array indexed by a run-time value goes to scratch memory; a vector element addressed by a
-    // wave-uniform index is one v_movrels / v_movreld through M0)
-    typedef float f32x32 __attribute__((ext_vector_type(32)));
-    f32x32 cl_lo, cl_hi;
-    if (REGCL) {
-#pragma unroll
-        for (int l = 0; l < 32; ++l) {
-            const int qa = (l * NW + w) * 64 + lane, qb = ((l + 32) * NW + w) * 64 + lane;
-            cl_lo[l] = qa < len ? closest[qa] : -1.f;   // +inf for points, -1 for the packing's unused slots (written by the sort)
-            cl_hi[l] = qb < len ? closest[qb] : -1.f;
-        }
-    }
-    auto cl_get = [&](int l) -> float { return l < 32 ? cl_lo[l & 31] : cl_hi[l & 31]; };   // l is wave-uniform: a scalar branch
-    auto cl_put = [&](int l, float v) {
-        if (l < 32) cl_lo[l & 31] = v;
-        else cl_hi[l & 31] = v;
-    };
     const int s0 = start ? min(max(start[b], 0), max(true_len - 1, 0)) : 0;  // `random_start_point` (utils.py:248)
     if (t == 0) {
         idx[0] = s0;  // slot 0 is index 0 even for an empty frame (utils.py:249-250)
@@ -403,11 +354,11 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
             // lanes are masked out of the values below): no exec-mask juggling around the four loads
             const int q0c = min(q0, len - 1), q1c = min(q1, len - 1);
             const float4 p0 = fps_load_point(pts + q0c);
-            const float c0 = REGCL ? cl_get(l0) : fps_load_closest(closest + q0c);
+            const float c0 = closest[q0c];
             float4 p1;
             float c1;
-            if (two) p1 = fps_load_point(pts + q1c), c1 = REGCL ? cl_get(l1) : fps_load_closest(closest + q1c);  // wave-uniform: a scalar branch; an unused load would still
-                                                                        // have to be waited for before its registers are reused
+            if (two) p1 = fps_load_point(pts + q1c), c1 = closest[q1c];  // wave-uniform: a scalar branch; an unused load would still have to be waited for
+                                                        // before its registers are reused
             if (first && !keep) {
                 // ... and while they are in flight: the best among this wave's UNCHANGED buckets
                 wl = wave_argbest(act ? -1.f : bmax, bidx, wv);
@@ -418,8 +369,7 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
                 const int o0 = ok0 ? __float_as_int(p0.w) : 0x7fffffff;
                 const float d = sqdist(sx, sy, sz, p0.x, p0.y, p0.z);
                 const bool lt = ok0 && d < c0;
-                if (REGCL) cl_put(l0, lt ? d : c0);
-                else if (lt) fps_store_closest(closest + q0, d);
+                if (lt) closest[q0] = d;
                 const float v0 = lt ? d : (ok0 ? c0 : -1.f);
                 float vmax;
                 const int L = wave_argbest(v0, o0, vmax);
@@ -432,8 +382,7 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
                 const int o1 = ok1 ? __float_as_int(p1.w) : 0x7fffffff;
                 const float d = sqdist(sx, sy, sz, p1.x, p1.y, p1.z);
                 const bool lt = ok1 && d < c1;
-                if (REGCL) cl_put(l1, lt ? d : c1);
-                else if (lt) fps_store_closest(closest + q1, d);
+                if (lt) closest[q1] = d;
                 const float v1 = lt ? d : (ok1 ? c1 : -1.f);
                 float vmax;
                 const int L = wave_argbest(v1, o1, vmax);
@@ -462,39 +411,6 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
         FPS_T(3);
         // cross-wave arg-max: lane reads entry (lane & 15), 16-lane row reduction, winner's fields by broadcast reads
         const int e = lane & (NW - 1);
-#if DPM_FPS_XBCAST
-        // (experiment of round 6, profiles/r06_fps.md) ONE LDS round trip: every lane reads candidate (lane & 15) whole, the winner's
-        // fields are spread over the row with row_newbcast DPP moves -- the lane is an immediate, hence the 16-way scalar branch
-        const float *rec = &s_ex[par][0][e];
-        const float ev = rec[0];
-        const int ei = __float_as_int(rec[NW]);
-        const float ex_ = rec[2 * NW], ey_ = rec[3 * NW], ez_ = rec[4 * NW];
-        const float gv = row16_max_f(ev);
-        unsigned eqm = (unsigned)(__ballot(ev == gv) & 0xFFFFull);
-        if (__popc(eqm) > 1) {  // equal maxima in different waves: smallest original index wins
-            const int imin = row16_min_i(ev == gv ? ei : 0x7fffffff);
-            eqm = (unsigned)(__ballot(ev == gv && ei == imin) & 0xFFFFull);
-        }
-        const int gw = __builtin_ctz(eqm);
-        int gi;
-#define DPM_BC(K)                                                                                                           \
-    case K:                                                                                                                 \
-        gi = __builtin_amdgcn_update_dpp(ei, ei, 0x150 + K, 0xF, 0xF, false);                                               \
-        sx = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ex_), __float_as_int(ex_), 0x150 + K, 0xF, 0xF, false)); \
-        sy = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ey_), __float_as_int(ey_), 0x150 + K, 0xF, 0xF, false)); \
-        sz = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ez_), __float_as_int(ez_), 0x150 + K, 0xF, 0xF, false)); \
-        break;
-        switch (gw) {
-            DPM_BC(0) DPM_BC(1) DPM_BC(2) DPM_BC(3) DPM_BC(4) DPM_BC(5) DPM_BC(6) DPM_BC(7) DPM_BC(8) DPM_BC(9) DPM_BC(10) DPM_BC(11)
-            DPM_BC(12) DPM_BC(13) DPM_BC(14)
-            default:
-                gi = __builtin_amdgcn_update_dpp(ei, ei, 0x15F, 0xF, 0xF, false);
-                sx = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ex_), __float_as_int(ex_), 0x15F, 0xF, 0xF, false));
-                sy = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ey_), __float_as_int(ey_), 0x15F, 0xF, 0xF, false));
-                sz = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ez_), __float_as_int(ez_), 0x15F, 0xF, 0xF, false));
-        }
-#undef DPM_BC
-#else
         const float ev = s_ex[par][0][e];
         const float gv = row16_max_f(ev);
         unsigned eqm = (unsigned)(__ballot(ev == gv) & 0xFFFFull);
@@ -507,7 +423,6 @@ __global__ __launch_bounds__(FB) void fps_bucket_kernel(const float *__restrict_
         const float *gx = &s_ex[par][1][gw];
         const int gi = __float_as_int(gx[0]);
         sx = gx[NW], sy = gx[2 * NW], sz = gx[3 * NW];
-#endif
         if (t == 0) {
             const int o = r & (OB - 1);
             s_oidx[o] = gi, s_oxyz[o][0] = sx, s_oxyz[o][1] = sy, s_oxyz[o][2] = sz;
@@ -593,12 +508,12 @@ static int fps_dispatch(const float *xyz, const int32_t *lengths, const int32_t 
             int xcds = dpm_knob("DPM_FPS_XCDS", 0);
             if (xcds > 0 && (B % xcds != 0 || 8 % xcds != 0)) xcds = 0;
             const int base = xcds > 0 ? (launches++ % (8 / xcds)) * xcds : 0;   // consecutive launches take consecutive XCD groups
-            hipLaunchKernelGGL((fps_bucket_kernel<DPM_FPS_REGCL != 0, true>), dim3(xcds > 0 ? B / xcds * 8 : B), dim3(FB), 0, st, xyz, lengths, N, K,
+            hipLaunchKernelGGL((fps_bucket_kernel<true>), dim3(xcds > 0 ? B / xcds * 8 : B), dim3(FB), 0, st, xyz, lengths, N, K,
                                pts, closest, idx, new_xyz, new_lengths, slots, start, dpm_knob("DPM_FPS_ABLATE", 0), dpm_knob("DPM_FPS_PACE", 0),
                                xcds, base);
         }
 #else
-        hipLaunchKernelGGL(fps_bucket_kernel<DPM_FPS_REGCL != 0>, dim3(B), dim3(FB), 0, st, xyz, lengths, N, K, pts, closest, idx, new_xyz,
+        hipLaunchKernelGGL(fps_bucket_kernel<false>, dim3(B), dim3(FB), 0, st, xyz, lengths, N, K, pts, closest, idx, new_xyz,
                            new_lengths, slots, start, 0, 0);
 #endif
         return dpm_launch_status();
@@ -613,7 +528,7 @@ static int fps_dispatch(const float *xyz, const int32_t *lengths, const int32_t 
 #endif
         float *closest = (float *)(pts + (size_t)B * N);
         hipLaunchKernelGGL(fps_bucket_sort_kernel, dim3(B), dim3(FB), 0, st, xyz, lengths, N, pts, closest);
-        hipLaunchKernelGGL(fps_bucket_kernel<DPM_FPS_REGCL != 0>, dim3(B), dim3(FB), 0, st, xyz, lengths, N, K, pts, closest, idx,
+        hipLaunchKernelGGL(fps_bucket_kernel<false>, dim3(B), dim3(FB), 0, st, xyz, lengths, N, K, pts, closest, idx,
                            new_xyz, new_lengths, 0, start, 0, 0);
         return dpm_launch_status();
     }

@@ -288,14 +288,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF == 1 ? 4
 // bits and the two-kernel form -- dpm_linear_bf16x3 + dpm_layernorm -- gives identical rows); WGM x WGN waves of (BM / WGM) x
 // (BN / WGN), 512 threads at 256 columns.  The epilogue stages the whole tile in LDS (inside the operand planes' footprint)
 // and normalises it row-wise with the lane-group arithmetic of layernorm_vec_kernel / gemm_ln_kernel.
-// NP > 1: the BN columns in NP passes of BN / NP over the same rows (X staged and split again per pass, W tile and LDS footprint
-// 1 / NP as large, the accumulators of all passes kept): 32 x 256 with NP = 2 has gemm_b3_kernel's loop, wave tile and 38 KB.
-template <int BM, int BN, int WGM, int WGN, int NP = 1>
+// NP: the kernel is written for the BN columns in NP passes of BN / NP over the same rows (X staged and split again per pass, W tile
+// and LDS footprint 1 / NP as large, the accumulators of all passes kept).  Only one pass is built: the two-pass form of 256 columns
+// lost (dpm_linear_layernorm_bf16x3 has the numbers) and left the tree.  NP stays as a constant of 1 because the kernel written
+// without its pass loop compiles to other instructions (profiles/csrc_prune_isa.md).
+template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_ln_b3_kernel(const float *__restrict__ X, int ldx, const uint16_t *__restrict__ Wp,
                                                                    int ldw, long long plane, const float *__restrict__ bias,
                                                                    const float *__restrict__ pre, const float *__restrict__ gamma,
                                                                    const float *__restrict__ beta, const float *__restrict__ post,
                                                                    float *__restrict__ out, int ldo, int R, int Cin, int act) {
+    constexpr int NP = 1;                                      // column passes
     constexpr int BNP = BN / NP;                               // columns per pass
     constexpr int T = 64 * WGM * WGN, WM = BM / WGM, WN = BNP / WGN, MB = WM / 16, NB = WN / 16, LDC = BN + 4;
     constexpr int XF = BM * 8, PX = (XF + T - 1) / T;          // float4 groups of the X tile, per thread
@@ -714,20 +717,18 @@ extern "C" int dpm_linear_layernorm_bf16x3(const float *x, int ldx, const void *
         !al(bias) || !al(pre) || !al(gamma) || !al(beta) || !al(post) || !al(out))
         return DPM_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-#define DPM_GLN3(BM, BN, WGM, WGN, NP)                                                                                         \
-    hipLaunchKernelGGL((gemm_ln_b3_kernel<BM, BN, WGM, WGN, NP>), dim3(dpm_cdiv(R, BM)), dim3(64 * WGM * WGN), 0, st, x, ldx,       \
+#define DPM_GLN3(BM, BN, WGM, WGN)                                                                                             \
+    hipLaunchKernelGGL((gemm_ln_b3_kernel<BM, BN, WGM, WGN>), dim3(dpm_cdiv(R, BM)), dim3(64 * WGM * WGN), 0, st, x, ldx,       \
                        (const uint16_t *)w_planes, ldw, plane_stride, bias, pre, gamma, beta, post, out, ldo, R, Cin, act)
     // every configuration gives the same bits (same instructions in the same order per output element).  256 columns: 64 rows
     // in one pass, 512 threads (wave tile 32 x 64, X split once).  History: with the first version's padded LDS rows this form
     // was faster alone (44 against 59 us) and made the pipelined step LONGER, so 32 rows x two passes of 128 columns (256
     // threads, 38 KB) shipped for a while; with the swizzled rows (half the LDS cycles) the one-pass form wins both ways:
-    // 4.19-4.20 against 4.27 ms per step.
-    if (Cout == 256) {
-        if (dpm_knob("DPM_GLN3_TWOPASS", 0)) DPM_GLN3(32, 256, 1, 4, 2);
-        else DPM_GLN3(64, 256, 2, 4, 1);
-    } else if (Cout == 128) DPM_GLN3(64, 128, 2, 2, 1);
-    else if (Cout == 64) DPM_GLN3(64, 64, 2, 2, 1);
-    else if (Cout == 32) DPM_GLN3(64, 32, 2, 2, 1);
+    // 4.19-4.20 against 4.27 ms per step, and the two-pass form is no longer built.
+    if (Cout == 256) DPM_GLN3(64, 256, 2, 4);
+    else if (Cout == 128) DPM_GLN3(64, 128, 2, 2);
+    else if (Cout == 64) DPM_GLN3(64, 64, 2, 2);
+    else if (Cout == 32) DPM_GLN3(64, 32, 2, 2);
     else return DPM_EUNSUPPORTED;
 #undef DPM_GLN3
     return dpm_launch_status();

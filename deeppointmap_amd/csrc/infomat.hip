@@ -339,7 +339,6 @@ __device__ __forceinline__ float quad_min(float v) {
 //  * the moments are summed as 64-bit integers (see the end of the kernel), so the result does not depend on the order the
 //    queries are walked in.
 __global__ __launch_bounds__(256) void nn1_match_kernel(PairArgs A, float r2, int ordered) {
-    valu_bound_priority();
     int pair, blk;
     pair_block(blk, pair);
     const float *p1 = pair_p1(A, pair);

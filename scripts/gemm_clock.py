@@ -1,10 +1,9 @@
-"""Shader clock / socket power (rocm-smi) while one GEMM variant runs in a loop: is a dense fp32-MFMA kernel power-limited?
-DPM_LIB=<experimental library> python scripts/gemm_clock.py"""
+"""Shader clock / socket power (rocm-smi) while the fp32 GEMM runs in a loop: is a dense fp32-MFMA kernel power-limited?
+python scripts/gemm_clock.py"""
 import json, os, subprocess, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from deeppointmap_amd import _lib, ops
-assert _lib.experimental()
+from deeppointmap_amd import ops
 dev = "cuda"
 x = torch.randn(32768, 256, device=dev); W = torch.randn(768, 256, device=dev) / 16; b = torch.randn(768, device=dev)
 out = torch.empty(32768, 768, device=dev)
@@ -16,8 +15,7 @@ def smi():
     return {k: v for k, v in card.items() if "sclk" in k.lower() or "power" in k.lower() or "mclk" in k.lower()}
 
 
-for mode, what in ((0, "64 x 64 kernel"), (1, "wave-specialised"), (2, "wave-specialised, paced"), (17, "wave-specialised, no memory traffic")):
-    os.environ["DPM_GEMM_WS"] = str(mode)
+for what in ("64 x 64 kernel",):
     got = []
     th = threading.Thread(target=lambda: (time.sleep(1.2), got.append(smi()), time.sleep(0.8), got.append(smi())))
     th.start()

@@ -69,6 +69,28 @@ def test_attention_core_vs_torch(ops):
         assert torch.equal(got, want), (U, M, B)
 
 
+def test_attention_every_launch_form_vs_torch(ops):
+    """The smallest shapes that take each launch of the head-width-32 kernel (attention_launch, csrc/decoder_ops.hip): eight waves
+    per workgroup (M >= 1024 in whole 128s, aligned rows), four waves, rows whose stride is no multiple of four floats (scalar
+    K / V loads and output stores), and a key mask in both row forms -- against fp64 torch like test_attention_core_vs_torch."""
+    gen = torch.Generator().manual_seed(17)
+    for B, M, N, pad, masked in [(1, 1024, 64, 0, False), (1, 128, 64, 0, False), (1, 128, 64, 3, False), (2, 64, 64, 0, True),
+                                 (2, 64, 64, 3, True)]:
+        q, k, v = (torch.randn(B * n, 256 + pad, generator=gen) for n in (M, N, N))
+        mask = torch.rand(B, N, generator=gen) < 0.3
+        mask[:, 0] = False
+        out = ops.attention(q.to(DEV)[:, :256], k.to(DEV)[:, :256], v.to(DEV)[:, :256], B, M, N, 8,
+                            key_mask=mask.view(torch.uint8).to(DEV) if masked else None).cpu()
+        qh = q[:, :256].reshape(B, M, 8, 32).transpose(1, 2).double()
+        kh = k[:, :256].reshape(B, N, 8, 32).transpose(1, 2).double()
+        vh = v[:, :256].reshape(B, N, 8, 32).transpose(1, 2).double()
+        sc = qh @ kh.transpose(-1, -2) / 32 ** 0.5
+        if masked:
+            sc = sc.masked_fill(mask[:, None, None, :], float("-inf"))
+        want = (torch.softmax(sc, -1) @ vh).transpose(1, 2).reshape(B * M, 256).float()
+        torch.testing.assert_close(out, want, rtol=1e-4, atol=2e-5)
+
+
 def test_attention_key_split_vs_torch(ops):
     """few queries against many keys (scan tokens attending a map tile) run key-split (dpm_attention_split): against fp64
     torch, against the plain kernel, ragged last ranges, strided operands and shifted keys; the split count depends on the

@@ -329,6 +329,26 @@ def test_fused_linear_layernorm_kernel_vs_torch(ops, monkeypatch, ln_b3):
         assert torch.equal(fused, split), key
 
 
+def test_fused_bf16x3_layernorm_gemm_smallest_shapes_vs_torch(ops, monkeypatch):
+    """dpm_linear_layernorm_bf16x3 at every width it launches, one 64-row workgroup and four K-tiles each: against the fp64
+    reference of the test above, at its tolerance, and equal to the two-kernel form bit for bit."""
+    from deeppointmap_amd import knobs
+    monkeypatch.setattr(knobs, "GEMM_BF16X3", True)
+    monkeypatch.setattr(knobs, "GEMM_LN_BF16X3", True)
+    gen = torch.Generator(device=DEV).manual_seed(19)
+    for R, Cin, Cout in [(64, 128, 256), (64, 128, 128), (64, 128, 64), (64, 128, 32)]:
+        x = torch.randn(R, Cin, device=DEV, generator=gen)
+        W = torch.randn(Cout, Cin, device=DEV, generator=gen) / Cin ** 0.5
+        b, gm, bt = (torch.randn(Cout, device=DEV, generator=gen) for _ in range(3))
+        pre, post = (torch.randn(R, Cout, device=DEV, generator=gen) for _ in range(2))
+        monkeypatch.setattr(ops, "FUSED_LN_MIN_ROWS", 0)
+        y = ops.linear_layernorm(x, W, b, gm, bt, act=ops.ACT_RELU, pre=pre, post=post)
+        z = torch.nn.functional.layer_norm(x.double() @ W.double().t() + b.double() + pre.double(), (Cout,), gm.double(), bt.double(), 1e-5)
+        torch.testing.assert_close(y, torch.relu(z + post.double()).float(), rtol=2e-5, atol=5e-5)
+        monkeypatch.setattr(ops, "FUSED_LN_MIN_ROWS", 1 << 30)
+        assert torch.equal(y, ops.linear_layernorm(x, W, b, gm, bt, act=ops.ACT_RELU, pre=pre, post=post)), Cout
+
+
 def test_bf16x3_linear_vs_fp64_and_layout_independence(ops, monkeypatch):
     """The bf16x3 GEMM (csrc/gemm_b3.hip: every fp32 operand split exactly into three bf16 terms, six term products accumulated
     in fp32) is what ops.linear runs for layers with K <= 512 when knobs.GEMM_BF16X3 is set: (i) its error against fp64 is at the level of the exact-fp32 MFMA
@@ -421,6 +441,19 @@ def test_linear_large_tiles_vs_torch(ops):
     Wb = torch.randn(2, 1024, 1024, device=DEV, generator=gen) / 32
     yb = ops.similarity_batched(xb, Wb)
     torch.testing.assert_close(yb, torch.bmm(xb.double(), Wb.double().transpose(1, 2)).float(), rtol=1e-5, atol=3e-5)
+
+
+def test_linear_fp32_every_tile_and_load_form_vs_torch(ops):
+    """dpm_linear's fp32 kernel at the smallest shapes that take each of its launches: 32 x 32 tiles and 64 x 64 tiles (more than
+    1024 rows), each with whole K-tiles, with a reduction that is a multiple of 4 only (16-byte loads, k tail tested) and with an odd
+    one (scalar loads) -- against an fp64 product like test_linear_layernorm_interp_vs_torch."""
+    gen = torch.Generator().manual_seed(23)
+    for R, Cin, Cout in [(64, 64, 128), (64, 36, 128), (64, 63, 128), (1025, 64, 36), (1025, 36, 36), (1025, 35, 36)]:
+        x, W, b = torch.randn(R, Cin, generator=gen), torch.randn(Cout, Cin, generator=gen) / Cin ** 0.5, torch.randn(Cout, generator=gen)
+        res = torch.randn(R, Cout, generator=gen)
+        y = ops.linear(x.to(DEV), W.to(DEV), b.to(DEV), act=ops.ACT_RELU, residual=res.to(DEV), exact=True).cpu()
+        want = torch.relu(x.double() @ W.double().t() + b.double() + res.double()).float()
+        torch.testing.assert_close(y, want, rtol=1e-5, atol=2e-5)
 
 
 def test_three_interp_vs_oracle(ops):
