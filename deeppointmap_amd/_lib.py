@@ -136,6 +136,9 @@ SIGNATURES = {
     "dpm_map_assemble_bwd": (I, [P, P, I, I, I, I, I, P, P]),
     "dpm_optim_chunk": (I, []),
     "dpm_optim_step": (I, [I, P, P, I, D, D, D, D, D, D, D, D, I, I, P]),
+    "dpm_flat_pack": (I, [P, P, I, P, LL, P]),
+    "dpm_flat_unpack": (I, [P, P, I, P, LL, P]),
+    "dpm_optim_step_synced": (I, [I, P, P, I, D, D, D, D, D, D, D, D, I, I, P, I, LL, D, P]),
 }
 
 

@@ -9,6 +9,10 @@ rebuilt only when an address changes (a gradient re-allocated after `zero_grad()
 `param_groups` on every step, so torch's schedulers drive these classes unchanged.  `step()` never waits for the device: the
 step counters are CPU tensors, as in torch's default (non-capturable) optimisers.
 
+Data-parallel training: `attach_grad_sync(sync)` (a `data_parallel.GradSync`) makes `step()` pack the gradients into one flat
+buffer, exchange it in one collective and run the same update rule on the rank-ordered mean in the same launch.  Not attached,
+nothing changes.
+
 Not supported, `ValueError`: `amsgrad=True`, `maximize=True`, parameters that are not fp32 or not on the GPU, sparse gradients.
 `foreach`, `fused`, `capturable` and `differentiable` are accepted and stored for state-dict compatibility; they select nothing.
 """
@@ -28,18 +32,29 @@ ADAMW, ADAM, SGD_ = 0, 1, 2   # include/dpm_hip.h: DPM_OPTIM_*
 _MAX_PLANS = 8
 
 
+def chunk_table(numels, chunk: int) -> np.ndarray:
+    """(n_chunks,2) int32 [tensor, chunk]: row k covers elements [chunk * CHUNK, min(numel, (chunk + 1) * CHUNK)) of its tensor"""
+    counts = (np.asarray(numels, np.int64) + chunk - 1) // chunk
+    which = np.repeat(np.arange(len(counts), dtype=np.int32), counts)
+    first = np.cumsum(counts) - counts
+    within = (np.arange(int(counts.sum()), dtype=np.int64) - np.repeat(first, counts)).astype(np.int32)
+    return np.stack([which, within], axis=1)
+
+
+def _addr(g) -> int:
+    """column 1 of a table row: a gradient's address, or the offset that stands in for it in a synced step"""
+    return g if isinstance(g, int) else g.data_ptr()
+
+
 class _Plan:
-    """the two device tables of one launch (and the pinned host copy they were sent from, which must outlive the transfer)"""
+    """the two device tables of one launch (and the pinned host copy they were sent from, which must outlive the transfer);
+    rows: one list of int64 per tensor, the last entry its numel"""
 
     def __init__(self, rows: List[List[int]], chunk: int, device):
-        tensors = np.asarray(rows, np.int64).reshape(-1, 5)
-        counts = (tensors[:, 4] + chunk - 1) // chunk
-        which = np.repeat(np.arange(len(rows), dtype=np.int32), counts)
-        first = np.cumsum(counts) - counts
-        within = (np.arange(int(counts.sum()), dtype=np.int64) - np.repeat(first, counts)).astype(np.int32)
-        chunks = np.stack([which, within], axis=1).reshape(-1)
-        self.n_chunks = int(counts.sum())
-        blob = np.concatenate([tensors.reshape(-1).view(np.int32), chunks])
+        tensors = np.asarray(rows, np.int64).reshape(len(rows), -1)
+        chunks = chunk_table(tensors[:, -1], chunk)
+        self.n_chunks = len(chunks)
+        blob = np.concatenate([tensors.reshape(-1).view(np.int32), chunks.reshape(-1)])
         self.host = torch.from_numpy(blob).pin_memory()
         self.dev = self.host.to(device, non_blocking=True)
         self.tensors_ptr = self.dev.data_ptr()
@@ -57,6 +72,7 @@ class _GroupStep(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._plans: Dict[tuple, _Plan] = {}
         self.plan_builds = 0   # how often the device tables were (re)built: only when an address changed
+        self._sync = None      # a data_parallel.GradSync: attach_grad_sync()
         for group in self.param_groups:
             for p in group["params"]:
                 self._check_param(p)
@@ -81,6 +97,46 @@ class _GroupStep(torch.optim.Optimizer):
                 st["step"] = st["step"].detach().to("cpu", torch.float32)
         self._plans.clear()
 
+    def attach_grad_sync(self, sync) -> None:
+        """Data-parallel steps: from now on `step()` packs the local gradients into `sync`'s flat buffer, runs its one collective
+        and updates EVERY tensor of its layout from the exchanged buffer in one launch per parameter group -- also a tensor whose
+        gradient is None on this rank (it contributes zeros, the other ranks' gradients still move it: all ranks stay identical).
+        State keys, step counting, `lr` from `param_groups` and the version bump are those of the plain step.  `p.grad` keeps the
+        LOCAL gradient: the average is never written back.  An inert `sync` (no process group, or one rank and no force) leaves
+        the plain step in place."""
+        ids = {id(p) for group in self.param_groups for p in group["params"]}
+        missing = [i for i, p in enumerate(sync.params) if id(p) not in ids]
+        if missing:
+            raise ValueError(f"{len(missing)} tensors of the GradSync layout are not parameters of this optimiser")
+        self._sync = sync
+        self._plans.clear()
+
+    def detach_grad_sync(self) -> None:
+        self._sync = None
+        self._plans.clear()
+
+    def _synced(self) -> bool:
+        return self._sync is not None and self._sync.active
+
+    def _items(self, group):
+        """(parameter, gradient) of the tensors of `group` that this step updates: those with a gradient -- or, with a grad
+        sync attached, (parameter, element offset into a slice) of those the layout holds"""
+        for p in group["params"]:
+            if self._synced():
+                off = self._sync.offset_of(p)
+                if off is not None:
+                    self._check_device(p)
+                    yield p, off
+            elif p.grad is not None:
+                yield p, self._grad(p)
+
+    @staticmethod
+    def _check_device(p):
+        if not p.is_cuda:
+            raise _lib.DpmError(f"parameters and gradients must be on the GPU, got {p.device} (no CPU fallback)")
+        if not p.is_contiguous():
+            raise ValueError("parameters must be contiguous (a view at an offset is fine, a strided one is not)")
+
     def _grad(self, p):
         g = p.grad
         if g.is_sparse:
@@ -97,7 +153,7 @@ class _GroupStep(torch.optim.Optimizer):
         """rows: [param, grad, state0, state1, numel] per tensor of `params`.  A gradient made contiguous for this call is freed on return;
         the caching allocator hands its memory out again only in stream order, after the kernel."""
         lib = _lib.load()
-        key = tuple(map(tuple, rows))
+        key = (self._synced(), *map(tuple, rows))
         plan = self._plans.get(key)
         if plan is None:
             if len(self._plans) >= _MAX_PLANS:
@@ -108,9 +164,14 @@ class _GroupStep(torch.optim.Optimizer):
                  first=0)
         a.update(scalars)
         stream = torch.cuda.current_stream(device)
-        _lib.check(lib.dpm_optim_step(algo, plan.tensors_ptr, plan.chunks_ptr, plan.n_chunks, a["lr"], a["beta1"], a["beta2"],
-                                      a["eps"], a["weight_decay"], a["step"], a["momentum"], a["dampening"], int(a["nesterov"]),
-                                      int(a["first"]), stream.cuda_stream), "dpm_optim_step")
+        common = (algo, plan.tensors_ptr, plan.chunks_ptr, plan.n_chunks, a["lr"], a["beta1"], a["beta2"], a["eps"],
+                  a["weight_decay"], a["step"], a["momentum"], a["dampening"], int(a["nesterov"]), int(a["first"]))
+        if self._synced():   # rows hold offsets into a slice of the exchanged buffer instead of gradient addresses
+            slices, n_slices, stride, divisor = self._sync.slices()
+            _lib.check(lib.dpm_optim_step_synced(*common, slices.data_ptr(), n_slices, stride, float(divisor), stream.cuda_stream),
+                       "dpm_optim_step_synced")
+        else:
+            _lib.check(lib.dpm_optim_step(*common, stream.cuda_stream), "dpm_optim_step")
         for p in params:   # an in-place update torch did not see: the derived-weight caches and captured graphs key on this
             torch.autograd.graph.increment_version(p)
 
@@ -120,6 +181,9 @@ class _GroupStep(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._synced():
+            self._sync.pack()
+            self._sync.exchange()
         for group in self.param_groups:
             self._step_group(group)
         return loss
@@ -142,10 +206,7 @@ class Adam(_GroupStep):
 
     def _step_group(self, group):
         by_step: Dict[float, list] = {}
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            g = self._grad(p)
+        for p, g in self._items(group):
             st = self.state[p]
             if len(st) == 0:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
@@ -155,7 +216,7 @@ class Adam(_GroupStep):
             by_step.setdefault(float(st["step"]), []).append((p, g, st))
         algo = ADAMW if group.get("decoupled_weight_decay", self.DECOUPLED) else ADAM
         for step, items in by_step.items():   # one launch unless earlier steps skipped some tensors (`grad is None`)
-            rows = [[p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
+            rows = [[p.data_ptr(), _addr(g), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
                     for p, g, st in items]
             self._launch(algo, [i[0] for i in items], rows, items[0][0].device, lr=group["lr"], beta1=group["betas"][0],
                          beta2=group["betas"][1], eps=group["eps"], weight_decay=group["weight_decay"],
@@ -189,10 +250,7 @@ class SGD(_GroupStep):
 
     def _step_group(self, group):
         old, new = [], []
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            g = self._grad(p)
+        for p, g in self._items(group):
             buf = None
             if group["momentum"] != 0:
                 st = self.state[p]
@@ -205,7 +263,8 @@ class SGD(_GroupStep):
         for first, items in ((1, new), (0, old)):
             if not items:
                 continue
-            rows = [[p.data_ptr(), g.data_ptr(), 0 if buf is None else buf.data_ptr(), 0, p.numel()] for p, g, buf in items]
+            rows = [[p.data_ptr(), _addr(g), 0 if buf is None else buf.data_ptr(), 0, p.numel()]
+                    for p, g, buf in items]
             self._launch(SGD_, [i[0] for i in items], rows, items[0][0].device, lr=group["lr"],
                          weight_decay=group["weight_decay"], momentum=group["momentum"], dampening=group["dampening"],
                          nesterov=group["nesterov"], first=first)

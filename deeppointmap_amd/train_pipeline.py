@@ -182,7 +182,7 @@ class DeepPointModelPipeline(nn.Module):
 
 
 class TrainStep:
-    """What pipeline/modules/trainer.py does around one optimiser step, without its DataLoader, tensorboard and DDP: the model,
+    """What pipeline/modules/trainer.py does around one optimiser step, without its DataLoader and tensorboard (its DDP: data_parallel.DataParallelTrainStep): the model,
     and the optimiser and scheduler that deeppointmap_amd.optim's factories build from `args.train.<stage>.optimizer` /
     `.scheduler` over the parameters the stage trains.  Epochs count from 1, as there."""
 
@@ -201,11 +201,16 @@ class TrainStep:
         if stage not in self.STAGES:
             raise ValueError(f"stage must be one of {self.STAGES}, got {stage!r}")
         self.stage = stage
-        getattr(self.model, stage)()
+        getattr(self.pipeline, stage)()
         cfg = self.train_cfg[stage] if isinstance(self.train_cfg, dict) else getattr(self.train_cfg, stage)
         self.optimizer = Optimizer(cfg.optimizer)(filter(lambda p: p.requires_grad, self.model.parameters()))
         self.scheduler = Scheduler(cfg.scheduler)(self.optimizer)
         self._entered = False
+
+    @property
+    def pipeline(self) -> DeepPointModelPipeline:
+        """the DeepPointModelPipeline itself (`self.model` may be a wrapper around it: data_parallel.DataParallelTrainStep)"""
+        return self.model
 
     def step(self, *data) -> dict:
         """model.train() once per epoch, forward, zero_grad, backward, optimizer.step() (trainer.py:159, 174-178)"""
@@ -238,17 +243,17 @@ class TrainStep:
 
     def state_dict(self) -> dict:
         """the reference's .ckpt layout"""
-        return {"encoder": self.model.encoder.state_dict(), "decoder": self.model.decoder.state_dict(),
+        return {"encoder": self.pipeline.encoder.state_dict(), "decoder": self.pipeline.decoder.state_dict(),
                 "optimizer": self.optimizer.state_dict(), "scheduler": self.scheduler.state_dict(),
                 "epoch": self.epoch, "step": self.step_count}
 
     def load_state_dict(self, state: dict) -> None:
-        self.model.encoder.load_state_dict(state["encoder"])
-        self.model.decoder.load_state_dict(state["decoder"])
+        self.pipeline.encoder.load_state_dict(state["encoder"])
+        self.pipeline.decoder.load_state_dict(state["decoder"])
         self.optimizer.load_state_dict(state["optimizer"])
         self.scheduler.load_state_dict(state["scheduler"])
         self.epoch, self.step_count = state["epoch"], state["step"]
 
     def weights(self) -> dict:
         """the reference's .pth layout"""
-        return {"encoder": self.model.encoder.state_dict(), "decoder": self.model.decoder.state_dict()}
+        return {"encoder": self.pipeline.encoder.state_dict(), "decoder": self.pipeline.decoder.state_dict()}

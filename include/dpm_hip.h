@@ -775,6 +775,30 @@ int dpm_optim_step(int algo, const long long *tensors, const int32_t *chunks, in
                    double eps, double weight_decay, double step, double momentum, double dampening, int nesterov, int first,
                    dpm_stream_t stream);
 
+/* Data-parallel training: the gradients of a stage in ONE flat fp32 buffer (csrc/optim.hip; replaces the per-tensor bucket copies
+ * of torch's DistributedDataParallel, which the reference wraps its model in at pipeline/modules/trainer.py:239-243).  table (T,3)
+ * int64 device table [address, offset, numel]: an fp32 tensor of numel elements and its element offset into flat (a multiple of 4
+ * by convention; any offset works, unaligned ones by scalar accesses); chunks as for dpm_optim_step.  flat[offset + i] =
+ * tensor[i]; address 0 (a gradient that is None on this rank) writes zeros.  Elements of flat outside every row -- the padding --
+ * are not touched.  flat_len: elements of flat, a multiple of 4; a row with offset + numel > flat_len moves nothing. */
+int dpm_flat_pack(const long long *table, const int32_t *chunks, int n_chunks, float *flat, long long flat_len,
+                  dpm_stream_t stream);
+/* The inverse, for the initial broadcast of rank 0's parameters (what DistributedDataParallel's constructor does,
+ * pipeline/modules/trainer.py:239-243): tensor[i] = flat[offset + i]; rows with address 0 are skipped. */
+int dpm_flat_unpack(const long long *table, const int32_t *chunks, int n_chunks, const float *flat, long long flat_len,
+                    dpm_stream_t stream);
+/* dpm_optim_step with the gradient taken from the exchanged flat buffers instead of a tensor (replaces DistributedDataParallel's
+ * all-reduce + unbucketing + the separate optimiser pass, pipeline/modules/trainer.py:239-243 and 176-178).  Column 1 of
+ * `tensors` is the tensor's element offset into a slice, not an address.  slices: n_slices >= 1 buffers of fp32, slice r at
+ * slices + r * slice_stride (slice_stride % 4 == 0, and offset + numel <= slice_stride for every row: others update nothing).
+ * Per element g = slice_0[i]; g = g + slice_r[i] for r = 1 .. n_slices - 1, in this order; g = g / (float)divisor (a true IEEE
+ * division, divisor >= 1); then the element rule of dpm_optim_step, the same code.  An all-gathered buffer passes n_slices = W,
+ * divisor = W; an all-reduced one n_slices = 1, divisor = W.  n_slices = 1, divisor = 1 is dpm_optim_step on that buffer. */
+int dpm_optim_step_synced(int algo, const long long *tensors, const int32_t *chunks, int n_chunks, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, double step, double momentum, double dampening,
+                          int nesterov, int first, const float *slices, int n_slices, long long slice_stride, double divisor,
+                          dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
