@@ -103,6 +103,8 @@ SIGNATURES = {
     "dpm_information_matrix_batched": (I, [P, I, P, P, I, P, I, D, P, I, P, P]),
     "dpm_infomat_build_grids": (I, [P, I, P, I, D, P, P]),
     "dpm_infomat_search_grids": (I, [P, I, P, P, I, P, I, D, P, I, P, P]),
+    "dpm_icp_workspace_bytes": (c_size_t, [I, I]),
+    "dpm_icp_refine_batched": (I, [P, I, I, P, P, P, P, I, P, I, P, P, I, D, D, P, P, P, P, P, P, P, P, P]),
     "dpm_voxel_map_workspace_bytes": (c_size_t, [LL]),
     "dpm_voxel_map_init": (I, [LL, P, P]),
     "dpm_voxel_map_bounds": (I, [P, P, P, I, LL, P, P]),

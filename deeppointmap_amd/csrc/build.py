@@ -41,6 +41,7 @@ SOURCES = {
     "decoder_ops.hip": [],
     "match.hip": [],
     "infomat.hip": [],
+    "icp.hip": [],
     "preprocess.hip": [],
     "voxel_sample.hip": [],
     "posegraph.hip": [],

@@ -1,0 +1,442 @@
+// Batched ICP: refines the relative pose of P scan pairs at once.  Stands in for the offline third-party ICP that made the
+// reference's per-scene refined_SE3.pkl (read by pipeline/modules/model_pipeline.py:199-282 through get_SE3_from_dict; no
+// file of the reference writes it).
+//
+// Target side, once per call: every pair's target scan is counting-sorted into a pose-independent 2-D xy grid -- the layout
+// of csrc/infomat.hip (cell edge half the radius and 5x5 cells, or one radius and 3x3 cells when that needs more than GMAX
+// cells per axis), built here by a pass of its own (setup, count, scan, scatter) that honours the per-frame point counts.
+// The order of the points inside a cell depends on scheduling (integer atomics); nothing downstream depends on it.
+//
+// Per iteration, two launches for all pairs together and no host synchronisation:
+//   accumulate: four lanes per source point scan the cells around the transformed point; the winner is the smallest
+//               (distance bits, original index) key, as in nn1_match_kernel.  Lane 0 of the quad adds the match's
+//               Gauss-Newton rows to 29 fp64 running sums (21 of H, 6 of g, count, squared residuals).  Queries are walked
+//               in INDEX order, the lanes / waves of a block are summed in a fixed tree and every block leaves one partial:
+//               the sums do not depend on scheduling.  No floating-point atomics.
+//   solve:      one wave per pair adds the partials in block order, solves H x = -g by Cholesky with a pivot test, composes
+//               the step onto the pose and sets the pair's `done` flag; blocks of a done pair return at once.
+// The step x = (w, v) moves a transformed point p' to p' + w x p' + v; it is applied as pose <- [exp(w) | v] o pose
+// (Rodrigues rotation, the translation taken as it is).
+#include "dpm_common.h"
+
+namespace {
+
+constexpr int GMAX = 512;   // grid cells per axis (upper bound)
+constexpr int NSUM = 29;    // H upper triangle (21), g (6), matches, sum of squared residuals
+constexpr int NSUM_PAD = 32;
+constexpr double PIV_EPS = 1e-9;  // a Cholesky pivot below PIV_EPS * (largest diagonal entry of its 3x3 block) is singular
+
+struct IcpHdr {   // start of every pair's workspace slice (256 bytes reserved)
+    float lox, loy, inv_cs;
+    int gx, gy, ncell, H;
+    int n1, n2;        // valid points of the source / target frame
+    int fs, fd;        // frame indices, clamped into [0, F)
+    int done;
+};
+
+struct IcpArgs {
+    const float *pcd;          // (F,3,N)
+    const float *normals;      // (F,N,3) or NULL (point metric)
+    const int32_t *lengths, *src, *dst;
+    int F, N, n_pairs;
+    char *ws;
+    size_t ws_stride;
+    double *pose;              // (P,16)
+    float *fitness, *rmse;
+    int32_t *iterations, *status;
+    int32_t *dbg_match;        // (P,N) or NULL
+    double *dbg_system;        // (P,NSUM) or NULL
+};
+
+__device__ __forceinline__ IcpHdr *hdr_of(const IcpArgs &a, int p) { return (IcpHdr *)(a.ws + (size_t)p * a.ws_stride); }
+// cell c holds sorted[cells[c] .. cells[c + 1])   (ncell + 1 entries)
+__device__ __forceinline__ int *cells_of(const IcpArgs &a, int p) { return (int *)(a.ws + (size_t)p * a.ws_stride + 256); }
+__device__ __forceinline__ float4 *sorted_of(const IcpArgs &a, int p) {
+    return (float4 *)(a.ws + (size_t)p * a.ws_stride + 256 + sizeof(int) * (size_t)(GMAX * GMAX + 4));
+}
+__device__ __forceinline__ double *partial_of(const IcpArgs &a, int p) { return (double *)(sorted_of(a, p) + a.N); }
+
+__device__ __forceinline__ int cell_coord(float v, float lo, float inv_cs, int g) {
+    return min(max((int)floorf((v - lo) * inv_cs), 0), g - 1);
+}
+
+// One workgroup per pair: frame indices and counts, the target's xy bounds, the grid header, and the cell counters zeroed.
+__global__ __launch_bounds__(1024) void icp_setup_kernel(IcpArgs A, float radius) {
+    const int pair = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    IcpHdr *hdr = hdr_of(A, pair);
+    const int fs = min(max(A.src[pair], 0), A.F - 1), fd = min(max(A.dst[pair], 0), A.F - 1);
+    const int n1 = min(max(A.lengths[fs], 0), A.N), n2 = min(max(A.lengths[fd], 0), A.N);
+    const float *p2 = A.pcd + (size_t)fd * 3 * A.N;
+    float lox = __builtin_inff(), loy = lox, hix = -lox, hiy = -lox;
+    for (int i = t; i < n2; i += 1024) {
+        const float x = p2[i], y = p2[(size_t)A.N + i];
+        lox = fminf(lox, x), hix = fmaxf(hix, x), loy = fminf(loy, y), hiy = fmaxf(hiy, y);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lox = fminf(lox, __shfl_xor(lox, off, 64)), loy = fminf(loy, __shfl_xor(loy, off, 64));
+        hix = fmaxf(hix, __shfl_xor(hix, off, 64)), hiy = fmaxf(hiy, __shfl_xor(hiy, off, 64));
+    }
+    __shared__ float red[4][16];
+    __shared__ int s_ncell;
+    if (lane == 0) red[0][w] = lox, red[1][w] = loy, red[2][w] = hix, red[3][w] = hiy;
+    __syncthreads();
+    if (t == 0) {
+        for (int k = 1; k < 16; ++k) {
+            lox = fminf(lox, red[0][k]), loy = fminf(loy, red[1][k]);
+            hix = fmaxf(hix, red[2][k]), hiy = fmaxf(hiy, red[3][k]);
+        }
+        // an empty target, or one with a non-finite coordinate (its bounds are no numbers to divide by): one empty-handed cell
+        const bool usable = n2 > 0 && hix - lox < 3e38f && hiy - loy < 3e38f && hix - lox >= 0.f && hiy - loy >= 0.f;
+        int gx = 1, gy = 1, H = 1;
+        float cs = radius;
+        if (usable) {
+            const float ext = fmaxf(fmaxf(hix - lox, hiy - loy), 1e-6f);
+            cs = fmaxf(radius * 0.5005f, ext / (float)(GMAX - 1)), H = 2;
+            if (cs >= radius) cs = fmaxf(radius, ext / (float)(GMAX - 1)), H = 1;
+            gx = min(GMAX, (int)((hix - lox) / cs) + 1), gy = min(GMAX, (int)((hiy - loy) / cs) + 1);
+        } else {
+            lox = 0.f, loy = 0.f;
+        }
+        hdr->lox = lox, hdr->loy = loy, hdr->inv_cs = 1.0f / cs, hdr->gx = gx, hdr->gy = gy, hdr->ncell = gx * gy, hdr->H = H;
+        hdr->n1 = n1, hdr->n2 = usable ? n2 : 0, hdr->fs = fs, hdr->fd = fd, hdr->done = 0;
+        s_ncell = gx * gy;
+    }
+    __syncthreads();
+    int *cells = cells_of(A, pair);
+    for (int c = t; c <= s_ncell; c += 1024) cells[c] = 0;
+}
+
+// PLACE = false: points per cell into cells[c + 1]; PLACE = true (after the scan, when cells[c + 1] is the start of cell c):
+// every point to its cell's next free slot, which leaves cells[c + 1] at the cell's end = the start of cell c + 1
+template <bool PLACE>
+__global__ __launch_bounds__(256) void icp_grid_kernel(IcpArgs A) {
+    const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const IcpHdr *hdr = hdr_of(A, pair);
+    if (i >= hdr->n2) return;
+    const float *p2 = A.pcd + (size_t)hdr->fd * 3 * A.N;
+    const float x = p2[i], y = p2[(size_t)A.N + i];
+    const int c = cell_coord(y, hdr->loy, hdr->inv_cs, hdr->gy) * hdr->gx + cell_coord(x, hdr->lox, hdr->inv_cs, hdr->gx);
+    int *slot = cells_of(A, pair) + 1 + c;
+    const int pos = atomicAdd(slot, 1);
+    if (PLACE) sorted_of(A, pair)[pos] = make_float4(x, y, p2[2 * (size_t)A.N + i], __int_as_float(i));
+}
+
+// exclusive prefix sum of cells[1 .. ncell] in place, one workgroup per pair (thread t owns a contiguous run of cells)
+__global__ __launch_bounds__(1024) void icp_scan_kernel(IcpArgs A) {
+    const int pair = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int *c = cells_of(A, pair) + 1;
+    const int ncell = hdr_of(A, pair)->ncell, per = (ncell + 1023) / 1024, a = min(t * per, ncell), b = min(a + per, ncell);
+    int sum = 0;
+    for (int k = a; k < b; ++k) sum += c[k];
+    int inc = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    __shared__ int wsum[16];
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int k = 0; k < w; ++k) run += wsum[k];
+    for (int k = a; k < b; ++k) {
+        const int n = c[k];
+        c[k] = run, run += n;
+    }
+}
+
+// pose <- init, the per-pair results to their start values
+__global__ void icp_init_kernel(IcpArgs A, const double *init) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.n_pairs) return;
+    for (int k = 0; k < 12; ++k) A.pose[(size_t)p * 16 + k] = init[(size_t)p * 16 + k];
+    A.pose[(size_t)p * 16 + 12] = 0.0, A.pose[(size_t)p * 16 + 13] = 0.0, A.pose[(size_t)p * 16 + 14] = 0.0;
+    A.pose[(size_t)p * 16 + 15] = 1.0;
+    A.fitness[p] = 0.f, A.rmse[p] = 0.f, A.iterations[p] = 0, A.status[p] = DPM_ICP_MAX_ITER;
+    if (A.dbg_system)
+        for (int k = 0; k < NSUM; ++k) A.dbg_system[(size_t)p * NSUM + k] = 0.0;
+}
+
+// a new stage of the schedule: every pair runs again from where it stands
+__global__ void icp_stage_kernel(IcpArgs A) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.n_pairs) return;
+    hdr_of(A, p)->done = 0;
+    A.status[p] = DPM_ICP_MAX_ITER;
+}
+
+// one match's row J (6) and residual e into the running sums
+__device__ __forceinline__ void add_row(double (&s)[NSUM], const double (&J)[6], double e) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) s[k] = fma(J[i], J[j], s[k]), ++k;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s[21 + i] = fma(J[i], e, s[21 + i]);
+    s[28] = fma(e, e, s[28]);
+}
+
+// Grid (nblk, n_pairs) -> (block within the pair, pair) such that all blocks of one pair run on the same XCD, whose L2 then
+// holds the one or two grids it is working on (pair_block of infomat.hip; workgroups are dealt round-robin to the 8 XCDs).
+// Which workgroup computes a (pair, block) partial changes nothing about the partial.
+__device__ __forceinline__ void pair_block(int &blk, int &pair) {
+    const int nblk = gridDim.x, npair = gridDim.y;
+    if (npair % 8 == 0) {
+        const unsigned L = blockIdx.y * nblk + blockIdx.x;
+        const unsigned xcd = L & 7, slot = L >> 3;
+        pair = (int)((slot / nblk) * 8 + xcd), blk = (int)(slot % nblk);
+    } else {
+        pair = blockIdx.y, blk = blockIdx.x;
+    }
+}
+
+template <int PLANE>
+__global__ __launch_bounds__(256) void icp_accumulate_kernel(IcpArgs A, float r2) {
+    int pair, blk;
+    pair_block(blk, pair);
+    const IcpHdr *hdr = hdr_of(A, pair);
+    if (hdr->done) return;
+    const int N = A.N, n1 = hdr->n1;
+    const float *p1 = A.pcd + (size_t)hdr->fs * 3 * N;
+    const float *p2 = A.pcd + (size_t)hdr->fd * 3 * N;
+    const float *nrm = PLANE ? A.normals + (size_t)hdr->fd * 3 * N : nullptr;
+    const int *cells = cells_of(A, pair);
+    const float4 *sorted = sorted_of(A, pair);
+    const int gx = hdr->gx, gy = hdr->gy, H = hdr->H;
+    const float inv_cs = hdr->inv_cs, lox = hdr->lox, loy = hdr->loy;
+    const double *pose = A.pose + (size_t)pair * 16;
+    float Rt[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Rt[k] = (float)pose[k];   // the search runs in fp32, like the information matrix's
+    const int quad = threadIdx.x >> 2, ql = threadIdx.x & 3;
+    double s[NSUM];
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) s[k] = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        const int i = blk * 256 + j * 64 + quad;   // uniform inside a quad
+        if (i >= n1) {
+            if (i < N && A.dbg_match && ql == 0) A.dbg_match[(size_t)pair * N + i] = -1;
+            continue;
+        }
+        const float x = p1[i], y = p1[(size_t)N + i], z = p1[2 * (size_t)N + i];
+        const float qx = fmaf(Rt[2], z, fmaf(Rt[1], y, Rt[0] * x)) + Rt[3];
+        const float qy = fmaf(Rt[6], z, fmaf(Rt[5], y, Rt[4] * x)) + Rt[7];
+        const float qz = fmaf(Rt[10], z, fmaf(Rt[9], y, Rt[8] * x)) + Rt[11];
+        const float flx = floorf((qx - lox) * inv_cs), fly = floorf((qy - loy) * inv_cs);
+        const int cx = (int)fmaxf(fminf(flx, 1e6f), -1e6f), cy = (int)fmaxf(fminf(fly, 1e6f), -1e6f);
+        const int xa = min(max(cx - H, 0), gx), xb = min(max(cx + H + 1, 0), gx);
+        unsigned long long best = ~0ull;
+        // a row's cells xa .. xb-1 are one range of `sorted`; the range ends of all rows are requested before the first is used
+        int rlo[5], rhi[5];
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int yy = cy - H + r;
+            const bool in = r <= 2 * H && yy >= 0 && yy < gy;
+            const int yc = min(max(yy, 0), gy - 1);
+            rlo[r] = in ? cells[yc * gx + xa] : 0, rhi[r] = in ? cells[yc * gx + xb] : 0;
+        }
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int lo = rlo[r], hi = rhi[r];
+            for (int p = lo + ql; p < hi; p += 4) {
+                const float4 t = sorted[p];
+                const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
+                const float d = (dx * dx + dy * dy) + dz * dz;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(t.w);
+                best = key < best ? key : best;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1) {
+            const unsigned long long o = (unsigned long long)__shfl_xor((long long)best, off, 64);
+            best = o < best ? o : best;
+        }
+        const bool hit = best != ~0ull && __uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
+        const int win = hit ? (int)(unsigned)best : -1;
+        if (ql != 0) continue;
+        if (A.dbg_match) A.dbg_match[(size_t)pair * N + i] = win;
+        if (!hit) continue;
+        const double px = qx, py = qy, pz = qz;
+        const double ex = px - (double)p2[win], ey = py - (double)p2[(size_t)N + win], ez = pz - (double)p2[2 * (size_t)N + win];
+        s[27] += 1.0;
+        if (PLANE) {
+            const double nx = nrm[3 * (size_t)win], ny = nrm[3 * (size_t)win + 1], nz = nrm[3 * (size_t)win + 2];
+            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+            add_row(s, J, (nx * ex + ny * ey) + nz * ez);
+        } else {
+            const double Jx[6] = {0.0, pz, -py, 1.0, 0.0, 0.0}, Jy[6] = {-pz, 0.0, px, 0.0, 1.0, 0.0},
+                         Jz[6] = {py, -px, 0.0, 0.0, 0.0, 1.0};
+            add_row(s, Jx, ex), add_row(s, Jy, ey), add_row(s, Jz, ez);
+        }
+    }
+    // lanes, then waves, in a fixed tree; one partial per block
+    __shared__ double sred[4][NSUM];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) {
+        double v = s[k];
+#pragma unroll
+        for (int off = 32; off >= 4; off >>= 1) v += __shfl_xor(v, off, 64);   // lanes 1..3 of a quad hold zeros
+        if (lane == 0) sred[w][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NSUM)
+        partial_of(A, pair)[(size_t)blk * NSUM_PAD + threadIdx.x] =
+            (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
+}
+
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < 1e300; }   // false for Inf and NaN
+
+__global__ __launch_bounds__(64) void icp_solve_kernel(IcpArgs A, double tol_rot, double tol_trans) {
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    IcpHdr *hdr = hdr_of(A, pair);
+    if (hdr->done) return;
+    __shared__ double S[NSUM_PAD];
+    if (lane < NSUM) {
+        const double *part = partial_of(A, pair);
+        const int nblk = (A.N + 255) / 256;
+        double v = 0.0;
+        for (int b = 0; b < nblk; ++b) v += part[(size_t)b * NSUM_PAD + lane];   // block order
+        S[lane] = v;
+        if (A.dbg_system) A.dbg_system[(size_t)pair * NSUM + lane] = v;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    const double cnt = S[27], rss = S[28];
+    if (!(cnt >= 1.0)) {
+        A.fitness[pair] = 0.f, A.rmse[pair] = 0.f, A.status[pair] = DPM_ICP_NO_MATCH, hdr->done = 1;
+        return;
+    }
+    A.fitness[pair] = (float)(cnt / (double)max(hdr->n1, 1));
+    const double ms = rss / cnt;
+    A.rmse[pair] = finite_d(ms) && ms >= 0.0 ? (float)sqrt(ms) : 0.f;
+    double Hm[6][6], L[6][6], g[6];
+    {
+        int k = 0;
+        for (int i = 0; i < 6; ++i)
+            for (int j = i; j < 6; ++j) Hm[i][j] = Hm[j][i] = S[k++];
+        for (int i = 0; i < 6; ++i) g[i] = S[21 + i];
+    }
+    bool ok = cnt >= 6.0;
+    for (int k = 0; k < NSUM && ok; ++k) ok = finite_d(S[k]);
+    const double bm[2] = {fmax(fmax(Hm[0][0], Hm[1][1]), Hm[2][2]), fmax(fmax(Hm[3][3], Hm[4][4]), Hm[5][5])};
+    for (int k = 0; k < 6 && ok; ++k) {
+        double d = Hm[k][k];
+        for (int m = 0; m < k; ++m) d -= L[k][m] * L[k][m];
+        if (!(d > PIV_EPS * bm[k / 3])) {
+            ok = false;
+            break;
+        }
+        L[k][k] = sqrt(d);
+        for (int i = k + 1; i < 6; ++i) {
+            double v = Hm[i][k];
+            for (int m = 0; m < k; ++m) v -= L[i][m] * L[k][m];
+            L[i][k] = v / L[k][k];
+        }
+    }
+    double x[6];
+    if (ok) {
+        double yv[6];
+        for (int i = 0; i < 6; ++i) {   // L y = -g
+            double v = -g[i];
+            for (int m = 0; m < i; ++m) v -= L[i][m] * yv[m];
+            yv[i] = v / L[i][i];
+        }
+        for (int i = 5; i >= 0; --i) {  // L^T x = y
+            double v = yv[i];
+            for (int m = i + 1; m < 6; ++m) v -= L[m][i] * x[m];
+            x[i] = v / L[i][i];
+        }
+        for (int i = 0; i < 6; ++i) ok = ok && finite_d(x[i]);
+    }
+    if (!ok) {   // the pose stays at its last good value
+        A.status[pair] = DPM_ICP_SINGULAR, hdr->done = 1;
+        return;
+    }
+    const double th2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2], th = sqrt(th2);
+    double a, b;   // exp(w) = I + a K + b K^2
+    if (th < 1e-8) a = 1.0, b = 0.5;
+    else a = sin(th) / th, b = (1.0 - cos(th)) / th2;
+    const double K[3][3] = {{0.0, -x[2], x[1]}, {x[2], 0.0, -x[0]}, {-x[1], x[0], 0.0}};
+    double E[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double k2 = 0.0;
+            for (int m = 0; m < 3; ++m) k2 += K[i][m] * K[m][j];
+            E[i][j] = (i == j ? 1.0 : 0.0) + a * K[i][j] + b * k2;
+        }
+    double *pose = A.pose + (size_t)pair * 16, out[12];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double v = 0.0;
+            for (int m = 0; m < 3; ++m) v += E[i][m] * pose[m * 4 + j];
+            out[i * 4 + j] = j == 3 ? v + x[3 + i] : v;
+        }
+    for (int k = 0; k < 12; ++k) ok = ok && finite_d(out[k]);
+    if (!ok) {
+        A.status[pair] = DPM_ICP_SINGULAR, hdr->done = 1;
+        return;
+    }
+    for (int k = 0; k < 12; ++k) pose[k] = out[k];
+    A.iterations[pair] += 1;
+    const double tr = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+    if (th < tol_rot && tr < tol_trans) A.status[pair] = DPM_ICP_CONVERGED, hdr->done = 1;
+}
+
+size_t slice_bytes(int N) {
+    const size_t b = 256 + sizeof(int) * (size_t)(GMAX * GMAX + 4) + sizeof(float4) * (size_t)N +
+                     sizeof(double) * NSUM_PAD * (size_t)dpm_cdiv(N, 256);
+    return (b + 255) & ~(size_t)255;
+}
+
+}  // namespace
+
+extern "C" size_t dpm_icp_workspace_bytes(int n_pairs, int N) {
+    if (n_pairs < 1 || N < 1) return 0;
+    return 256 + (size_t)n_pairs * slice_bytes(N);
+}
+
+extern "C" int dpm_icp_refine_batched(const float *pcd, int F, int N, const int32_t *lengths, const float *normals,
+                                      const int32_t *src_frame, const int32_t *dst_frame, int n_pairs,
+                                      const double *init_pose, int metric, const double *stage_max_dist,
+                                      const int32_t *stage_max_iter, int n_stages, double tol_rot, double tol_trans,
+                                      double *pose, float *fitness, float *rmse, int32_t *iterations, int32_t *status,
+                                      int32_t *debug_match, double *debug_system, void *workspace, dpm_stream_t stream) {
+    DPM_CHECK_ARG(pcd && lengths && src_frame && dst_frame && init_pose && stage_max_dist && stage_max_iter && workspace);
+    DPM_CHECK_ARG(pose && fitness && rmse && iterations && status && pose != init_pose);
+    DPM_CHECK_ARG(F >= 1 && N >= 1 && n_pairs >= 1 && n_stages >= 1 && n_stages <= 16 && tol_rot >= 0.0 && tol_trans >= 0.0);
+    DPM_CHECK_ARG(metric == DPM_ICP_POINT || metric == DPM_ICP_PLANE);
+    DPM_CHECK_ARG(metric == DPM_ICP_POINT || normals);
+    if ((long long)n_pairs * N > 0x7fffffffLL || n_pairs > 65535) return DPM_EUNSUPPORTED;
+    double rmax = 0.0;
+    for (int s = 0; s < n_stages; ++s) {
+        DPM_CHECK_ARG(stage_max_dist[s] > 0.0 && stage_max_dist[s] < 1e18 && stage_max_iter[s] >= 0);
+        rmax = stage_max_dist[s] > rmax ? stage_max_dist[s] : rmax;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    IcpArgs A{};
+    A.pcd = pcd, A.normals = normals, A.lengths = lengths, A.src = src_frame, A.dst = dst_frame;
+    A.F = F, A.N = N, A.n_pairs = n_pairs;
+    A.ws = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), A.ws_stride = slice_bytes(N);
+    A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
+    A.dbg_match = debug_match, A.dbg_system = debug_system;
+    const dim3 per_point(dpm_cdiv(N, 256), n_pairs);
+    // the grids serve every stage: cells sized for the largest radius of the schedule
+    hipLaunchKernelGGL(icp_init_kernel, dim3(dpm_cdiv(n_pairs, 64)), dim3(64), 0, st, A, init_pose);
+    hipLaunchKernelGGL(icp_setup_kernel, dim3(n_pairs), dim3(1024), 0, st, A, (float)rmax);
+    hipLaunchKernelGGL(icp_grid_kernel<false>, per_point, dim3(256), 0, st, A);
+    hipLaunchKernelGGL(icp_scan_kernel, dim3(n_pairs), dim3(1024), 0, st, A);
+    hipLaunchKernelGGL(icp_grid_kernel<true>, per_point, dim3(256), 0, st, A);
+    for (int s = 0; s < n_stages; ++s) {
+        const float r2 = (float)(stage_max_dist[s] * stage_max_dist[s]);
+        if (s > 0) hipLaunchKernelGGL(icp_stage_kernel, dim3(dpm_cdiv(n_pairs, 64)), dim3(64), 0, st, A);
+        for (int it = 0; it < stage_max_iter[s]; ++it) {
+            if (metric == DPM_ICP_PLANE) hipLaunchKernelGGL(icp_accumulate_kernel<1>, per_point, dim3(256), 0, st, A, r2);
+            else hipLaunchKernelGGL(icp_accumulate_kernel<0>, per_point, dim3(256), 0, st, A, r2);
+            hipLaunchKernelGGL(icp_solve_kernel, dim3(n_pairs), dim3(64), 0, st, A, tol_rot, tol_trans);
+        }
+    }
+    return dpm_launch_status();
+}

@@ -980,6 +980,77 @@ def information_matrix_grids(pcd: torch.Tensor, dst_frame: torch.Tensor, radius:
     return ws
 
 
+# -- batched ICP (csrc/icp.hip; the table builder on top of it is refine.py) -------------------------------------------------
+ICP_POINT, ICP_PLANE = 0, 1
+ICP_CONVERGED, ICP_MAX_ITER, ICP_NO_MATCH, ICP_SINGULAR = 0, 1, 2, 3
+ICP_NSUM = 29   # debug_system: H upper triangle (21), g (6), matches, squared residuals
+
+
+def icp_target_normals(pcd: torch.Tensor, lengths: torch.Tensor, dst_frame: torch.Tensor, radius: float = 1.0) -> torch.Tensor:
+    """(F,N,3) fp32: dpm_point_normals of the valid points of every distinct frame in dst_frame, zeros elsewhere -- the
+    `normals` of icp_refine(metric="plane").  Reads lengths and dst_frame on the host (one synchronisation)."""
+    _chk(pcd, torch.float32, "pcd"), _chk(lengths, torch.int32, "lengths"), _chk(dst_frame, torch.int32, "dst_frame")
+    F, _, N = pcd.shape
+    lib = _lib.load()
+    normals = torch.zeros(F, N, 3, device=pcd.device, dtype=torch.float32)
+    ws = torch.empty(lib.dpm_knn_self_workspace_bytes(N), device=pcd.device, dtype=torch.uint8)
+    counts = lengths.tolist()
+    for f in sorted(set(dst_frame.tolist())):
+        if not 0 <= f < F:
+            raise ValueError(f"dst_frame: frame {f} outside [0, {F})")
+        n = min(max(int(counts[f]), 0), N)
+        if n == 0:
+            continue
+        xyz = pcd[f, :, :n].t().contiguous()
+        out = torch.empty(n, 3, device=pcd.device, dtype=torch.float32)
+        _lib.check(lib.dpm_point_normals(_ptr(xyz), n, float(radius), _ptr(out), _ptr(ws), _stream(pcd)), "dpm_point_normals")
+        normals[f, :n] = out
+    return normals
+
+
+def icp_refine(pcd: torch.Tensor, lengths: torch.Tensor, src_frame: torch.Tensor, dst_frame: torch.Tensor, init: torch.Tensor,
+               schedule, metric: int = ICP_PLANE, tol_rot: float = 1e-7, tol_trans: float = 1e-6,
+               normals: Optional[torch.Tensor] = None, debug: bool = False):
+    """pcd (F,3,N) fp32 metres, lengths (F,) int32, pair p = (src_frame[p], dst_frame[p]) int32, init (P,4,4) fp64: the pose
+    of the source in the target; schedule = [(max_dist, max_iter), ...]; normals (F,N,3) for ICP_PLANE (icp_target_normals).
+    -> pose (P,4,4) fp64, fitness (P,) fp32, rmse (P,) fp32, iterations (P,) int32, status (P,) int32[, match (P,N) int32,
+    system (P,29) fp64 with debug].  All on the GPU; no host synchronisation, capturable in a graph."""
+    _chk(pcd, torch.float32, "pcd"), _chk(lengths, torch.int32, "lengths"), _chk(init, torch.float64, "init")
+    _chk(src_frame, torch.int32, "src_frame"), _chk(dst_frame, torch.int32, "dst_frame")
+    F, three, N = pcd.shape
+    P_ = src_frame.numel()
+    if three != 3 or lengths.numel() != F or dst_frame.numel() != P_ or tuple(init.shape) != (P_, 4, 4):
+        raise ValueError("icp_refine: pcd (F,3,N), lengths (F,), src_frame / dst_frame (P,), init (P,4,4)")
+    if metric == ICP_PLANE:
+        if normals is None:
+            raise ValueError("icp_refine: the plane metric needs normals (icp_target_normals)")
+        _chk(normals, torch.float32, "normals")
+        if tuple(normals.shape) != (F, N, 3):
+            raise ValueError("normals: expected (F,N,3)")
+    else:
+        normals = None
+    stages = [(float(d), int(n)) for d, n in schedule]
+    dist = (ctypes.c_double * len(stages))(*[d for d, _ in stages])
+    iters = (ctypes.c_int32 * len(stages))(*[n for _, n in stages])
+    dev = pcd.device
+    lib = _lib.load()
+    pose = torch.empty(P_, 4, 4, device=dev, dtype=torch.float64)
+    fitness = torch.empty(P_, device=dev, dtype=torch.float32)
+    rmse = torch.empty(P_, device=dev, dtype=torch.float32)
+    iterations = torch.empty(P_, device=dev, dtype=torch.int32)
+    status = torch.empty(P_, device=dev, dtype=torch.int32)
+    match = torch.full((P_, N), -1, device=dev, dtype=torch.int32) if debug else None
+    system = torch.zeros(P_, ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
+    ws = torch.empty(lib.dpm_icp_workspace_bytes(P_, N), device=dev, dtype=torch.uint8)
+    _lib.check(lib.dpm_icp_refine_batched(_ptr(pcd), F, N, _ptr(lengths), _ptr(normals), _ptr(src_frame), _ptr(dst_frame), P_,
+                                          _ptr(init), int(metric), ctypes.addressof(dist), ctypes.addressof(iters), len(stages),
+                                          float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse),
+                                          _ptr(iterations), _ptr(status), _ptr(match), _ptr(system), _ptr(ws), _stream(pcd)),
+               "dpm_icp_refine_batched")
+    out = (pose, fitness, rmse, iterations, status)
+    return out + (match, system) if debug else out
+
+
 # -- the global map (csrc/voxel_map.hip; orchestration in globalmap.py) ------------------------------------------------------
 VOXEL_MAP_HDR_BYTES = 256   # the workspace header globalmap.py reads back between the calls (include/dpm_hip.h)
 

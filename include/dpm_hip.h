@@ -566,6 +566,40 @@ int dpm_infomat_search_grids(const float *pcd, int N, const int32_t *src_frame, 
                              int n_pairs, const float *Rt, int rt_stride, double radius, float *out,
                              int out_stride, void *workspace, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- refined poses --------- */
+
+/* Batched ICP.  Stands in for the offline third-party ICP that produced the per-scene refined_SE3.pkl the reference's
+ * training step reads (pipeline/modules/model_pipeline.py:199-282, dataloader/body.py:142-146); nothing in the reference
+ * writes that file.  pcd (F,3,N) fp32 channel-first scans in metres, lengths (F) valid leading points per frame; pair p
+ * registers frame src_frame[p] onto frame dst_frame[p] starting from init_pose + 16*p (4x4 row-major fp64, the pose of
+ * the source in the target).  metric DPM_ICP_POINT: residual R p + t - q; DPM_ICP_PLANE: n . (R p + t - q) with the
+ * target normals `normals` (F,N,3) fp32 (dpm_point_normals of each target frame; NULL for the point metric).  q is the
+ * exact nearest target point within the stage's max_dist (ties to the smaller index).  The schedule -- stage_max_dist /
+ * stage_max_iter, n_stages <= 16 entries in HOST memory -- runs back to back on grids built once; every stage restarts
+ * all pairs from where they stand.  A pair stops when its rotation step < tol_rot (rad) and its translation step <
+ * tol_trans (m).  Outputs per pair: pose (16 fp64; must not alias init_pose), fitness = matches / source points and rmse
+ * of the matches at the last evaluated pose, iterations (steps taken, summed over the stages), status of the last stage.
+ * A system that cannot be solved (no match; fewer than six matches, a Cholesky pivot below 1e-9 of its block's largest
+ * diagonal entry, a non-finite sum) leaves the pose at its last good value: no NaN or Inf is ever written to it.
+ * debug_match (P,N) int32 / debug_system (P,29) fp64, both NULL-able: the matched original target index of every source
+ * point (-1: none) and the summed system [H upper triangle row-major (21), g (6), matches, squared residuals] of the last
+ * search that ran.  Two launches per iteration, no host synchronisation, capturable in a HIP graph; the same call twice
+ * gives identical bytes, and a pair's bytes do not depend on the other pairs of the call.
+ * workspace: dpm_icp_workspace_bytes(n_pairs, N). */
+#define DPM_ICP_POINT 0
+#define DPM_ICP_PLANE 1
+#define DPM_ICP_CONVERGED 0
+#define DPM_ICP_MAX_ITER 1
+#define DPM_ICP_NO_MATCH 2
+#define DPM_ICP_SINGULAR 3
+size_t dpm_icp_workspace_bytes(int n_pairs, int N);
+int dpm_icp_refine_batched(const float *pcd, int F, int N, const int32_t *lengths, const float *normals,
+                           const int32_t *src_frame, const int32_t *dst_frame, int n_pairs, const double *init_pose,
+                           int metric, const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages,
+                           double tol_rot, double tol_trans, double *pose, float *fitness, float *rmse,
+                           int32_t *iterations, int32_t *status, int32_t *debug_match, double *debug_system,
+                           void *workspace, dpm_stream_t stream);
+
 /* ---------------------------------------------------------------- global map ------------ */
 
 /* ResultLogger.draw_trajectory's point-cloud map (system/modules/recoder.py:167-190): every scan's cloud moved by its
