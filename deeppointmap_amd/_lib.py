@@ -97,6 +97,7 @@ SIGNATURES = {
     "dpm_points_affine": (I, [P, P, I, I, P, P, P]),
     "dpm_gather_points": (I, [P, P, P, I, P, I, I, P, P, P, P]),
     "dpm_pack_frames": (I, [P, P, P, I, I, P, P, P, P]),
+    "dpm_ingest_frames": (I, [P, P, LL, I, I, I, P, P, P, P, P]),
     "dpm_map_tile": (I, [P, P, P, P, I, I, I, P, P]),
     "dpm_infomat_workspace_bytes": (c_size_t, [I, I, I]),
     "dpm_information_matrix": (I, [P, I, P, I, P, D, P, P, P]),

@@ -34,6 +34,7 @@ import contextlib
 import ctypes
 import math
 import random as _pyrandom
+import threading
 from typing import List, Sequence
 
 import numpy as np
@@ -90,6 +91,26 @@ class PointCloud:
         self.has_norm = self.has_label = self.has_image = self.has_uvd = False
 
     norm = label = image = uvd = None
+
+    @classmethod
+    def from_buffers(cls, xyz, idx, count, R=None, T=None, host_n=None):
+        """a frame over buffers that exist already (views of ops.ingest_frames' arena): xyz (cap,3) fp32, idx (cap,) int32,
+        count (1,) int32 on the GPU, nothing copied.  `host_n` = the length when the host knows it (nothing can have been
+        dropped), else None: the first reader of `nbr_point` synchronises.  R / T as in the constructor."""
+        ops._chk(xyz, torch.float32, "xyz"), ops._chk(idx, torch.int32, "idx"), ops._chk(count, torch.int32, "count")
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or idx.shape != xyz.shape[:1] or count.numel() != 1:
+            raise ValueError("from_buffers takes xyz (cap,3), idx (cap,), count (1,)")
+        host = lambda a: (torch.from_numpy(a) if isinstance(a, np.ndarray) else a).detach().to("cpu", torch.float32)
+        self = cls.__new__(cls)
+        self.xyz, self.idx, self.count = xyz, idx, count.reshape(1)
+        self._host_n = None if host_n is None else int(host_n)
+        self.R = host(R) if R is not None else torch.eye(3, dtype=torch.float32)
+        self.T = host(T) if T is not None else torch.zeros(3, 1, dtype=torch.float32)
+        self.calib = torch.eye(4, dtype=torch.float32)
+        self._flags = []
+        self._stream = None
+        self.has_norm = self.has_label = self.has_image = self.has_uvd = False
+        return self
 
     @property
     def device(self):
@@ -538,22 +559,32 @@ class DrawSource:
         return torch.sort(keys, stable=True).indices.to(torch.int32)
 
 
-_ACTIVE: List[DrawSource] = []
+_ACTIVE = threading.local()    # .stack: the `draws()` blocks open in THIS thread (the loader's thread has a stack of its own)
+
+
+def _stack() -> List[DrawSource]:
+    try:
+        return _ACTIVE.stack
+    except AttributeError:
+        _ACTIVE.stack = []
+        return _ACTIVE.stack
 
 
 def _source() -> DrawSource:
-    return _ACTIVE[-1] if _ACTIVE else _DEFAULT
+    stack = _stack()
+    return stack[-1] if stack else _DEFAULT
 
 
 @contextlib.contextmanager
 def draws(rng="reference", record=False):
-    """the DrawSource the class layer uses inside the block"""
+    """the DrawSource the class layer uses inside the block, in the calling thread"""
     src = rng if isinstance(rng, DrawSource) else DrawSource(rng, record)
-    _ACTIVE.append(src)
+    stack = _stack()
+    stack.append(src)
     try:
         yield src
     finally:
-        _ACTIVE.pop()
+        stack.pop()
 
 
 def replay(pcd, records):

@@ -55,6 +55,7 @@ SOURCES = {
     "augment.hip": [],
     "map_assemble.hip": [],
     "optim.hip": [],
+    "ingest.hip": [],
 }
 
 

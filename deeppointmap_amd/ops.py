@@ -1819,3 +1819,75 @@ def map_assemble(coor: torch.Tensor, fea: torch.Tensor, mask: torch.Tensor, rel:
     Differentiable with respect to fea ONLY: the xyz rows and coor get no gradient (the decoder's rule), and the
     backward is a gather of the two descriptor gradients' feature rows -- exact, identical bytes on every run."""
     return _MapAssemble.apply(fea, coor, mask, rel, gt, S, S1, coor_scale)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# batched frame ingest (csrc/ingest.hip)
+# ------------------------------------------------------------------------------------------------------------
+INGEST_CHUNK = 4096   # records per compaction block of csrc/ingest.hip (the entry point refuses any other value)
+
+
+def ingest_layout(shapes):
+    """shapes: per frame (rows, stride in floats).  -> (per-frame offsets in 32-bit words from the start of the staging
+    block, size of the block in bytes): the header of F x 4 int64, then the frames' records back to back."""
+    off, offsets = 8 * len(shapes), []
+    for rows, stride in shapes:
+        offsets.append(off)
+        off += int(rows) * int(stride)
+    return offsets, 4 * off
+
+
+def ingest_stage(frames, block: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames: per frame (rows (n,stride) float32 numpy array of whole records, drop_nan) -> the staging block of
+    dpm_ingest_frames, a uint8 host tensor (pinned when it is allocated here).  `block`: a staging slot to fill instead
+    (it must be large enough; the filled prefix is returned)."""
+    import numpy as np
+    shapes = []
+    for rows, _ in frames:
+        if rows.dtype != np.float32 or rows.ndim != 2 or rows.shape[1] < 3:
+            raise ValueError("a frame's records are a float32 array (rows, stride >= 3)")
+        shapes.append(rows.shape)
+    offsets, nbytes = ingest_layout(shapes)
+    if block is None:
+        block = torch.empty(nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    elif block.dtype != torch.uint8 or block.is_cuda or not block.is_contiguous() or block.numel() < nbytes:
+        raise ValueError(f"the staging slot must be a contiguous uint8 host tensor of at least {nbytes} bytes")
+    block = block[:nbytes]
+    view = block.numpy()
+    header = view[:32 * len(frames)].view(np.int64).reshape(len(frames), 4)
+    words = view.view(np.float32)
+    for f, ((rows, drop_nan), off) in enumerate(zip(frames, offsets)):
+        header[f] = (off, rows.shape[0], rows.shape[1], int(bool(drop_nan)))
+        words[off:off + rows.size].reshape(rows.shape)[...] = rows   # a plain copy: the bytes of every float survive
+    return block
+
+
+def ingest_frames(block: torch.Tensor, F: int, capacity: int, device=None, staging_dev: Optional[torch.Tensor] = None):
+    """One asynchronous copy of the staging block (ingest_stage) and three launches on the current stream, no host
+    synchronisation: -> xyz (F,capacity,3) fp32 = the kept records' first three floats as bits, in input order, zero at and
+    past the count; idx (F,capacity) int32 = 0..capacity-1; count (F,) int32.  Frame f equals
+    PointCloud(reader's filtered array, capacity=capacity) byte for byte (augment.PointCloud.from_buffers wraps it).
+    A row count above `capacity` raises ValueError before anything is queued.  The caller leaves `block` untouched until
+    the stream has passed the copy; `staging_dev`: device bytes to copy into (allocated here otherwise)."""
+    import numpy as np
+    F, capacity = int(F), int(capacity)
+    if block.dtype != torch.uint8 or block.is_cuda or not block.is_contiguous() or block.numel() < 32 * F or F < 1:
+        raise ValueError("block: a contiguous uint8 host tensor from ingest_stage holding F >= 1 frames")
+    header = block.numpy()[:32 * F].view(np.int64).reshape(F, 4)
+    for f in range(F):
+        if header[f, 1] > capacity:
+            raise ValueError(f"frame {f} has {int(header[f, 1])} records, more than the capacity {capacity}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        if staging_dev is None:
+            staging_dev = torch.empty(block.numel(), device=dev, dtype=torch.uint8)
+        _chk(staging_dev, torch.uint8, "staging_dev")
+        if staging_dev.numel() < block.numel():
+            raise ValueError("staging_dev is smaller than the staging block")
+        xyz = torch.empty(F, capacity, 3, device=dev, dtype=torch.float32)
+        idx = torch.empty(F, capacity, device=dev, dtype=torch.int32)
+        count = torch.empty(F, device=dev, dtype=torch.int32)
+        ws = torch.empty(F * ((capacity + INGEST_CHUNK - 1) // INGEST_CHUNK), device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().dpm_ingest_frames(block.data_ptr(), _ptr(staging_dev), block.numel(), F, capacity, INGEST_CHUNK,
+                                                 _ptr(xyz), _ptr(idx), _ptr(count), _ptr(ws), _stream(xyz)), "dpm_ingest_frames")
+    return xyz, idx, count

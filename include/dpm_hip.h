@@ -531,6 +531,24 @@ int dpm_gather_points(const float *xyz, const int32_t *idx_in, const int32_t *co
 int dpm_pack_frames(const float *const *xyz, const int32_t *const *counts, const int32_t *capacities, int S,
                     int padding_to, float *points, unsigned char *padding, int32_t *status, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- frame ingest ---------- */
+
+/* The device side of "F scan files arrive": what dataloader/heads/bin.py:16-17 (drop a record when one of its first
+ * three floats is NaN) and dataloader/transforms.py's PointCloud.__init__ (the frame's buffers) do per frame, for a whole
+ * batch in ONE asynchronous copy and THREE launches whatever F is, without a host synchronisation.
+ * staging_host: a (pinned) block of staging_bytes bytes, as 32-bit words: a header of F x 4 int64 = (offset of the
+ * frame's first record in words from the start of the block, rows, stride in floats >= 3, drop_nan 0 / 1), then the
+ * records.  staging_dev: device memory of the same size, the target of the copy; the caller keeps both untouched until
+ * the stream has passed this call.  Outputs, frames of the layout of the training transforms: xyz (F,capacity,3) = the
+ * kept records' first three floats in input order, moved AS BITS (NaN payloads, -0.0, denormals survive), rows at and
+ * past the count zero; idx (F,capacity) = 0..capacity-1; count (F,) = kept records.  Each frame equals
+ * PointCloud(filtered array, capacity) byte for byte; no atomics, two runs give identical bytes.
+ * Every header field is checked on the host before anything is queued: rows > capacity, a stride below 3, records
+ * outside the block are DPM_EINVAL.  chunk must be the kernels' compaction chunk (4096): the caller sizes
+ * workspace = F * ceil(capacity / chunk) int32 with it. */
+int dpm_ingest_frames(const void *staging_host, void *staging_dev, long long staging_bytes, int F, int capacity,
+                      int chunk, float *xyz, int32_t *idx, int32_t *count, void *workspace, dpm_stream_t stream);
+
 /* ---------------------------------------------------------------- map tiles ------------- */
 
 /* PoseGraph.__global_mapping + centring of global_map_query_graph (system/modules/pose_graph.py:373-409,
