@@ -90,6 +90,9 @@ SIGNATURES = {
     "dpm_point_normals": (I, [P, I, D, P, P, P]),
     "dpm_lowpass_similarity": (I, [P, P, I, I, I, P, P]),
     "dpm_stat_filter": (I, [P, I, D, I, D, P, P, P, P, P, P]),
+    "dpm_filter_dc_workspace_bytes": (c_size_t, [I, I]),
+    "dpm_outlier_filter_dc": (I, [P, P, P, I, I, D, D, D, P, P, P, P, P]),
+    "dpm_lowpass_filter_dc": (I, [P, P, P, I, D, I, D, I, D, D, P, P, P, P, P]),
     "dpm_augment_workspace_bytes": (c_size_t, [I, LL]),
     "dpm_ground_filter": (I, [P, P, P, I, I, I, D, D, I, P, P, P, P, P]),
     "dpm_voxel_select": (I, [P, P, P, I, D, I, LL, P, P, P, P, P]),

@@ -340,31 +340,43 @@ def farthest_point_sample(pcd, num):
     return gather_points(pcd, sel, num)
 
 
+def _filter_workspace(pcd, K):
+    return torch.empty(_lib.load().dpm_filter_dc_workspace_bytes(pcd.cap, int(K)), device=pcd.device, dtype=torch.uint8)
+
+
 def outlier_filter(pcd, nb_neighbors, std_ratio):
-    """OutlierFilter through preprocess.outlier_filter (needs the length on the host: one synchronisation)"""
-    from . import preprocess
-    n = pcd.nbr_point
-    if n <= nb_neighbors:
+    """OutlierFilter (transforms.py:230-246) with the length read on the device: no host synchronisation.  A frame of
+    at most nb_neighbors points passes through (decided on the device)."""
+    from .preprocess import KNN_CELL
+    if pcd.cap == 0:
         return pcd
-    kept, kidx = preprocess.outlier_filter(pcd.xyz[:n], int(nb_neighbors), float(std_ratio), idx=pcd.idx[:n])
-    return _replace(pcd, kept, kidx)
+    with torch.cuda.device(pcd.device):
+        xo, io, no = _outputs(pcd)
+        ws = _filter_workspace(pcd, nb_neighbors)
+        _lib.check(_lib.load().dpm_outlier_filter_dc(ops._ptr(pcd.xyz), ops._ptr(pcd.idx), ops._ptr(pcd.count), pcd.cap,
+                                                     int(nb_neighbors), float(std_ratio), KNN_CELL, 1.0, ops._ptr(xo),
+                                                     ops._ptr(io), ops._ptr(no), ops._ptr(ws), ops._stream(pcd.xyz)),
+                   "dpm_outlier_filter_dc")
+    pcd._set(xo, io, no)
+    return pcd
 
 
 def lowpass_filter(pcd, normals_radius, normals_num, filter_std, flux=2, max_remain=-1):
-    """LowPassFilter through preprocess.lowpass_filter (needs the length on the host: one synchronisation)"""
-    from . import preprocess
-    n = pcd.nbr_point
-    if n <= normals_num:
+    """LowPassFilter (transforms.py:256-289) with the length read on the device: no host synchronisation.  A frame of
+    at most normals_num points passes through (decided on the device)."""
+    from .preprocess import KNN_CELL
+    if max_remain > 0:
+        raise NotImplementedError("max_remain > 0 is not used by any shipped config and is not implemented")
+    if pcd.cap == 0:
         return pcd
-    kept, kidx = preprocess.lowpass_filter(pcd.xyz[:n], normals_radius, normals_num, filter_std, flux, max_remain, idx=pcd.idx[:n])
-    return _replace(pcd, kept, kidx)
-
-
-def _replace(pcd, xyz, idx):
-    _SYNCS[0] += 1   # preprocess._stat_filter read the survivor count
-    m = xyz.shape[0]
-    pcd._set(xyz.contiguous(), idx.contiguous(), torch.full((1,), m, device=pcd.device, dtype=torch.int32))
-    pcd._host_n = m
+    with torch.cuda.device(pcd.device):
+        xo, io, no = _outputs(pcd)
+        ws = _filter_workspace(pcd, normals_num)
+        _lib.check(_lib.load().dpm_lowpass_filter_dc(ops._ptr(pcd.xyz), ops._ptr(pcd.idx), ops._ptr(pcd.count), pcd.cap,
+                                                     float(normals_radius), int(normals_num), float(filter_std), int(flux),
+                                                     KNN_CELL, 1.0, ops._ptr(xo), ops._ptr(io), ops._ptr(no), ops._ptr(ws),
+                                                     ops._stream(pcd.xyz)), "dpm_lowpass_filter_dc")
+    pcd._set(xo, io, no)
     return pcd
 
 
@@ -440,6 +452,60 @@ def collate_frames(frames: Sequence[PointCloud], padding_to: int = -1):
             points, padding = points[:, :, :0], padding[:, :0]
         up = lambda ts: torch.stack(ts).to(dev)
         return points, up([f.R for f in frames]), up([f.T for f in frames]), padding, up([f.calib for f in frames])
+
+
+def collate_each(frames: Sequence[PointCloud], padding_to: int = -1, extra=None):
+    """ToTensor(padding_to) on every frame ON ITS OWN, for a group of frames at once: -> (per frame (pcd (3,P), padding (P,)
+    bool) on the GPU, the lengths, `extra` on the host).  P = padding_to, or with padding_to <= 0 the frame's own length, as
+    the reference's ToTensor pads (transforms.py:69-98) -- so frame f equals collate_frames([f], padding_to), but the whole
+    group costs ONE host synchronisation: the lengths, every deferred error flag and `extra` (an int32 tensor on the GPU the
+    caller wants on the host: the ingest counts of a scene loader) come back together."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("no frames")
+    dev = frames[0].device
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        for f in frames:
+            if f._stream is not None and f._stream != cur:
+                cur.wait_stream(f._stream)
+                for t in (f.xyz, f.count):
+                    t.record_stream(cur)
+                f._stream = None
+        flags = [(st, msg) for f in frames for st, msg in f._flags]
+        live = [k for k, f in enumerate(frames) if f.cap > 0]
+        P = int(padding_to) if padding_to > 0 else max([frames[k].cap for k in live] + [1])
+        rows = [st.flatten() for st, _ in flags]
+        if live:
+            points, padding, status = _pack([frames[k] for k in live], P, dev)
+            rows.append(status.flatten())
+        if extra is not None:
+            rows.append(extra.flatten().to(torch.int32))
+        _SYNCS[0] += 1
+        host = torch.cat(rows).cpu().tolist() if rows else []      # the one host sync of the group
+        for f in frames:
+            f._flags = []
+        for k, (_, msg) in enumerate(flags):
+            if host[2 * k + 1]:
+                raise ValueError(msg)
+        base = 2 * len(flags)
+        lengths = [0] * len(frames)
+        for j, k in enumerate(live):
+            lengths[k] = host[base + 2 * j]
+            if padding_to > 0 and host[base + 2 * j + 1]:
+                raise RuntimeError(f"The number of Point Cloud ({lengths[k]}) is greater than `padding_to` ({P})")
+        extra_host = host[base + 2 * len(live):]
+        out, row = [], {k: j for j, k in enumerate(live)}
+        for k, (f, n) in enumerate(zip(frames, lengths)):
+            f._host_n = n
+            if k not in row:
+                Pk = P if padding_to > 0 else 0
+                out.append((torch.zeros(3, Pk, device=dev), torch.ones(Pk, device=dev, dtype=torch.bool)))
+            elif padding_to > 0:
+                out.append((points[row[k]], padding[row[k]]))
+            else:
+                out.append((points[row[k], :, :n].contiguous(), padding[row[k], :n].contiguous()))
+        return out, lengths, extra_host
 
 
 def to_tensor(pcd, padding_to=-1, use_calib=False, use_norm=False, use_uvd=False, use_image=False):

@@ -33,6 +33,7 @@
 //    become ~150 per centre.  A centre with nothing inside the radius (only padded centres) falls
 //    back to a full scan for its nearest point.
 #include "dpm_common.h"
+#include "filter_dc.h"
 #include "topk_emulate.h"
 #include <type_traits>
 
@@ -1233,7 +1234,12 @@ __global__ __launch_bounds__(TIE_T) void knn_tie_kernel(const float *__restrict_
 // (sparse far-range points) until the block covers the grid.  Distances are the direct form (dx^2+dy^2)+dz^2;
 // the K+1 nearest (the point itself first) are ordered by (distance, index) and column 0 is dropped.
 // ---------------------------------------------------------------------------------------------
+// DC (device count): N is the frame's CAPACITY and sizes the launch; the length is count[0] clamped to [0, N].  A wave
+// whose row is at or past it exits before its first load of a point, and so does every wave of a frame of at most `kmin`
+// points (the filters pass such a frame through unchanged).
+template <bool DC>
 __global__ __launch_bounds__(WPB * 64) void knn_self_kernel(const float *__restrict__ pts, int N, int K,
+                                                            const int32_t *__restrict__ count, int kmin,
                                                             const KnnGrid *__restrict__ hdr,
                                                             const int *__restrict__ start,
                                                             const float4 *__restrict__ sorted,
@@ -1247,6 +1253,10 @@ __global__ __launch_bounds__(WPB * 64) void knn_self_kernel(const float *__restr
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = blockIdx.x * WPB + w;
     if (q >= N) return;
+    if (DC) {
+        const int n = min(max(count[0], 0), N);
+        if (q >= n || n <= kmin) return;
+    }
     LdsF cd = (LdsF)s_d[w], td = (LdsF)s_td[w];
     LdsI ci = (LdsI)s_i[w], ti = (LdsI)s_ti[w];
     const KnnGrid G = hdr[0];
@@ -1336,7 +1346,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+template <bool DC>  // DC: as in knn_self_kernel
 __global__ __launch_bounds__(WPB * 64) void point_normals_kernel(const float *__restrict__ pts, int N, float r2,
+                                                                 const int32_t *__restrict__ count, int kmin,
                                                                  const KnnGrid *__restrict__ hdr,
                                                                  const int *__restrict__ start,
                                                                  const float4 *__restrict__ sorted,
@@ -1344,6 +1356,10 @@ __global__ __launch_bounds__(WPB * 64) void point_normals_kernel(const float *__
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = blockIdx.x * WPB + w;
     if (q >= N) return;
+    if (DC) {
+        const int n = min(max(count[0], 0), N);
+        if (q >= n || n <= kmin) return;
+    }
     const KnnGrid G = hdr[0];
     const float qx = pts[3 * q], qy = pts[3 * q + 1], qz = pts[3 * q + 2];
     const int cx = min(max((int)floorf((qx - G.lox) * G.inv_cs), 0), G.g - 1);
@@ -1609,8 +1625,8 @@ extern "C" int dpm_knn_self(const float *xyz, int N, int K, double cell, int32_t
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, len_dev, N, (float)cell, 0.f, hdr, start, sorted,
                        tie_count);
-    hipLaunchKernelGGL(knn_self_kernel, dim3(dpm_cdiv(N, WPB)), dim3(WPB * 64), 0, st, xyz, N, K, hdr, start, sorted, idx,
-                       dist2, mean_dist);
+    hipLaunchKernelGGL(knn_self_kernel<false>, dim3(dpm_cdiv(N, WPB)), dim3(WPB * 64), 0, st, xyz, N, K,
+                       (const int32_t *)nullptr, 0, hdr, start, sorted, idx, dist2, mean_dist);
     return dpm_launch_status();
 }
 
@@ -1634,7 +1650,98 @@ extern "C" int dpm_point_normals(const float *xyz, int N, double radius, float *
     // cell edge slightly above the radius: the 3x3 block then contains every point strictly within it
     hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, len_dev, N, (float)(radius * 1.001), 0.f, hdr, start,
                        sorted, tie_count);
-    hipLaunchKernelGGL(point_normals_kernel, dim3(dpm_cdiv(N, WPB)), dim3(WPB * 64), 0, st, xyz, N,
-                       (float)(radius * radius), hdr, start, sorted, normals);
+    hipLaunchKernelGGL(point_normals_kernel<false>, dim3(dpm_cdiv(N, WPB)), dim3(WPB * 64), 0, st, xyz, N,
+                       (float)(radius * radius), (const int32_t *)nullptr, 0, hdr, start, sorted, normals);
+    return dpm_launch_status();
+}
+
+// ---- OutlierFilter / LowPassFilter with the frame's length in device memory -------------------------------------
+// The kernels of dpm_knn_self / dpm_point_normals / dpm_lowpass_similarity / dpm_stat_filter, launched at the frame's
+// capacity with the count read through its pointer (the grid build has always read its length that way): nothing here
+// needs the host to know how long the frame is, so a chain of transforms is queued without a synchronisation.  Same
+// arithmetic, same order, same bytes as those four entry points on xyz[:count].
+namespace {
+struct FilterWs {  // layout of dpm_filter_dc_workspace_bytes: the self-kNN grid, then the per-point arrays
+    KnnGrid *hdr;
+    int *start;
+    float4 *sorted;
+    int *tie_count;
+    float *stat;       // (cap)     mean neighbour distance / similarity
+    float *normals;    // (cap,3)   LowPassFilter only
+    int32_t *nn;       // (cap,K)   LowPassFilter only
+};
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+FilterWs carve_filter(void *workspace, int cap) {
+    FilterWs w;
+    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    const uintptr_t base = p;
+    w.hdr = (KnnGrid *)p;
+    p = (p + sizeof(KnnGrid) + 255) & ~(uintptr_t)255;
+    w.start = (int *)p;
+    p = (p + sizeof(int) * (size_t)(GDIM * GDIM + 1) + 255) & ~(uintptr_t)255;
+    w.sorted = (float4 *)p;
+    p = (p + sizeof(float4) * (size_t)cap + 255) & ~(uintptr_t)255;
+    w.tie_count = (int *)p;
+    p = base + align256(dpm_knn_self_workspace_bytes(cap));
+    w.stat = (float *)p;
+    p += align256(sizeof(float) * (size_t)cap);
+    w.normals = (float *)p;
+    p += align256(sizeof(float) * 3 * (size_t)cap);
+    w.nn = (int32_t *)p;
+    return w;
+}
+// one frame of at most `cap` points whose length is count[0]: the build clamps it to [0, cap] itself
+void launch_self_grid_dc(const float *xyz, const int32_t *count, int cap, float cell, const FilterWs &w, hipStream_t st) {
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, count, cap, cell, 0.f, w.hdr, w.start, w.sorted,
+                       w.tie_count);
+}
+}  // namespace
+
+extern "C" size_t dpm_filter_dc_workspace_bytes(int cap, int K) {
+    if (cap < 0) cap = 0;
+    if (K < 0) K = 0;
+    return 256 + align256(dpm_knn_self_workspace_bytes(cap)) + align256(sizeof(float) * (size_t)cap) +
+           align256(sizeof(float) * 3 * (size_t)cap) + align256(sizeof(int32_t) * (size_t)cap * (size_t)K);
+}
+
+extern "C" int dpm_outlier_filter_dc(const float *xyz, const int32_t *idx, const int32_t *count, int cap, int nb_neighbors,
+                                     double std_ratio, double cell, double ratio, float *xyz_out, int32_t *idx_out,
+                                     int32_t *count_out, void *workspace, dpm_stream_t stream) {
+    DPM_CHECK_ARG(cap >= 0 && nb_neighbors >= 1 && cell > 0.0 && ratio != 0.0);
+    if (nb_neighbors + 1 > KMAX) return DPM_EUNSUPPORTED;
+    if (cap == 0) return DPM_OK;
+    DPM_CHECK_ARG(xyz && count && xyz_out && count_out && workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const FilterWs w = carve_filter(workspace, cap);
+    launch_self_grid_dc(xyz, count, cap, (float)cell, w, st);
+    hipLaunchKernelGGL(knn_self_kernel<true>, dim3(dpm_cdiv(cap, WPB)), dim3(WPB * 64), 0, st, xyz, cap, nb_neighbors, count,
+                       nb_neighbors, w.hdr, w.start, w.sorted, (int32_t *)nullptr, (float *)nullptr, w.stat);
+    dpm_detail::launch_stat_filter_dc(w.stat, count, cap, nb_neighbors, (float)std_ratio, 0, (float)ratio, xyz, idx, xyz_out,
+                                      idx_out, count_out, st);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_lowpass_filter_dc(const float *xyz, const int32_t *idx, const int32_t *count, int cap,
+                                     double normals_radius, int normals_num, double filter_std, int flux, double cell,
+                                     double ratio, float *xyz_out, int32_t *idx_out, int32_t *count_out, void *workspace,
+                                     dpm_stream_t stream) {
+    DPM_CHECK_ARG(cap >= 0 && normals_num >= 1 && flux >= 1 && flux <= normals_num && normals_radius > 0.0 && cell > 0.0 &&
+                  ratio != 0.0);
+    if (normals_num + 1 > KMAX || flux > DPM_FILTER_FLUX_MAX) return DPM_EUNSUPPORTED;
+    if (cap == 0) return DPM_OK;
+    DPM_CHECK_ARG(xyz && count && xyz_out && count_out && workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const FilterWs w = carve_filter(workspace, cap);
+    // two grids, as in the synchronous path: edge slightly above the radius for the normals (the 3x3 block then holds every
+    // point strictly within it), `cell` for the neighbour search; the second build overwrites the first in stream order
+    launch_self_grid_dc(xyz, count, cap, (float)(normals_radius * 1.001), w, st);
+    hipLaunchKernelGGL(point_normals_kernel<true>, dim3(dpm_cdiv(cap, WPB)), dim3(WPB * 64), 0, st, xyz, cap,
+                       (float)(normals_radius * normals_radius), count, normals_num, w.hdr, w.start, w.sorted, w.normals);
+    launch_self_grid_dc(xyz, count, cap, (float)cell, w, st);
+    hipLaunchKernelGGL(knn_self_kernel<true>, dim3(dpm_cdiv(cap, WPB)), dim3(WPB * 64), 0, st, xyz, cap, normals_num, count,
+                       normals_num, w.hdr, w.start, w.sorted, w.nn, (float *)nullptr, (float *)nullptr);
+    dpm_detail::launch_lowpass_sim_dc(w.normals, w.nn, count, cap, normals_num, flux, w.stat, st);
+    dpm_detail::launch_stat_filter_dc(w.stat, count, cap, normals_num, (float)filter_std, 1, (float)ratio, xyz, idx, xyz_out,
+                                      idx_out, count_out, st);
     return dpm_launch_status();
 }

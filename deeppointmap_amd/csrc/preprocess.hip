@@ -10,6 +10,7 @@
 // final gather.  Arithmetic mirrors numpy/torch fp32 on the CPU: (x - min) / voxel_size truncated toward zero,
 // true division for the normalisation (torch's in-place `/=` on CPU tensors).
 #include "dpm_common.h"
+#include "filter_dc.h"
 
 namespace {
 
@@ -175,13 +176,22 @@ __global__ __launch_bounds__(256) void pre_write_kernel(const float *__restrict_
 // LowPassFilter similarity (transforms.py:279-281): sim[i] = sum of the `flux` largest |n_i . n_j| over the K
 // nearest neighbours j of i.  One thread per point.
 // ------------------------------------------------------------------------------------------
-constexpr int FLUX_MAX = 8;
+constexpr int FLUX_MAX = DPM_FILTER_FLUX_MAX;
 
+// DC (device count): N is the frame's CAPACITY and sizes the launch; the length is count[0] clamped to [0, N].  A thread
+// whose row is at or past it exits before its first load, and so does every thread of a frame of at most K points (the
+// filter passes such a frame through unchanged).
+template <bool DC>
 __global__ __launch_bounds__(256) void lowpass_sim_kernel(const float *__restrict__ normals,
                                                           const int32_t *__restrict__ idx, int N, int K, int flux,
+                                                          const int32_t *__restrict__ count,
                                                           float *__restrict__ sim) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
+    if (DC) {
+        const int n = min(max(count[0], 0), N);
+        if (i >= n || n <= K) return;
+    }
     const float nx = normals[3 * (size_t)i], ny = normals[3 * (size_t)i + 1], nz = normals[3 * (size_t)i + 2];
     float top[FLUX_MAX];
 #pragma unroll
@@ -210,9 +220,12 @@ __global__ __launch_bounds__(256) void lowpass_sim_kernel(const float *__restric
 // 282-287): mean and unbiased std of stat[0..N) (fp64 accumulation, rounded to fp32 like the torch scalars),
 // mode 0 keeps stat <= mean + k*std, mode 1 keeps stat > mean - k*std; survivors keep their order.
 // One 1024-thread workgroup (scans after voxel sampling have a few 10^4 points).
+// DC (device count): N arrives as the frame's CAPACITY, the length is count[0] clamped to [0, N]; a frame of at most
+// `kmin` points passes through (every live row kept, `stat` -- which nothing wrote -- never read).
 // ------------------------------------------------------------------------------------------
+template <bool DC>
 __global__ __launch_bounds__(1024) void stat_filter_kernel(const float *__restrict__ stat, int N, float k_std, int mode,
-                                                           float ratio,
+                                                           float ratio, const int32_t *__restrict__ count, int kmin,
                                                            const float *__restrict__ xyz_in,
                                                            const int32_t *__restrict__ idx_in,
                                                            float *__restrict__ xyz_out, int32_t *__restrict__ idx_out,
@@ -221,6 +234,8 @@ __global__ __launch_bounds__(1024) void stat_filter_kernel(const float *__restri
     __shared__ int s_cnt[16];
     __shared__ double s_bcast;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (DC) N = min(max(count[0], 0), N);
+    const bool pass = DC && N <= kmin;  // uniform over the workgroup
     auto block_sum = [&](double v) -> double {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -235,18 +250,21 @@ __global__ __launch_bounds__(1024) void stat_filter_kernel(const float *__restri
         __syncthreads();
         return s_bcast;
     };
-    double a = 0.0;
-    for (int i = t; i < N; i += 1024) a += (double)stat[i];
-    const double mean = block_sum(a) / (double)N;
-    double q = 0.0;
-    for (int i = t; i < N; i += 1024) {
-        const double d = (double)stat[i] - mean;
-        q += d * d;
+    float thr = 0.f;
+    if (!pass) {
+        double a = 0.0;
+        for (int i = t; i < N; i += 1024) a += (double)stat[i];
+        const double mean = block_sum(a) / (double)N;
+        double q = 0.0;
+        for (int i = t; i < N; i += 1024) {
+            const double d = (double)stat[i] - mean;
+            q += d * d;
+        }
+        const double var = N > 1 ? block_sum(q) / (double)(N - 1) : 0.0;
+        const float mean_f = (float)mean, std_f = (float)sqrt(var);
+        thr = mode == 0 ? mean_f + k_std * std_f : mean_f - k_std * std_f;
     }
-    const double var = N > 1 ? block_sum(q) / (double)(N - 1) : 0.0;
-    const float mean_f = (float)mean, std_f = (float)sqrt(var);
-    const float thr = mode == 0 ? mean_f + k_std * std_f : mean_f - k_std * std_f;
-    auto keep = [&](int i) -> bool { return i < N && (mode == 0 ? stat[i] <= thr : stat[i] > thr); };
+    auto keep = [&](int i) -> bool { return i < N && (pass || (mode == 0 ? stat[i] <= thr : stat[i] > thr)); };
     // stable compaction: wave w owns the contiguous range [w*per, (w+1)*per) and walks it 64 points at a time
     const int per = ((N + 15) / 16 + 63) & ~63, i0 = min(w * per, N), i1 = min(i0 + per, N);
     int c = 0;
@@ -308,8 +326,8 @@ extern "C" int dpm_lowpass_similarity(const float *normals, const int32_t *idx, 
                                       dpm_stream_t stream) {
     DPM_CHECK_ARG(normals && idx && sim && N >= 1 && K >= 1 && flux >= 1 && flux <= K);
     if (flux > FLUX_MAX) return DPM_EUNSUPPORTED;
-    hipLaunchKernelGGL(lowpass_sim_kernel, dim3(dpm_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, normals, idx, N, K, flux,
-                       sim);
+    hipLaunchKernelGGL(lowpass_sim_kernel<false>, dim3(dpm_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, normals, idx, N, K,
+                       flux, (const int32_t *)nullptr, sim);
     return dpm_launch_status();
 }
 
@@ -317,8 +335,21 @@ extern "C" int dpm_stat_filter(const float *stat, int N, double k_std, int mode,
                                const int32_t *idx_in, float *xyz_out, int32_t *idx_out, int32_t *n_out,
                                dpm_stream_t stream) {
     DPM_CHECK_ARG(stat && xyz_in && xyz_out && n_out && N >= 1 && (mode == 0 || mode == 1) && ratio != 0.0);
-    hipLaunchKernelGGL(stat_filter_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, stat, N, (float)k_std, mode,
-                       (float)ratio, xyz_in,
-                       idx_in, xyz_out, idx_out, n_out);
+    hipLaunchKernelGGL(stat_filter_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, stat, N, (float)k_std, mode,
+                       (float)ratio, (const int32_t *)nullptr, 0, xyz_in, idx_in, xyz_out, idx_out, n_out);
     return dpm_launch_status();
+}
+
+// ---- device-count launchers for dpm_outlier_filter_dc / dpm_lowpass_filter_dc (knn.hip, next to the grid build) ----
+void dpm_detail::launch_lowpass_sim_dc(const float *normals, const int32_t *idx, const int32_t *count, int cap, int K, int flux,
+                                       float *sim, hipStream_t st) {
+    hipLaunchKernelGGL(lowpass_sim_kernel<true>, dim3(dpm_cdiv(cap, 256)), dim3(256), 0, st, normals, idx, cap, K, flux, count,
+                       sim);
+}
+
+void dpm_detail::launch_stat_filter_dc(const float *stat, const int32_t *count, int cap, int kmin, float k_std, int mode,
+                                       float ratio, const float *xyz_in, const int32_t *idx_in, float *xyz_out,
+                                       int32_t *idx_out, int32_t *count_out, hipStream_t st) {
+    hipLaunchKernelGGL(stat_filter_kernel<true>, dim3(1), dim3(1024), 0, st, stat, cap, k_std, mode, ratio, count, kmin, xyz_in,
+                       idx_in, xyz_out, idx_out, count_out);
 }

@@ -102,33 +102,16 @@ class _Slot:
         return self.block
 
 
-class EpochLoader:
-    """for ep in epochs: loader.set_epoch(ep); for batch in loader: step(*batch)      (module docstring)
+class _ReadAhead:
+    """What EpochLoader and SceneLoader share: the background thread that builds work units ahead on a stream of its own,
+    the bounded queue and the event hand-over to the consumer's stream, the pinned staging slots, the thread pool of the
+    file readers, and the failure handling (every wait has a timeout, an exception of the thread is re-raised by next(),
+    close() stops and joins).  A subclass gives `_build(unit, slot)` and starts an iteration with `_start(units)`."""
 
-    dataset: dataset.SlamDatasets; transform: the chain WITHOUT its ToTensor; stage: 'registration' | 'loop_detection';
-    capacity: rows of every frame's buffer (a file with more records raises ValueError before anything is queued);
-    padding_to: the ToTensor padding (-1: the longest frame of the batch); num_workers: threads that read files (at most
-    16; 0 reads in the loader's thread); timeout: seconds any single wait may take."""
-
-    def __init__(self, dataset, transform, stage, batch_size, *, rng, prefetch=2, streams=4, rank=0, world=1, shuffle=True,
-                 capacity, padding_to, num_workers=0, timeout=300.0, device=None):
-        if stage not in STAGES:
-            raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
-        self.reference = isinstance(rng, str)
-        if self.reference and rng != "reference":
-            raise ValueError("rng is 'reference' or an int seed")
-        if not self.reference and (isinstance(rng, bool) or not isinstance(rng, int)):
-            raise ValueError("rng is 'reference' or an int seed")
-        if self.reference and prefetch != 0:
-            raise ValueError("rng='reference' draws from the global generators in step order: it requires prefetch=0")
-        if prefetch < 0 or batch_size < 1 or capacity < 1:
-            raise ValueError("prefetch >= 0, batch_size >= 1, capacity >= 1")
-        self.dataset, self.transform, self.stage, self.batch_size = dataset, transform, stage, int(batch_size)
-        self.seed = None if self.reference else int(rng)
-        self.prefetch, self.streams, self.rank, self.world, self.shuffle = int(prefetch), int(streams), int(rank), int(world), shuffle
-        self.capacity, self.padding_to, self.timeout = int(capacity), int(padding_to), float(timeout)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.epoch = 1
+    def __init__(self, prefetch, num_workers, timeout, device):
+        self.prefetch, self.timeout = int(prefetch), float(timeout)
+        self._device = None if device is None else torch.device(device)     # None: the current device at first use
+        self._workers = min(int(num_workers), 16)
         self._pool = ThreadPoolExecutor(max_workers=min(int(num_workers), 16)) if num_workers > 0 else None
         self._slots = [_Slot() for _ in range(max(self.prefetch, 1))]
         self._stream = None
@@ -137,16 +120,12 @@ class EpochLoader:
         self._queue = None
         self._batches = None
         self._pos = 0
-        self._py = self._gen = None
-        n = len(dataset)
-        self._steps = (n if world == 1 else -(-n // world)) // self.batch_size
 
-    # ---- the epoch
-    def set_epoch(self, epoch: int) -> None:
-        self.epoch = int(epoch)
-
-    def __len__(self) -> int:
-        return self._steps
+    @property
+    def device(self):
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        return self._device
 
     def __enter__(self):
         return self
@@ -154,17 +133,8 @@ class EpochLoader:
     def __exit__(self, *exc):
         self.close()
 
-    def __iter__(self):
-        self._halt()
-        getattr(self.dataset, self.stage)()
-        if self.reference:
-            # DataLoader.__iter__ draws its base seed from the default generator before the sampler draws its own
-            torch.empty((), dtype=torch.int64).random_()
-            self._py, self._gen = _pyrandom, "reference"
-        else:
-            self._py = _pyrandom.Random(derive_seed(self.seed, self.epoch, self.rank, 1))
-            self._gen = torch.Generator(device=self.device).manual_seed(derive_seed(self.seed, self.epoch, self.rank, 2))
-        self._batches = epoch_indices(len(self.dataset), self.batch_size, self.epoch, self.seed, self.rank, self.world, self.shuffle)
+    def _start(self, units):
+        self._batches = units
         self._pos = 0
         if self.prefetch > 0:
             if self._stream is None:
@@ -176,7 +146,8 @@ class EpochLoader:
             self._thread.start()
         return self
 
-    def __next__(self):
+    def _next_unit(self):
+        """the next built unit; its tensors are safe to use on the consumer's current stream"""
         if self._batches is None:
             raise RuntimeError("iterate the loader (iter(loader)) before calling next()")
         if self.prefetch == 0:
@@ -204,10 +175,18 @@ class EpochLoader:
             raise payload
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(event)
-        for t in payload:
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                t.record_stream(cur)
+        for t in self._tensors(payload):
+            t.record_stream(cur)
         return payload
+
+    @staticmethod
+    def _tensors(payload):
+        for t in payload:
+            if isinstance(t, torch.Tensor):
+                if t.is_cuda:
+                    yield t
+            elif isinstance(t, (list, tuple)):
+                yield from _ReadAhead._tensors(t)
 
     # ---- the loader's thread
     def _run(self, batches, q, stop):
@@ -258,27 +237,94 @@ class EpochLoader:
             self._pool.shutdown(wait=True)
             self._pool = None
 
+    def _map(self, fn, keys):
+        """fn over keys, in order, on the readers' thread pool when there is one"""
+        if self._pool is None:
+            return [fn(k) for k in keys]
+        return list(self._pool.map(fn, keys, timeout=self.timeout))
+
+    def _ingest(self, raws, names, slot, capacity):
+        """raws: per frame (rows, stride, R, T, drop_nan) -> stage into the pinned slot, one copy, ops.ingest_frames on the
+        current stream: xyz (F,capacity,3), idx (F,capacity), count (F,).  A frame with more records than the capacity
+        raises ValueError (naming it) before anything is queued."""
+        for (rows, *_), name in zip(raws, names):
+            if rows.shape[0] > capacity:
+                raise ValueError(f"frame {name} has {rows.shape[0]} records, more than the capacity {capacity}")
+        _, nbytes = ops.ingest_layout([r[0].shape for r in raws])
+        block = ops.ingest_stage([(r[0], r[4]) for r in raws], block=slot.take(nbytes, self.timeout))
+        xyz, idx, count = ops.ingest_frames(block, len(raws), capacity, device=self.device)
+        slot.event = torch.cuda.Event()
+        slot.event.record(torch.cuda.current_stream(self.device))
+        return xyz, idx, count
+
+
+class EpochLoader(_ReadAhead):
+    """for ep in epochs: loader.set_epoch(ep); for batch in loader: step(*batch)      (module docstring)
+
+    dataset: dataset.SlamDatasets; transform: the chain WITHOUT its ToTensor; stage: 'registration' | 'loop_detection';
+    capacity: rows of every frame's buffer (a file with more records raises ValueError before anything is queued);
+    padding_to: the ToTensor padding (-1: the longest frame of the batch); num_workers: threads that read files (at most
+    16; 0 reads in the loader's thread); timeout: seconds any single wait may take."""
+
+    def __init__(self, dataset, transform, stage, batch_size, *, rng, prefetch=2, streams=4, rank=0, world=1, shuffle=True,
+                 capacity, padding_to, num_workers=0, timeout=300.0, device=None):
+        if stage not in STAGES:
+            raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
+        self.reference = isinstance(rng, str)
+        if self.reference and rng != "reference":
+            raise ValueError("rng is 'reference' or an int seed")
+        if not self.reference and (isinstance(rng, bool) or not isinstance(rng, int)):
+            raise ValueError("rng is 'reference' or an int seed")
+        if self.reference and prefetch != 0:
+            raise ValueError("rng='reference' draws from the global generators in step order: it requires prefetch=0")
+        if prefetch < 0 or batch_size < 1 or capacity < 1:
+            raise ValueError("prefetch >= 0, batch_size >= 1, capacity >= 1")
+        _ReadAhead.__init__(self, prefetch, num_workers, timeout, device)
+        self._device = self.device      # resolved here: the device current when the loader is made
+        self.dataset, self.transform, self.stage, self.batch_size = dataset, transform, stage, int(batch_size)
+        self.seed = None if self.reference else int(rng)
+        self.streams, self.rank, self.world, self.shuffle = int(streams), int(rank), int(world), shuffle
+        self.capacity, self.padding_to = int(capacity), int(padding_to)
+        self.epoch = 1
+        self._py = self._gen = None
+        n = len(dataset)
+        self._steps = (n if world == 1 else -(-n // world)) // self.batch_size
+
+    # ---- the epoch
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def __len__(self) -> int:
+        return self._steps
+
+    def __iter__(self):
+        self._halt()
+        getattr(self.dataset, self.stage)()
+        if self.reference:
+            # DataLoader.__iter__ draws its base seed from the default generator before the sampler draws its own
+            torch.empty((), dtype=torch.int64).random_()
+            self._py, self._gen = _pyrandom, "reference"
+        else:
+            self._py = _pyrandom.Random(derive_seed(self.seed, self.epoch, self.rank, 1))
+            self._gen = torch.Generator(device=self.device).manual_seed(derive_seed(self.seed, self.epoch, self.rank, 2))
+        return self._start(epoch_indices(len(self.dataset), self.batch_size, self.epoch, self.seed, self.rank, self.world,
+                                         self.shuffle))
+
+    def __next__(self):
+        return self._next_unit()
+
     # ---- one batch
     def _read(self, keys):
         """keys: (dataset, scene, frame) -> per frame (rows, stride, R, T, drop_nan)"""
         def one(key):
             d, s, f = key
             return self.dataset.dataset_list[d].scene_list[s].read_raw(f)
-        if self._pool is None:
-            return [one(k) for k in keys]
-        return list(self._pool.map(one, keys, timeout=self.timeout))
+        return self._map(one, keys)
 
     def _frames(self, keys, slot):
         """read, stage, copy, ingest -> the frames of the batch, every one of capacity `capacity`"""
         raws = self._read(keys)
-        for (rows, *_), key in zip(raws, keys):
-            if rows.shape[0] > self.capacity:
-                raise ValueError(f"frame {key} has {rows.shape[0]} records, more than the capacity {self.capacity}")
-        _, nbytes = ops.ingest_layout([r[0].shape for r in raws])
-        block = ops.ingest_stage([(r[0], r[4]) for r in raws], block=slot.take(nbytes, self.timeout))
-        xyz, idx, count = ops.ingest_frames(block, len(raws), self.capacity, device=self.device)
-        slot.event = torch.cuda.Event()
-        slot.event.record(torch.cuda.current_stream(self.device))
+        xyz, idx, count = self._ingest(raws, keys, slot, self.capacity)
         return [augment.PointCloud.from_buffers(xyz[f], idx[f], count[f:f + 1], R, T, host_n=None if drop else rows.shape[0])
                 for f, (rows, _, R, T, drop) in enumerate(raws)]
 
@@ -304,3 +350,118 @@ class EpochLoader:
             return pcd, R, T, padding, calib, plan["info"], s1
         src, dst = slice(0, None, 2), slice(1, None, 2)
         return tuple(t[half].contiguous() for half in (src, dst) for t in (pcd, R, T, padding, calib))
+
+
+# ------------------------------------------------------------------------------------------------------------
+# inference: the frames of one scene, in file order
+# ------------------------------------------------------------------------------------------------------------
+def scene_groups(n: int, group: int) -> List[List[int]]:
+    """the frames 0..n-1 in consecutive groups of `group`; the last one may be short"""
+    if n < 0 or group < 1:
+        raise ValueError("n >= 0, group >= 1")
+    return [list(range(a, min(a + group, n))) for a in range(0, n, group)]
+
+
+def split_chain(transform):
+    """PointCloudTransforms / Compose -> (the chain without its ToTensor, that ToTensor's padding_to or -1)"""
+    chain = getattr(transform, "transforms", None)
+    if isinstance(chain, augment.Compose):      # PointCloudTransforms holds the Compose
+        chain = chain.transforms
+    if not isinstance(chain, (list, tuple)):
+        raise ValueError("transform is an augment.PointCloudTransforms or an augment.Compose")
+    body = [t for t in chain if not isinstance(t, augment.ToTensor)]
+    heads = [t for t in chain if isinstance(t, augment.ToTensor)]
+    if len(heads) > 1 or (heads and chain[-1] is not heads[0]):
+        raise ValueError("ToTensor may only end the chain")
+    if heads and heads[0].use_calib:
+        raise ValueError("the inference item carries no calib: ToTensor(use_calib=True) is a training setting")
+    return augment.Compose(body), (int(heads[0].padding_to) if heads else -1)
+
+
+class SceneLoader(_ReadAhead):
+    """for pcd, R, T, padding, original in SceneLoader(agent, PointCloudTransforms(args, mode='infer')): system.step(...)
+
+    Stands where the reference's infer.py puts DataLoader(agent.set_independent(transforms), batch_size=1, shuffle=False,
+    num_workers=8) (pipeline/infer.py:85-98).  `agent`: a dataset.BasicAgent, whose file_list is the frame order.
+    `transform`: the inference chain; it runs without its ToTensor, whose padding_to decides P (-1: every frame keeps its
+    own length).  A background thread reads `group` consecutive frames ahead (readers' read_raw on a pool of at most 16
+    threads), stages them into one pinned slot and queues ops.ingest_frames, augment.transform_frames and the packing on
+    a stream of its own; every length of the group -- the ingest counts `original` needs and every deferred error flag
+    with them -- comes back in ONE host synchronisation.  Items are yielded frame by frame, each what the reference's loop
+    receives: [points (1,3,P), R (1,3,3), T (1,3,1), padding (1,P) bool, original (1,N,3)], on the GPU; `original` is the
+    frame as read, after the reader's NaN filter.  The consumer's stream waits on the group's event.  The bytes of frame i
+    do not depend on group, prefetch, streams or timing.
+
+    capacity: rows of every frame's buffer; None = the largest record count of the group (known from the staging headers
+    before anything is queued); a file with more records than a fixed capacity raises ValueError naming it.  prefetch 0
+    builds each group in the caller's thread.  A reader's exception is re-raised by next() with the file's name."""
+
+    def __init__(self, agent, transform, *, group=4, prefetch=2, streams=4, capacity=None, device=None, timeout=300.0):
+        if isinstance(group, bool) or not isinstance(group, int) or group < 1:
+            raise ValueError("group is an int >= 1")
+        if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
+            raise ValueError("prefetch is an int >= 0")
+        if not isinstance(streams, int) or streams < 1:
+            raise ValueError("streams is an int >= 1")
+        if capacity is not None and (not isinstance(capacity, int) or capacity < 1):
+            raise ValueError("capacity is None or an int >= 1")
+        if not timeout > 0:
+            raise ValueError("timeout > 0")
+        if not hasattr(agent, "file_list") or not hasattr(agent, "reader"):
+            raise ValueError("agent is a dataset.BasicAgent (file_list, reader)")
+        self.chain, self.padding_to = split_chain(transform)
+        _ReadAhead.__init__(self, prefetch, min(group, 16), timeout, device)    # touches no device
+        self.agent, self.group, self.streams, self.capacity = agent, group, streams, capacity
+        self.files = list(agent.file_list)
+        self.groups = scene_groups(len(self.files), group)
+        self._pending, self._done = [], False
+
+    def __len__(self) -> int:
+        return len(self.files)
+
+    def __iter__(self):
+        self._halt()
+        self._pending, self._done = [], False
+        if self._pool is None:      # closed before: it can be iterated again
+            self._pool = ThreadPoolExecutor(max_workers=self._workers)
+        return self._start(self.groups)
+
+    def __next__(self):
+        if self._done:
+            raise StopIteration
+        if not self._pending:
+            try:
+                self._pending = list(self._next_unit())
+            except StopIteration:
+                self._done = True
+                raise
+        return self._pending.pop(0)
+
+    def close(self):
+        self._pending, self._done = [], False
+        _ReadAhead.close(self)
+
+    def _read_one(self, k):
+        path = self.files[k]
+        try:
+            return self.agent.reader.read_raw(path)
+        except Exception as e:
+            raise RuntimeError(f"reading {path} failed: {type(e).__name__}: {e}") from e
+
+    def _build(self, indices, slot):
+        raws = self._map(self._read_one, indices)
+        names = [self.files[k] for k in indices]
+        cap = self.capacity if self.capacity is not None else max(max(r[0].shape[0] for r in raws), 1)
+        xyz, idx, count = self._ingest(raws, names, slot, cap)
+        original = xyz.clone()      # the chain may act in place on the ingest arena
+        frames = [augment.PointCloud.from_buffers(xyz[f], idx[f], count[f:f + 1], R, T, host_n=None if drop else rows.shape[0])
+                  for f, (rows, _, R, T, drop) in enumerate(raws)]
+        frames = augment.transform_frames(frames, self.chain, streams=self.streams)
+        try:
+            packed, _, n_in = augment.collate_each(frames, self.padding_to, extra=count)
+        except (ValueError, RuntimeError) as e:
+            raise type(e)(f"{e} (frames {', '.join(names)})") from e
+        dev = self.device
+        return [[pts.unsqueeze(0), fr.R.unsqueeze(0).to(dev), fr.T.unsqueeze(0).to(dev), pad.unsqueeze(0),
+                 original[f, :n].unsqueeze(0)]
+                for f, ((pts, pad), fr, n) in enumerate(zip(packed, frames, n_in))]

@@ -127,14 +127,18 @@ def preprocess_scan(xyz: torch.Tensor, voxel_size: float = 0.3, min_dis: float =
 
 
 def preprocess_scans(scans, voxel_size: float = 0.3, min_dis: float = 1.0, max_dis: float = 60.0, ratio: float = 60.0,
-                     padding_to: int = -1, max_cells: int = MAX_CELLS, streams: int = 4):
-    """The head of the shipped chain (VoxelSample -> DistanceSample -> CoordinatesNormalization) for a LIST of raw scans
+                     padding_to: int = -1, max_cells: int = MAX_CELLS, streams: int = 4, outlier=None, lowpass=None):
+    """The shipped chain (VoxelSample -> DistanceSample [-> OutlierFilter] [-> LowPassFilter] -> CoordinatesNormalization;
+    outlier / lowpass as in preprocess_scan, both None = the head of the chain alone) for a LIST of raw scans
     ((N_i,3|4) fp32, CPU or GPU) in one go: the scans' kernels are spread over `streams` HIP streams (one voxel-grid
     workspace per stream), their output lengths come back with ONE host synchronisation, and the results are packed into
     the batch the encoder -- and the reference's multi-thread extractor, system/core.py:141-169 -- takes:
     points (B,3,M) fp32, padding (B,M) bool (True past a scan's length), lengths list.  M = the longest scan, or
     `padding_to` when positive (ToTensor(padding_to), configs/infer/*.yaml:29; scans longer than it are an error).
-    Per scan the points are bit-identical to preprocess_scan()."""
+    Per scan the points are bit-identical to preprocess_scan() with the same arguments.  The filters take each scan's length
+    from device memory (dpm_outlier_filter_dc / dpm_lowpass_filter_dc read the count dpm_preprocess_scan leaves in its
+    status), so they cost no synchronisation of their own; a scan that reaches a filter with no more points than its
+    neighbour count passes through it (preprocess_scan raises there)."""
     if not scans:
         raise ValueError("no scans")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -143,6 +147,10 @@ def preprocess_scans(scans, voxel_size: float = 0.3, min_dis: float = 1.0, max_d
     side = [torch.cuda.Stream(device=dev) for _ in range(min(streams, len(scans)))]
     work = [torch.empty(lib.dpm_preprocess_workspace_bytes(max_cells), device=dev, dtype=torch.uint8) for _ in side]
     status = torch.zeros(len(scans), 2, device=dev, dtype=torch.int32)
+    filters = outlier is not None or lowpass is not None
+    if lowpass is not None and len(lowpass) > 4 and lowpass[4] > 0:
+        raise NotImplementedError("max_remain > 0 is not used by any shipped config and is not implemented")
+    kept_n = torch.zeros(len(scans), device=dev, dtype=torch.int32) if filters else None   # counts after the last filter
     outs = []
     for st in side:
         st.wait_stream(cur)
@@ -156,17 +164,41 @@ def preprocess_scans(scans, voxel_size: float = 0.3, min_dis: float = 1.0, max_d
             out = torch.empty(N, 3, device=dev, dtype=torch.float32)
             idx = torch.empty(N, device=dev, dtype=torch.int32)
             _lib.check(lib.dpm_preprocess_scan(ops._ptr(x), N, stride, float(voxel_size), float(min_dis), float(max_dis),
-                                               float(ratio), int(max_cells), ops._ptr(out), ops._ptr(idx), N,
-                                               ops._ptr(status[b]), ops._ptr(work[b % len(side)]), st.cuda_stream),
-                       "dpm_preprocess_scan")
+                                               1.0 if filters else float(ratio), int(max_cells), ops._ptr(out),
+                                               ops._ptr(idx), N, ops._ptr(status[b]), ops._ptr(work[b % len(side)]),
+                                               st.cuda_stream), "dpm_preprocess_scan")
+            count = status[b, :1]
+            # CoordinatesNormalization (a true division) rides on the last filter, as in preprocess_scan
+            if outlier is not None:
+                K, last = int(outlier[0]), lowpass is None
+                xo, io = torch.empty_like(out), torch.empty_like(idx)
+                no = kept_n[b:b + 1] if last else torch.zeros(1, device=dev, dtype=torch.int32)
+                ws = torch.empty(lib.dpm_filter_dc_workspace_bytes(N, K), device=dev, dtype=torch.uint8)
+                _lib.check(lib.dpm_outlier_filter_dc(ops._ptr(out), ops._ptr(idx), ops._ptr(count), N, K, float(outlier[1]),
+                                                     KNN_CELL, float(ratio) if last else 1.0, ops._ptr(xo), ops._ptr(io),
+                                                     ops._ptr(no), ops._ptr(ws), st.cuda_stream), "dpm_outlier_filter_dc")
+                out, idx, count = xo, io, no
+            if lowpass is not None:
+                K = int(lowpass[1])
+                xo, io, no = torch.empty_like(out), torch.empty_like(idx), kept_n[b:b + 1]
+                ws = torch.empty(lib.dpm_filter_dc_workspace_bytes(N, K), device=dev, dtype=torch.uint8)
+                _lib.check(lib.dpm_lowpass_filter_dc(ops._ptr(out), ops._ptr(idx), ops._ptr(count), N, float(lowpass[0]), K,
+                                                     float(lowpass[2]), int(lowpass[3]), KNN_CELL, float(ratio), ops._ptr(xo),
+                                                     ops._ptr(io), ops._ptr(no), ops._ptr(ws), st.cuda_stream),
+                           "dpm_lowpass_filter_dc")
+                out = xo
             out.record_stream(cur)  # allocated on the side stream, packed into the batch on the caller's stream below
             outs.append(out)
     for st in side:
         cur.wait_stream(st)
-    st_host = status.cpu().tolist()  # the one host sync of the batch
+    if filters:
+        host = torch.cat([status.flatten(), kept_n]).cpu().tolist()  # the one host sync of the batch
+        st_host, lengths = list(zip(host[0:2 * len(scans):2], host[1:2 * len(scans):2])), host[2 * len(scans):]
+    else:
+        st_host = status.cpu().tolist()  # the one host sync of the batch
+        lengths = [n for n, _ in st_host]
     if any(o for _, o in st_host):
         raise ValueError(f"voxel grid exceeds max_cells={max_cells}; crop the scans or raise max_cells")
-    lengths = [n for n, _ in st_host]
     M = max(lengths) if padding_to <= 0 else padding_to
     if max(lengths) > M:
         raise ValueError(f"a scan keeps {max(lengths)} points, more than padding_to={padding_to}")

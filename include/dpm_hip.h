@@ -476,6 +476,30 @@ int dpm_lowpass_similarity(const float *normals, const int32_t *idx, int N, int 
 int dpm_stat_filter(const float *stat, int N, double k_std, int mode, double ratio, const float *xyz_in,
                     const int32_t *idx_in, float *xyz_out, int32_t *idx_out, int32_t *n_out, dpm_stream_t stream);
 
+/* The two filters whole, with the frame's length in DEVICE memory (the rule of the training transforms below): xyz
+ * (capacity,3) fp32, idx (capacity,) int32 [original indices, NULL-able: positions], count (1,) int32.  The length is
+ * count[0] clamped to [0, capacity]; every launch is sized by the capacity, rows at and past the count are never read, and
+ * the host never waits.  Survivors land in input order below count_out[0] in xyz_out (capacity,3) [divided by `ratio`, a
+ * true division: CoordinatesNormalization folded in, 1.0 = untouched] and idx_out (capacity,) [NULL-able].  Outputs must not
+ * alias inputs.  Same kernels, same arithmetic and, on xyz[:count], the same bytes as the building blocks above; two runs
+ * give identical bytes.  A frame of at most K points (K = nb_neighbors / normals_num; 0 and 1 included) passes through:
+ * its live rows in order, count_out = count.  `cell` = edge of the neighbour-search grid, as in dpm_knn_self.
+ *
+ * dpm_outlier_filter_dc: OutlierFilter (transforms.py:230-246, pytorch3d branch): mean distance to the nb_neighbors
+ *   nearest other points, keep stat <= mean + std_ratio * std.
+ * dpm_lowpass_filter_dc: LowPassFilter (transforms.py:256-289, max_remain off): normals within normals_radius, the
+ *   normals_num nearest other points, the sum of the `flux` largest |n_i . n_j|, keep stat > mean - filter_std * std.
+ * Checked before anything is queued: DPM_EINVAL for capacity < 0, K < 1, flux < 1 or flux > K; DPM_EUNSUPPORTED for
+ * K + 1 > 64 or flux > 8; capacity 0 returns DPM_OK at once.  workspace: dpm_filter_dc_workspace_bytes(capacity, K)
+ * (the search grid, the sorted points, the statistic, the normals and the neighbour indices of one frame). */
+size_t dpm_filter_dc_workspace_bytes(int capacity, int K);
+int dpm_outlier_filter_dc(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, int nb_neighbors,
+                          double std_ratio, double cell, double ratio, float *xyz_out, int32_t *idx_out,
+                          int32_t *count_out, void *workspace, dpm_stream_t stream);
+int dpm_lowpass_filter_dc(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity,
+                          double normals_radius, int normals_num, double filter_std, int flux, double cell, double ratio,
+                          float *xyz_out, int32_t *idx_out, int32_t *count_out, void *workspace, dpm_stream_t stream);
+
 /* ---------------------------------------------------------------- training transforms --- */
 
 /* The transforms only training configs use (dataloader/transforms.py).  ONE RULE: a frame is a fixed-capacity buffer
