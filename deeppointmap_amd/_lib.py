@@ -145,6 +145,9 @@ SIGNATURES = {
     "dpm_flat_pack": (I, [P, P, I, P, LL, P]),
     "dpm_flat_unpack": (I, [P, P, I, P, LL, P]),
     "dpm_optim_step_synced": (I, [I, P, P, I, D, D, D, D, D, D, D, D, I, I, P, I, LL, D, P]),
+    "dpm_lidar_cull": (I, [P, P, I, P, P, I, D, I, P, P, P, P]),
+    "dpm_lidar_cast": (I, [P, P, P, I, I, P, I, I, D, D, P, P, P, P]),
+    "dpm_lidar_emit": (I, [P, P, P, P, I, I, P, P, D, P, P, I, P, P, P, P, P, P]),
 }
 
 

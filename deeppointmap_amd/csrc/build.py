@@ -56,6 +56,7 @@ SOURCES = {
     "map_assemble.hip": [],
     "optim.hip": [],
     "ingest.hip": [],
+    "lidar_sim.hip": [],
 }
 
 

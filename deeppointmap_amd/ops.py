@@ -1891,3 +1891,108 @@ def ingest_frames(block: torch.Tensor, F: int, capacity: int, device=None, stagi
         _lib.check(_lib.load().dpm_ingest_frames(block.data_ptr(), _ptr(staging_dev), block.numel(), F, capacity, INGEST_CHUNK,
                                                  _ptr(xyz), _ptr(idx), _ptr(count), _ptr(ws), _stream(xyz)), "dpm_ingest_frames")
     return xyz, idx, count
+
+
+# ------------------------------------------------------------------------------------------------------------
+# LiDAR simulator (csrc/lidar_sim.hip)
+# ------------------------------------------------------------------------------------------------------------
+LIDAR_REC = 16        # floats of a kept record
+LIDAR_PRIM = 10       # doubles of a scene primitive
+LIDAR_BOX, LIDAR_CYLINDER = 0, 1
+LIDAR_MAX_RAYS = 1 << 24
+
+
+def _lidar_arg(t, dtype, name: str, shape_ok: bool, shape: str):
+    """dtype (TypeError) and shape (ValueError) before the device: a host-side mistake is reported without a GPU"""
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if not shape_ok:
+        raise ValueError(f"{name}: expected {shape}, got {tuple(t.shape)}")
+    return t
+
+
+def _lidar_dev(**tensors):
+    for name, t in tensors.items():
+        if t is not None:
+            _chk(t, t.dtype, name)
+
+
+def lidar_cull(prims: torch.Tensor, kind: torch.Tensor, ground: torch.Tensor, poses: torch.Tensor, max_range: float,
+               max_kept: int):
+    """dpm_lidar_cull: prims (P,10) float64, kind (P,) int32, ground (2,) float64, poses (F,4,4) float64 sensor-to-world ->
+    kept (F,max_kept,16) fp32 sensor-frame records in ascending primitive index, plane (F,4) fp32, status (F,2) int32 =
+    (primitives in range, overflow flag).  One launch, no host synchronisation: the CALLER raises on the flag at read-back."""
+    max_kept = int(max_kept)
+    if max_kept < 1 or not float(max_range) > 0:
+        raise ValueError("max_kept >= 1 and max_range > 0")
+    _lidar_arg(prims, torch.float64, "prims", prims.dim() == 2 and prims.shape[1] == LIDAR_PRIM, f"(P,{LIDAR_PRIM})")
+    _lidar_arg(kind, torch.int32, "kind", kind.shape == prims.shape[:1], "(P,)")
+    _lidar_arg(ground, torch.float64, "ground", ground.shape == (2,), "(2,)")
+    _lidar_arg(poses, torch.float64, "poses", poses.dim() == 3 and poses.shape[1:] == (4, 4) and poses.shape[0] >= 1, "(F,4,4), F >= 1")
+    _lidar_dev(prims=prims, kind=kind, ground=ground, poses=poses)
+    P, F, dev = prims.shape[0], poses.shape[0], poses.device
+    with torch.cuda.device(dev):
+        kept = torch.empty(F, max_kept, LIDAR_REC, device=dev, dtype=torch.float32)
+        plane = torch.empty(F, 4, device=dev, dtype=torch.float32)
+        status = torch.empty(F, 2, device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().dpm_lidar_cull(_ptr(prims), _ptr(kind), P, _ptr(ground), _ptr(poses), F, float(max_range),
+                                              max_kept, _ptr(kept), _ptr(plane), _ptr(status), _stream(poses)), "dpm_lidar_cull")
+    return kept, plane, status
+
+
+def lidar_cast(kept: torch.Tensor, plane: torch.Tensor, status: torch.Tensor, P: int, dirs: torch.Tensor, min_range: float,
+               max_range: float):
+    """dpm_lidar_cast: the outputs of lidar_cull, P = the scene's primitive count (the ground's id), dirs (rays,3) fp32
+    unit directions -> range (F,rays) fp32, prim (F,rays) int32 (index, P = ground, -1 = no return), cos_inc (F,rays)."""
+    if not 0.0 <= float(min_range) < float(max_range) or int(P) < 0:
+        raise ValueError("0 <= min_range < max_range and P >= 0")
+    _lidar_arg(kept, torch.float32, "kept", kept.dim() == 3 and kept.shape[2] == LIDAR_REC and kept.shape[0] >= 1 and kept.shape[1] >= 1,
+               f"(F,max_kept,{LIDAR_REC})")
+    F, max_kept = kept.shape[:2]
+    _lidar_arg(plane, torch.float32, "plane", plane.shape == (F, 4), "(F,4)")
+    _lidar_arg(status, torch.int32, "status", status.shape == (F, 2), "(F,2)")
+    _lidar_arg(dirs, torch.float32, "dirs", dirs.dim() == 2 and dirs.shape[1] == 3 and 1 <= dirs.shape[0] <= LIDAR_MAX_RAYS,
+               "(rays,3), 1 <= rays <= 2^24")
+    _lidar_dev(kept=kept, plane=plane, status=status, dirs=dirs)
+    rays, dev = dirs.shape[0], kept.device
+    with torch.cuda.device(dev):
+        rng = torch.empty(F, rays, device=dev, dtype=torch.float32)
+        prim = torch.empty(F, rays, device=dev, dtype=torch.int32)
+        cos_inc = torch.empty(F, rays, device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().dpm_lidar_cast(_ptr(kept), _ptr(plane), _ptr(status), max_kept, int(P), _ptr(dirs), rays, F,
+                                              float(min_range), float(max_range), _ptr(rng), _ptr(prim), _ptr(cos_inc),
+                                              _stream(kept)), "dpm_lidar_cast")
+    return rng, prim, cos_inc
+
+
+def lidar_emit(rng: torch.Tensor, prim: torch.Tensor, cos_inc: torch.Tensor, dirs: torch.Tensor, albedo: torch.Tensor,
+               class_id: torch.Tensor, noise: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
+               drop_prob: float = 0.0):
+    """dpm_lidar_emit: the outputs of lidar_cast, albedo (P+1,) fp32 and class_id (P+1,) int32 with the ground last, optional
+    noise / u (F,rays) fp32 -> xyz (F,rays,3), idx (F,rays) ray indices, count (F,), intensity (F,rays), label (F,rays)."""
+    if not 0.0 <= float(drop_prob) <= 1.0:
+        raise ValueError("drop_prob in [0, 1]")
+    _lidar_arg(rng, torch.float32, "range", rng.dim() == 2 and rng.shape[0] >= 1 and 1 <= rng.shape[1] <= LIDAR_MAX_RAYS,
+               "(F,rays), F >= 1, 1 <= rays <= 2^24")
+    F, rays = rng.shape
+    _lidar_arg(prim, torch.int32, "prim", prim.shape == rng.shape, "(F,rays)")
+    _lidar_arg(cos_inc, torch.float32, "cos_inc", cos_inc.shape == rng.shape, "(F,rays)")
+    _lidar_arg(dirs, torch.float32, "dirs", dirs.shape == (rays, 3), "(rays,3)")
+    _lidar_arg(albedo, torch.float32, "albedo", albedo.dim() == 1 and albedo.shape[0] >= 1, "(P+1,)")
+    _lidar_arg(class_id, torch.int32, "class_id", class_id.shape == albedo.shape, "(P+1,)")
+    for name, t in (("noise", noise), ("u", u)):
+        if t is not None:
+            _lidar_arg(t, torch.float32, name, t.shape == rng.shape, "(F,rays)")
+    _lidar_dev(range=rng, prim=prim, cos_inc=cos_inc, dirs=dirs, albedo=albedo, class_id=class_id, noise=noise, u=u)
+    dev = rng.device
+    with torch.cuda.device(dev):
+        xyz = torch.empty(F, rays, 3, device=dev, dtype=torch.float32)
+        idx = torch.empty(F, rays, device=dev, dtype=torch.int32)
+        count = torch.empty(F, device=dev, dtype=torch.int32)
+        intensity = torch.empty(F, rays, device=dev, dtype=torch.float32)
+        label = torch.empty(F, rays, device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().dpm_lidar_emit(_ptr(rng), _ptr(prim), _ptr(cos_inc), _ptr(dirs), rays, F, _ptr(noise), _ptr(u),
+                                              float(drop_prob), _ptr(albedo), _ptr(class_id), albedo.shape[0] - 1, _ptr(xyz),
+                                              _ptr(idx), _ptr(count), _ptr(intensity), _ptr(label), _stream(rng)),
+                   "dpm_lidar_emit")
+    return xyz, idx, count, intensity, label

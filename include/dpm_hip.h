@@ -875,6 +875,40 @@ int dpm_optim_step_synced(int algo, const long long *tensors, const int32_t *chu
                           int nesterov, int first, const float *slices, int n_slices, long long slice_stride, double divisor,
                           dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- LiDAR simulator -------- */
+
+/* A spinning-LiDAR model ray-cast through a procedural scene (csrc/lidar_sim.hip; deeppointmap_amd/lidar_sim.py builds the
+ * scenes).  It has no counterpart in the reference.  A batch of F frames takes these three calls = three launches,
+ * whatever F is, without a host synchronisation; the sequence can be captured in a graph.
+ * Scene: prims (P,10) float64 = centre x y z (a cylinder: the centre of its base), three extents (a box: half extents
+ * along its own axes; a cylinder: radius, height, 0), cos and sin of the yaw about world z (a cylinder: 1, 0), the z offset
+ * of the bounding sphere's centre from the centre and its radius; kind (P,) 0 = box, 1 = capped vertical cylinder;
+ * ground (2,) float64 = (z0, 1.0 when the plane z = z0 exists else 0.0).  poses (F,4,4) float64 row-major sensor-to-world.
+ * dpm_lidar_cull moves every primitive into frame f's sensor frame in float64, rounds to float32 and keeps, in ascending
+ * primitive index, those whose bounding sphere reaches the ball of max_range: kept (F,max_kept,16) fp32 records = the
+ * sensor's origin in the primitive's coordinates (3), the three rows that take a sensor-frame direction to those
+ * coordinates (9), the extents (3), and primitive index | kind << 30 as bits; plane (F,4) = the ground's unit normal and
+ * offset in the sensor frame (zeros without ground); status (F,2) = (kept primitives, 1 when that exceeds max_kept: the
+ * surplus is dropped and the caller raises at its next read-back). */
+int dpm_lidar_cull(const double *prims, const int32_t *kind, int P, const double *ground, const double *poses, int F,
+                   double max_range, int max_kept, float *kept, float *plane, int32_t *status, dpm_stream_t stream);
+/* One lane per ray: dirs (rays,3) fp32 unit directions in the sensor frame.  Per ray of every frame the smallest t > 0
+ * over all kept surfaces and the ground; equal t goes to the lowest primitive index, the ground last; an origin inside a
+ * primitive sees its exit face.  Outputs (F,rays): range fp32, prim int32 (primitive index, P for the ground, -1 for no
+ * return), cos_inc = |normal . direction|.  A nearest hit below min_range or beyond max_range is no return (range 0,
+ * prim -1, cos_inc 0).  Arithmetic is + - * / sqrt, each rounded once. */
+int dpm_lidar_cast(const float *kept, const float *plane, const int32_t *status, int max_kept, int P, const float *dirs,
+                   int rays, int F, double min_range, double max_range, float *range, int32_t *prim, float *cos_inc,
+                   dpm_stream_t stream);
+/* Returns -> frames in the layout of the training transforms.  A ray returns when prim >= 0 and (u == NULL or
+ * u >= (float)drop_prob); its point is (range + noise) * dir (noise (F,rays) metres or NULL).  xyz (F,rays,3), idx (F,rays)
+ * = the ray index of every row, count (F,): the returns in ray order, rows at and past the count zero.  intensity (F,rays)
+ * = albedo[prim] * cos_inc and label (F,rays) = class_id[prim] per RAY (0 / -1 without a hit); albedo, class_id (P+1,)
+ * with the ground at P.  No atomics: two runs give identical bytes. */
+int dpm_lidar_emit(const float *range, const int32_t *prim, const float *cos_inc, const float *dirs, int rays, int F,
+                   const float *noise, const float *u, double drop_prob, const float *albedo, const int32_t *class_id, int P,
+                   float *xyz, int32_t *idx, int32_t *count, float *intensity, int32_t *label, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
