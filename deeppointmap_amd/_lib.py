@@ -148,6 +148,11 @@ SIGNATURES = {
     "dpm_lidar_cull": (I, [P, P, I, P, P, I, D, I, P, P, P, P]),
     "dpm_lidar_cast": (I, [P, P, P, I, I, P, I, I, D, D, P, P, P, P]),
     "dpm_lidar_emit": (I, [P, P, P, P, I, I, P, P, D, P, P, I, P, P, P, P, P, P]),
+    "dpm_scene_distance": (I, [P, I, P, I, D, I, D, D, D, P, P, P]),
+    "dpm_cloud_nn_workspace_bytes": (c_size_t, [I, I]),
+    "dpm_cloud_nn": (I, [P, I, P, I, D, D, D, D, P, P, P, P]),
+    "dpm_distance_stats_workspace_bytes": (c_size_t, [I, I, I]),
+    "dpm_distance_stats": (I, [P, I, P, P, I, I, P, I, D, P, P, P]),
 }
 
 

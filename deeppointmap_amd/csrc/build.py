@@ -57,6 +57,7 @@ SOURCES = {
     "optim.hip": [],
     "ingest.hip": [],
     "lidar_sim.hip": [],
+    "map_eval.hip": [],
 }
 
 

@@ -1996,3 +1996,87 @@ def lidar_emit(rng: torch.Tensor, prim: torch.Tensor, cos_inc: torch.Tensor, dir
                                               _ptr(idx), _ptr(count), _ptr(intensity), _ptr(label), _stream(rng)),
                    "dpm_lidar_emit")
     return xyz, idx, count, intensity, label
+
+
+# ------------------------------------------------------------------------------------------------------------
+# map evaluation (csrc/map_eval.hip)
+# ------------------------------------------------------------------------------------------------------------
+MAP_EVAL_REC = 12            # floats of a scene record
+STATS_COLS = 5               # columns of the statistics table before the thresholds
+STATS_MAX_THRESHOLDS = 8
+STATS_MAX_CLASSES = 256
+
+
+def _origin3(origin):
+    o = [float(v) for v in origin]
+    if len(o) != 3:
+        raise ValueError("origin: three numbers")
+    return o
+
+
+def scene_distance(points: torch.Tensor, records: torch.Tensor, ground: Optional[float], origin):
+    """dpm_scene_distance: points (3,M) fp32, records (P,12) fp32 (evaluate.scene_records), ground = z0 - origin_z or None,
+    origin three floats -> dist (M,) fp32, surf (M,) int32 (0..P-1, P = ground, -1 = none).  One launch, no synchronisation."""
+    _lidar_arg(points, torch.float32, "points", points.dim() == 2 and points.shape[0] == 3, "(3,M)")
+    _lidar_arg(records, torch.float32, "records", records.dim() == 2 and records.shape[1] == MAP_EVAL_REC, f"(P,{MAP_EVAL_REC})")
+    o = _origin3(origin)
+    _lidar_dev(points=points, records=records)
+    M, P, dev = points.shape[1], records.shape[0], points.device
+    with torch.cuda.device(dev):
+        dist = torch.empty(M, device=dev, dtype=torch.float32)
+        surf = torch.empty(M, device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().dpm_scene_distance(_ptr(points), M, _ptr(records) if P else None, P,
+                                                  0.0 if ground is None else float(ground), int(ground is not None), *o,
+                                                  _ptr(dist), _ptr(surf), _stream(points)), "dpm_scene_distance")
+    return dist, surf
+
+
+def cloud_nn(query: torch.Tensor, target: torch.Tensor, max_dist: float, origin):
+    """dpm_cloud_nn: query (3,Nq), target (3,Nt) fp32 -> dist (Nq,) fp32 (+inf without a neighbour within max_dist),
+    idx (Nq,) int32 (-1).  Five launches, no synchronisation."""
+    if not 0.0 < float(max_dist) < 1e18:
+        raise ValueError("0 < max_dist < 1e18")
+    _lidar_arg(query, torch.float32, "query", query.dim() == 2 and query.shape[0] == 3, "(3,Nq)")
+    _lidar_arg(target, torch.float32, "target", target.dim() == 2 and target.shape[0] == 3, "(3,Nt)")
+    o = _origin3(origin)
+    _lidar_dev(query=query, target=target)
+    Nq, Nt, dev = query.shape[1], target.shape[1], query.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        dist = torch.empty(Nq, device=dev, dtype=torch.float32)
+        idx = torch.empty(Nq, device=dev, dtype=torch.int32)
+        ws = torch.empty(lib.dpm_cloud_nn_workspace_bytes(Nq, Nt), device=dev, dtype=torch.uint8)
+        _lib.check(lib.dpm_cloud_nn(_ptr(query) if Nq else None, Nq, _ptr(target) if Nt else None, Nt, float(max_dist), *o,
+                                    _ptr(dist), _ptr(idx), _ptr(ws), _stream(query)), "dpm_cloud_nn")
+    return dist, idx
+
+
+def distance_stats(dist: torch.Tensor, thresholds, max_dist: float, surf: Optional[torch.Tensor] = None,
+                   class_id: Optional[torch.Tensor] = None, n_classes: int = 0) -> torch.Tensor:
+    """dpm_distance_stats: dist (M,) fp32, thresholds a sequence of at most 8 numbers (rounded to fp32), optional surf (M,)
+    int32 with class_id (P+1,) int32 and n_classes -> (n_classes + 1, 5 + T) float64 on the device: per class, then in total,
+    matched count, unmatched count, sum d, sum d^2, max d, count with d <= thresholds[t].  Two launches, no synchronisation."""
+    thr = (ctypes.c_float * max(len(thresholds), 1))(*[float(t) for t in thresholds])
+    T, C = len(thresholds), int(n_classes)
+    if T > STATS_MAX_THRESHOLDS:
+        raise ValueError(f"at most {STATS_MAX_THRESHOLDS} thresholds")
+    if not 0 <= C <= STATS_MAX_CLASSES or not float(max_dist) > 0:
+        raise ValueError(f"0 <= n_classes <= {STATS_MAX_CLASSES} and max_dist > 0")
+    _lidar_arg(dist, torch.float32, "dist", dist.dim() == 1, "(M,)")
+    if C:
+        if surf is None or class_id is None:
+            raise ValueError("n_classes > 0 needs surf and class_id")
+        _lidar_arg(surf, torch.int32, "surf", surf.shape == dist.shape, "(M,)")
+        _lidar_arg(class_id, torch.int32, "class_id", class_id.dim() == 1 and class_id.shape[0] >= 1, "(P+1,)")
+    else:
+        surf = class_id = None
+    _lidar_dev(dist=dist, surf=surf, class_id=class_id)
+    M, dev = dist.shape[0], dist.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty(C + 1, STATS_COLS + T, device=dev, dtype=torch.float64)
+        ws = torch.empty(lib.dpm_distance_stats_workspace_bytes(M, C, T), device=dev, dtype=torch.uint8)
+        _lib.check(lib.dpm_distance_stats(_ptr(dist) if M else None, M, _ptr(surf), _ptr(class_id),
+                                          0 if class_id is None else class_id.shape[0], C, ctypes.addressof(thr) if T else None,
+                                          T, float(max_dist), _ptr(out), _ptr(ws), _stream(dist)), "dpm_distance_stats")
+    return out

@@ -231,6 +231,49 @@ class ResultLogger:
     def save_map(self, *a, **k) -> None:
         pass
 
+    def evaluate(self, file_name: str = "metrics", scene=None, voxel_size: float = 0.5, thresholds=(0.05, 0.1, 0.2, 0.5),
+                 max_dist: float = 1.0) -> dict:
+        """The run in numbers (evaluate.py has the definitions); -> the dict that is also written to <file_name>.json when
+        the logger has a directory.  Nothing calls this by default.
+          "trajectory": ate (se3-aligned), rpe (delta 1) and the KITTI segment errors of SE3_pred against SE3_gt over the
+                        scans that have a ground truth, by timestep; None without any;
+          "map_to_map": with `slam_system.result_maps`: the voxel map of the retained clouds under SE3_pred against the voxel
+                        map of the SAME clouds under SE3_gt (both globalmap.voxel_map at `voxel_size`; only scans that have
+                        a cloud, a pose and a ground truth); None without them;
+          "map_accuracy": with a lidar_sim.Scene: the voxel map of every retained cloud under SE3_pred against the scene's
+                        surfaces; None without a scene or without clouds."""
+        from . import evaluate as ev
+        b = self.backend
+        out = dict(scans=len(b.type), voxel_size=float(voxel_size), trajectory=None, map_to_map=None, map_accuracy=None)
+        toks = [t for t in sorted(b.type, key=lambda t: t & 0xFFFF) if t in b.gt and t in b.poses]
+        if toks:
+            est = torch.stack([b.poses[t] for t in toks]).double().numpy()
+            gt = torch.stack([b.gt[t] for t in toks]).double().numpy()
+            out["trajectory"] = ev.trajectory_metrics(est, gt)
+        if b.result_maps and b.map_clouds is not None:
+            from .globalmap import voxel_map
+            full = [t for t in b.type if t in b.map_clouds and t in b.poses]
+            both = [t for t in full if t in b.gt]
+            pred = None
+            if both:
+                clouds = [b.map_clouds[t] for t in both]
+                pred, _ = voxel_map(clouds, [b.poses[t] for t in both], voxel_size, device=b.device)
+                ref, _ = voxel_map(clouds, [b.gt[t] for t in both], voxel_size, device=b.device)
+                if pred.shape[1] and ref.shape[1]:
+                    out["map_to_map"] = ev.map_to_map(pred, ref, thresholds, max_dist)
+                    out["map_to_map"]["scans"] = len(both)
+            if scene is not None and full:
+                if pred is None or len(both) != len(full):
+                    pred = self._maps(voxel_size)[0]
+                if pred is not None and pred.shape[1]:
+                    out["map_accuracy"] = ev.map_accuracy(pred, scene, thresholds, max_dist)
+                    out["map_accuracy"]["scans"] = len(full)
+        if self.log_dir is not None:
+            import json
+            with open(self._path(file_name + ".json"), "w") as f:
+                json.dump(out, f, indent=1)
+        return out
+
 
 class SlamSystem:
     EXTRACTOR_BATCHSIZE = MTExtractor.EXTRACTOR_BATCHSIZE

@@ -909,6 +909,54 @@ int dpm_lidar_emit(const float *range, const int32_t *prim, const float *cos_inc
                    const float *noise, const float *u, double drop_prob, const float *albedo, const int32_t *class_id, int P,
                    float *xyz, int32_t *idx, int32_t *count, float *intensity, int32_t *label, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- map evaluation -------- */
+
+/* How far a point-cloud map lies from the surfaces it should lie on (csrc/map_eval.hip; deeppointmap_amd/evaluate.py is the
+ * caller).  No counterpart in the reference.  Clouds are (3,M) fp32 channel-first on the device (what globalmap.voxel_map
+ * returns).  Every entry point takes an origin of three doubles by value and shifts every point ONCE, q = (float)((double)p -
+ * origin); everything after that is fp32 in + - * / sqrt, each rounded once, on numbers no larger than the map's extent.  No
+ * floating-point atomics: two runs give identical bytes.  Every call runs on `stream` without a host synchronisation.
+ *
+ * dpm_scene_distance: per point the unsigned distance to the nearest surface of a simulator scene and that surface's id.
+ * records (P,12) fp32, prepared in float64 and rounded once: centre - origin (3), cos and sin of the yaw (a cylinder: 1, 0),
+ * the extents (a box: its half extents; a cylinder: radius, HALF height, 0, the centre being the middle of its axis), the kind
+ * (0 = box, 1 = cylinder) as BITS, three floats of padding.  ground = z0 - origin_z (rounded to fp32 here), has_ground != 0
+ * when the plane exists.  With d = q - centre, in this order of operations:
+ *   box       lx = cos*dx + sin*dy, ly = cos*dy - sin*dx, lz = dz; a_k = |l_k| - h_k, o_k = max(a_k, 0);
+ *             dist = |sqrt((ox*ox + oy*oy) + oz*oz) + min(max(ax, max(ay, az)), 0)|
+ *   cylinder  a0 = sqrt(dx*dx + dy*dy) - r, a1 = |dz| - hh, o_k = max(a_k, 0);
+ *             dist = |sqrt(o0*o0 + o1*o1) + min(max(a0, a1), 0)|
+ *   ground    |qz - ground|
+ * The records are walked in ascending index and a strictly smaller distance wins, the ground last: equal distances keep the
+ * lower index and the ground loses ties.  dist (M,) fp32, surf (M,) int32 = 0..P-1, P for the ground.  A point whose shifted
+ * coordinates are not all finite, or an empty scene (P = 0 and no ground), gives +inf and -1.  P x M evaluations: no culling. */
+int dpm_scene_distance(const float *points, int M, const float *records, int P, double ground, int has_ground, double origin_x,
+                       double origin_y, double origin_z, float *dist, int32_t *surf, dpm_stream_t stream);
+/* Exact truncated nearest neighbour from query (3,Nq) to target (3,Nt): the winner is the target with the smallest
+ * d2 = (dx*dx + dy*dy) + dz*dz on the shifted coordinates among those with d2 <= (float)(max_dist * max_dist); equal d2 goes to
+ * the smaller target index (the (distance bits, index) key of csrc/icp.hip).  dist (Nq,) = sqrt(d2) or +inf without one,
+ * idx (Nq,) int32 or -1.  Targets with a non-finite coordinate are nobody's neighbour, queries with one have none.  The target
+ * side is counting-sorted once per call into a uniform grid with a cell edge of max(1.001 max_dist, extent / 127) -- at most
+ * 128 cells per axis; beyond that the edge grows, the result stays exact and only the candidate count grows -- and every
+ * query looks into 3 x 3 x 3 cells.  Nt = 0 is allowed (every query: +inf, -1).  workspace: dpm_cloud_nn_workspace_bytes. */
+size_t dpm_cloud_nn_workspace_bytes(int Nq, int Nt);
+int dpm_cloud_nn(const float *query, int Nq, const float *target, int Nt, double max_dist, double origin_x, double origin_y,
+                 double origin_z, float *dist, int32_t *idx, void *workspace, dpm_stream_t stream);
+/* A distance array -> out (C+1, 5+T) float64 in two launches: rows = class 0..C-1, then the total over EVERY point; columns =
+ * matched count, unmatched count, sum of d, sum of d*d, max d, count with d <= thresholds[t].  A point is matched when its
+ * distance is finite and <= (float)max_dist; the sums, the maximum and the threshold counts are taken over matched points (0
+ * without any).  A point's class is class_id[surf[i]] (surf (M,) int32 into class_id (n_surf,) int32; a surf outside
+ * [0, n_surf) or a class outside [0, C) counts in the total only); C = 0 takes no surf and gives the total row alone.
+ * thresholds: T <= DPM_STATS_MAX_THRESHOLDS floats ON THE HOST, read before the launch.  Orders: every block takes a contiguous
+ * chunk of the points, lane t of 256 walks first + t, first + t + 256, ... adding (double)d and (double)d * (double)d; the 64
+ * lanes of a wave are added by the xor butterfly 32, 16, .. 1, the four waves as (w0 + w1) + (w2 + w3); one final block adds the
+ * blocks' partials in block order.  workspace: dpm_distance_stats_workspace_bytes. */
+#define DPM_STATS_MAX_THRESHOLDS 8
+#define DPM_STATS_MAX_CLASSES 256
+size_t dpm_distance_stats_workspace_bytes(int M, int C, int T);
+int dpm_distance_stats(const float *dist, int M, const int32_t *surf, const int32_t *class_id, int n_surf, int C,
+                       const float *thresholds, int T, double max_dist, double *out, void *workspace, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
