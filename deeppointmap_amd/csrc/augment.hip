@@ -13,7 +13,7 @@
 // survivors of its 4096-item chunk, ONE workgroup scans the block counts, a block writes its survivors at its offset.
 // No kernel waits on another workgroup; the only atomics are integer atomics (the ground filter's cell table on
 // order-preserving images of z, the voxel grid's minima), which are associative: two runs give identical bytes.
-#include "dpm_common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -58,28 +58,9 @@ template <class K>
 __global__ __launch_bounds__(1024) void sel_scan_kernel(const K keep, int *__restrict__ bcount, int max_blocks,
                                                         int32_t *__restrict__ n_out) {
     __shared__ int wsum[16];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int nblk = (int)min((long long)max_blocks, (keep.n() + CH - 1) / CH);
-    const int per = (max_blocks + 1023) / 1024;
-    const int b0 = min(t * per, nblk), b1 = min(b0 + per, nblk);
-    int s = 0;
-    for (int b = b0; b < b1; ++b) s += bcount[b];
-    int inc = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int run = inc - s;
-    for (int k = 0; k < w; ++k) run += wsum[k];
-    for (int b = b0; b < b1; ++b) {
-        const int v = bcount[b];
-        bcount[b] = run;
-        run += v;
-    }
-    if (t == 1023) *n_out = run;
+    const int run = block_scan_runs(bcount, nblk, (max_blocks + 1023) / 1024, wsum);
+    if (threadIdx.x == 1023) *n_out = run;
 }
 
 template <class K>
@@ -90,7 +71,7 @@ __global__ __launch_bounds__(256) void sel_write_kernel(const K keep, const int 
     const long long n = keep.n(), c0 = (long long)blockIdx.x * CH;
     if (c0 >= n) return;
     // thread t owns 16 CONSECUTIVE items so that the block-level order equals the domain's order
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     int src[CH / 256], cnt = 0;
 #pragma unroll
     for (int k = 0; k < CH / 256; ++k) {
@@ -98,16 +79,7 @@ __global__ __launch_bounds__(256) void sel_write_kernel(const K keep, const int 
         src[k] = c < n ? keep.src(c) : -1;
         cnt += src[k] >= 0;
     }
-    int inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int pos = boff[blockIdx.x] + inc - cnt;
-    for (int k = 0; k < w; ++k) pos += s_w[k];
+    int pos = block_scan_exclusive(cnt, s_w, boff[blockIdx.x]);
 #pragma unroll
     for (int k = 0; k < CH / 256; ++k) {
         const int g = src[k];

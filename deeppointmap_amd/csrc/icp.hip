@@ -17,7 +17,8 @@
 //               the step onto the pose and sets the pair's `done` flag; blocks of a done pair return at once.
 // The step x = (w, v) moves a transformed point p' to p' + w x p' + v; it is applied as pose <- [exp(w) | v] o pose
 // (Rodrigues rotation, the translation taken as it is).
-#include "dpm_common.h"
+#include "block_scan.h"
+#include "cell_grid.h"
 
 namespace {
 
@@ -55,10 +56,6 @@ __device__ __forceinline__ float4 *sorted_of(const IcpArgs &a, int p) {
     return (float4 *)(a.ws + (size_t)p * a.ws_stride + 256 + sizeof(int) * (size_t)(GMAX * GMAX + 4));
 }
 __device__ __forceinline__ double *partial_of(const IcpArgs &a, int p) { return (double *)(sorted_of(a, p) + a.N); }
-
-__device__ __forceinline__ int cell_coord(float v, float lo, float inv_cs, int g) {
-    return min(max((int)floorf((v - lo) * inv_cs), 0), g - 1);
-}
 
 // One workgroup per pair: frame indices and counts, the target's xy bounds, the grid header, and the cell counters zeroed.
 __global__ __launch_bounds__(1024) void icp_setup_kernel(IcpArgs A, float radius) {
@@ -107,8 +104,7 @@ __global__ __launch_bounds__(1024) void icp_setup_kernel(IcpArgs A, float radius
     for (int c = t; c <= s_ncell; c += 1024) cells[c] = 0;
 }
 
-// PLACE = false: points per cell into cells[c + 1]; PLACE = true (after the scan, when cells[c + 1] is the start of cell c):
-// every point to its cell's next free slot, which leaves cells[c + 1] at the cell's end = the start of cell c + 1
+// the two passes of the counting sort around icp_scan_kernel (grid_count_or_place of cell_grid.h)
 template <bool PLACE>
 __global__ __launch_bounds__(256) void icp_grid_kernel(IcpArgs A) {
     const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
@@ -117,33 +113,14 @@ __global__ __launch_bounds__(256) void icp_grid_kernel(IcpArgs A) {
     const float *p2 = A.pcd + (size_t)hdr->fd * 3 * A.N;
     const float x = p2[i], y = p2[(size_t)A.N + i];
     const int c = cell_coord(y, hdr->loy, hdr->inv_cs, hdr->gy) * hdr->gx + cell_coord(x, hdr->lox, hdr->inv_cs, hdr->gx);
-    int *slot = cells_of(A, pair) + 1 + c;
-    const int pos = atomicAdd(slot, 1);
-    if (PLACE) sorted_of(A, pair)[pos] = make_float4(x, y, p2[2 * (size_t)A.N + i], __int_as_float(i));
+    grid_count_or_place<PLACE>(cells_of(A, pair), sorted_of(A, pair), A.N, c, x, y, PLACE ? p2[2 * (size_t)A.N + i] : 0.f, i);
 }
 
 // exclusive prefix sum of cells[1 .. ncell] in place, one workgroup per pair (thread t owns a contiguous run of cells)
 __global__ __launch_bounds__(1024) void icp_scan_kernel(IcpArgs A) {
-    const int pair = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int *c = cells_of(A, pair) + 1;
-    const int ncell = hdr_of(A, pair)->ncell, per = (ncell + 1023) / 1024, a = min(t * per, ncell), b = min(a + per, ncell);
-    int sum = 0;
-    for (int k = a; k < b; ++k) sum += c[k];
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
     __shared__ int wsum[16];
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int k = 0; k < w; ++k) run += wsum[k];
-    for (int k = a; k < b; ++k) {
-        const int n = c[k];
-        c[k] = run, run += n;
-    }
+    const int pair = blockIdx.x, ncell = hdr_of(A, pair)->ncell;
+    block_scan_runs(cells_of(A, pair) + 1, ncell, (ncell + 1023) / 1024, wsum);
 }
 
 // pose <- init, the per-pair results to their start values
@@ -176,20 +153,6 @@ __device__ __forceinline__ void add_row(double (&s)[NSUM], const double (&J)[6],
 #pragma unroll
     for (int i = 0; i < 6; ++i) s[21 + i] = fma(J[i], e, s[21 + i]);
     s[28] = fma(e, e, s[28]);
-}
-
-// Grid (nblk, n_pairs) -> (block within the pair, pair) such that all blocks of one pair run on the same XCD, whose L2 then
-// holds the one or two grids it is working on (pair_block of infomat.hip; workgroups are dealt round-robin to the 8 XCDs).
-// Which workgroup computes a (pair, block) partial changes nothing about the partial.
-__device__ __forceinline__ void pair_block(int &blk, int &pair) {
-    const int nblk = gridDim.x, npair = gridDim.y;
-    if (npair % 8 == 0) {
-        const unsigned L = blockIdx.y * nblk + blockIdx.x;
-        const unsigned xcd = L & 7, slot = L >> 3;
-        pair = (int)((slot / nblk) * 8 + xcd), blk = (int)(slot % nblk);
-    } else {
-        pair = blockIdx.y, blk = blockIdx.x;
-    }
 }
 
 template <int PLANE>
@@ -238,21 +201,8 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(IcpArgs A, float r2
             rlo[r] = in ? cells[yc * gx + xa] : 0, rhi[r] = in ? cells[yc * gx + xb] : 0;
         }
 #pragma unroll
-        for (int r = 0; r < 5; ++r) {
-            const int lo = rlo[r], hi = rhi[r];
-            for (int p = lo + ql; p < hi; p += 4) {
-                const float4 t = sorted[p];
-                const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
-                const float d = (dx * dx + dy * dy) + dz * dz;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(t.w);
-                best = key < best ? key : best;
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            const unsigned long long o = (unsigned long long)__shfl_xor((long long)best, off, 64);
-            best = o < best ? o : best;
-        }
+        for (int r = 0; r < 5; ++r) quad_scan_range(sorted, rlo[r], rhi[r], ql, qx, qy, qz, best);
+        best = quad_min_key(best);
         const bool hit = best != ~0ull && __uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
         const int win = hit ? (int)(unsigned)best : -1;
         if (ql != 0) continue;

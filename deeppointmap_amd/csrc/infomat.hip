@@ -9,7 +9,7 @@
 // cells around it (65 536^2 = 4.3e9 pair evaluations become ~6e6).  Summing the three outer
 // products gives a matrix that depends on ten moments (n, sum x, y, z, xx, yy, zz, xy, xz, yz);
 // they are accumulated in fp64 and rounded once to the fp32 6x6 the reference returns.
-#include "dpm_common.h"
+#include "cell_grid.h"
 #include <type_traits>
 
 namespace {
@@ -130,25 +130,6 @@ __global__ __launch_bounds__(64) void grid_setup_kernel(PairArgs A, float radius
         (void)frexpf(fmaxf(amax, 1e-30f), &e);  // amax < 2^e
         hdr->qexp = bits - e;
     }
-}
-
-// Grid (nblk, n_pairs) -> (block within the pair, pair) such that ALL blocks of one pair run on the SAME XCD.
-// Workgroups are dealt round-robin to the 8 XCDs by linear id and every XCD has a private 4 MB L2; with the
-// plain mapping each L2 sees the grids of all pairs at once (64 x 1 MB: every candidate load misses to the
-// fabric -- 4.8 GB per launch measured), with this one it holds the one or two pairs it is working on.
-__device__ __forceinline__ void pair_block(int &blk, int &pair) {
-    const int nblk = gridDim.x, npair = gridDim.y;
-    if (npair % 8 == 0) {
-        const unsigned L = blockIdx.y * nblk + blockIdx.x;
-        const unsigned xcd = L & 7, slot = L >> 3;
-        pair = (int)((slot / nblk) * 8 + xcd), blk = (int)(slot % nblk);
-    } else {
-        pair = blockIdx.y, blk = blockIdx.x;
-    }
-}
-
-__device__ __forceinline__ int cell_coord(float v, float lo, float inv_cs, int g) {
-    return min(max((int)floorf((v - lo) * inv_cs), 0), g - 1);
 }
 
 // Counting sort of pcd2 into the grid as FOUR short chip-wide kernels with a few KB of LDS each (round 3).  The one-kernel

@@ -16,7 +16,7 @@
 // so each frame equals PointCloud(filtered array, capacity=cap) byte for byte.  No atomics at all: two runs give identical
 // bytes.  Every header field is checked on the host BEFORE anything is queued (a row count above the capacity is DPM_EINVAL),
 // and the kernels clamp what they read from the device copy of the header all the same.
-#include "dpm_common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void ingest_write_kernel(const long long *__re
     int32_t *oi = idx + (size_t)f * cap;
     const long long c0 = (long long)blockIdx.x * CH;
     // thread t owns 16 CONSECUTIVE records so that the block-level order equals the input order
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     bool keep[CH / 256];
     int cnt = 0;
 #pragma unroll
@@ -109,16 +109,7 @@ __global__ __launch_bounds__(256) void ingest_write_kernel(const long long *__re
         keep[k] = c < fr.rows && keeps(fr, (int)c);
         cnt += keep[k];
     }
-    int inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int pos = boff[(size_t)f * nblk + blockIdx.x] + inc - cnt;
-    for (int k = 0; k < w; ++k) pos += s_w[k];
+    int pos = block_scan_exclusive(cnt, s_w, boff[(size_t)f * nblk + blockIdx.x]);
 #pragma unroll
     for (int k = 0; k < CH / 256; ++k) {
         if (!keep[k]) continue;

@@ -32,7 +32,7 @@
 //    in the sorted array, so a centre reads three short ranges.  65 536 x 4096 pair evaluations
 //    become ~150 per centre.  A centre with nothing inside the radius (only padded centres) falls
 //    back to a full scan for its nearest point.
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "filter_dc.h"
 #include "topk_emulate.h"
 #include <type_traits>
@@ -582,16 +582,7 @@ __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float *__res
     int local[PER], tsum = 0;
 #pragma unroll
     for (int q = 0; q < PER; ++q) local[q] = s_hist[t * PER + q], tsum += local[q];
-    int inc = tsum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wsum[w] = inc;
-    __syncthreads();
-    int run = inc - tsum;
-    for (int k = 0; k < w; ++k) run += s_wsum[k];
+    int run = block_scan_exclusive(tsum, s_wsum);
     int *start = start_all + (size_t)b * (GDIM * GDIM + 1);
 #pragma unroll
     for (int q = 0; q < PER; ++q) {

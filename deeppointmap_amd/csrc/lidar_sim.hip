@@ -18,7 +18,7 @@
 // restatement that follows the order of operations gives the same bits.  No atomics.
 #include <math.h>
 
-#include "dpm_common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -221,17 +221,9 @@ __global__ __launch_bounds__(256) void lidar_emit_kernel(const float *__restrict
         keep[k] = r < rays && returns(prim, u, drop, fo + r);
         cnt += keep[k];
     }
-    int inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
+    int pos = block_scan_exclusive(cnt, s_w);   // its barrier also publishes s_a / s_b
     const int n = s_b[0] + s_b[1] + s_b[2] + s_b[3];
-    int pos = s_a[0] + s_a[1] + s_a[2] + s_a[3] + inc - cnt;
-    for (int k = 0; k < w; ++k) pos += s_w[k];
+    pos += s_a[0] + s_a[1] + s_a[2] + s_a[3];
     float *ox = xyz + 3 * fo;
     int32_t *oi = idx + fo;
 #pragma unroll

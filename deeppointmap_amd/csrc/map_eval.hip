@@ -19,7 +19,8 @@
 // index) key makes the result independent of it.
 #include <math.h>
 
-#include "dpm_common.h"
+#include "block_scan.h"
+#include "cell_grid.h"
 
 namespace {
 
@@ -104,9 +105,6 @@ __device__ __forceinline__ int *nn_cells(const NnArgs &a) { return (int *)(a.ws 
 __device__ __forceinline__ float4 *nn_sorted(const NnArgs &a) {
     return (float4 *)(a.ws + 256 + sizeof(int) * ((size_t)GMAX * GMAX * GMAX + 4));
 }
-__device__ __forceinline__ int nn_coord(float v, float lo, float inv_cs, int g) {
-    return min(max((int)floorf((v - lo) * inv_cs), 0), g - 1);
-}
 
 // One workgroup: the bounds of the shifted targets with finite coordinates, the grid header, the cell counters zeroed.
 // Cell edge = max(1.001 max_dist, extent / (GMAX - 1)): past GMAX cells per axis the edge grows, the search stays exact.
@@ -153,8 +151,7 @@ __global__ __launch_bounds__(1024) void nn_setup_kernel(NnArgs A, float radius) 
     for (int c = t; c <= s_ncell; c += 1024) cells[c] = 0;
 }
 
-// PLACE = false: targets per cell into cells[c + 1]; PLACE = true (after the scan, when cells[c + 1] is the start of cell c):
-// every target to its cell's next free slot, which leaves cells[c + 1] at the cell's end = the start of cell c + 1.
+// the two passes of the counting sort around nn_scan_kernel (grid_count_or_place of cell_grid.h).
 // A target with a non-finite coordinate is in no cell: it is nobody's neighbour.
 template <bool PLACE>
 __global__ __launch_bounds__(256) void nn_grid_kernel(NnArgs A) {
@@ -164,34 +161,16 @@ __global__ __launch_bounds__(256) void nn_grid_kernel(NnArgs A) {
     const float x = shifted(A.tgt[i], A.ox), y = shifted(A.tgt[(size_t)A.Nt + i], A.oy),
                 z = shifted(A.tgt[2 * (size_t)A.Nt + i], A.oz);
     if (!(finite_f(x) && finite_f(y) && finite_f(z))) return;
-    const int c = (nn_coord(z, hdr->loz, hdr->inv_cs, hdr->gz) * hdr->gy + nn_coord(y, hdr->loy, hdr->inv_cs, hdr->gy)) * hdr->gx +
-                  nn_coord(x, hdr->lox, hdr->inv_cs, hdr->gx);
-    const int pos = atomicAdd(nn_cells(A) + 1 + c, 1);
-    if (PLACE && pos >= 0 && pos < A.Nt) nn_sorted(A)[pos] = make_float4(x, y, z, __int_as_float(i));
+    const int c = (cell_coord(z, hdr->loz, hdr->inv_cs, hdr->gz) * hdr->gy + cell_coord(y, hdr->loy, hdr->inv_cs, hdr->gy)) * hdr->gx +
+                  cell_coord(x, hdr->lox, hdr->inv_cs, hdr->gx);
+    grid_count_or_place<PLACE>(nn_cells(A), nn_sorted(A), A.Nt, c, x, y, z, i);
 }
 
 // exclusive prefix sum of cells[1 .. ncell] in place, one workgroup (thread t owns a contiguous run of cells)
 __global__ __launch_bounds__(1024) void nn_scan_kernel(NnArgs A) {
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int *c = nn_cells(A) + 1;
-    const int ncell = nn_hdr(A)->ncell, per = (ncell + 1023) / 1024, a = min(t * per, ncell), b = min(a + per, ncell);
-    int sum = 0;
-    for (int k = a; k < b; ++k) sum += c[k];
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
     __shared__ int wsum[16];
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int k = 0; k < w; ++k) run += wsum[k];
-    for (int k = a; k < b; ++k) {
-        const int n = c[k];
-        c[k] = run, run += n;
-    }
+    const int ncell = nn_hdr(A)->ncell;
+    block_scan_runs(nn_cells(A) + 1, ncell, (ncell + 1023) / 1024, wsum);
 }
 
 // grid (ceil(Nq / 64)), 256 threads: four lanes per query.  d2 = (dx*dx + dy*dy) + dz*dz on the shifted coordinates; the
@@ -224,21 +203,8 @@ __global__ __launch_bounds__(256) void nn_search_kernel(NnArgs A, float r2, floa
         rlo[r] = in ? cells[row + xa] : 0, rhi[r] = in ? cells[row + xb] : 0;
     }
 #pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        const int lo = max(rlo[r], 0), hi = min(rhi[r], A.Nt);
-        for (int p = lo + ql; p < hi; p += 4) {
-            const float4 t = sorted[p];
-            const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
-            const float d = (dx * dx + dy * dy) + dz * dz;
-            const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(t.w);
-            best = key < best ? key : best;
-        }
-    }
-#pragma unroll
-    for (int off = 1; off <= 2; off <<= 1) {
-        const unsigned long long o = (unsigned long long)__shfl_xor((long long)best, off, 64);
-        best = o < best ? o : best;
-    }
+    for (int r = 0; r < 9; ++r) quad_scan_range(sorted, max(rlo[r], 0), min(rhi[r], A.Nt), ql, qx, qy, qz, best);
+    best = quad_min_key(best);
     if (ql != 0) return;
     const float d2 = __uint_as_float((unsigned)(best >> 32));
     const bool hit = best != ~0ull && d2 <= r2;   // a NaN distance is no hit

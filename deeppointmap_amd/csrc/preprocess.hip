@@ -9,7 +9,7 @@
 // predicate that preserves order, so it is folded into the same compaction, and the division by `ratio` into the
 // final gather.  Arithmetic mirrors numpy/torch fp32 on the CPU: (x - min) / voxel_size truncated toward zero,
 // true division for the normalisation (torch's in-place `/=` on CPU tensors).
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "filter_dc.h"
 
 namespace {
@@ -104,28 +104,9 @@ __global__ __launch_bounds__(256) void pre_count_kernel(const float *__restrict_
 __global__ __launch_bounds__(1024) void pre_scan_kernel(PreHdr *__restrict__ hdr, int *__restrict__ bcount, int max_blocks) {
     __shared__ int wsum[16];
     if (hdr->overflow) return;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int nblk = (int)((hdr->ncell + CH - 1) / CH);
-    const int per = (max_blocks + 1023) / 1024;
-    const int b0 = t * per, b1 = min(b0 + per, nblk);
-    int s = 0;
-    for (int b = b0; b < b1; ++b) s += bcount[b];
-    int inc = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int run = inc - s;
-    for (int k = 0; k < w; ++k) run += wsum[k];
-    for (int b = b0; b < b1; ++b) {
-        const int v = bcount[b];
-        bcount[b] = run;
-        run += v;
-    }
-    if (t == 1023) hdr->n_out = run;
+    const int run = block_scan_runs(bcount, nblk, (max_blocks + 1023) / 1024, wsum);
+    if (threadIdx.x == 1023) hdr->n_out = run;
 }
 
 __global__ __launch_bounds__(256) void pre_write_kernel(const float *__restrict__ xyz, int stride, float dmin, float dmax,
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(256) void pre_write_kernel(const float *__restrict_
     const long long c0 = (long long)blockIdx.x * CH;
     if (c0 >= hdr->ncell) return;
     // thread t owns 16 CONSECUTIVE cells so that the block-level order equals cell order
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     int idx[CH / 256], cnt = 0;
 #pragma unroll
     for (int k = 0; k < CH / 256; ++k) {
@@ -149,16 +130,7 @@ __global__ __launch_bounds__(256) void pre_write_kernel(const float *__restrict_
         idx[k] = g;
         cnt += g != 0x7fffffff;
     }
-    int inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int pos = boff[blockIdx.x] + inc - cnt;
-    for (int k = 0; k < w; ++k) pos += s_w[k];
+    int pos = block_scan_exclusive(cnt, s_w, boff[blockIdx.x]);
 #pragma unroll
     for (int k = 0; k < CH / 256; ++k) {
         const int g = idx[k];

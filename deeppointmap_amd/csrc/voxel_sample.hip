@@ -18,7 +18,7 @@
 // Arithmetic mirrors torch's fp32 CPU kernels operation by operation (the library is built with -ffp-contract=off).
 #include <vector>
 
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "topk_emulate.h"
 
 namespace {
@@ -177,29 +177,9 @@ __global__ __launch_bounds__(256) void vox_count_kernel(const VoxHdr *__restrict
 // exclusive scan of a frame's chunk counts (in place) + number of occupied voxels
 __global__ __launch_bounds__(1024) void vox_scan_kernel(int nchunk, int *__restrict__ bcount, int32_t *__restrict__ n_unique) {
     __shared__ int wsum[16];
-    __shared__ int carry;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int *c = bcount + (size_t)b * nchunk;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nchunk; base += 1024) {
-        const int i = base + t;
-        const int v = i < nchunk ? c[i] : 0;
-        int inc = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int before = carry;
-        for (int k = 0; k < w; ++k) before += wsum[k];
-        if (i < nchunk) c[i] = before + inc - v;
-        __syncthreads();
-        if (t == 1023) carry = before + inc;
-        __syncthreads();
-    }
-    if (t == 0) n_unique[b] = carry;
+    const int b = blockIdx.x;
+    const int run = block_scan_runs(bcount + (size_t)b * nchunk, nchunk, (nchunk + 1023) / 1024, wsum);
+    if (threadIdx.x == 1023) n_unique[b] = run;
 }
 
 // ordered compaction of one chunk: thread t owns cells [16 t, 16 t + 16) of the chunk
@@ -209,7 +189,7 @@ __global__ __launch_bounds__(256) void vox_write_kernel(const VoxHdr *__restrict
                                                         const int *__restrict__ boff, int N, int32_t *__restrict__ ufirst,
                                                         int32_t *__restrict__ ucnt) {
     __shared__ int wsum[4];
-    const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
     const VoxHdr h = hdr[b];
     const long long nc = h.over != 0.f ? 0 : vox_ncell(h) + 1;
     const size_t base = (size_t)b * (size_t)(max_cells + 1);
@@ -217,15 +197,7 @@ __global__ __launch_bounds__(256) void vox_write_kernel(const VoxHdr *__restrict
     unsigned occ = 0;
     for (int k = 0; k < 16; ++k) occ |= (c0 + k < nc && cnt[base + c0 + k] != 0u) ? (1u << k) : 0u;
     const int mine = __popc(occ);
-    int inc = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int pos = boff[(size_t)b * nchunk + chunk] + inc - mine;
-    for (int k = 0; k < w; ++k) pos += wsum[k];
+    int pos = block_scan_exclusive(mine, wsum, boff[(size_t)b * nchunk + chunk]);
     for (int k = 0; k < 16; ++k)
         if ((occ >> k) & 1u) {
             ufirst[(size_t)b * N + pos] = (int32_t)(unsigned)(keys[base + c0 + k] & 0xffffffffull);

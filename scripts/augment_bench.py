@@ -84,7 +84,8 @@ def main():
         def gpu(rng, keep=False):
             def run():
                 chain = augment.get_transforms(SPEC)
-                pcds, rec = augment.transform_frames([augment.PointCloud(x) for x in dev], chain, rng=rng, return_draws=keep)
+                out = augment.transform_frames([augment.PointCloud(x) for x in dev], chain, rng=rng, return_draws=keep)
+                pcds, rec = out if keep else (out, None)   # the draws come back only when asked for
                 batch = augment.collate_frames(pcds, -1)
                 if keep:
                     kept["records"], kept["shape"] = rec, tuple(batch[0].shape)

@@ -50,9 +50,15 @@ def sizes(ops):
     return C, [0, 1, 2, C - 1, C, C + 1, 2 * C + 1], 2 * C + 64      # the capacity is no multiple of the chunk
 
 
-@pytest.mark.parametrize("stride", [3, 4])
-def test_every_length_alone_and_in_one_batch(mods, stride):
+@pytest.mark.parametrize("stride,chunks", [(3, 3), (4, 3), (4, 65)], ids=["3", "4", "4-65chunks"])
+def test_every_length_alone_and_in_one_batch(mods, stride, chunks):
     C, lengths, cap = sizes(mods[2])
+    if chunks == 65:   # more than 64 chunks: the scan's one wave takes the chunk counts in two rounds and carries the sum over
+        rows = records(64 * C + 1, stride, 9)
+        rows[::1000, 1] = np.nan
+        _, _, count = check(mods, [(rows, True)], 64 * C + 64)
+        assert count[0] == rows.shape[0] - len(rows[::1000])
+        return
     frames = [(records(n, stride, 10 + k), stride == 4) for k, n in enumerate(lengths)]
     for fr in frames:                                  # a batch of one frame
         check(mods, [fr], cap)
