@@ -98,6 +98,7 @@ SIGNATURES = {
     "dpm_voxel_select": (I, [P, P, P, I, D, I, LL, P, P, P, P, P]),
     "dpm_mask_select": (I, [P, P, P, I, I, D, D, P, D, P, I, P, P, P, P, P]),
     "dpm_points_affine": (I, [P, P, I, I, P, P, P]),
+    "dpm_points_deskew": (I, [P, P, P, I, I, P, I, I, P, D, P]),
     "dpm_gather_points": (I, [P, P, P, I, P, I, I, P, P, P, P]),
     "dpm_pack_frames": (I, [P, P, P, I, I, P, P, P, P]),
     "dpm_ingest_frames": (I, [P, P, LL, I, I, I, P, P, P, P, P]),
@@ -147,6 +148,8 @@ SIGNATURES = {
     "dpm_optim_step_synced": (I, [I, P, P, I, D, D, D, D, D, D, D, D, I, I, P, I, LL, D, P]),
     "dpm_lidar_cull": (I, [P, P, I, P, P, I, D, I, P, P, P, P]),
     "dpm_lidar_cast": (I, [P, P, P, I, I, P, I, I, D, D, P, P, P, P]),
+    "dpm_lidar_cull_sweep": (I, [P, P, I, P, P, P, I, I, D, I, P, P, P, P, P]),
+    "dpm_lidar_cast_sweep": (I, [P, P, P, I, I, P, I, I, P, I, D, D, P, P, P, P]),
     "dpm_lidar_emit": (I, [P, P, P, P, I, I, P, P, D, P, P, I, P, P, P, P, P, P]),
     "dpm_scene_distance": (I, [P, I, P, I, D, I, D, D, D, P, P, P]),
     "dpm_cloud_nn_workspace_bytes": (c_size_t, [I, I]),

@@ -91,6 +91,7 @@ class PointCloud:
         self.has_norm = self.has_label = self.has_image = self.has_uvd = False
 
     norm = label = image = uvd = None
+    sweep_motion = None       # D (4,4) float64 numpy of a raw frame taken by a moving sensor (lidar_sim.py); `deskew` clears it
 
     @classmethod
     def from_buffers(cls, xyz, idx, count, R=None, T=None, host_n=None):
@@ -301,6 +302,48 @@ def vertical_correct(pcd, angle):
         return pcd
     a = math.radians(angle)
     return _affine(pcd, 3, [math.sin(a), math.cos(a)])
+
+
+_TIME_MODES = {"column": ops.DESKEW_COLUMN, "azimuth": ops.DESKEW_AZIMUTH, "times": ops.DESKEW_TIMES}
+
+
+def deskew(pcd, motion, time="column", azimuth_steps=None, times=None, reference=0.0):
+    """Remove the distortion of a sweep taken by a moving sensor (lidar_sim.py's motion model; no counterpart in the
+    reference, which assumes compensated scans).  motion (4,4) = D, the sensor's pose at the end of the sweep in its frame at
+    the start.  A row p measured at sweep fraction s becomes D(reference)^-1 D(s) p, the point in the sensor's frame at the
+    reference time, with s from
+      time="column":  (idx % azimuth_steps) / azimuth_steps -- right anywhere in a chain: idx survives sampling and shuffles;
+      time="azimuth": the row's own azimuth, rounded to a column when azimuth_steps is given -- RAW frames only;
+      time="times":   times[idx], fp32 fractions on the GPU indexed by the original row.
+    In place, one launch, no host synchronisation.  The frame's pose moves to P(reference) = P D(reference) (float32, like
+    every pose a frame carries) and its `sweep_motion` is cleared."""
+    from .lidar_sim import motion_at
+    if time not in _TIME_MODES:
+        raise ValueError("time is 'column', 'azimuth' or 'times'")
+    if time == "column" and (azimuth_steps is None or int(azimuth_steps) < 1):
+        raise ValueError("time='column' needs azimuth_steps >= 1")
+    if time == "times" and times is None:
+        raise ValueError("time='times' needs times")
+    if not 0.0 <= float(reference) <= 1.0:
+        raise ValueError("reference in [0, 1]")
+    D = np.asarray(motion, dtype=np.float64)
+    if D.shape != (4, 4):
+        raise ValueError("motion: (4,4)")
+    if pcd.cap:
+        ops.points_deskew(pcd.xyz, pcd.idx, pcd.count, D, _TIME_MODES[time], int(azimuth_steps or 0),
+                          times if time == "times" else None, float(reference))
+    if reference != 0.0:
+        ref = torch.from_numpy(motion_at(D, reference)).to(torch.float32)
+        pcd.R, pcd.T = pcd.R @ ref[:3, :3], pcd.T + pcd.R @ ref[:3, 3:]
+    pcd.sweep_motion = None
+    return pcd
+
+
+def constant_velocity_motion(P_prev, P_cur):
+    """the motion a caller WITHOUT ground truth predicts for the sweep that starts at P_cur: the previous relative pose
+    P_prev^-1 P_cur (4,4) float64, i.e. the sensor goes on as it did between the last two sweeps"""
+    from .lidar_sim import sweep_delta
+    return sweep_delta(np.asarray(P_prev, np.float64).reshape(4, 4), np.asarray(P_cur, np.float64).reshape(4, 4))
 
 
 def gather_points(pcd, sel, limit=-1):
@@ -887,6 +930,28 @@ class RandomPosJitter(_Repr):
             return pcd
         jitter = src.normal_points(lambda: pcd.nbr_point, pcd.cap, pcd.device, self.mean, self.std)
         return _apply("random_pos_jitter", pcd, jitter=jitter)
+
+
+class Deskew(_Repr):
+    """motion: "frame" (the frame's own `sweep_motion`, as lidar_sim sets it on frames simulated with sweep motion), a (4,4)
+    array, or a callable pcd -> (4,4) (constant_velocity_motion of the caller's last two poses, for one).  Not one of the
+    reference's transforms: it assumes compensated scans."""
+
+    def __init__(self, motion="frame", time="column", azimuth_steps=None, reference=0.0):
+        self.motion, self.time, self.azimuth_steps, self.reference = motion, time, azimuth_steps, reference
+
+    def __call__(self, pcd):
+        if isinstance(self.motion, str):
+            if self.motion != "frame":
+                raise ValueError("motion is 'frame', a (4,4) array or a callable pcd -> (4,4)")
+            if pcd.sweep_motion is None:
+                raise ValueError("Deskew('frame'): this frame carries no sweep_motion (it was not taken with sweep motion, or "
+                                 "it has been deskewed already)")
+            motion = pcd.sweep_motion
+        else:
+            motion = self.motion(pcd) if callable(self.motion) else self.motion
+        return _apply("deskew", pcd, motion=np.asarray(motion, np.float64), time=self.time, azimuth_steps=self.azimuth_steps,
+                      reference=self.reference)
 
 
 class ToGPU(_Repr):

@@ -58,6 +58,7 @@ SOURCES = {
     "ingest.hip": [],
     "lidar_sim.hip": [],
     "map_eval.hip": [],
+    "deskew.hip": [],
 }
 
 

@@ -14,11 +14,17 @@
 //                   augment.hip in ONE launch: every block counts the keep flags of the whole frame (the part before its
 //                   chunk is its offset, the total is the count), then writes its chunk like ingest.hip does.
 //
+// Sweep motion, still three launches: dpm_lidar_cull_sweep takes a start and an end pose per frame, keeps what
+// the max_range ball enlarged by the sensor's travel reaches, and writes the frame's column table (Exp(s_c w) and s_c t_D per
+// azimuth column, float64 rounded once); dpm_lidar_cast_sweep turns every ray by its column's entry and moves its origin.
+// Both are the MOVING instantiation of the kernels below; the static one compiles to the code it was before the template.
+//
 // Arithmetic: + - * / sqrt, each rounded once (the build has contraction off; there is no fmaf here), so a float32 numpy
 // restatement that follows the order of operations gives the same bits.  No atomics.
 #include <math.h>
 
 #include "block_scan.h"
+#include "sweep_motion.h"
 
 namespace {
 
@@ -27,15 +33,33 @@ constexpr int PRM = 10;     // doubles per scene primitive: c(3) h(3) cos sin sp
 constexpr int TILE = 64;    // records per LDS tile of the cast
 constexpr int CH = 4096;    // rays per compaction block of the emit
 constexpr int KIND_SHIFT = 30;
+constexpr int COL = 12;     // floats per column of a sweep table: Exp(s_c w) row-major (9), s_c t_D (3)
 
-// ---- cull: grid (F), 256 threads
+// ---- cull: grid (F), 256 threads.  MOVING: poses = the start poses, poses1 = the end poses, A columns, table (F,A,COL)
+template <bool MOVING>
 __global__ __launch_bounds__(256) void lidar_cull_kernel(const double *__restrict__ prims, const int32_t *__restrict__ kind, int P,
                                                          const double *__restrict__ ground, const double *__restrict__ poses,
                                                          double max_range, int max_kept, float *__restrict__ kept,
-                                                         float *__restrict__ plane, int32_t *__restrict__ status) {
+                                                         float *__restrict__ plane, int32_t *__restrict__ status,
+                                                         const double *__restrict__ poses1, int A, float *__restrict__ table) {
     __shared__ int s_w[4];
     const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
     const double *M = poses + 16 * (size_t)f;
+    if constexpr (MOVING) {
+        // every thread derives the frame's motion itself (a few dozen float64 operations); the reach grows by the travel
+        const SweepMotion mo = sweep_motion(M, poses1 + 16 * (size_t)f);
+        max_range += sqrt((mo.t[0] * mo.t[0] + mo.t[1] * mo.t[1]) + mo.t[2] * mo.t[2]);
+        float *col = table + (size_t)f * A * COL;
+        for (int c = t; c < A; c += 256) {
+            const double sc = (double)c / (double)A;
+            double E[9];
+            sweep_exp(mo, sc, E);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) col[(size_t)c * COL + i] = (float)E[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) col[(size_t)c * COL + 9 + i] = (float)(sc * mo.t[i]);
+        }
+    }
     const double R00 = M[0], R01 = M[1], R02 = M[2], tx = M[3];
     const double R10 = M[4], R11 = M[5], R12 = M[6], ty = M[7];
     const double R20 = M[8], R21 = M[9], R22 = M[10], tz = M[11];
@@ -100,18 +124,30 @@ __device__ __forceinline__ bool slab(float o, float dd, float lo, float hi, floa
     return true;
 }
 
-// ---- cast: grid (ceil(rays / 256), F), 256 threads, one lane per ray
+// ---- cast: grid (ceil(rays / 256), F), 256 threads, one lane per ray.  MOVING: ray r belongs to column r % A of the table
+template <bool MOVING>
 __global__ __launch_bounds__(256) void lidar_cast_kernel(const float *__restrict__ kept, const float *__restrict__ plane,
                                                          const int32_t *__restrict__ status, int max_kept, int P,
                                                          const float *__restrict__ dirs, int rays, float min_range,
                                                          float max_range, float *__restrict__ range, int32_t *__restrict__ prim,
-                                                         float *__restrict__ cos_inc) {
+                                                         float *__restrict__ cos_inc, const float *__restrict__ table, int A) {
     __shared__ float s_rec[TILE * REC];
     const int f = blockIdx.y;
     const int r = blockIdx.x * 256 + threadIdx.x;
     const bool live = r < rays;
-    const float d0 = live ? dirs[3 * (size_t)r] : 1.f, d1 = live ? dirs[3 * (size_t)r + 1] : 0.f,
-                d2 = live ? dirs[3 * (size_t)r + 2] : 0.f;
+    float d0 = live ? dirs[3 * (size_t)r] : 1.f, d1 = live ? dirs[3 * (size_t)r + 1] : 0.f,
+          d2 = live ? dirs[3 * (size_t)r + 2] : 0.f;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;   // MOVING: the sensor's origin at the ray's time, in the frame of the start pose
+    if constexpr (MOVING) {
+        if (live) {   // the ray's direction in the frame of the start pose: d' = R_c d
+            const float *e = table + ((size_t)f * A + r % A) * COL;
+            const float x = d0, y = d1, z = d2;
+            d0 = (e[0] * x + e[1] * y) + e[2] * z;
+            d1 = (e[3] * x + e[4] * y) + e[5] * z;
+            d2 = (e[6] * x + e[7] * y) + e[8] * z;
+            o0 = e[9], o1 = e[10], o2 = e[11];
+        }
+    }
     const int n = max(0, min(status[2 * f], max_kept));
     const float *rec = kept + (size_t)f * max_kept * REC;
     float best = INFINITY, bcos = 0.f;
@@ -123,7 +159,10 @@ __global__ __launch_bounds__(256) void lidar_cast_kernel(const float *__restrict
         __syncthreads();
         for (int k = 0; k < m; ++k) {
             const float *q = s_rec + k * REC;
-            const float ox = q[0], oy = q[1], oz = q[2];
+            // MOVING: the moved origin in the primitive's coordinates, q.o + U o_c
+            const float ox = MOVING ? q[0] + ((q[3] * o0 + q[4] * o1) + q[5] * o2) : q[0];
+            const float oy = MOVING ? q[1] + ((q[6] * o0 + q[7] * o1) + q[8] * o2) : q[1];
+            const float oz = MOVING ? q[2] + ((q[9] * o0 + q[10] * o1) + q[11] * o2) : q[2];
             const float dx = (q[3] * d0 + q[4] * d1) + q[5] * d2;
             const float dy = (q[6] * d0 + q[7] * d1) + q[8] * d2;
             const float dz = (q[9] * d0 + q[10] * d1) + q[11] * d2;
@@ -174,7 +213,7 @@ __global__ __launch_bounds__(256) void lidar_cast_kernel(const float *__restrict
         const float *g = plane + 4 * (size_t)f;
         const float den = (g[0] * d0 + g[1] * d1) + g[2] * d2;
         if (den != 0.f) {
-            const float t = g[3] / den;
+            const float t = (MOVING ? g[3] - ((g[0] * o0 + g[1] * o1) + g[2] * o2) : g[3]) / den;
             if (t > 0.f && t < best) best = t, bcos = fabsf(den), bid = P;
         }
     }
@@ -260,8 +299,19 @@ extern "C" int dpm_lidar_cull(const double *prims, const int32_t *kind, int P, c
     DPM_CHECK_ARG(P >= 0 && P < (1 << KIND_SHIFT) && (P == 0 || (prims && kind)));
     DPM_CHECK_ARG(ground && poses && kept && plane && status);
     DPM_CHECK_ARG(F >= 1 && F <= 65535 && max_kept >= 1 && max_range > 0.0);
-    hipLaunchKernelGGL(lidar_cull_kernel, dim3(F), dim3(256), 0, (hipStream_t)stream, prims, kind, P, ground, poses, max_range,
-                       max_kept, kept, plane, status);
+    hipLaunchKernelGGL(lidar_cull_kernel<false>, dim3(F), dim3(256), 0, (hipStream_t)stream, prims, kind, P, ground, poses,
+                       max_range, max_kept, kept, plane, status, (const double *)nullptr, 0, (float *)nullptr);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_lidar_cull_sweep(const double *prims, const int32_t *kind, int P, const double *ground, const double *poses0,
+                                    const double *poses1, int F, int azimuth_steps, double max_range, int max_kept, float *kept,
+                                    float *plane, int32_t *status, float *table, dpm_stream_t stream) {
+    DPM_CHECK_ARG(P >= 0 && P < (1 << KIND_SHIFT) && (P == 0 || (prims && kind)));
+    DPM_CHECK_ARG(ground && poses0 && poses1 && kept && plane && status && table);
+    DPM_CHECK_ARG(F >= 1 && F <= 65535 && max_kept >= 1 && max_range > 0.0 && azimuth_steps >= 1 && azimuth_steps <= (1 << 24));
+    hipLaunchKernelGGL(lidar_cull_kernel<true>, dim3(F), dim3(256), 0, (hipStream_t)stream, prims, kind, P, ground, poses0,
+                       max_range, max_kept, kept, plane, status, poses1, azimuth_steps, table);
     return dpm_launch_status();
 }
 
@@ -271,8 +321,21 @@ extern "C" int dpm_lidar_cast(const float *kept, const float *plane, const int32
     DPM_CHECK_ARG(kept && plane && status && dirs && range && prim && cos_inc);
     DPM_CHECK_ARG(P >= 0 && P < (1 << KIND_SHIFT) && max_kept >= 1 && rays >= 1 && rays <= (1 << 24) && F >= 1 && F <= 65535);
     DPM_CHECK_ARG(min_range >= 0.0 && max_range > min_range);
-    hipLaunchKernelGGL(lidar_cast_kernel, dim3(dpm_cdiv(rays, 256), F), dim3(256), 0, (hipStream_t)stream, kept, plane, status,
-                       max_kept, P, dirs, rays, (float)min_range, (float)max_range, range, prim, cos_inc);
+    hipLaunchKernelGGL(lidar_cast_kernel<false>, dim3(dpm_cdiv(rays, 256), F), dim3(256), 0, (hipStream_t)stream, kept, plane,
+                       status, max_kept, P, dirs, rays, (float)min_range, (float)max_range, range, prim, cos_inc,
+                       (const float *)nullptr, 0);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_lidar_cast_sweep(const float *kept, const float *plane, const int32_t *status, int max_kept, int P,
+                                    const float *dirs, int rays, int F, const float *table, int azimuth_steps, double min_range,
+                                    double max_range, float *range, int32_t *prim, float *cos_inc, dpm_stream_t stream) {
+    DPM_CHECK_ARG(kept && plane && status && dirs && table && range && prim && cos_inc);
+    DPM_CHECK_ARG(P >= 0 && P < (1 << KIND_SHIFT) && max_kept >= 1 && rays >= 1 && rays <= (1 << 24) && F >= 1 && F <= 65535);
+    DPM_CHECK_ARG(azimuth_steps >= 1 && rays % azimuth_steps == 0 && min_range >= 0.0 && max_range > min_range);
+    hipLaunchKernelGGL(lidar_cast_kernel<true>, dim3(dpm_cdiv(rays, 256), F), dim3(256), 0, (hipStream_t)stream, kept, plane,
+                       status, max_kept, P, dirs, rays, (float)min_range, (float)max_range, range, prim, cos_inc, table,
+                       azimuth_steps);
     return dpm_launch_status();
 }
 

@@ -14,11 +14,18 @@ Host side (numpy, float64, deterministic):
 * `circuit(scene, spacing, laps)`: (F,4,4) float64 sensor poses round the scene's outer loop of roads, heading along the
   tangent, roll and pitch small and NON-zero.
 * `LidarModel`: beam elevations x azimuth steps; ray r = beam * azimuth_steps + column.  The unit directions are computed
-  once in float64 and rounded to float32: the kernels evaluate no trigonometry.  One pose per frame (no sweep motion).
+  once in float64 and rounded to float32: the kernels evaluate no trigonometry.
+* Sweep motion (optional).  ONE definition, used by the simulator, by `augment.deskew` and by the restatement
+  (tests/lidar_sweep_restated.py): a frame has a start pose P0 and an end pose P1, sensor-to-world, float64.
+  D = P0^-1 P1 = (R_D, t_D), w = Log(R_D), a rotation vector with angle below pi.  At sweep fraction s in [0, 1] the sensor is
+  at P(s) = P0 D(s), D(s) = (Exp(s w), s t_D): a constant turn rate about a fixed axis, the origin on a straight line at
+  constant speed.  All beams of column c fire at s_c = c / azimuth_steps.  A raw point is t * dir in the sensor's frame AT
+  ITS OWN TIME; deskewing to the reference time s_ref maps a raw point p fired at s to D(s_ref)^-1 D(s) p.
+  `sweep_delta`, `motion_at`, `sweep_poses` are the host side of it.  Without end poses: one pose per frame, as before.
 
 GPU side, following augment.py's two layers:
 
-* FUNCTIONAL: `cast_rays(scene_dev, poses, model)` -> (range, prim, cos_inc), `emit_frames(...)` -> frames
+* FUNCTIONAL: `cast_rays(scene_dev, poses, model, poses_end=None)` -> (range, prim, cos_inc), `emit_frames(...)` -> frames
   (`augment.PointCloud.from_buffers`, idx = the ray index, so ring = idx // azimuth_steps and column = idx % azimuth_steps
   stay recoverable), intensity and label.  Every random quantity (`noise`, `u`) is an argument.  Three launches for F frames,
   no host synchronisation.  More than `max_kept` primitives in range of a frame raise ValueError at the frames' next
@@ -236,6 +243,60 @@ def circuit(scene: Scene, spacing: float = 2.0, laps: int = 1, radius: float = 6
 
 
 # ------------------------------------------------------------------------------------------------------------
+# sweep motion (module docstring; csrc/sweep_motion.h is the same definition for the kernels)
+# ------------------------------------------------------------------------------------------------------------
+def _rot_log(R):
+    """the rotation vector of R (3,3), angle below pi: from the antisymmetric part sin(angle) k and the trace"""
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]], np.float64)
+    n = float(np.sqrt(v @ v))
+    if n == 0.0:
+        return np.zeros(3)
+    return v / n * math.atan2(n, 0.5 * (float(np.trace(R)) - 1.0))
+
+
+def _rot_exp(w):
+    """Rodrigues' formula with 1 - cos a = 2 sin^2(a / 2)"""
+    a = float(np.sqrt(w @ w))
+    if a == 0.0:
+        return np.eye(3)
+    k = w / a
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + math.sin(a) * K + 2.0 * math.sin(0.5 * a) ** 2 * (K @ K)
+
+
+def sweep_delta(P0, P1) -> np.ndarray:
+    """D = P0^-1 P1 for poses (4,4) or (F,4,4) float64: the sensor's pose at the end of the sweep in its frame at the start"""
+    P0, P1 = np.asarray(P0, np.float64), np.asarray(P1, np.float64)
+    if P0.shape != P1.shape or P0.shape[-2:] != (4, 4):
+        raise ValueError("start and end poses: (4,4) or (F,4,4), alike")
+    D = np.zeros_like(P0)
+    Rt = np.swapaxes(P0[..., :3, :3], -1, -2)
+    D[..., :3, :3] = Rt @ P1[..., :3, :3]
+    D[..., :3, 3] = (Rt @ (P1[..., :3, 3] - P0[..., :3, 3])[..., None])[..., 0]
+    D[..., 3, 3] = 1.0
+    return D
+
+
+def motion_at(D, s: float) -> np.ndarray:
+    """D(s) = (Exp(s Log R_D), s t_D) as (4,4) float64: D(0) = I, D(1) = D"""
+    D = np.asarray(D, np.float64).reshape(4, 4)
+    out = np.eye(4)
+    out[:3, :3] = _rot_exp(float(s) * _rot_log(D[:3, :3]))
+    out[:3, 3] = float(s) * D[:3, 3]
+    return out
+
+
+def sweep_poses(poses):
+    """(P0, P1), each (F,4,4), for a trajectory whose sensor turns once between consecutive poses: P1[f] = poses[f + 1], the
+    last frame goes on by its previous delta (a single pose stands still)"""
+    P0 = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    P1 = np.empty_like(P0)
+    P1[:-1] = P0[1:]
+    P1[-1] = P0[-1] @ sweep_delta(P0[-2], P0[-1]) if P0.shape[0] > 1 else P0[-1]
+    return P0, P1
+
+
+# ------------------------------------------------------------------------------------------------------------
 # sensor
 # ------------------------------------------------------------------------------------------------------------
 class LidarModel:
@@ -305,12 +366,13 @@ def _dirs(model: LidarModel, dev):
 
 
 class Cast(tuple):
-    """(range, prim, cos_inc), each (F,rays), with `status` (F,2) = (primitives in range, overflow flag) of the cull and
-    `max_kept`.  check() reads the flags back (a host synchronisation) and raises ValueError on an overflow."""
+    """(range, prim, cos_inc), each (F,rays), with `status` (F,2) = (primitives in range, overflow flag) of the cull,
+    `max_kept` and, of a cast with sweep motion, the column `table` (F,azimuth_steps,12), else None.  check() reads the flags
+    back (a host synchronisation) and raises ValueError on an overflow."""
 
-    def __new__(cls, rng, prim, cos_inc, status, max_kept):
+    def __new__(cls, rng, prim, cos_inc, status, max_kept, table=None):
         self = super().__new__(cls, (rng, prim, cos_inc))
-        self.status, self.max_kept = status, max_kept
+        self.status, self.max_kept, self.table = status, max_kept, table
         return self
 
     def check(self):
@@ -318,31 +380,48 @@ class Cast(tuple):
             raise ValueError(OVERFLOW.format(self.max_kept))
 
 
-def cast_rays(scene_dev: SceneDevice, poses, model: LidarModel, max_kept: Optional[int] = None, dirs=None) -> Cast:
+def cast_rays(scene_dev: SceneDevice, poses, model: LidarModel, max_kept: Optional[int] = None, dirs=None,
+              poses_end=None) -> Cast:
     """two launches, no host synchronisation.  poses (F,4,4) float64 sensor-to-world (numpy or tensor); max_kept: room for
-    the primitives within max_range of one frame (default: all of them, which cannot overflow)."""
+    the primitives within max_range of one frame (default: all of them, which cannot overflow).  poses_end (F,4,4): the
+    sensor moves from poses[f] to poses_end[f] during frame f (module docstring); range is then measured from the sensor's
+    origin at the ray's own time, and max_kept counts the primitives within max_range + the travel."""
     dev = scene_dev.device
     max_kept = max(scene_dev.P, 1) if max_kept is None else int(max_kept)
     with torch.cuda.device(dev):
         poses = _poses(poses, dev)
         dirs = _dirs(model, dev) if dirs is None else dirs
-        kept, plane, status = ops.lidar_cull(scene_dev.prims, scene_dev.kind, scene_dev.ground, poses, model.max_range, max_kept)
-        rng, prim, cos_inc = ops.lidar_cast(kept, plane, status, scene_dev.P, dirs, model.min_range, model.max_range)
-    return Cast(rng, prim, cos_inc, status, max_kept)
+        if poses_end is None:
+            kept, plane, status = ops.lidar_cull(scene_dev.prims, scene_dev.kind, scene_dev.ground, poses, model.max_range, max_kept)
+            rng, prim, cos_inc = ops.lidar_cast(kept, plane, status, scene_dev.P, dirs, model.min_range, model.max_range)
+            return Cast(rng, prim, cos_inc, status, max_kept)
+        poses_end = _poses(poses_end, dev)
+        if poses_end.shape != poses.shape:
+            raise ValueError("poses_end: one end pose per frame")
+        kept, plane, status, table = ops.lidar_cull_sweep(scene_dev.prims, scene_dev.kind, scene_dev.ground, poses, poses_end,
+                                                          model.azimuth_steps, model.max_range, max_kept)
+        rng, prim, cos_inc = ops.lidar_cast_sweep(kept, plane, status, table, scene_dev.P, dirs, model.min_range, model.max_range)
+    return Cast(rng, prim, cos_inc, status, max_kept, table)
 
 
 def emit_frames(rng, prim, cos_inc, model: LidarModel, poses, noise=None, u=None, *, scene: SceneDevice, status=None,
-                max_kept=None, dirs=None):
+                max_kept=None, dirs=None, poses_end=None):
     """one launch, no host synchronisation: -> (frames, intensity (F,rays), label (F,rays)).  Frame f is an
     augment.PointCloud over xyz (rays,3), idx (rays,) = ray indices, count (1,) with R, T = the pose (poses on the HOST:
     numpy or a CPU tensor) and host_n=None.  noise (F,rays) metres along the ray; u (F,rays) uniform draws, a ray with
     u < model.drop_prob is dropped.  `scene` carries the albedo and class tables; `status` = Cast.status arms the frames'
-    deferred overflow error."""
+    deferred overflow error.  poses_end: the end poses of a cast with sweep motion; the frames keep R, T = the START pose and
+    carry `sweep_motion` = D (4,4) float64 numpy (None otherwise): the rows are raw, each in the sensor's frame at its time."""
     from .augment import PointCloud
-    host = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
-    host = host.astype(np.float64).reshape(-1, 4, 4)
+    as_host = lambda p: (p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)).astype(np.float64).reshape(-1, 4, 4)
+    host = as_host(poses)
     if host.shape[0] != rng.shape[0]:
         raise ValueError("one pose per frame")
+    motion = None
+    if poses_end is not None:
+        if as_host(poses_end).shape != host.shape:
+            raise ValueError("poses_end: one end pose per frame")
+        motion = sweep_delta(host, as_host(poses_end))
     with torch.cuda.device(rng.device):
         dirs = _dirs(model, rng.device) if dirs is None else dirs
         xyz, idx, count, intensity, label = ops.lidar_emit(rng, prim, cos_inc, dirs, scene.albedo, scene.class_id, noise=noise,
@@ -353,6 +432,8 @@ def emit_frames(rng, prim, cos_inc, model: LidarModel, poses, noise=None, u=None
                                       host_n=None)
         if status is not None:
             pcd._flags.append((status[f], OVERFLOW.format(max_kept)))
+        if motion is not None:
+            pcd.sweep_motion = motion[f].copy()
         frames.append(pcd)
     return frames, intensity, label
 
@@ -374,12 +455,13 @@ class LidarSimulator:
         self.model, self.rng, self.max_kept = model, rng, max_kept
         self.dirs = _dirs(model, self.scene.device)
 
-    def frames(self, poses, return_channels: bool = False):
+    def frames(self, poses, return_channels: bool = False, *, poses_end=None):
         """poses (F,4,4) on the host -> F frames for transform_frames / collate_frames; with return_channels also
-        intensity and label (F,rays), indexed by RAY (a frame's idx picks its rows)."""
+        intensity and label (F,rays), indexed by RAY (a frame's idx picks its rows).  poses_end (F,4,4): sweep motion
+        (module docstring): raw frames under their start pose, `sweep_motion` set for augment.Deskew("frame")."""
         dev, m = self.scene.device, self.model
         with torch.cuda.device(dev):
-            cast = cast_rays(self.scene, poses, m, self.max_kept, dirs=self.dirs)
+            cast = cast_rays(self.scene, poses, m, self.max_kept, dirs=self.dirs, poses_end=poses_end)
             noise = u = None
             if self.rng is not None:
                 shape = cast[0].shape
@@ -388,7 +470,7 @@ class LidarSimulator:
                 if m.drop_prob > 0:
                     u = torch.rand(shape, device=dev, generator=self.rng)
             frames, intensity, label = emit_frames(*cast, m, poses, noise=noise, u=u, scene=self.scene, status=cast.status,
-                                                   max_kept=cast.max_kept, dirs=self.dirs)
+                                                   max_kept=cast.max_kept, dirs=self.dirs, poses_end=poses_end)
         return (frames, intensity, label) if return_channels else frames
 
 
@@ -410,7 +492,7 @@ def _agent_sizes(agents, F):
 
 
 def write_scene(root, dataset: str, scene_name: str, sim, poses, agents=None, fmt: str = "npz",
-                refined_distance: Optional[float] = None, batch: int = 8) -> List[str]:
+                refined_distance: Optional[float] = None, batch: int = 8, poses_end=None, deskew: Optional[float] = None) -> List[str]:
     """Writes root/<dataset>/<scene_name>/<agent>/<n>.npz (lidar_pcd (N,4) float32 = x y z intensity, ego_rotation (3,3),
     ego_translation (3,1) float64) for every pose, n = the frame's index in the scene; -> the files in frame order.
     sim: a LidarSimulator, or the scans themselves, one (N,4) array per pose.  agents: None (one agent `0`), a number of
@@ -418,13 +500,27 @@ def write_scene(root, dataset: str, scene_name: str, sim, poses, agents=None, fm
     fmt="bin": KITTI records (N,4) float32 in <n>.bin; that format carries no pose, so the poses go to `poses.txt` (one row
     of 12 numbers per frame) and the frame distances, which SlamDatasets would read from the npz files, are written as its
     `frame_dis.npy` cache.  refined_distance: also write refined_SE3.pkl through refine.write_refined_table with the EXACT
-    relative pose of every pair i < j whose positions are within that distance."""
+    relative pose of every pair i < j whose positions are within that distance.
+    poses_end (with a simulator): sweep motion from poses[f] to poses_end[f].  By default the RAW clouds are written under
+    the start pose, as a spinning sensor delivers them; deskew=s_ref writes the clouds compensated with the true motion
+    (augment.deskew by column) under the pose P(s_ref) = P0 D(s_ref).  The files have the same keys either way."""
     from . import refine
     from .dataset import pairwise_frame_dis
     if fmt not in ("npz", "bin"):
         raise ValueError("fmt is 'npz' or 'bin'")
     poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
     F = poses.shape[0]
+    starts = poses
+    if poses_end is not None:
+        if not hasattr(sim, "frames"):
+            raise ValueError("poses_end needs a simulator: scans given as arrays are written as they are")
+        poses_end = np.asarray(poses_end, np.float64).reshape(-1, 4, 4)
+        if poses_end.shape != poses.shape:
+            raise ValueError("poses_end: one end pose per frame")
+        if deskew is not None:      # the pose the compensated cloud belongs to
+            poses = np.stack([P0 @ motion_at(D, deskew) for P0, D in zip(starts, sweep_delta(starts, poses_end))])
+    elif deskew is not None:
+        raise ValueError("deskew needs poses_end")
     sizes = _agent_sizes(agents, F)
     width = len(str(len(sizes) - 1))
     scene_root = os.path.join(str(root), dataset, scene_name)
@@ -440,9 +536,15 @@ def write_scene(root, dataset: str, scene_name: str, sim, poses, agents=None, fm
     for a in range(0, F, batch):
         b = min(a + batch, F)
         if simulated:
-            frames, intensity, _ = sim.frames(poses[a:b], return_channels=True)
+            if poses_end is None:
+                frames, intensity, _ = sim.frames(poses[a:b], return_channels=True)
+            else:
+                frames, intensity, _ = sim.frames(starts[a:b], return_channels=True, poses_end=poses_end[a:b])
             scans = []
             for f, pcd in enumerate(frames):
+                if deskew is not None:
+                    from .augment import deskew as _deskew
+                    pcd = _deskew(pcd, pcd.sweep_motion, time="column", azimuth_steps=sim.model.azimuth_steps, reference=deskew)
                 n = pcd.nbr_point
                 rows = torch.cat([pcd.xyz[:n], intensity[f][pcd.idx[:n].long()].unsqueeze(1)], dim=1)
                 scans.append(rows.cpu().numpy())

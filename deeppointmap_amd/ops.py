@@ -1898,6 +1898,7 @@ def ingest_frames(block: torch.Tensor, F: int, capacity: int, device=None, stagi
 # ------------------------------------------------------------------------------------------------------------
 LIDAR_REC = 16        # floats of a kept record
 LIDAR_PRIM = 10       # doubles of a scene primitive
+LIDAR_COL = 12        # floats per column of a sweep table
 LIDAR_BOX, LIDAR_CYLINDER = 0, 1
 LIDAR_MAX_RAYS = 1 << 24
 
@@ -1965,6 +1966,60 @@ def lidar_cast(kept: torch.Tensor, plane: torch.Tensor, status: torch.Tensor, P:
     return rng, prim, cos_inc
 
 
+def lidar_cull_sweep(prims: torch.Tensor, kind: torch.Tensor, ground: torch.Tensor, poses0: torch.Tensor, poses1: torch.Tensor,
+                     azimuth_steps: int, max_range: float, max_kept: int):
+    """dpm_lidar_cull_sweep: lidar_cull about poses0 for a sensor that moves to poses1 (F,4,4) float64 during the sweep: the
+    max_range ball grows by the travel -> kept, plane, status as lidar_cull, and table (F,azimuth_steps,12) fp32 = per
+    column the rotation Exp(s_c w) (9) and the origin s_c t_D (3) in the frame of poses0."""
+    max_kept, A = int(max_kept), int(azimuth_steps)
+    if max_kept < 1 or not float(max_range) > 0 or not 1 <= A <= LIDAR_MAX_RAYS:
+        raise ValueError("max_kept >= 1, max_range > 0 and 1 <= azimuth_steps <= 2^24")
+    _lidar_arg(prims, torch.float64, "prims", prims.dim() == 2 and prims.shape[1] == LIDAR_PRIM, f"(P,{LIDAR_PRIM})")
+    _lidar_arg(kind, torch.int32, "kind", kind.shape == prims.shape[:1], "(P,)")
+    _lidar_arg(ground, torch.float64, "ground", ground.shape == (2,), "(2,)")
+    _lidar_arg(poses0, torch.float64, "poses0", poses0.dim() == 3 and poses0.shape[1:] == (4, 4) and poses0.shape[0] >= 1, "(F,4,4), F >= 1")
+    _lidar_arg(poses1, torch.float64, "poses1", poses1.shape == poses0.shape, "(F,4,4)")
+    _lidar_dev(prims=prims, kind=kind, ground=ground, poses0=poses0, poses1=poses1)
+    P, F, dev = prims.shape[0], poses0.shape[0], poses0.device
+    with torch.cuda.device(dev):
+        kept = torch.empty(F, max_kept, LIDAR_REC, device=dev, dtype=torch.float32)
+        plane = torch.empty(F, 4, device=dev, dtype=torch.float32)
+        status = torch.empty(F, 2, device=dev, dtype=torch.int32)
+        table = torch.empty(F, A, LIDAR_COL, device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().dpm_lidar_cull_sweep(_ptr(prims), _ptr(kind), P, _ptr(ground), _ptr(poses0), _ptr(poses1), F, A,
+                                                    float(max_range), max_kept, _ptr(kept), _ptr(plane), _ptr(status),
+                                                    _ptr(table), _stream(poses0)), "dpm_lidar_cull_sweep")
+    return kept, plane, status, table
+
+
+def lidar_cast_sweep(kept: torch.Tensor, plane: torch.Tensor, status: torch.Tensor, table: torch.Tensor, P: int,
+                     dirs: torch.Tensor, min_range: float, max_range: float):
+    """dpm_lidar_cast_sweep: lidar_cast over the outputs of lidar_cull_sweep; ray r fires from column r % azimuth_steps of the
+    table (rays a multiple of azimuth_steps); range is measured from the sensor's origin at the ray's own time."""
+    if not 0.0 <= float(min_range) < float(max_range) or int(P) < 0:
+        raise ValueError("0 <= min_range < max_range and P >= 0")
+    _lidar_arg(kept, torch.float32, "kept", kept.dim() == 3 and kept.shape[2] == LIDAR_REC and kept.shape[0] >= 1 and kept.shape[1] >= 1,
+               f"(F,max_kept,{LIDAR_REC})")
+    F, max_kept = kept.shape[:2]
+    _lidar_arg(plane, torch.float32, "plane", plane.shape == (F, 4), "(F,4)")
+    _lidar_arg(status, torch.int32, "status", status.shape == (F, 2), "(F,2)")
+    _lidar_arg(dirs, torch.float32, "dirs", dirs.dim() == 2 and dirs.shape[1] == 3 and 1 <= dirs.shape[0] <= LIDAR_MAX_RAYS,
+               "(rays,3), 1 <= rays <= 2^24")
+    rays = dirs.shape[0]
+    _lidar_arg(table, torch.float32, "table", table.dim() == 3 and table.shape[0] == F and table.shape[2] == LIDAR_COL
+               and table.shape[1] >= 1 and rays % table.shape[1] == 0, f"(F,azimuth_steps,{LIDAR_COL}), azimuth_steps dividing rays")
+    _lidar_dev(kept=kept, plane=plane, status=status, table=table, dirs=dirs)
+    dev = kept.device
+    with torch.cuda.device(dev):
+        rng = torch.empty(F, rays, device=dev, dtype=torch.float32)
+        prim = torch.empty(F, rays, device=dev, dtype=torch.int32)
+        cos_inc = torch.empty(F, rays, device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().dpm_lidar_cast_sweep(_ptr(kept), _ptr(plane), _ptr(status), max_kept, int(P), _ptr(dirs), rays, F,
+                                                    _ptr(table), table.shape[1], float(min_range), float(max_range), _ptr(rng),
+                                                    _ptr(prim), _ptr(cos_inc), _stream(kept)), "dpm_lidar_cast_sweep")
+    return rng, prim, cos_inc
+
+
 def lidar_emit(rng: torch.Tensor, prim: torch.Tensor, cos_inc: torch.Tensor, dirs: torch.Tensor, albedo: torch.Tensor,
                class_id: torch.Tensor, noise: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
                drop_prob: float = 0.0):
@@ -1996,6 +2051,37 @@ def lidar_emit(rng: torch.Tensor, prim: torch.Tensor, cos_inc: torch.Tensor, dir
                                               _ptr(idx), _ptr(count), _ptr(intensity), _ptr(label), _stream(rng)),
                    "dpm_lidar_emit")
     return xyz, idx, count, intensity, label
+
+
+# ------------------------------------------------------------------------------------------------------------
+# deskew (csrc/deskew.hip)
+# ------------------------------------------------------------------------------------------------------------
+DESKEW_COLUMN, DESKEW_AZIMUTH, DESKEW_TIMES = 0, 1, 2
+
+
+def points_deskew(xyz: torch.Tensor, idx: torch.Tensor, count: torch.Tensor, motion, time_mode: int, azimuth_steps: int = 0,
+                  times: Optional[torch.Tensor] = None, s_ref: float = 0.0):
+    """dpm_points_deskew, in place: xyz (cap,3) fp32, idx (cap,) int32, count (1,) int32 on the GPU; motion (4,4) float64 on
+    the HOST = D, the sensor's pose at the end of the sweep in its frame at the start; time_mode DESKEW_COLUMN (idx %
+    azimuth_steps), DESKEW_AZIMUTH (the point's own azimuth, rounded to a column when azimuth_steps > 0) or DESKEW_TIMES
+    (times[idx], fp32 on the GPU); every row p measured at fraction s becomes D(s_ref)^-1 D(s) p."""
+    import numpy as np
+    _lidar_arg(xyz, torch.float32, "xyz", xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.shape[0] >= 1, "(cap,3), cap >= 1")
+    _lidar_arg(idx, torch.int32, "idx", idx.shape == xyz.shape[:1], "(cap,)")
+    _lidar_arg(count, torch.int32, "count", count.numel() == 1, "(1,)")
+    if times is not None:
+        _lidar_arg(times, torch.float32, "times", times.dim() == 1 and times.shape[0] >= 1, "(n,), n >= 1")
+    _lidar_dev(xyz=xyz, idx=idx, count=count, times=times)
+    D = np.ascontiguousarray(np.asarray(motion, dtype=np.float64))
+    if D.shape != (4, 4) or not np.isfinite(D).all():
+        raise ValueError("motion: a finite (4,4) matrix")
+    m = (ctypes.c_double * 16)(*D.reshape(-1).tolist())
+    with torch.cuda.device(xyz.device):
+        _lib.check(_lib.load().dpm_points_deskew(_ptr(xyz), _ptr(idx), _ptr(count), xyz.shape[0], int(time_mode), _ptr(times),
+                                                 0 if times is None else times.shape[0], int(azimuth_steps),
+                                                 ctypes.cast(m, ctypes.c_void_p), float(s_ref), _stream(xyz)),
+                   "dpm_points_deskew")
+    return xyz
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -552,6 +552,19 @@ int dpm_points_affine(float *xyz, const int32_t *count, int capacity, int mode, 
                       const float *jitter, dpm_stream_t stream);
 int dpm_gather_points(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, const int32_t *sel,
                       int n_sel, int limit, float *out_xyz, int32_t *out_idx, int32_t *out_count, dpm_stream_t stream);
+/* Deskew (csrc/deskew.hip; no counterpart in the reference, which assumes compensated scans): in place on the first count
+ * rows, one launch, no host synchronisation.  motion: 16 doubles in HOST memory, D = P0^-1 P1 row-major, the sensor's pose
+ * at the end of the sweep in its frame at the start; the sensor is at D(s) = (Exp(s Log R_D), s t_D) at sweep fraction s.
+ * A row measured at fraction s becomes D(s_ref)^-1 D(s) p, 0 <= s_ref <= 1.  Where s comes from, time_mode:
+ *   0  the column of the row's ray: s = (idx[i] mod azimuth_steps) / azimuth_steps, azimuth_steps >= 1;
+ *   1  the row's own azimuth: s = frac(atan2f(y, x) / 2 pi); with azimuth_steps > 0 rounded to the nearest column
+ *      (column azimuth_steps is column 0), with 0 continuous.  Raw frames only: any transform that turns the points first
+ *      makes it meaningless; idx may be NULL;
+ *   2  times[idx[i]], n_times fp32 fractions by ORIGINAL row; a row whose index lies outside [0, n_times) stays as it is.
+ * The axis, the angle, t_D and D(s_ref)^-1 are derived in float64 on the host; the kernel works in float32.  An identity
+ * motion (bit-equal to the identity matrix) launches nothing: the rows keep their bytes. */
+int dpm_points_deskew(float *xyz, const int32_t *idx, const int32_t *count, int capacity, int time_mode, const float *times,
+                      int n_times, int azimuth_steps, const double *motion, double s_ref, dpm_stream_t stream);
 int dpm_pack_frames(const float *const *xyz, const int32_t *const *counts, const int32_t *capacities, int S,
                     int padding_to, float *points, unsigned char *padding, int32_t *status, dpm_stream_t stream);
 
@@ -900,6 +913,20 @@ int dpm_lidar_cull(const double *prims, const int32_t *kind, int P, const double
 int dpm_lidar_cast(const float *kept, const float *plane, const int32_t *status, int max_kept, int P, const float *dirs,
                    int rays, int F, double min_range, double max_range, float *range, int32_t *prim, float *cos_inc,
                    dpm_stream_t stream);
+/* Sweep motion: the sensor moves from poses0[f] to poses1[f] (both (F,4,4) float64 sensor-to-world) while it fires its
+ * azimuth_steps columns, column c at sweep fraction s_c = c / azimuth_steps from the pose P0 D(s_c), D = P0^-1 P1, D(s) =
+ * (Exp(s Log R_D), s t_D), rotation angle below pi.  dpm_lidar_cull_sweep is dpm_lidar_cull about poses0 with the
+ * max_range ball enlarged by |t_D|, and also writes table (F,azimuth_steps,12) fp32 = Exp(s_c Log R_D) row-major (9) and
+ * s_c t_D (3), computed in float64 and rounded once.  dpm_lidar_cast_sweep is dpm_lidar_cast with ray r (of column
+ * r mod azimuth_steps; rays a multiple of azimuth_steps) turned by its column's rotation and cast from its column's
+ * origin; range is measured from that origin, so dpm_lidar_emit's t * dir is the point in the sensor's frame at the
+ * ray's own time.  With poses1 == poses0 the table is exactly identity and zero and the outputs equal the static calls'. */
+int dpm_lidar_cull_sweep(const double *prims, const int32_t *kind, int P, const double *ground, const double *poses0,
+                         const double *poses1, int F, int azimuth_steps, double max_range, int max_kept, float *kept,
+                         float *plane, int32_t *status, float *table, dpm_stream_t stream);
+int dpm_lidar_cast_sweep(const float *kept, const float *plane, const int32_t *status, int max_kept, int P, const float *dirs,
+                         int rays, int F, const float *table, int azimuth_steps, double min_range, double max_range,
+                         float *range, int32_t *prim, float *cos_inc, dpm_stream_t stream);
 /* Returns -> frames in the layout of the training transforms.  A ray returns when prim >= 0 and (u == NULL or
  * u >= (float)drop_prob); its point is (range + noise) * dir (noise (F,rays) metres or NULL).  xyz (F,rays,3), idx (F,rays)
  * = the ray index of every row, count (F,): the returns in ray order, rows at and past the count zero.  intensity (F,rays)
