@@ -1266,7 +1266,9 @@ __global__ __launch_bounds__(WPB * 64) void knn_self_kernel(const float *__restr
             const int lo = start[yy * G.g + x0], hi = start[yy * G.g + x1 + 1];
             for (int base = lo; base < hi; base += 64) {
                 const int p = base + lane;
-                float d = __builtin_inff();
+                // a lane without a point offers NaN, which no comparison admits: with +inf it would pass the self search's
+                // unbounded admission test (inf <= inf) and, in a cloud of fewer than K+1 points, come out as a neighbour
+                float d = __builtin_nanf("");
                 int i = 0x7fffffff;
                 if (p < hi) {
                     const float4 t4 = sorted[p];

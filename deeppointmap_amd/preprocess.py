@@ -10,7 +10,8 @@
     # -> (1,3,M) normalised, (1,M) all-False: the encoder's inputs
 
 The two filters run through pytorch3d / open3d in the reference (absent here), so their restatement is pinned by
-the oracle only (oracle.outlier_filter / lowpass_filter, scipy cKDTree), not by the reference's own output.
+the oracle (oracle.outlier_filter / lowpass_filter, scipy cKDTree) and, kernel by kernel, by brute-force restatements on
+exact cases (tests/test_gpu_filters_exact.py), not by the reference's own output.
 """
 from __future__ import annotations
 

@@ -622,12 +622,20 @@ def outlier_filter(xyz: Tensor, nb_neighbors: int = 10, std_ratio: float = 3.0) 
 
 def point_normals(xyz: Tensor, radius: float) -> Tensor:
     """open3d estimate_normals(KDTreeSearchParamRadius(radius)) restated: covariance of the points within the radius
-    (the point included) from fp64 cumulants, eigenvector of the smallest eigenvalue; < 3 points -> (0,0,1)."""
+    (the point included) from fp64 cumulants, eigenvector of the smallest eigenvalue; < 3 points -> (0,0,1).
+    Membership is the rule csrc/knn.hip documents for point_normals_kernel: the fp32 direct-form squared distance
+    STRICTLY below float32(radius^2) (open3d's radius search is strict).  The KD-tree only proposes candidates, out to
+    a slightly larger radius; every candidate is then tested with that rule."""
     from scipy.spatial import cKDTree
-    p = xyz.numpy().astype(np.float64)
+    p32 = xyz.numpy().astype(np.float32)
+    p = p32.astype(np.float64)
     tree = cKDTree(p)
+    r2 = np.float32(radius * radius)
     out = np.zeros((p.shape[0], 3), dtype=np.float32)
-    for i, nb in enumerate(tree.query_ball_point(p, r=radius)):
+    for i, nb in enumerate(tree.query_ball_point(p, r=radius * 1.001 + 1e-6)):
+        nb = np.sort(np.asarray(nb, dtype=np.int64))
+        d = p32[i] - p32[nb]
+        nb = nb[(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] < r2]
         if len(nb) < 3:
             out[i] = (0.0, 0.0, 1.0)
             continue
