@@ -10,7 +10,7 @@ import ctypes
 import os
 
 import torch  # noqa: F401  -- must precede the CDLL below: libdpm_hip.so has to bind to the HIP runtime torch ships
-from ctypes import c_char_p, c_double, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_int, c_longlong, c_size_t, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPM_LIB (read once, at import): another build of the library for A/B measurements (csrc/build.py --out).  bench.py refuses
@@ -156,6 +156,12 @@ SIGNATURES = {
     "dpm_cloud_nn": (I, [P, I, P, I, D, D, D, D, P, P, P, P]),
     "dpm_distance_stats_workspace_bytes": (c_size_t, [I, I, I]),
     "dpm_distance_stats": (I, [P, I, P, P, I, I, P, I, D, P, P, P]),
+    "dpm_local_map_bytes": (c_size_t, [I, I]),
+    "dpm_local_map_init": (I, [P, I, I, P]),
+    "dpm_local_map_insert": (I, [P, I, I, I, D, P, P, P, P, I, P, c_uint, D, D, P]),
+    "dpm_local_map_prune": (I, [P, I, I, I, D, P, P, D, P]),
+    "dpm_local_map_register": (I, [P, I, I, I, D, P, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P, P]),
+    "dpm_local_map_export": (I, [P, I, I, I, P, P, P, P, P, I, P]),
 }
 
 

@@ -59,6 +59,7 @@ SOURCES = {
     "lidar_sim.hip": [],
     "map_eval.hip": [],
     "deskew.hip": [],
+    "local_map.hip": [],
 }
 
 

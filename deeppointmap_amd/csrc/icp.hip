@@ -19,13 +19,13 @@
 // (Rodrigues rotation, the translation taken as it is).
 #include "block_scan.h"
 #include "cell_grid.h"
+#include "gn_solve.h"
 
 namespace {
 
 constexpr int GMAX = 512;   // grid cells per axis (upper bound)
-constexpr int NSUM = 29;    // H upper triangle (21), g (6), matches, sum of squared residuals
+constexpr int NSUM = GN_NSUM;   // H upper triangle (21), g (6), matches, sum of squared residuals
 constexpr int NSUM_PAD = 32;
-constexpr double PIV_EPS = 1e-9;  // a Cholesky pivot below PIV_EPS * (largest diagonal entry of its 3x3 block) is singular
 
 struct IcpHdr {   // start of every pair's workspace slice (256 bytes reserved)
     float lox, loy, inv_cs;
@@ -237,8 +237,6 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(IcpArgs A, float r2
             (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
 }
 
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < 1e300; }   // false for Inf and NaN
-
 __global__ __launch_bounds__(64) void icp_solve_kernel(IcpArgs A, double tol_rot, double tol_trans) {
     const int pair = blockIdx.x, lane = threadIdx.x;
     IcpHdr *hdr = hdr_of(A, pair);
@@ -254,85 +252,7 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(IcpArgs A, double tol_rot
     }
     __syncthreads();
     if (lane != 0) return;
-    const double cnt = S[27], rss = S[28];
-    if (!(cnt >= 1.0)) {
-        A.fitness[pair] = 0.f, A.rmse[pair] = 0.f, A.status[pair] = DPM_ICP_NO_MATCH, hdr->done = 1;
-        return;
-    }
-    A.fitness[pair] = (float)(cnt / (double)max(hdr->n1, 1));
-    const double ms = rss / cnt;
-    A.rmse[pair] = finite_d(ms) && ms >= 0.0 ? (float)sqrt(ms) : 0.f;
-    double Hm[6][6], L[6][6], g[6];
-    {
-        int k = 0;
-        for (int i = 0; i < 6; ++i)
-            for (int j = i; j < 6; ++j) Hm[i][j] = Hm[j][i] = S[k++];
-        for (int i = 0; i < 6; ++i) g[i] = S[21 + i];
-    }
-    bool ok = cnt >= 6.0;
-    for (int k = 0; k < NSUM && ok; ++k) ok = finite_d(S[k]);
-    const double bm[2] = {fmax(fmax(Hm[0][0], Hm[1][1]), Hm[2][2]), fmax(fmax(Hm[3][3], Hm[4][4]), Hm[5][5])};
-    for (int k = 0; k < 6 && ok; ++k) {
-        double d = Hm[k][k];
-        for (int m = 0; m < k; ++m) d -= L[k][m] * L[k][m];
-        if (!(d > PIV_EPS * bm[k / 3])) {
-            ok = false;
-            break;
-        }
-        L[k][k] = sqrt(d);
-        for (int i = k + 1; i < 6; ++i) {
-            double v = Hm[i][k];
-            for (int m = 0; m < k; ++m) v -= L[i][m] * L[k][m];
-            L[i][k] = v / L[k][k];
-        }
-    }
-    double x[6];
-    if (ok) {
-        double yv[6];
-        for (int i = 0; i < 6; ++i) {   // L y = -g
-            double v = -g[i];
-            for (int m = 0; m < i; ++m) v -= L[i][m] * yv[m];
-            yv[i] = v / L[i][i];
-        }
-        for (int i = 5; i >= 0; --i) {  // L^T x = y
-            double v = yv[i];
-            for (int m = i + 1; m < 6; ++m) v -= L[m][i] * x[m];
-            x[i] = v / L[i][i];
-        }
-        for (int i = 0; i < 6; ++i) ok = ok && finite_d(x[i]);
-    }
-    if (!ok) {   // the pose stays at its last good value
-        A.status[pair] = DPM_ICP_SINGULAR, hdr->done = 1;
-        return;
-    }
-    const double th2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2], th = sqrt(th2);
-    double a, b;   // exp(w) = I + a K + b K^2
-    if (th < 1e-8) a = 1.0, b = 0.5;
-    else a = sin(th) / th, b = (1.0 - cos(th)) / th2;
-    const double K[3][3] = {{0.0, -x[2], x[1]}, {x[2], 0.0, -x[0]}, {-x[1], x[0], 0.0}};
-    double E[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double k2 = 0.0;
-            for (int m = 0; m < 3; ++m) k2 += K[i][m] * K[m][j];
-            E[i][j] = (i == j ? 1.0 : 0.0) + a * K[i][j] + b * k2;
-        }
-    double *pose = A.pose + (size_t)pair * 16, out[12];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double v = 0.0;
-            for (int m = 0; m < 3; ++m) v += E[i][m] * pose[m * 4 + j];
-            out[i * 4 + j] = j == 3 ? v + x[3 + i] : v;
-        }
-    for (int k = 0; k < 12; ++k) ok = ok && finite_d(out[k]);
-    if (!ok) {
-        A.status[pair] = DPM_ICP_SINGULAR, hdr->done = 1;
-        return;
-    }
-    for (int k = 0; k < 12; ++k) pose[k] = out[k];
-    A.iterations[pair] += 1;
-    const double tr = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
-    if (th < tol_rot && tr < tol_trans) A.status[pair] = DPM_ICP_CONVERGED, hdr->done = 1;
+    gn_solve_step(S, hdr->n1, A.pose + (size_t)pair * 16, A.fitness, A.rmse, A.iterations, A.status, pair, &hdr->done, tol_rot, tol_trans);
 }
 
 size_t slice_bytes(int N) {

@@ -1,0 +1,508 @@
+// The rolling local map of the geometric odometry (deeppointmap_amd/odometry.py) and the registration of a scan against it.
+// The reference has no counterpart: it estimates poses with its learned pipeline only.
+//
+// Map: an open-addressing table of cap_vox slots (a power of two, linear probing, empty key ~0) keyed by the voxel
+// coordinate floor(p / v) per axis, 3 x 21 bits biased by 2^20 as in csrc/voxel_map.hip.  p is the fp32 point in the MAP
+// frame: world minus a float64 `origin` fixed when the map is made; a pose enters as R -> (float)R and
+// t -> (float)(t - origin), the difference formed in fp64 and rounded once (csrc/map_eval.hip's shift).  A voxel has
+// S = s^3 sub-cells, s in {1, 2, 3}; sub-cell (a, b, c) -> (c * s + b) * s + a.  Per axis, in fp32:
+//     f = p / v (correctly rounded division),  voxel = floor(f),  sub = min((int)((f - voxel) * s), s - 1).
+// Each sub-cell holds at most one point: an owner word (stamp << 32) | row and a float4 (x, y, z, 0).
+//
+// RULE: a sub-cell belongs to the point with the smallest owner word ever offered to it.  The stamp counts frames, so an
+// older frame is never displaced, and within a frame the smaller row (the frame's `idx`, the ORIGINAL row number, which
+// survives sampling and shuffles) wins: "at most S points a voxel, first come first kept" with "first" defined.  Only
+// integer atomics: the content reachable by key is a function of the inserted points alone.  Slot positions are not (two
+// voxels racing for one probe chain), and nothing reads them.
+//
+//   claim    per valid row: range gate on the SENSOR-frame point, r2 = (x*x + y*y) + z*z, kept when
+//            (float)(min_range^2) <= r2 <= (float)(max_range^2) (a NaN fails);  transform
+//            q = fma(R2, z, fma(R1, y, R0 * x)) + t, the arithmetic of the registration search;  a coordinate outside the
+//            21 bits is dropped and counted (header word 1);  find or claim the voxel (atomicCAS on the key);  atomicMin on
+//            the sub-cell's owner word.  No free slot within cap_vox probes: header word 0 (overflow) counts the point,
+//            and the map is defined only while that word is 0.
+//   commit   the same arithmetic (the same bits), a read-only probe, and the coordinates written where the owner word is
+//            the point's own.  A launch boundary lies between the atomics and these plain stores.
+//   prune    the other half of the double buffer is cleared, then every voxel whose centre c = ((float)voxel + 0.5f) * v
+//            has (dx*dx + dy*dy) + dz*dz <= (float)(radius^2) from the pose's translation is claimed there and its S
+//            sub-cells are copied.  A voxel is one key: the copy has one writer.
+//   export   (key, sub-cell, owner, xyz) of every occupied sub-cell in arrival order + their number; Python sorts.
+//
+// Registration: per iteration two launches, no host synchronisation, capturable on one stream.
+//   accumulate: four lanes per query, queries in ROW order.  The query is moved by the device pose rounded to fp32; lane l
+//               of the quad probes neighbours n = l, l + 4, ... of the 27 voxels around it (n = ((dz+1) * 3 + (dy+1)) * 3 +
+//               (dx+1)) read-only and scans their occupied sub-cells; the winner is the smallest 64-bit key
+//               (distance bits, n * 32 + sub-cell): ties are broken by geometry alone.  A hit needs d2 <= (float)(max_dist^2);
+//               max_dist <= v (checked on the host), so in exact arithmetic no nearer point lies outside the 27 voxels.
+//               Lane 0 adds the point-to-point rows, weighted w = (kappa / (kappa + e.e))^2 (Geman-McClure, kappa =
+//               kernel_scale^2, 0 = unweighted), to the 29 fp64 sums of csrc/icp.hip: H and g weighted, the match count and
+//               the squared residuals not.  Lanes, then waves, in a fixed tree; one partial per block.
+//   solve:      one wave adds the partials in block order; the step is csrc/gn_solve.h, taken on the pose in the map frame
+//               (where the rows were formed) and shifted back; a step not taken leaves the pose's bytes alone.
+#include "cell_grid.h"
+#include "gn_solve.h"
+
+namespace {
+
+constexpr unsigned long long EMPTY = ~0ull;
+constexpr int NSUM = GN_NSUM, NSUM_PAD = 32;
+constexpr int LM_BLOCK = 256;
+
+struct MapHdr {   // 256 bytes
+    unsigned overflow, outside, pad[62];
+};
+
+struct Map {
+    unsigned char *base;
+    int cap_vox, s, S, half;
+    float v;
+    double ox, oy, oz;
+    __host__ __device__ size_t half_bytes() const { return (size_t)cap_vox * 8 + (size_t)cap_vox * S * 24; }
+    __host__ __device__ unsigned long long *keys(int h) const { return (unsigned long long *)(base + 256 + (size_t)h * half_bytes()); }
+    __host__ __device__ unsigned long long *owner(int h) const { return keys(h) + cap_vox; }
+    __host__ __device__ float4 *pts(int h) const { return (float4 *)(owner(h) + (size_t)cap_vox * S); }
+    __host__ __device__ MapHdr *hdr() const { return (MapHdr *)base; }
+};
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {   // splitmix64 finaliser, as voxel_map.hip
+    k ^= k >> 30;
+    k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27;
+    k *= 0x94d049bb133111ebull;
+    return k ^ (k >> 31);
+}
+
+// the fp32 pose of the map frame: 9 rotation entries row-major, then the translation minus the origin
+struct Pose32 {
+    float R[9], t[3];
+};
+
+__device__ __forceinline__ Pose32 load_pose(const double *pose, const Map &M) {
+    Pose32 P;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) P.R[3 * i + j] = (float)pose[4 * i + j];
+    P.t[0] = (float)(pose[3] - M.ox), P.t[1] = (float)(pose[7] - M.oy), P.t[2] = (float)(pose[11] - M.oz);
+    return P;
+}
+
+__device__ __forceinline__ void xform(const Pose32 &P, float x, float y, float z, float q[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = fmaf(P.R[3 * a + 2], z, fmaf(P.R[3 * a + 1], y, P.R[3 * a] * x)) + P.t[a];
+}
+
+// voxel coordinate (biased by 2^20) and sub-cell coordinate of one axis; 0 when the 21 bits cannot hold it (or NaN)
+__device__ __forceinline__ int axis_cell(float p, float v, int s, int &vox, int &sub) {
+    const float f = __fdiv_rn(p, v), fl = floorf(f);
+    if (!(fl >= -1048576.f && fl < 1048576.f)) return 0;
+    vox = (int)fl + 1048576;
+    sub = min((int)((f - fl) * (float)s), s - 1);
+    return 1;
+}
+
+__device__ __forceinline__ unsigned long long pack_key(int x, int y, int z) {
+    return (unsigned long long)x | ((unsigned long long)y << 21) | ((unsigned long long)z << 42);
+}
+
+// slot of `key` in a table nobody is writing, or -1
+__device__ __forceinline__ int find_slot(const unsigned long long *keys, int cap_vox, unsigned long long key) {
+    int slot = (int)(mix64(key) & (unsigned long long)(cap_vox - 1));
+    for (int probe = 0; probe < cap_vox; ++probe) {
+        const unsigned long long k = keys[slot];
+        if (k == key) return slot;
+        if (k == EMPTY) return -1;
+        slot = (slot + 1) & (cap_vox - 1);
+    }
+    return -1;
+}
+
+// slot of `key`, claimed if new, in a table other lanes are claiming in; -1 when no slot is free
+__device__ __forceinline__ int claim_slot(unsigned long long *keys, int cap_vox, unsigned long long key) {
+    int slot = (int)(mix64(key) & (unsigned long long)(cap_vox - 1));
+    for (int probe = 0; probe < cap_vox; ++probe) {
+        unsigned long long k = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == EMPTY) k = atomicCAS(&keys[slot], EMPTY, key);
+        if (k == EMPTY || k == key) return slot;
+        slot = (slot + 1) & (cap_vox - 1);
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(LM_BLOCK) void lm_clear_kernel(Map M, int h, bool header) {
+    const size_t tid = (size_t)blockIdx.x * LM_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * LM_BLOCK;
+    if (header && tid < 64) ((unsigned *)M.base)[tid] = 0u;
+    unsigned long long *w = M.keys(h);   // the keys and the owner words are one run of cap_vox * (1 + S) words of ~0
+    const size_t n = (size_t)M.cap_vox * (size_t)(1 + M.S);
+    for (size_t i = tid; i < n; i += stride) w[i] = EMPTY;
+}
+
+struct Frame {
+    const float *xyz;        // (cap,3)
+    const int32_t *idx;      // (cap,) original row numbers
+    const int32_t *count;    // (1,)
+    int cap;
+};
+
+// what claim and commit compute alike for row i; false when the row offers nothing
+__device__ __forceinline__ bool row_cell(const Map &M, const Frame &F, const Pose32 &P, int i, float lo2, float hi2,
+                                         unsigned long long &key, int &sub, float q[3], bool &outside) {
+    const float x = F.xyz[3 * (size_t)i], y = F.xyz[3 * (size_t)i + 1], z = F.xyz[3 * (size_t)i + 2];
+    const float r2 = (x * x + y * y) + z * z;
+    outside = false;
+    if (!(r2 >= lo2 && r2 <= hi2)) return false;
+    xform(P, x, y, z, q);
+    int vx, vy, vz, sx, sy, sz;
+    if (!(axis_cell(q[0], M.v, M.s, vx, sx) & axis_cell(q[1], M.v, M.s, vy, sy) & axis_cell(q[2], M.v, M.s, vz, sz))) {
+        outside = true;
+        return false;
+    }
+    key = pack_key(vx, vy, vz), sub = (sz * M.s + sy) * M.s + sx;
+    return true;
+}
+
+template <bool COMMIT>
+__global__ __launch_bounds__(LM_BLOCK) void lm_insert_kernel(Map M, Frame F, const double *pose, unsigned stamp, float lo2,
+                                                             float hi2) {
+    const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
+    const int n = min(max(F.count[0], 0), F.cap);
+    if (i >= n) return;
+    const Pose32 P = load_pose(pose, M);
+    unsigned long long key;
+    int sub;
+    float q[3];
+    bool outside;
+    if (!row_cell(M, F, P, i, lo2, hi2, key, sub, q, outside)) {
+        if (!COMMIT && outside) atomicAdd(&M.hdr()->outside, 1u);
+        return;
+    }
+    const unsigned long long word = ((unsigned long long)stamp << 32) | (unsigned)F.idx[i];
+    if (!COMMIT) {
+        const int slot = claim_slot(M.keys(M.half), M.cap_vox, key);
+        if (slot < 0) {
+            atomicAdd(&M.hdr()->overflow, 1u);
+            return;
+        }
+        atomicMin(&M.owner(M.half)[(size_t)slot * M.S + sub], word);
+    } else {
+        const int slot = find_slot(M.keys(M.half), M.cap_vox, key);
+        if (slot < 0) return;   // counted as overflow by claim
+        const size_t c = (size_t)slot * M.S + sub;
+        if (M.owner(M.half)[c] == word) M.pts(M.half)[c] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+}
+
+// one thread per slot of the current half; survivors move to the other half (cleared before this launch)
+__global__ __launch_bounds__(LM_BLOCK) void lm_prune_kernel(Map M, const double *pose, float r2) {
+    const int slot = blockIdx.x * LM_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long key = M.keys(M.half)[slot];
+    if (key == EMPTY) return;
+    const float tx = (float)(pose[3] - M.ox), ty = (float)(pose[7] - M.oy), tz = (float)(pose[11] - M.oz);
+    const float cx = ((float)((int)(key & 0x1FFFFF) - 1048576) + 0.5f) * M.v;
+    const float cy = ((float)((int)((key >> 21) & 0x1FFFFF) - 1048576) + 0.5f) * M.v;
+    const float cz = ((float)((int)((key >> 42) & 0x1FFFFF) - 1048576) + 0.5f) * M.v;
+    const float dx = cx - tx, dy = cy - ty, dz = cz - tz;
+    if (!((dx * dx + dy * dy) + dz * dz <= r2)) return;
+    const int to = claim_slot(M.keys(1 - M.half), M.cap_vox, key);   // never full: no more keys than the old half held
+    if (to < 0) {
+        atomicAdd(&M.hdr()->overflow, 1u);
+        return;
+    }
+    const unsigned long long *ow = M.owner(M.half) + (size_t)slot * M.S;
+    const float4 *pt = M.pts(M.half) + (size_t)slot * M.S;
+    unsigned long long *ow2 = M.owner(1 - M.half) + (size_t)to * M.S;
+    float4 *pt2 = M.pts(1 - M.half) + (size_t)to * M.S;
+    for (int c = 0; c < M.S; ++c) {
+        const unsigned long long o = ow[c];
+        if (o == EMPTY) continue;
+        ow2[c] = o, pt2[c] = pt[c];
+    }
+}
+
+__global__ __launch_bounds__(LM_BLOCK) void lm_export_kernel(Map M, unsigned long long *keys, int32_t *sub,
+                                                             unsigned long long *owner, float *xyz, int32_t *count,
+                                                             int max_out) {
+    const size_t n = (size_t)M.cap_vox * M.S;
+    for (size_t c = (size_t)blockIdx.x * LM_BLOCK + threadIdx.x; c < n; c += (size_t)gridDim.x * LM_BLOCK) {
+        const unsigned long long o = M.owner(M.half)[c];
+        if (o == EMPTY) continue;
+        const unsigned long long key = M.keys(M.half)[c / M.S];
+        if (key == EMPTY) continue;
+        const int pos = atomicAdd(count, 1);
+        if (pos < 0 || pos >= max_out) continue;
+        const float4 p = M.pts(M.half)[c];
+        keys[pos] = key, sub[pos] = (int32_t)(c % M.S), owner[pos] = o;
+        xyz[3 * (size_t)pos] = p.x, xyz[3 * (size_t)pos + 1] = p.y, xyz[3 * (size_t)pos + 2] = p.z;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ registration
+struct RegHdr {   // start of the workspace (256 bytes), then one partial of NSUM_PAD doubles per block
+    int done, n1;
+};
+
+struct RegArgs {
+    Map M;
+    Frame F;
+    RegHdr *hdr;
+    double *partial;
+    double *pose;
+    float *fitness, *rmse;
+    int32_t *iterations, *status;
+    long long *dbg_key;     // (cap,) or NULL
+    int32_t *dbg_sub;       // (cap,) or NULL
+    double *dbg_system;     // (NSUM,) or NULL
+};
+
+__global__ void lm_reg_init_kernel(RegArgs A, const double *init) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    for (int k = 0; k < 12; ++k) A.pose[k] = init[k];
+    A.pose[12] = 0.0, A.pose[13] = 0.0, A.pose[14] = 0.0, A.pose[15] = 1.0;
+    *A.fitness = 0.f, *A.rmse = 0.f, *A.iterations = 0, *A.status = DPM_ICP_MAX_ITER;
+    A.hdr->done = 0, A.hdr->n1 = min(max(A.F.count[0], 0), A.F.cap);
+    if (A.dbg_system)
+        for (int k = 0; k < NSUM; ++k) A.dbg_system[k] = 0.0;
+}
+
+__global__ void lm_reg_stage_kernel(RegArgs A) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    A.hdr->done = 0;
+    *A.status = DPM_ICP_MAX_ITER;
+}
+
+// one weighted row: H += w J^T J, g += w J^T e, squared residuals += e e
+__device__ __forceinline__ void add_row_w(double (&s)[NSUM], const double (&J)[6], double e, double w) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const double wj = w * J[i];
+#pragma unroll
+        for (int j = i; j < 6; ++j) s[k] = fma(wj, J[j], s[k]), ++k;
+        s[21 + i] = fma(wj, e, s[21 + i]);
+    }
+    s[28] = fma(e, e, s[28]);
+}
+
+__global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, float r2, double kappa) {
+    if (A.hdr->done) return;
+    const Map &M = A.M;
+    const int blk = blockIdx.x, n1 = A.hdr->n1, cap = A.F.cap;
+    const Pose32 P = load_pose(A.pose, M);
+    const unsigned long long *keys = M.keys(M.half), *owner = M.owner(M.half);
+    const float4 *pts = M.pts(M.half);
+    const int quad = threadIdx.x >> 2, ql = threadIdx.x & 3;
+    double s[NSUM];
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) s[k] = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        const int i = blk * 256 + j * 64 + quad;   // uniform inside a quad
+        if (i >= n1) {
+            if (i < cap && ql == 0) {
+                if (A.dbg_key) A.dbg_key[i] = -1;
+                if (A.dbg_sub) A.dbg_sub[i] = -1;
+            }
+            continue;
+        }
+        float q[3];
+        xform(P, A.F.xyz[3 * (size_t)i], A.F.xyz[3 * (size_t)i + 1], A.F.xyz[3 * (size_t)i + 2], q);
+        int vx, vy, vz, sx, sy, sz;
+        const bool inside = axis_cell(q[0], M.v, M.s, vx, sx) & axis_cell(q[1], M.v, M.s, vy, sy) & axis_cell(q[2], M.v, M.s, vz, sz);
+        unsigned long long best = ~0ull;
+        int best_slot = -1;
+        if (inside) {
+            for (int n = ql; n < 27; n += 4) {
+                const int x = vx + n % 3 - 1, y = vy + (n / 3) % 3 - 1, z = vz + n / 9 - 1;
+                if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) continue;
+                const int slot = find_slot(keys, M.cap_vox, pack_key(x, y, z));
+                if (slot < 0) continue;
+                for (int c = 0; c < M.S; ++c) {
+                    if (owner[(size_t)slot * M.S + c] == EMPTY) continue;
+                    const float4 t = pts[(size_t)slot * M.S + c];
+                    const float dx = q[0] - t.x, dy = q[1] - t.y, dz = q[2] - t.z;
+                    const unsigned long long key =
+                        ((unsigned long long)__float_as_uint((dx * dx + dy * dy) + dz * dz) << 32) | (unsigned)(n * 32 + c);
+                    if (key < best) best = key, best_slot = slot;
+                }
+            }
+        }
+        const unsigned long long mine = best;
+        best = quad_min_key(best);
+        const bool hit = best != ~0ull && __uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
+        // the winner's slot, from the lane that found it (keys of different lanes differ in n)
+        int win_slot = mine == best ? best_slot : -1;
+        win_slot = max(win_slot, __shfl_xor(win_slot, 1, 64));
+        win_slot = max(win_slot, __shfl_xor(win_slot, 2, 64));
+        if (ql != 0) continue;
+        const int c = (int)((unsigned)best & 31u);
+        if (A.dbg_key) A.dbg_key[i] = hit ? (long long)keys[win_slot] : -1;
+        if (A.dbg_sub) A.dbg_sub[i] = hit ? c : -1;
+        if (!hit) continue;
+        const float4 t = pts[(size_t)win_slot * M.S + c];
+        const double px = q[0], py = q[1], pz = q[2];
+        const double ex = px - (double)t.x, ey = py - (double)t.y, ez = pz - (double)t.z;
+        double w = 1.0;
+        if (kappa > 0.0) {
+            const double r = kappa / (kappa + ((ex * ex + ey * ey) + ez * ez));
+            w = r * r;
+        }
+        s[27] += 1.0;
+        const double Jx[6] = {0.0, pz, -py, 1.0, 0.0, 0.0}, Jy[6] = {-pz, 0.0, px, 0.0, 1.0, 0.0},
+                     Jz[6] = {py, -px, 0.0, 0.0, 0.0, 1.0};
+        add_row_w(s, Jx, ex, w), add_row_w(s, Jy, ey, w), add_row_w(s, Jz, ez, w);
+    }
+    // lanes, then waves, in a fixed tree; one partial per block
+    __shared__ double sred[4][NSUM];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) {
+        double v = s[k];
+#pragma unroll
+        for (int off = 32; off >= 4; off >>= 1) v += __shfl_xor(v, off, 64);   // lanes 1..3 of a quad hold zeros
+        if (lane == 0) sred[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NSUM)
+        A.partial[(size_t)blk * NSUM_PAD + threadIdx.x] =
+            (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
+}
+
+__global__ __launch_bounds__(64) void lm_solve_kernel(RegArgs A, double tol_rot, double tol_trans) {
+    const int lane = threadIdx.x;
+    if (A.hdr->done) return;
+    __shared__ double S[NSUM_PAD];
+    if (lane < NSUM) {
+        const int nblk = (A.F.cap + 255) / 256;
+        double v = 0.0;
+        for (int b = 0; b < nblk; ++b) v += A.partial[(size_t)b * NSUM_PAD + lane];   // block order
+        S[lane] = v;
+        if (A.dbg_system) A.dbg_system[lane] = v;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    // the rows were formed in the map frame, so the step acts on the pose there; a step that was not taken leaves the
+    // world pose's bytes alone
+    double local[12];
+    for (int k = 0; k < 12; ++k) local[k] = A.pose[k];
+    local[3] -= A.M.ox, local[7] -= A.M.oy, local[11] -= A.M.oz;
+    const int before = A.iterations[0];
+    gn_solve_step(S, A.hdr->n1, local, A.fitness, A.rmse, A.iterations, A.status, 0, &A.hdr->done, tol_rot, tol_trans);
+    if (A.iterations[0] == before) return;
+    local[3] += A.M.ox, local[7] += A.M.oy, local[11] += A.M.oz;
+    for (int k = 0; k < 12; ++k) A.pose[k] = local[k];
+}
+
+inline unsigned grid_for(size_t items) {
+    const size_t b = (items + LM_BLOCK - 1) / LM_BLOCK;
+    return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
+}
+
+inline bool map_ok(const void *map, int cap_vox, int subdiv) {
+    return map && ((uintptr_t)map & 15) == 0 && cap_vox >= 2 && cap_vox <= (1 << 24) && (cap_vox & (cap_vox - 1)) == 0 &&
+           subdiv >= 1 && subdiv <= 3;
+}
+
+inline Map make_map(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin) {
+    Map M;
+    M.base = (unsigned char *)map, M.cap_vox = cap_vox, M.s = subdiv, M.S = subdiv * subdiv * subdiv, M.half = half;
+    M.v = (float)voxel;
+    M.ox = origin ? origin[0] : 0.0, M.oy = origin ? origin[1] : 0.0, M.oz = origin ? origin[2] : 0.0;
+    return M;
+}
+
+inline bool geometry_ok(int half, double voxel, const double *origin) {
+    if (!((half == 0 || half == 1) && origin && voxel > 0.0 && voxel < 1e18 && (float)voxel > 0.f)) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!(origin[a] > -1e300 && origin[a] < 1e300)) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" size_t dpm_local_map_bytes(int cap_vox, int subdiv) {
+    if (!map_ok((const void *)16, cap_vox, subdiv)) return 0;
+    return 256 + 2 * make_map(nullptr, cap_vox, subdiv, 0, 1.0, nullptr).half_bytes();
+}
+
+extern "C" int dpm_local_map_init(void *map, int cap_vox, int subdiv, dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv));
+    const Map M = make_map(map, cap_vox, subdiv, 0, 1.0, nullptr);
+    const unsigned g = grid_for((size_t)cap_vox * (size_t)(1 + M.S));
+    hipLaunchKernelGGL(lm_clear_kernel, dim3(g), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, 0, true);
+    hipLaunchKernelGGL(lm_clear_kernel, dim3(g), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, 1, false);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_local_map_insert(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                    const float *xyz, const int32_t *idx, const int32_t *count, int cap,
+                                    const double *pose, unsigned stamp, double min_range, double max_range,
+                                    dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
+    DPM_CHECK_ARG(xyz && idx && count && pose && cap >= 0 && stamp < 0xFFFFFFFFu);
+    DPM_CHECK_ARG(min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
+    if (cap == 0) return DPM_OK;
+    const Map M = make_map(map, cap_vox, subdiv, half, voxel, origin);
+    const Frame F{xyz, idx, count, cap};
+    const float lo2 = (float)(min_range * min_range), hi2 = (float)(max_range * max_range);
+    hipLaunchKernelGGL(lm_insert_kernel<false>, dim3(dpm_cdiv(cap, LM_BLOCK)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, F,
+                       pose, stamp, lo2, hi2);
+    hipLaunchKernelGGL(lm_insert_kernel<true>, dim3(dpm_cdiv(cap, LM_BLOCK)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, F,
+                       pose, stamp, lo2, hi2);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                   const double *pose, double radius, dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
+    DPM_CHECK_ARG(pose && radius >= 0.0 && radius < 1e18);
+    const Map M = make_map(map, cap_vox, subdiv, half, voxel, origin);
+    hipLaunchKernelGGL(lm_clear_kernel, dim3(grid_for((size_t)cap_vox * (size_t)(1 + M.S))), dim3(LM_BLOCK), 0,
+                       (hipStream_t)stream, M, 1 - half, false);
+    hipLaunchKernelGGL(lm_prune_kernel, dim3(dpm_cdiv(cap_vox, LM_BLOCK)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, pose,
+                       (float)(radius * radius));
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_local_map_register(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                      const float *xyz, const int32_t *count, int cap, const double *init_pose,
+                                      const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages,
+                                      double kernel_scale, double tol_rot, double tol_trans, double *pose, float *fitness,
+                                      float *rmse, int32_t *iterations, int32_t *status, long long *debug_key,
+                                      int32_t *debug_sub, double *debug_system, void *workspace, dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
+    DPM_CHECK_ARG(xyz && count && init_pose && stage_max_dist && stage_max_iter && workspace && cap >= 1);
+    DPM_CHECK_ARG(pose && fitness && rmse && iterations && status && pose != init_pose);
+    DPM_CHECK_ARG(n_stages >= 1 && n_stages <= 16 && tol_rot >= 0.0 && tol_trans >= 0.0 && kernel_scale >= 0.0 && kernel_scale < 1e18);
+    for (int s = 0; s < n_stages; ++s)
+        DPM_CHECK_ARG(stage_max_dist[s] > 0.0 && stage_max_dist[s] <= (double)(float)voxel && stage_max_iter[s] >= 0);
+    hipStream_t st = (hipStream_t)stream;
+    RegArgs A{};
+    A.M = make_map((void *)map, cap_vox, subdiv, half, voxel, origin);
+    A.F = Frame{xyz, nullptr, count, cap};
+    unsigned char *ws = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    A.hdr = (RegHdr *)ws, A.partial = (double *)(ws + 256);
+    A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
+    A.dbg_key = debug_key, A.dbg_sub = debug_sub, A.dbg_system = debug_system;
+    const double kappa = kernel_scale * kernel_scale;
+    hipLaunchKernelGGL(lm_reg_init_kernel, dim3(1), dim3(64), 0, st, A, init_pose);
+    for (int s = 0; s < n_stages; ++s) {
+        const float r2 = (float)(stage_max_dist[s] * stage_max_dist[s]);
+        if (s > 0) hipLaunchKernelGGL(lm_reg_stage_kernel, dim3(1), dim3(64), 0, st, A);
+        for (int it = 0; it < stage_max_iter[s]; ++it) {
+            hipLaunchKernelGGL(lm_accumulate_kernel, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa);
+            hipLaunchKernelGGL(lm_solve_kernel, dim3(1), dim3(64), 0, st, A, tol_rot, tol_trans);
+        }
+    }
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_local_map_export(const void *map, int cap_vox, int subdiv, int half, unsigned long long *keys,
+                                    int32_t *sub, unsigned long long *owner, float *xyz, int32_t *count, int max_out,
+                                    dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && (half == 0 || half == 1) && count && max_out >= 0);
+    DPM_CHECK_ARG(max_out == 0 || (keys && sub && owner && xyz));
+    const Map M = make_map((void *)map, cap_vox, subdiv, half, 1.0, nullptr);
+    hipLaunchKernelGGL(lm_export_kernel, dim3(grid_for((size_t)cap_vox * M.S)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, keys,
+                       sub, owner, xyz, count, max_out);
+    return dpm_launch_status();
+}

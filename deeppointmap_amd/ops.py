@@ -2166,3 +2166,115 @@ def distance_stats(dist: torch.Tensor, thresholds, max_dist: float, surf: Option
                                           0 if class_id is None else class_id.shape[0], C, ctypes.addressof(thr) if T else None,
                                           T, float(max_dist), _ptr(out), _ptr(ws), _stream(dist)), "dpm_distance_stats")
     return out
+
+
+# -- the rolling local map and the registration against it (csrc/local_map.hip; orchestration in odometry.py) ----------------
+LOCAL_MAP_HDR_WORDS = 64    # the map buffer's header as int32 words: [0] points that found no slot, [1] points outside the keys
+
+
+def _local_map_args(table: torch.Tensor, cap_vox: int, subdiv: int, origin=None):
+    _chk(table, torch.uint8, "table")
+    if table.numel() != _lib.load().dpm_local_map_bytes(int(cap_vox), int(subdiv)) or table.numel() == 0:
+        raise ValueError("table: dpm_local_map_bytes(cap_vox, subdiv) bytes, cap_vox a power of two in [2, 2^24], subdiv in 1..3")
+    if origin is None:
+        return None
+    o = (ctypes.c_double * 3)(*[float(v) for v in origin])
+    return o
+
+
+def local_map_new(cap_vox: int, subdiv: int, device) -> torch.Tensor:
+    """an empty map: the uint8 buffer every other local_map_* call takes"""
+    n = _lib.load().dpm_local_map_bytes(int(cap_vox), int(subdiv))
+    if n == 0:
+        raise ValueError("cap_vox: a power of two in [2, 2^24]; subdiv: 1, 2 or 3")
+    with torch.cuda.device(device):
+        table = torch.empty(n, device=device, dtype=torch.uint8)
+        _lib.check(_lib.load().dpm_local_map_init(_ptr(table), int(cap_vox), int(subdiv), _stream(table)), "dpm_local_map_init")
+    return table
+
+
+def local_map_insert(table, cap_vox, subdiv, half, voxel, origin, xyz, idx, count, pose, stamp, min_range, max_range):
+    """dpm_local_map_insert: xyz (cap,3) fp32, idx (cap,) int32, count (1,) int32, pose (4,4) fp64, all on the GPU"""
+    o = _local_map_args(table, cap_vox, subdiv, origin)
+    _chk(xyz, torch.float32, "xyz"), _chk(idx, torch.int32, "idx"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or idx.shape != xyz.shape[:1] or count.numel() != 1 or pose.numel() != 16:
+        raise ValueError("local_map_insert: xyz (cap,3), idx (cap,), count (1,), pose (4,4)")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_local_map_insert(_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o),
+                                                    _ptr(xyz), _ptr(idx), _ptr(count), xyz.shape[0], _ptr(pose), int(stamp),
+                                                    float(min_range), float(max_range), _stream(table)), "dpm_local_map_insert")
+
+
+def local_map_prune(table, cap_vox, subdiv, half, voxel, origin, pose, radius):
+    """dpm_local_map_prune: half `half` -> the other half; the caller works on 1 - half afterwards"""
+    o = _local_map_args(table, cap_vox, subdiv, origin)
+    _chk(pose, torch.float64, "pose")
+    if pose.numel() != 16:
+        raise ValueError("local_map_prune: pose (4,4)")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_local_map_prune(_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o),
+                                                   _ptr(pose), float(radius), _stream(table)), "dpm_local_map_prune")
+
+
+def local_map_register(table, cap_vox, subdiv, half, voxel, origin, xyz, count, init, schedule, kernel_scale=0.0,
+                       tol_rot=1e-7, tol_trans=1e-6, debug=False):
+    """dpm_local_map_register: xyz (cap,3) fp32, count (1,) int32, init (4,4) fp64 on the GPU; schedule = [(max_dist, max_iter),
+    ...] with every max_dist <= voxel -> pose (4,4) fp64, fitness, rmse (1,) fp32, iterations, status (1,) int32[, key (cap,)
+    int64, sub (cap,) int32, system (29,) fp64 with debug].  No host synchronisation, capturable in a graph."""
+    o = _local_map_args(table, cap_vox, subdiv, origin)
+    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(init, torch.float64, "init")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1 or count.numel() != 1 or tuple(init.shape) != (4, 4):
+        raise ValueError("local_map_register: xyz (cap,3) with cap >= 1, count (1,), init (4,4)")
+    stages = [(float(d), int(n)) for d, n in schedule]
+    if not stages:
+        raise ValueError("schedule: at least one (max_dist, max_iter) stage")
+    dist = (ctypes.c_double * len(stages))(*[d for d, _ in stages])
+    iters = (ctypes.c_int32 * len(stages))(*[n for _, n in stages])
+    dev, cap = table.device, xyz.shape[0]
+    with torch.cuda.device(dev):
+        pose = torch.empty(4, 4, device=dev, dtype=torch.float64)
+        fitness = torch.empty(1, device=dev, dtype=torch.float32)
+        rmse = torch.empty(1, device=dev, dtype=torch.float32)
+        iterations = torch.empty(1, device=dev, dtype=torch.int32)
+        status = torch.empty(1, device=dev, dtype=torch.int32)
+        key = torch.full((cap,), -1, device=dev, dtype=torch.int64) if debug else None
+        sub = torch.full((cap,), -1, device=dev, dtype=torch.int32) if debug else None
+        system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
+        ws = torch.empty(512 + 256 * ((cap + 255) // 256), device=dev, dtype=torch.uint8)
+        _lib.check(_lib.load().dpm_local_map_register(
+            _ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(count), cap,
+            _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), len(stages), float(kernel_scale), float(tol_rot),
+            float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations), _ptr(status), _ptr(key), _ptr(sub),
+            _ptr(system), _ptr(ws), _stream(table)), "dpm_local_map_register")
+    out = (pose, fitness, rmse, iterations, status)
+    return out + (key, sub, system) if debug else out
+
+
+def local_map_export(table, cap_vox, subdiv, half, max_out=None):
+    """dpm_local_map_export -> (keys (n,) int64 holding the uint64 keys' bits, sub (n,) int32, owner (n,) int64, xyz (n,3) fp32),
+    in no defined order; max_out None: counted first (a host synchronisation), then exported whole (a second one).
+    max_out = 0 -> the count alone, as an int."""
+    _local_map_args(table, cap_vox, subdiv)
+    dev = table.device
+    lib = _lib.load()
+
+    def call(n):
+        with torch.cuda.device(dev):
+            count = torch.zeros(1, device=dev, dtype=torch.int32)
+            keys = torch.empty(n, device=dev, dtype=torch.int64)
+            sub = torch.empty(n, device=dev, dtype=torch.int32)
+            owner = torch.empty(n, device=dev, dtype=torch.int64)
+            xyz = torch.empty(n, 3, device=dev, dtype=torch.float32)
+            _lib.check(lib.dpm_local_map_export(_ptr(table), int(cap_vox), int(subdiv), int(half), _ptr(keys) if n else None,
+                                                _ptr(sub) if n else None, _ptr(owner) if n else None, _ptr(xyz) if n else None,
+                                                _ptr(count), n, _stream(table)), "dpm_local_map_export")
+        return count, keys, sub, owner, xyz
+
+    if max_out is None or int(max_out) == 0:
+        n = int(call(0)[0].item())
+        if max_out is not None:
+            return n
+        max_out = n
+    count, keys, sub, owner, xyz = call(int(max_out))
+    n = min(int(count.item()), int(max_out))
+    return keys[:n], sub[:n], owner[:n], xyz[:n]

@@ -984,6 +984,63 @@ size_t dpm_distance_stats_workspace_bytes(int M, int C, int T);
 int dpm_distance_stats(const float *dist, int M, const int32_t *surf, const int32_t *class_id, int n_surf, int C,
                        const float *thresholds, int T, double max_dist, double *out, void *workspace, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- geometric odometry -------- */
+
+/* A rolling hashed voxel map and the registration of a scan against it (csrc/local_map.hip; deeppointmap_amd/odometry.py is
+ * the caller).  No counterpart in the reference, which estimates poses with its learned pipeline only.
+ *
+ * The map is one device buffer of dpm_local_map_bytes(cap_vox, subdiv) bytes, 16-byte aligned: a 256-byte header (word 0:
+ * points that found no free slot, word 1: points outside the key range) and two halves, each an open-addressing table of
+ * cap_vox slots (a power of two in [2, 2^24], linear probing from splitmix64(key) & (cap_vox - 1), empty key ~0) with
+ * S = subdiv^3 sub-cells a slot, subdiv in {1, 2, 3}.  `half` (0 or 1) names the half a call works on; the caller flips it
+ * after every prune.  `voxel` (metres) and `origin` (three doubles ON THE HOST, read before the launch) must be the same in
+ * every call on one map.  Poses are 16 doubles (4x4 row-major, sensor -> world) IN DEVICE MEMORY: a call queues behind the
+ * kernel that wrote them without a host read.  In the map frame a pose is R -> (float)R, t -> (float)(t - origin), a point
+ * is q = fma(R2, z, fma(R1, y, R0 * x)) + t per axis, and per axis f = q / voxel (fp32, correctly rounded), the voxel is
+ * floor(f) (kept when in [-2^20, 2^20); the key packs the three, biased by 2^20, 21 bits each, x lowest) and the sub-cell
+ * coordinate min((int)((f - floor f) * subdiv), subdiv - 1); sub-cell number (c * subdiv + b) * subdiv + a for (x, y, z) =
+ * (a, b, c).  A sub-cell holds one point: an owner word (stamp << 32) | row and its fp32 map-frame coordinates.
+ * RULE: a sub-cell belongs to the smallest owner word ever offered to it -- an older frame (smaller stamp) is never
+ * displaced, within a frame the smaller row wins.  Integer atomics only: what a key leads to is a function of the inserted
+ * points alone (slot positions are not); two runs export identical bytes once sorted.  The map is defined only while header
+ * word 0 is zero.  Every call runs on `stream` without a host synchronisation. */
+size_t dpm_local_map_bytes(int cap_vox, int subdiv);
+/* header zeroed, both halves empty */
+int dpm_local_map_init(void *map, int cap_vox, int subdiv, dpm_stream_t stream);
+/* One frame in two launches (claim, commit).  xyz (cap,3) fp32 row-major, idx (cap,) int32 = the row number the rule sees
+ * (a frame's original rows, carried through sampling), count (1,) int32 on the device: rows at and past it are neither read
+ * nor written.  A row is offered when (float)(min_range^2) <= (x*x + y*y) + z*z <= (float)(max_range^2) on the SENSOR-frame
+ * point (a NaN fails).  stamp < 2^32 - 1 must grow from frame to frame. */
+int dpm_local_map_insert(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin, const float *xyz,
+                         const int32_t *idx, const int32_t *count, int cap, const double *pose, unsigned stamp,
+                         double min_range, double max_range, dpm_stream_t stream);
+/* Half `half` -> the other half (cleared first): a voxel survives when its centre c = ((float)voxel_index + 0.5f) * voxel per
+ * axis has (dx*dx + dy*dy) + dz*dz <= (float)(radius^2) from the pose's map-frame translation; its sub-cells are copied. */
+int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin, const double *pose,
+                        double radius, dpm_stream_t stream);
+/* Robust point-to-point ICP of the frame's first count rows against the map, from init_pose (device), over the schedule
+ * (stage_max_dist, stage_max_iter: n_stages <= 16 values ON THE HOST): two launches per iteration, capturable.  Every
+ * stage_max_dist must be <= voxel: a query looks into the 3 x 3 x 3 voxels around its own.  The match is the occupied
+ * sub-cell with the smallest key (bits of d2 = (dx*dx + dy*dy) + dz*dz, n * 32 + sub-cell), n = ((dz+1) * 3 + (dy+1)) * 3 +
+ * (dx+1) the neighbour's number, accepted when d2 <= (float)(max_dist^2).  Rows: point-to-point, weighted
+ * w = (k / (k + e.e))^2 with k = kernel_scale^2 (metres; 0: w = 1), summed in fp64 in a fixed order into the 29 values of
+ * dpm_icp_refine_batched (H and g weighted; match count and squared residuals not); solve, update, stop rule and the
+ * DPM_ICP_* statuses as there.  NO_MATCH (also: empty map, count 0) and SINGULAR leave the pose where it was; no NaN or Inf
+ * is written.  pose (16), fitness, rmse, iterations, status: one value each, on the device.  Optional: debug_key / debug_sub
+ * (cap,) the matched voxel key and sub-cell of every row at the last evaluated pose (-1: none), debug_system (29).
+ * workspace: 512 + 256 * ceil(cap / 256) bytes. */
+int dpm_local_map_register(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                           const float *xyz, const int32_t *count, int cap, const double *init_pose,
+                           const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages, double kernel_scale,
+                           double tol_rot, double tol_trans, double *pose, float *fitness, float *rmse, int32_t *iterations,
+                           int32_t *status, long long *debug_key, int32_t *debug_sub, double *debug_system, void *workspace,
+                           dpm_stream_t stream);
+/* Every occupied sub-cell of half `half`, in no defined order: keys / owner (max_out,) uint64, sub (max_out,) int32,
+ * xyz (max_out,3) fp32 map-frame.  count (1,) int32, ZEROED BY THE CALLER, receives their number, which may exceed max_out
+ * (the rest is not written; max_out = 0 only counts). */
+int dpm_local_map_export(const void *map, int cap_vox, int subdiv, int half, unsigned long long *keys, int32_t *sub,
+                         unsigned long long *owner, float *xyz, int32_t *count, int max_out, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
