@@ -162,6 +162,9 @@ SIGNATURES = {
     "dpm_local_map_prune": (I, [P, I, I, I, D, P, P, D, P]),
     "dpm_local_map_register": (I, [P, I, I, I, D, P, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P, P]),
     "dpm_local_map_export": (I, [P, I, I, I, P, P, P, P, P, I, P]),
+    "dpm_local_map_planes": (I, [P, I, I, I, D, P, D, P, P, P]),
+    "dpm_local_map_register_planes": (I, [P, I, I, I, D, P, P, P, I, D, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P,
+                                          P]),
 }
 
 

@@ -39,6 +39,24 @@
 //               the squared residuals not.  Lanes, then waves, in a fixed tree; one partial per block.
 //   solve:      one wave adds the partials in block order; the step is csrc/gn_solve.h, taken on the pose in the map frame
 //               (where the rows were formed) and shifted back; a step not taken leaves the pose's bytes alone.
+//
+// Voxel planes (dpm_local_map_planes): a cache derived from the map, one float4 (normal, w) and one count per SLOT of the
+// current half, in caller-owned buffers.  One launch, four lanes a slot.  The centre of a held voxel is
+// c = ((float)index + 0.5f) * v per axis; every occupied sub-cell point p of the 27 voxels around it with d = p - c (fp32) and
+// (dx*dx + dy*dy) + dz*dz <= (float)(plane_radius^2) is a member (plane_radius <= 1.5 v: the ball lies inside the 27 voxels).
+// Lane l adds the ten cumulants of d (n, 3 first, 6 second moments) in fp64 over the neighbours n = l, l + 4, ... ascending,
+// sub-cells ascending; the four lanes are added as (l0 + l1) + (l2 + l3).  So a voxel's plane is a function of the map's
+// content alone.  Lane 0 forms the scatter matrix n * S_ab - S_a * S_b (the covariance times n^2: exactly zero where the
+// points' coordinates are, which a quotient by n would not keep), runs the cyclic Jacobi of csrc/knn.hip's
+// point_normals_kernel in fp64 and orders the eigenvalues ascending, the smaller axis first among equals.  The normal is
+// the unit eigenvector of the smallest, rounded to fp32, its sign such that the component of largest magnitude (of the fp32
+// values; the first axis among equals) is positive; w = (float)(max(l0, 0) / l1).  Fewer than 3 members, or a line, l1 <= 1e-8 l2
+// (which includes l1 <= 0; see LINE_RATIO): (0, 0, 0, -1).  An empty slot: (0, 0, 0, -1) and count 0.
+//
+// Plane rows (dpm_local_map_register_planes): lm_accumulate_kernel<true>.  Search, tie-break and key as above; the matched
+// point's voxel (its slot) gives a row only when counts >= min_points and 0 <= w <= (float)max_ratio:
+// e = (nx*ex + ny*ey) + nz*ez, J = (p x n, n) -- csrc/icp.hip's plane row -- weighted (kappa / (kappa + e*e))^2.  A match
+// whose voxel has no such plane contributes nothing and is not counted.
 #include "cell_grid.h"
 #include "gn_solve.h"
 
@@ -237,6 +255,104 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_export_kernel(Map M, unsigned lon
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------- voxel planes
+// cyclic Jacobi of a symmetric 3 x 3 matrix in fp64, the loop of csrc/knn.hip's point_normals_kernel: A becomes diagonal
+// (the eigenvalues), the columns of V the eigenvectors
+__device__ __forceinline__ void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
+    for (int sweep = 0; sweep < 12; ++sweep) {
+        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
+        if (off <= 1e-300 || off <= 1e-18 * (fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]))) break;
+        for (int p = 0; p < 2; ++p)
+            for (int r = p + 1; r < 3; ++r) {
+                if (A[p][r] == 0.0) continue;
+                const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double cs_ = 1.0 / sqrt(t * t + 1.0), sn = t * cs_;
+                for (int k = 0; k < 3; ++k) {  // A <- A J
+                    const double akp = A[k][p], akr = A[k][r];
+                    A[k][p] = cs_ * akp - sn * akr, A[k][r] = sn * akp + cs_ * akr;
+                }
+                for (int k = 0; k < 3; ++k) {  // A <- J^T A,  V <- V J
+                    const double apk = A[p][k], ark = A[r][k];
+                    A[p][k] = cs_ * apk - sn * ark, A[r][k] = sn * apk + cs_ * ark;
+                    const double vkp = V[k][p], vkr = V[k][r];
+                    V[k][p] = cs_ * vkp - sn * vkr, V[k][r] = sn * vkp + cs_ * vkr;
+                }
+            }
+    }
+}
+
+// A point set whose middle eigenvalue is at most this fraction of its largest is a LINE: it has no plane.  In exact arithmetic
+// that is l1 = 0 (a ring of a spinning sensor on a flat wall), but the map's coordinates are fp32: a line a metre long comes
+// back 2^-24 |p| thick, l1 / l2 near 1e-11 at |p| = 50 m instead of 0, and the eigenvector of l0 is then whatever that rounding
+// left.  1e-8 is a thickness of 1e-4 of the length: 16 times the rounding of a coordinate at 100 m over one metre, and a
+// hundredth of what a sensor with 1 cm of range noise draws.
+constexpr double LINE_RATIO = 1e-8;
+
+// four lanes per slot of the current half, 64 slots a block
+__global__ __launch_bounds__(LM_BLOCK) void lm_planes_kernel(Map M, float r2, float4 *planes, int32_t *counts) {
+    const int slot = blockIdx.x * (LM_BLOCK / 4) + (threadIdx.x >> 2), ql = threadIdx.x & 3;   // uniform inside a quad
+    if (slot >= M.cap_vox) return;
+    const unsigned long long *keys = M.keys(M.half), *owner = M.owner(M.half);
+    const float4 *pts = M.pts(M.half);
+    const unsigned long long key = keys[slot];
+    if (key == EMPTY) {
+        if (ql == 0) planes[slot] = make_float4(0.f, 0.f, 0.f, -1.f), counts[slot] = 0;
+        return;
+    }
+    const int vx = (int)(key & 0x1FFFFF), vy = (int)((key >> 21) & 0x1FFFFF), vz = (int)((key >> 42) & 0x1FFFFF);
+    const float cx = ((float)(vx - 1048576) + 0.5f) * M.v, cy = ((float)(vy - 1048576) + 0.5f) * M.v,
+                cz = ((float)(vz - 1048576) + 0.5f) * M.v;
+    double m[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // n, x, y, z, xx, xy, xz, yy, yz, zz
+    for (int n = ql; n < 27; n += 4) {
+        const int x = vx + n % 3 - 1, y = vy + (n / 3) % 3 - 1, z = vz + n / 9 - 1;
+        if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) continue;
+        const int nb = n == 13 ? slot : find_slot(keys, M.cap_vox, pack_key(x, y, z));
+        if (nb < 0) continue;
+        for (int c = 0; c < M.S; ++c) {
+            if (owner[(size_t)nb * M.S + c] == EMPTY) continue;
+            const float4 t = pts[(size_t)nb * M.S + c];
+            const float dx = t.x - cx, dy = t.y - cy, dz = t.z - cz;
+            if (!((dx * dx + dy * dy) + dz * dz <= r2)) continue;
+            const double X = dx, Y = dy, Z = dz;
+            m[0] += 1.0, m[1] += X, m[2] += Y, m[3] += Z;
+            m[4] += X * X, m[5] += X * Y, m[6] += X * Z, m[7] += Y * Y, m[8] += Y * Z, m[9] += Z * Z;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {   // (l0 + l1) + (l2 + l3)
+        m[k] += __shfl_xor(m[k], 1, 64);
+        m[k] += __shfl_xor(m[k], 2, 64);
+    }
+    if (ql != 0) return;
+    float4 out = make_float4(0.f, 0.f, 0.f, -1.f);
+    const double n = m[0];
+    if (n >= 3.0) {
+        double A[3][3] = {{n * m[4] - m[1] * m[1], n * m[5] - m[1] * m[2], n * m[6] - m[1] * m[3]},
+                          {0, n * m[7] - m[2] * m[2], n * m[8] - m[2] * m[3]},
+                          {0, 0, n * m[9] - m[3] * m[3]}};
+        A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
+        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+        jacobi3(A, V);
+        // ascending, the smaller axis first among equals: e0 the smallest, e1 the smaller of the other two
+        int e0 = 0;
+        if (A[1][1] < A[e0][e0]) e0 = 1;
+        if (A[2][2] < A[e0][e0]) e0 = 2;
+        const int ea = e0 == 0 ? 1 : 0, eb = e0 == 2 ? 1 : 2;
+        const int e1 = A[eb][eb] < A[ea][ea] ? eb : ea;
+        const double l0 = A[e0][e0], l1 = A[e1][e1], l2 = A[3 - e0 - e1][3 - e0 - e1];
+        const double vx_ = V[0][e0], vy_ = V[1][e0], vz_ = V[2][e0], nr = sqrt(vx_ * vx_ + vy_ * vy_ + vz_ * vz_);
+        if (l1 > LINE_RATIO * l2 && nr > 0.0) {   // also false for l1 <= 0 and for a NaN
+            float nx = (float)(vx_ / nr), ny = (float)(vy_ / nr), nz = (float)(vz_ / nr);
+            const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
+            const float lead = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+            const float sg = lead < 0.f ? -1.f : 1.f;
+            out = make_float4(sg * nx + 0.f, sg * ny + 0.f, sg * nz + 0.f, (float)((l0 > 0.0 ? l0 : 0.0) / l1));   // + 0: no -0
+        }
+    }
+    planes[slot] = out, counts[slot] = (int32_t)n;
+}
+
 // ------------------------------------------------------------------------------------------------------------ registration
 struct RegHdr {   // start of the workspace (256 bytes), then one partial of NSUM_PAD doubles per block
     int done, n1;
@@ -284,7 +400,16 @@ __device__ __forceinline__ void add_row_w(double (&s)[NSUM], const double (&J)[6
     s[28] = fma(e, e, s[28]);
 }
 
-__global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, float r2, double kappa) {
+// the plane cache of the current half and the gate a voxel's plane passes to give a row (all unused when !PLANE)
+struct PlaneArgs {
+    const float4 *planes;
+    const int32_t *counts;
+    int min_points;
+    float max_ratio;
+};
+
+template <bool PLANE>
+__global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, float r2, double kappa, PlaneArgs PA) {
     if (A.hdr->done) return;
     const Map &M = A.M;
     const int blk = blockIdx.x, n1 = A.hdr->n1, cap = A.F.cap;
@@ -328,28 +453,45 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, floa
         }
         const unsigned long long mine = best;
         best = quad_min_key(best);
-        const bool hit = best != ~0ull && __uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
+        bool hit = best != ~0ull &&__uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
         // the winner's slot, from the lane that found it (keys of different lanes differ in n)
         int win_slot = mine == best ? best_slot : -1;
         win_slot = max(win_slot, __shfl_xor(win_slot, 1, 64));
         win_slot = max(win_slot, __shfl_xor(win_slot, 2, 64));
         if (ql != 0) continue;
         const int c = (int)((unsigned)best & 31u);
+        float4 pl = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (PLANE && hit) {   // the matched point's voxel gives a row only with a plane that passes the gate
+            pl = PA.planes[win_slot];
+            hit = PA.counts[win_slot] >= PA.min_points && pl.w >= 0.f && pl.w <= PA.max_ratio;
+        }
         if (A.dbg_key) A.dbg_key[i] = hit ? (long long)keys[win_slot] : -1;
         if (A.dbg_sub) A.dbg_sub[i] = hit ? c : -1;
         if (!hit) continue;
         const float4 t = pts[(size_t)win_slot * M.S + c];
         const double px = q[0], py = q[1], pz = q[2];
         const double ex = px - (double)t.x, ey = py - (double)t.y, ez = pz - (double)t.z;
-        double w = 1.0;
-        if (kappa > 0.0) {
-            const double r = kappa / (kappa + ((ex * ex + ey * ey) + ez * ez));
-            w = r * r;
-        }
         s[27] += 1.0;
-        const double Jx[6] = {0.0, pz, -py, 1.0, 0.0, 0.0}, Jy[6] = {-pz, 0.0, px, 0.0, 1.0, 0.0},
-                     Jz[6] = {py, -px, 0.0, 0.0, 0.0, 1.0};
-        add_row_w(s, Jx, ex, w), add_row_w(s, Jy, ey, w), add_row_w(s, Jz, ez, w);
+        if (PLANE) {
+            const double nx = pl.x, ny = pl.y, nz = pl.z;
+            const double e = (nx * ex + ny * ey) + nz * ez;
+            double w = 1.0;
+            if (kappa > 0.0) {
+                const double r = kappa / (kappa + e * e);
+                w = r * r;
+            }
+            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+            add_row_w(s, J, e, w);
+        } else {
+            double w = 1.0;
+            if (kappa > 0.0) {
+                const double r = kappa / (kappa + ((ex * ex + ey * ey) + ez * ez));
+                w = r * r;
+            }
+            const double Jx[6] = {0.0, pz, -py, 1.0, 0.0, 0.0}, Jy[6] = {-pz, 0.0, px, 0.0, 1.0, 0.0},
+                         Jz[6] = {py, -px, 0.0, 0.0, 0.0, 1.0};
+            add_row_w(s, Jx, ex, w), add_row_w(s, Jy, ey, w), add_row_w(s, Jz, ez, w);
+        }
     }
     // lanes, then waves, in a fixed tree; one partial per block
     __shared__ double sred[4][NSUM];
@@ -463,12 +605,14 @@ extern "C" int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half,
     return dpm_launch_status();
 }
 
-extern "C" int dpm_local_map_register(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
-                                      const float *xyz, const int32_t *count, int cap, const double *init_pose,
-                                      const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages,
-                                      double kernel_scale, double tol_rot, double tol_trans, double *pose, float *fitness,
-                                      float *rmse, int32_t *iterations, int32_t *status, long long *debug_key,
-                                      int32_t *debug_sub, double *debug_system, void *workspace, dpm_stream_t stream) {
+namespace {
+
+// both registrations: PA = nullptr is point-to-point
+int register_impl(const PlaneArgs *PA, const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                  const float *xyz, const int32_t *count, int cap, const double *init_pose, const double *stage_max_dist,
+                  const int32_t *stage_max_iter, int n_stages, double kernel_scale, double tol_rot, double tol_trans,
+                  double *pose, float *fitness, float *rmse, int32_t *iterations, int32_t *status, long long *debug_key,
+                  int32_t *debug_sub, double *debug_system, void *workspace, dpm_stream_t stream) {
     DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
     DPM_CHECK_ARG(xyz && count && init_pose && stage_max_dist && stage_max_iter && workspace && cap >= 1);
     DPM_CHECK_ARG(pose && fitness && rmse && iterations && status && pose != init_pose);
@@ -484,16 +628,57 @@ extern "C" int dpm_local_map_register(const void *map, int cap_vox, int subdiv, 
     A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
     A.dbg_key = debug_key, A.dbg_sub = debug_sub, A.dbg_system = debug_system;
     const double kappa = kernel_scale * kernel_scale;
+    const PlaneArgs none{nullptr, nullptr, 0, 0.f};
     hipLaunchKernelGGL(lm_reg_init_kernel, dim3(1), dim3(64), 0, st, A, init_pose);
     for (int s = 0; s < n_stages; ++s) {
         const float r2 = (float)(stage_max_dist[s] * stage_max_dist[s]);
         if (s > 0) hipLaunchKernelGGL(lm_reg_stage_kernel, dim3(1), dim3(64), 0, st, A);
         for (int it = 0; it < stage_max_iter[s]; ++it) {
-            hipLaunchKernelGGL(lm_accumulate_kernel, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa);
+            if (PA) hipLaunchKernelGGL(lm_accumulate_kernel<true>, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa, *PA);
+            else hipLaunchKernelGGL(lm_accumulate_kernel<false>, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa, none);
             hipLaunchKernelGGL(lm_solve_kernel, dim3(1), dim3(64), 0, st, A, tol_rot, tol_trans);
         }
     }
     return dpm_launch_status();
+}
+
+}  // namespace
+
+extern "C" int dpm_local_map_register(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                      const float *xyz, const int32_t *count, int cap, const double *init_pose,
+                                      const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages,
+                                      double kernel_scale, double tol_rot, double tol_trans, double *pose, float *fitness,
+                                      float *rmse, int32_t *iterations, int32_t *status, long long *debug_key,
+                                      int32_t *debug_sub, double *debug_system, void *workspace, dpm_stream_t stream) {
+    return register_impl(nullptr, map, cap_vox, subdiv, half, voxel, origin, xyz, count, cap, init_pose, stage_max_dist,
+                         stage_max_iter, n_stages, kernel_scale, tol_rot, tol_trans, pose, fitness, rmse, iterations, status,
+                         debug_key, debug_sub, debug_system, workspace, stream);
+}
+
+extern "C" int dpm_local_map_planes(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                    double plane_radius, float *planes, int32_t *counts, dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
+    DPM_CHECK_ARG(planes && counts && ((uintptr_t)planes & 15) == 0);
+    DPM_CHECK_ARG(plane_radius > 0.0 && plane_radius <= 1.5 * (double)(float)voxel);
+    const Map M = make_map((void *)map, cap_vox, subdiv, half, voxel, origin);
+    hipLaunchKernelGGL(lm_planes_kernel, dim3(dpm_cdiv(cap_vox, LM_BLOCK / 4)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M,
+                       (float)(plane_radius * plane_radius), (float4 *)planes, counts);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_local_map_register_planes(const void *map, int cap_vox, int subdiv, int half, double voxel,
+                                             const double *origin, const float *planes, const int32_t *counts, int min_points,
+                                             double max_ratio, const float *xyz, const int32_t *count, int cap,
+                                             const double *init_pose, const double *stage_max_dist,
+                                             const int32_t *stage_max_iter, int n_stages, double kernel_scale, double tol_rot,
+                                             double tol_trans, double *pose, float *fitness, float *rmse, int32_t *iterations,
+                                             int32_t *status, long long *debug_key, int32_t *debug_sub, double *debug_system,
+                                             void *workspace, dpm_stream_t stream) {
+    DPM_CHECK_ARG(planes && counts && ((uintptr_t)planes & 15) == 0 && min_points >= 0 && max_ratio >= 0.0 && max_ratio < 1e18);
+    const PlaneArgs PA{(const float4 *)planes, counts, min_points, (float)max_ratio};
+    return register_impl(&PA, map, cap_vox, subdiv, half, voxel, origin, xyz, count, cap, init_pose, stage_max_dist,
+                         stage_max_iter, n_stages, kernel_scale, tol_rot, tol_trans, pose, fitness, rmse, iterations, status,
+                         debug_key, debug_sub, debug_system, workspace, stream);
 }
 
 extern "C" int dpm_local_map_export(const void *map, int cap_vox, int subdiv, int half, unsigned long long *keys,

@@ -1,15 +1,17 @@
-"""A geometric LiDAR odometry on the GPU: a rolling hashed voxel map and robust point-to-point ICP of every scan against it
-(csrc/local_map.hip), in the KISS-ICP family.  The reference has no counterpart: its poses come from the learned pipeline
+"""A geometric LiDAR odometry on the GPU: a rolling hashed voxel map and robust ICP of every scan against it
+(csrc/local_map.hip), in the KISS-ICP family: point-to-point rows, or point-to-plane rows on one plane per voxel, and
+optionally KISS-ICP's adaptive gate.  The reference has no counterpart: its poses come from the learned pipeline
 only.  Here it gives the evaluation tools (evaluate.py) a system to judge, the learned pipeline a baseline, the deskew
 (augment.deskew) its motion source without ground truth, and refine.build_refined_table global poses to start from.
 
-`LocalMap` is the map: insert, prune, register, read-back.  Its content is a function of the inserted points alone
+`LocalMap` is the map: insert, prune, planes, register, read-back.  Its content is a function of the inserted points alone
 (DESIGN §7j): a sub-cell of a voxel keeps the point of the oldest frame, and within a frame of the smallest original row.
 `LidarOdometry.step` is one frame: constant-velocity prediction on the host, optional deskew with that prediction, thinning
 with augment.voxel_sample, then register -> insert -> prune queued on the device pose, and ONE read-back.
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -34,10 +36,12 @@ class LocalMap:
     subdivisions^3 sub-cells of one point each.  Coordinates are kept in fp32 relative to `origin` (three float64; default:
     the translation of the first inserted pose), so work far from the world's zero keeps fp32 accuracy.  Points are
     offered when min_range <= |p| <= max_range in the sensor frame.  A map that ran out of slots is undefined: `overflow`
-    is then non-zero and every read-back (`points`, `n_points`, `check`) raises ValueError."""
+    is then non-zero and every read-back (`points`, `n_points`, `check`, `export_planes`) raises ValueError.
+    plane_radius: a voxel's plane is fitted to the map points within this distance of its centre (default and at most
+    1.5 * voxel_size: the ball must lie inside the 27 voxels around it)."""
 
     def __init__(self, voxel_size: float = 1.0, subdivisions: int = 3, max_voxels: int = 1 << 17, max_range: float = 100.0,
-                 min_range: float = 0.0, origin=None, device=None):
+                 min_range: float = 0.0, origin=None, device=None, plane_radius: Optional[float] = None):
         if not voxel_size > 0 or subdivisions not in (1, 2, 3):
             raise ValueError("voxel_size > 0 and subdivisions in 1, 2, 3")
         if max_voxels < 2 or max_voxels > 1 << 24 or max_voxels & (max_voxels - 1):
@@ -50,6 +54,11 @@ class LocalMap:
         self.device = device
         self.table: Optional[torch.Tensor] = None
         self.half, self.stamp = 0, 0
+        self.plane_radius = 1.5 * float(np.float32(self.voxel_size)) if plane_radius is None else float(plane_radius)
+        if not 0.0 < self.plane_radius <= 1.5 * float(np.float32(self.voxel_size)):
+            raise ValueError("0 < plane_radius <= 1.5 * voxel_size (a voxel's plane looks into the 27 voxels around it)")
+        self._planes = None          # (planes, counts) of the current half, per slot: a cache derived from the map
+        self._planes_stale = True    # set by insert and prune, so the host knows without a read
 
     # -- plumbing
     def _ready(self, dev, pose=None):
@@ -78,6 +87,7 @@ class LocalMap:
         ops.local_map_insert(*self._args(), pcd.xyz, pcd.idx, pcd.count, _pose_tensor(pose, self.device), self.stamp,
                              self.min_range, self.max_range)
         self.stamp += 1
+        self._planes_stale = True
         return self
 
     def prune(self, pose, radius: Optional[float] = None):
@@ -85,17 +95,40 @@ class LocalMap:
         self._ready(self.device if self.device is not None else augment._device(), pose)
         ops.local_map_prune(*self._args(), _pose_tensor(pose, self.device), self.max_range if radius is None else float(radius))
         self.half = 1 - self.half
+        self._planes_stale = True
         return self
 
+    def planes(self):
+        """(planes (max_voxels,4) float32 (normal, w), counts (max_voxels,) int32) on the device, per SLOT of the current
+        half: one plane per held voxel (csrc/local_map.hip), w = smallest / middle eigenvalue, -1 where no plane is defined.
+        Recomputed in one launch when the map has changed since the last call; the tensors are reused."""
+        self._ready(self.device if self.device is not None else augment._device())
+        if self._planes_stale or self._planes is None:
+            self._planes = ops.local_map_planes(*self._args(), self.plane_radius, *(self._planes or (None, None)))
+            self._planes_stale = False
+        return self._planes
+
     def register(self, pcd, init, schedule: Sequence[Tuple[float, int]] = ((1.0, 30),), kernel_scale: float = 0.0,
-                 tol_rot: float = 1e-7, tol_trans: float = 1e-6, debug: bool = False):
+                 tol_rot: float = 1e-7, tol_trans: float = 1e-6, debug: bool = False, metric: str = "point",
+                 min_points: int = 5, max_ratio: float = 0.1):
         """ICP of the frame against the map from `init` (4,4) over schedule = [(max_dist <= voxel_size, max_iter), ...] ->
-        refine.IcpResult with one problem (pose (1,4,4) float64, ...), all on the device[, (key, sub, system) with debug]"""
+        refine.IcpResult with one problem (pose (1,4,4) float64, ...), all on the device[, (key, sub, system) with debug].
+        metric "point": point-to-point rows.  "plane": the row of a match is its distance along the plane of the matched
+        point's voxel (`planes()`), given only when that plane rests on >= min_points points and is flat, 0 <= w <= max_ratio;
+        other matches give nothing, and debug's key and sub are -1 for them."""
+        if metric not in ("point", "plane"):
+            raise ValueError("metric is 'point' or 'plane'")
         if any(float(d) > float(np.float32(self.voxel_size)) for d, _ in schedule):
             raise ValueError("register: every max_dist of the schedule must be <= voxel_size (the search looks into 27 voxels)")
         self._ready(pcd.device, init)
-        out = ops.local_map_register(*self._args(), pcd.xyz, pcd.count, _pose_tensor(init, self.device), schedule, kernel_scale,
-                                     tol_rot, tol_trans, debug=debug)
+        if metric == "plane":
+            planes, counts = self.planes()
+            out = ops.local_map_register_planes(*self._args(), planes, counts, min_points, max_ratio, pcd.xyz, pcd.count,
+                                                _pose_tensor(init, self.device), schedule, kernel_scale, tol_rot, tol_trans,
+                                                debug=debug)
+        else:
+            out = ops.local_map_register(*self._args(), pcd.xyz, pcd.count, _pose_tensor(init, self.device), schedule,
+                                         kernel_scale, tol_rot, tol_trans, debug=debug)
         res = IcpResult(out[0].reshape(1, 4, 4), *out[1:5])
         return (res, out[5:]) if debug else res
 
@@ -138,6 +171,47 @@ class LocalMap:
         xyz = self.export()[3]
         return xyz.astype(np.float64) + (self.origin if self.origin is not None else 0.0)
 
+    def export_planes(self):
+        """(key (m,) int64, count (m,) int32, normal (m,3) float32, w (m,) float32) numpy of the held voxels, sorted by key:
+        the same bytes whatever the order the points arrived in and whichever slots the voxels sit in"""
+        if self.table is None:
+            return np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros((0, 3), np.float32), np.zeros(0, np.float32)
+        self.check()
+        planes, counts = self.planes()
+        S = self.subdivisions ** 3
+        at = 256 + self.half * (self.max_voxels * 8 + self.max_voxels * S * 24)
+        augment._SYNCS[0] += 3
+        keys = self.table[at:at + 8 * self.max_voxels].view(torch.int64).cpu().numpy()
+        planes, counts = planes.cpu().numpy(), counts.cpu().numpy()
+        held = np.nonzero(keys != -1)[0]
+        held = held[np.argsort(keys[held], kind="stable")]
+        return keys[held], counts[held], planes[held, :3].copy(), planes[held, 3].copy()
+
+
+def adaptive_sigma(deviations, sigma0: float, min_motion: float = 0.0) -> float:
+    """KISS-ICP's adaptive threshold: sqrt(mean d^2) over the deviations d > min_motion (metres; how far the registered pose
+    lay from the predicted one), `sigma0` while there is none"""
+    d = [float(x) for x in deviations if float(x) > min_motion]
+    if not d:
+        return float(sigma0)
+    return math.sqrt(sum(x * x for x in d) / len(d))
+
+
+def prediction_deviation(pred, pose, max_range: float) -> float:
+    """delta = |t| + 2 max_range sin(theta / 2) of pred^-1 pose (4,4 float64): how far a point at max_range is moved by the
+    error of the prediction"""
+    D = np.linalg.inv(np.asarray(pred, np.float64)) @ np.asarray(pose, np.float64)
+    R = D[:3, :3]     # sin and cos of the angle, so that a small one is not lost in an arc cosine near 1
+    theta = math.atan2(0.5 * math.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2 + (R[1, 0] - R[0, 1]) ** 2),
+                       (float(np.trace(R)) - 1.0) / 2.0)
+    return float(np.linalg.norm(D[:3, 3])) + 2.0 * float(max_range) * math.sin(theta / 2.0)
+
+
+def adaptive_stage(sigma: float, voxel_size: float, max_iter: int):
+    """((max_dist, max_iter), kernel_scale) of a step whose threshold is sigma: the gate 3 sigma, clipped at voxel_size (as
+    fp32, the search's own bound: it looks into 27 voxels), and the Geman-McClure scale sigma / 3"""
+    return (min(3.0 * float(sigma), float(np.float32(voxel_size))), int(max_iter)), float(sigma) / 3.0
+
 
 class OdometryStep(NamedTuple):
     pose: np.ndarray          # (4,4) float64, sensor -> world
@@ -162,9 +236,15 @@ class LidarOdometry:
     there.  sample_map / sample_register: augment.voxel_sample edges for the points that are inserted and, thinned once
     more, for the points that are registered; None or 0 leaves the frame as it is.  first_pose: the first frame's pose
     (default identity).  initial_motion (4,4): the motion assumed between the first two frames, where constant velocity has
-    nothing to extrapolate (default: none) -- from the vehicle's speed, say.  A sparse sensor over flat ground needs it: the
-    rings a scan draws on the ground travel with the sensor, so a second frame started one metre off settles on "no motion"
-    (profiles/sim_odometry_eval.md).
+    nothing to extrapolate (default: none) -- from the vehicle's speed, say.  A sparse sensor over flat ground needs it with
+    metric "point": the rings a scan draws on the ground travel with the sensor, so a second frame started one metre off
+    settles on "no motion" (profiles/sim_odometry_eval.md).  metric "plane": point-to-plane rows on one plane per voxel
+    (LocalMap.planes; plane_radius, min_points, max_ratio as in LocalMap.register) -- a ground point then has no say about
+    motion inside the ground plane; one more launch a step.  adaptive = (sigma0, min_motion): instead of `schedule` and
+    `kernel_scale` every step registers with ONE stage (min(3 sigma, voxel_size), max_iter of the schedule's last stage) and
+    kernel_scale sigma / 3, sigma = adaptive_sigma of the deviations between predicted and registered pose so far (those above
+    min_motion; sigma0 before there is one).  The gate is clipped at voxel_size because the search looks into 27 voxels.
+    `gates` lists (schedule, kernel_scale) of every registered step.
 
     One host synchronisation per step, counted in augment.host_syncs(): the read-back of the pose, the registration's
     results and the device-side error flags together.  The caller's frame keeps its bytes: the work is done on a copy."""
@@ -173,12 +253,21 @@ class LidarOdometry:
                  schedule: Sequence[Tuple[float, int]] = ((1.0, 30),), kernel_scale: float = 0.1, deskew: bool = False,
                  time: str = "column", azimuth_steps: Optional[int] = None, sample_map: Optional[float] = None,
                  sample_register: Optional[float] = None, max_voxels: int = 1 << 17, first_pose=None, initial_motion=None,
-                 tol_rot: float = 1e-7, tol_trans: float = 1e-6):
+                 tol_rot: float = 1e-7, tol_trans: float = 1e-6, metric: str = "point", plane_radius: Optional[float] = None,
+                 min_points: int = 5, max_ratio: float = 0.1, adaptive: Optional[Tuple[float, float]] = None):
         if time not in ("column", "azimuth"):
             raise ValueError("time is 'column' or 'azimuth'")
+        if metric not in ("point", "plane"):
+            raise ValueError("metric is 'point' or 'plane'")
+        if adaptive is not None and not (len(adaptive) == 2 and adaptive[0] > 0 and adaptive[1] >= 0):
+            raise ValueError("adaptive: (sigma0 > 0, min_motion >= 0)")
         if deskew and time == "column" and not azimuth_steps:
             raise ValueError("deskew with time='column' needs azimuth_steps")
-        self.local_map = LocalMap(voxel_size, subdivisions, max_voxels, max_range, min_range)
+        self.local_map = LocalMap(voxel_size, subdivisions, max_voxels, max_range, min_range, plane_radius=plane_radius)
+        self.metric, self.min_points, self.max_ratio = metric, int(min_points), float(max_ratio)
+        self.adaptive = None if adaptive is None else (float(adaptive[0]), float(adaptive[1]))
+        self.deviations: list = []   # the prediction's error at every registered step (adaptive gate)
+        self.gates: list = []        # (schedule, kernel_scale) of every registered step
         self.schedule = [(float(d), int(n)) for d, n in schedule]
         if not self.schedule or any(d > float(np.float32(voxel_size)) or d <= 0 for d, _ in self.schedule):
             raise ValueError("schedule: stages (max_dist, max_iter) with 0 < max_dist <= voxel_size")
@@ -201,6 +290,15 @@ class LidarOdometry:
         if not self.poses:
             return self.first_pose.copy()
         return self.poses[-1] @ self.predicted_motion()
+
+    def gate(self):
+        """((max_dist, max_iter), ...) and kernel_scale of the next registration: the schedule and scale given, or with
+        `adaptive` the one stage that follows from the deviations so far"""
+        if self.adaptive is None:
+            return self.schedule, self.kernel_scale
+        sigma = adaptive_sigma(self.deviations, *self.adaptive)
+        stage, scale = adaptive_stage(sigma, self.local_map.voxel_size, self.schedule[-1][1])
+        return [stage], scale
 
     def step(self, pcd) -> OdometryStep:
         dev = pcd.device
@@ -228,7 +326,13 @@ class LidarOdometry:
                     reg = augment.voxel_sample(_copy(work), self.sample_register)
                     flags += [st[1:2] for st, _ in reg._flags]      # the copy starts without flags
                     messages += [msg for _, msg in reg._flags]
-                res = lm.register(reg, pred, self.schedule, self.kernel_scale, self.tol_rot, self.tol_trans)
+                schedule, kernel_scale = self.gate()
+                self.gates.append((tuple(schedule), kernel_scale))
+                if self.metric == "point":
+                    res = lm.register(reg, pred, schedule, kernel_scale, self.tol_rot, self.tol_trans)
+                else:
+                    res = lm.register(reg, pred, schedule, kernel_scale, self.tol_rot, self.tol_trans, metric=self.metric,
+                                      min_points=self.min_points, max_ratio=self.max_ratio)
                 # a failed registration (NO_MATCH, SINGULAR: possibly after steps that led nowhere) keeps the prediction, and
                 # its frame must not enter the map: pose and count are chosen on the device, so insert and prune still
                 # queue without a host read
@@ -256,6 +360,8 @@ class LidarOdometry:
             U, _, Vt = np.linalg.svd(pose[:3, :3])
             pose[:3, :3] = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt))]) @ Vt
         out = OdometryStep(pose, float(host[16]), float(host[17]), int(host[18]), int(host[19]))
+        if not first and out.status in (CONVERGED, MAX_ITER):
+            self.deviations.append(prediction_deviation(pred, pose, lm.max_range))
         self.poses.append(out.pose)
         self.steps.append(out)
         return out

@@ -2216,8 +2216,36 @@ def local_map_prune(table, cap_vox, subdiv, half, voxel, origin, pose, radius):
                                                    _ptr(pose), float(radius), _stream(table)), "dpm_local_map_prune")
 
 
+def local_map_planes(table, cap_vox, subdiv, half, voxel, origin, plane_radius, planes=None, counts=None):
+    """dpm_local_map_planes -> (planes (cap_vox,4) fp32 (normal, w), counts (cap_vox,) int32) per SLOT of half `half`, written
+    into the given buffers or new ones.  One launch, no host synchronisation, capturable in a graph."""
+    o = _local_map_args(table, cap_vox, subdiv, origin)
+    dev = table.device
+    with torch.cuda.device(dev):
+        planes = torch.empty(int(cap_vox), 4, device=dev, dtype=torch.float32) if planes is None else planes
+        counts = torch.empty(int(cap_vox), device=dev, dtype=torch.int32) if counts is None else counts
+        _chk(planes, torch.float32, "planes"), _chk(counts, torch.int32, "counts")
+        if tuple(planes.shape) != (int(cap_vox), 4) or tuple(counts.shape) != (int(cap_vox),):
+            raise ValueError("local_map_planes: planes (cap_vox,4), counts (cap_vox,)")
+        _lib.check(_lib.load().dpm_local_map_planes(_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel),
+                                                    ctypes.addressof(o), float(plane_radius), _ptr(planes), _ptr(counts),
+                                                    _stream(table)), "dpm_local_map_planes")
+    return planes, counts
+
+
+def local_map_register_planes(table, cap_vox, subdiv, half, voxel, origin, planes, counts, min_points, max_ratio, xyz, count,
+                              init, schedule, kernel_scale=0.0, tol_rot=1e-7, tol_trans=1e-6, debug=False):
+    """dpm_local_map_register_planes: local_map_register with point-to-plane rows on the planes / counts local_map_planes
+    wrote for this map and half; key and sub of debug are -1 where the match gave no row"""
+    _chk(planes, torch.float32, "planes"), _chk(counts, torch.int32, "counts")
+    if tuple(planes.shape) != (int(cap_vox), 4) or tuple(counts.shape) != (int(cap_vox),):
+        raise ValueError("local_map_register_planes: planes (cap_vox,4), counts (cap_vox,)")
+    return local_map_register(table, cap_vox, subdiv, half, voxel, origin, xyz, count, init, schedule, kernel_scale, tol_rot,
+                              tol_trans, debug, _plane=(planes, counts, int(min_points), float(max_ratio)))
+
+
 def local_map_register(table, cap_vox, subdiv, half, voxel, origin, xyz, count, init, schedule, kernel_scale=0.0,
-                       tol_rot=1e-7, tol_trans=1e-6, debug=False):
+                       tol_rot=1e-7, tol_trans=1e-6, debug=False, _plane=None):
     """dpm_local_map_register: xyz (cap,3) fp32, count (1,) int32, init (4,4) fp64 on the GPU; schedule = [(max_dist, max_iter),
     ...] with every max_dist <= voxel -> pose (4,4) fp64, fitness, rmse (1,) fp32, iterations, status (1,) int32[, key (cap,)
     int64, sub (cap,) int32, system (29,) fp64 with debug].  No host synchronisation, capturable in a graph."""
@@ -2241,11 +2269,16 @@ def local_map_register(table, cap_vox, subdiv, half, voxel, origin, xyz, count, 
         sub = torch.full((cap,), -1, device=dev, dtype=torch.int32) if debug else None
         system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
         ws = torch.empty(512 + 256 * ((cap + 255) // 256), device=dev, dtype=torch.uint8)
-        _lib.check(_lib.load().dpm_local_map_register(
-            _ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(count), cap,
-            _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), len(stages), float(kernel_scale), float(tol_rot),
-            float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations), _ptr(status), _ptr(key), _ptr(sub),
-            _ptr(system), _ptr(ws), _stream(table)), "dpm_local_map_register")
+        head = (_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o))
+        tail = (_ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), len(stages),
+                float(kernel_scale), float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations),
+                _ptr(status), _ptr(key), _ptr(sub), _ptr(system), _ptr(ws), _stream(table))
+        if _plane is None:
+            _lib.check(_lib.load().dpm_local_map_register(*head, *tail), "dpm_local_map_register")
+        else:
+            planes, counts, min_points, max_ratio = _plane
+            _lib.check(_lib.load().dpm_local_map_register_planes(*head, _ptr(planes), _ptr(counts), min_points, max_ratio, *tail),
+                       "dpm_local_map_register_planes")
     out = (pose, fitness, rmse, iterations, status)
     return out + (key, sub, system) if debug else out
 

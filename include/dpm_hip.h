@@ -1040,6 +1040,33 @@ int dpm_local_map_register(const void *map, int cap_vox, int subdiv, int half, d
  * (the rest is not written; max_out = 0 only counts). */
 int dpm_local_map_export(const void *map, int cap_vox, int subdiv, int half, unsigned long long *keys, int32_t *sub,
                          unsigned long long *owner, float *xyz, int32_t *count, int max_out, dpm_stream_t stream);
+/* One plane per held voxel of half `half`, a cache derived from the map in caller-owned buffers indexed by SLOT: planes
+ * (cap_vox,4) fp32 (nx, ny, nz, w), 16-byte aligned, and counts (cap_vox,) int32.  One launch, capturable.  The voxel's centre
+ * is c = ((float)voxel_index + 0.5f) * voxel per axis; its members are the occupied sub-cell points p of the 27 voxels around
+ * it with d = p - c (fp32) and (dx*dx + dy*dy) + dz*dz <= (float)(plane_radius^2); 0 < plane_radius <= 1.5 voxel, so the ball
+ * lies inside those voxels (a point exactly 1.5 voxel from c along +x, +y or +z lies on the far face of a neighbour and so
+ * in the voxel after it: not a member).  counts = the number of members.  The ten cumulants of d are summed in fp64 in an order fixed by
+ * the geometry (neighbour number as in dpm_local_map_register, then sub-cell), the scatter matrix n S_ab - S_a S_b (the
+ * covariance times n^2) is diagonalised by cyclic Jacobi in fp64, the eigenvalues l0 <= l1 <= l2 ordered with the smaller
+ * axis first among equals.  The normal is the unit eigenvector of l0 rounded to fp32, signed so that its component of
+ * largest magnitude (the first axis among equal fp32 magnitudes) is positive; w = (float)(max(l0, 0) / l1), the flatness.
+ * counts < 3, or l1 <= 1e-8 l2 -- a line to the precision fp32 coordinates have, which includes l1 <= 0; its "normal" would
+ * be rounding noise --: (0, 0, 0, -1).  A slot without a voxel: (0, 0, 0, -1) and count 0.  A voxel's plane is a function of
+ * the map's content alone, not of slot positions or arrival order.  The buffers are stale after any insert or prune. */
+int dpm_local_map_planes(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                         double plane_radius, float *planes, int32_t *counts, dpm_stream_t stream);
+/* dpm_local_map_register with point-to-plane rows: the same search, tie-break, schedule, solve, statuses and workspace.
+ * planes / counts: what dpm_local_map_planes wrote for this map and half.  The matched point's voxel gives a row only when
+ * counts >= min_points and 0 <= w <= (float)max_ratio: e = (nx*ex + ny*ey) + nz*ez with (ex, ey, ez) = query - match,
+ * J = (p x n, n) as DPM_ICP_PLANE, weighted (k / (k + e*e))^2 with k = kernel_scale^2.  A match whose voxel has no such plane
+ * contributes nothing: the match count (fitness, rmse, NO_MATCH) counts rows, and debug_key / debug_sub are -1 for it. */
+int dpm_local_map_register_planes(const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                  const float *planes, const int32_t *counts, int min_points, double max_ratio,
+                                  const float *xyz, const int32_t *count, int cap, const double *init_pose,
+                                  const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages,
+                                  double kernel_scale, double tol_rot, double tol_trans, double *pose, float *fitness,
+                                  float *rmse, int32_t *iterations, int32_t *status, long long *debug_key, int32_t *debug_sub,
+                                  double *debug_system, void *workspace, dpm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,9 @@
 lidar_sim.street_scene(2), 64 beams x 2048 columns, one metre apart.
   insert           claim + commit of the first frame into an empty map (the init that empties it is timed apart)
   prune            the clear of the other half + the re-claim, everything surviving
-  per iteration    (register with --iters iterations and the stop rule off - register with none) / iters: accumulate + solve
+  planes           one plane per voxel over ALL slots of the table (dpm_local_map_planes), the map holding the first frame
+  per iteration    (register with --iters iterations and the stop rule off - register with none) / iters: accumulate + solve,
+                   with point rows and with plane rows
   register         a default run of the second frame (30 iterations at most) from a start 0.1 m off
   step             LidarOdometry.step of the second frame, host time around the call: its one synchronisation included
   batched ICP      dpm_icp_refine_batched, point metric, on the same frame pair and start: grids and per iteration
@@ -64,6 +66,17 @@ def main():
     none = timed(lambda: m.register(frames[1], P[2], [(1.0, 0)]), a.reps, a.warmup)
     t = timed(lambda: m.register(frames[1], P[2], [(1.0, a.iters)], kernel_scale=0.1, tol_rot=0.0, tol_trans=0.0), a.reps, a.warmup)
     rows.append((f"register, {a.iters} iterations, stop rule off, {n[1]} points", t, (t[0] - none[0]) / a.iters))
+    point_iter = (t[0] - none[0]) / a.iters
+    planes_t = timed(lambda: ops.local_map_planes(*m._args(), m.plane_radius, *m.planes()), a.reps, a.warmup)
+    rows.append((f"planes, all {m.max_voxels} slots, {held} points held (one launch)", planes_t, None))
+    counts, w = m.planes()[1], m.planes()[0][:, 3]
+    n_vox, n_flat = int((counts > 0).sum()), int(((counts >= 5) & (w >= 0) & (w <= 0.1)).sum())
+    none_p = timed(lambda: m.register(frames[1], P[2], [(1.0, 0)], metric="plane"), a.reps, a.warmup)
+    t = timed(lambda: m.register(frames[1], P[2], [(1.0, a.iters)], kernel_scale=0.1, tol_rot=0.0, tol_trans=0.0, metric="plane"),
+              a.reps, a.warmup)
+    rows.append((f"register with plane rows, {a.iters} iterations, stop rule off (planes cached)", t, (t[0] - none_p[0]) / a.iters))
+    res_p = m.register(frames[1], P[2], [(1.0, 30)], kernel_scale=0.1, metric="plane")
+    err_p = float(np.linalg.norm(res_p.pose[0].cpu().numpy()[:3, 3] - poses[1][:3, 3]))
     res = m.register(frames[1], P[2], [(1.0, 30)], kernel_scale=0.1)
     rows.append(("register, default run (30 iterations at most)", timed(lambda: m.register(frames[1], P[2], [(1.0, 30)], kernel_scale=0.1),
                                                                    a.reps, a.warmup), None))
@@ -105,6 +118,11 @@ def main():
         f.write(f"\nDefault run: {int(res.iterations)} iterations, status {int(res.status)}, fitness {float(res.fitness):.3f}, refined "
                 f"translation {err:.4f} m from the exact pose (start 0.1 m off); the step took {s.iterations} iterations.  init and "
                 "prune write every key and owner word of a half (28 words a slot here) whatever the map holds.\n"
+                f"Plane rows: {n_vox} voxels held, {n_flat} of them give rows (>= 5 points, w <= 0.1); default run "
+                f"{int(res_p.iterations)} iterations, status {int(res_p.status)}, fitness {float(res_p.fitness):.3f}, refined translation "
+                f"{err_p:.4f} m from the exact pose.  The planes launch over all slots costs {planes_t[0] / point_iter:.2f} point "
+                "iterations" + (": more than one, and it is paid once a step; recomputing only the voxels whose 27-neighbourhood an "
+                                "insert or a prune changed is the next step.\n" if planes_t[0] > point_iter else ".\n") +
                 "Not run: hardware counters of the new kernels; other sensor sizes; the batched ICP with more than one pair.\n")
     print(open(os.path.join(ROOT, "profiles", "lidar_odometry_bench.md")).read())
 

@@ -2,7 +2,8 @@
   raw        the frames as a moving sensor takes them
   predicted  deskewed by the odometry's own constant-velocity prediction (LidarOdometry(deskew=True))
   true       deskewed with the motion the simulator used (the frames' sweep_motion) before the odometry sees them
-and, next to them, the same circuit without sweep motion.  For each: ATE, RPE and KITTI segment errors against the exact
+and, next to them, the same circuit without sweep motion, there also with point-to-plane rows (metric="plane") and with the
+adaptive gate on top (adaptive=(spacing, 0.1)).  For each: ATE, RPE and KITTI segment errors against the exact
 poses (evaluate.trajectory_metrics) and map_accuracy of the odometry's own map, the points it holds at the end under the poses
 it estimated, against the scene.  The motion between the first two frames is given to every run (initial_motion): see
 LidarOdometry's docstring.  --no-initial-motion adds the run without it.  A report, not a target: nothing is asserted.
@@ -28,9 +29,10 @@ def accuracy_md():
         return False
     lines = list(dict.fromkeys(open(src).read().splitlines()))
     with open(os.path.join(ROOT, "profiles", "lidar_odometry_accuracy.md"), "w") as f:
-        f.write("# Local map and geometric odometry: observed errors\n\nEvery comparison tests/test_gpu_local_map.py and "
-                "tests/test_gpu_lidar_odometry.py made on the GPU, as they logged it; the bounds are derived in those files.  "
-                "`r32` / `r64`: the numpy restatement (tests/lidar_odometry_restated.py) in float32 and float64.  The reference "
+        f.write("# Local map and geometric odometry: observed errors\n\nEvery comparison tests/test_gpu_local_map.py, "
+                "tests/test_gpu_lidar_odometry.py, tests/test_gpu_local_map_planes.py and tests/test_gpu_lidar_odometry_plane.py made "
+                "on the GPU, as they logged it; the bounds are derived in those files.  `r32` / `r64`: the numpy restatement "
+                "(tests/lidar_odometry_restated.py, tests/lidar_plane_restated.py) in float32 and float64.  The reference "
                 "has no geometric odometry: there is nothing else to compare with.\n\n```\n")
         f.write("\n".join(lines) + "\n```\n")
     return True
@@ -88,8 +90,17 @@ def main():
         azimuth_steps=model.azimuth_steps)
     run("sweep motion, deskewed with the true motion",
         [augment.deskew(f, f.sweep_motion, time="column", azimuth_steps=model.azimuth_steps) for f in sim.frames(P0, poses_end=P1)])
+    # point-to-plane rows, and with them the adaptive gate (sigma0 = the spacing, min_motion 0.1 m: KISS-ICP's defaults scaled)
+    adaptive = (a.spacing, 0.1)
+    run("no sweep motion, plane", sim.frames(poses), metric="plane")
+    run("no sweep motion, plane + adaptive", sim.frames(poses), metric="plane", adaptive=adaptive)
+    run("sweep motion, deskewed by the own prediction, plane + adaptive", sim.frames(P0, poses_end=P1), deskew=True, time="column",
+        azimuth_steps=model.azimuth_steps, metric="plane", adaptive=adaptive)
     if a.no_initial_motion:
         run("no sweep motion, initial_motion not given", sim.frames(poses), initial_motion=None)
+        run("no sweep motion, plane, initial_motion not given", sim.frames(poses), initial_motion=None, metric="plane")
+        run("no sweep motion, plane + adaptive, initial_motion not given", sim.frames(poses), initial_motion=None, metric="plane",
+            adaptive=adaptive)
 
     def num(d, k, fmt="{:.4f}"):
         return "-" if not d or d.get(k) is None else fmt.format(d[k])
@@ -98,7 +109,8 @@ def main():
         f.write(f"`python scripts/sim_odometry_eval.py --frames {a.frames} --spacing {a.spacing} --beams {a.beams} --columns {a.columns} "
                 f"--sigma {a.sigma}{' --no-initial-motion' if a.no_initial_motion else ''}` on {torch.cuda.get_device_name(0)}: lidar_sim.street_scene(2), {F} poses of its circuit "
                 f"{a.spacing} m apart, {a.beams} beams x {a.columns} columns, range noise {a.sigma} m; LidarOdometry with its defaults, "
-                "sample_map 0.25 m, sample_register 0.75 m, the first motion given.  A report, not a target.\n\n"
+                "sample_map 0.25 m, sample_register 0.75 m, the first motion given unless the row says otherwise; `plane`: "
+                f"metric=\"plane\", `adaptive`: adaptive=({a.spacing}, 0.1).  A report, not a target.\n\n"
                 "| input | ATE rmse m | ATE max m | RPE trans rmse m | RPE rot rmse rad | KITTI t % | KITTI r deg/m | failed steps | "
                 "map points | map mean dist m | map rmse m |\n|---|---|---|---|---|---|---|---|---|---|---|\n")
         for name, m, acc, bad, n in rows:
