@@ -45,6 +45,15 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// splitmix64 finaliser: where a key of the voxel hash tables (voxel_map.hip, local_map.hip) starts probing
+__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {
+    k ^= k >> 30;
+    k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27;
+    k *= 0x94d049bb133111ebull;
+    return k ^ (k >> 31);
+}
+
 // ---- exact three-way bf16 split of an fp32 value (csrc/gemm_b3.hip says what it is for): x = hi + mid + lo, each term a
 // truncation to the top 16 bits of a float, each remainder exact.  hi / mid come back masked, lo unmasked (its truncation
 // happens where the term is stored: pack2 / a 16-bit store of the upper half).

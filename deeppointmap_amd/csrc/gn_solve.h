@@ -1,13 +1,119 @@
-// The Gauss-Newton step of the registration kernels (icp.hip, local_map.hip), run by ONE lane on the 29 summed values
-// S = [H upper triangle row-major (21), g (6), matches, sum of squared residuals]:  fitness and rmse, H x = -g by Cholesky
-// with a pivot test, the step x = (w, v) composed onto the pose as pose <- [exp(w) | v] o pose (Rodrigues rotation, the
-// translation taken as it is), the stop rule and the status.  No match: NO_MATCH; a system that cannot be solved, or a
-// step / pose that is no number: SINGULAR -- both leave the pose at its last good value and set *done.  Everything fp64.
+// The Gauss-Newton step of the two registrations (icp.hip: batched scan pairs; local_map.hip: a scan against the rolling map),
+// written once.  The accumulate kernels keep their searches; what follows the match is here, and its order of operations is
+// part of the contract (the tests compare bytes and fp64 floors):
+//   the search pose: the fp64 pose minus an origin, rounded to fp32, and q = fma(R2, z, fma(R1, y, R0 * x)) + t;
+//   the rows of a match into the 29 fp64 sums S = [H upper triangle row-major (21), g (6), matches, sum of squared residuals]:
+//     H and g weighted (Geman-McClure), the count (the caller's s[27] += 1.0) and the squared residuals not;
+//   the block reduction, lanes then waves in a fixed tree, and the solve kernels' sum of the blocks' partials in block order:
+//     the sums do not depend on scheduling, no floating-point atomics;
+//   gn_solve_step, run by ONE lane on S: fitness and rmse, H x = -g by Cholesky with a pivot test, the step x = (w, v) composed
+//     onto the pose as pose <- [exp(w) | v] o pose (Rodrigues rotation, the translation taken as it is), the stop rule and the
+//     status.  No match: NO_MATCH; a system that cannot be solved, or a step / pose that is no number: SINGULAR -- both leave
+//     the pose at its last good value and set *done;
+//   the start values of a problem.
 #pragma once
 #include "dpm_common.h"
 
-constexpr int GN_NSUM = 29;
+constexpr int GN_NSUM = 29, GN_NSUM_PAD = 32;
 constexpr double GN_PIV_EPS = 1e-9;  // a Cholesky pivot below GN_PIV_EPS * (largest diagonal entry of its 3x3 block) is singular
+
+// the fp32 pose the searches run with: 9 rotation entries row-major, then the translation minus the origin, the difference
+// formed in fp64 and rounded once.  (icp_accumulate_kernel writes the same arithmetic out, with no origin.)
+struct GnPose32 {
+    float R[9], t[3];
+};
+
+__device__ __forceinline__ GnPose32 gn_load_pose(const double *pose, double ox, double oy, double oz) {
+    GnPose32 P;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) P.R[3 * i + j] = (float)pose[4 * i + j];
+    P.t[0] = (float)(pose[3] - ox), P.t[1] = (float)(pose[7] - oy), P.t[2] = (float)(pose[11] - oz);
+    return P;
+}
+
+__device__ __forceinline__ void gn_xform(const GnPose32 &P, float x, float y, float z, float q[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = fmaf(P.R[3 * a + 2], z, fmaf(P.R[3 * a + 1], y, P.R[3 * a] * x)) + P.t[a];
+}
+
+// one row J (6) with residual e and weight w: H += w J^T J, g += w J^T e, squared residuals += e e  (w = 1.0 folds away)
+__device__ __forceinline__ void gn_add_row(double (&s)[GN_NSUM], const double (&J)[6], double e, double w) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const double wj = w * J[i];
+#pragma unroll
+        for (int j = i; j < 6; ++j) s[k] = fma(wj, J[j], s[k]), ++k;
+        s[21 + i] = fma(wj, e, s[21 + i]);
+    }
+    s[28] = fma(e, e, s[28]);
+}
+
+// Geman-McClure weight of a match with squared residual E; kappa = kernel_scale^2, 0: unweighted
+__device__ __forceinline__ double gn_weight(double kappa, double E) {
+    if (!(kappa > 0.0)) return 1.0;
+    const double r = kappa / (kappa + E);
+    return r * r;
+}
+
+// point-to-point: the three rows of the moved point p with residual e = p - target
+__device__ __forceinline__ void gn_point_rows(double (&s)[GN_NSUM], const double (&p)[3], const double (&e)[3], double w) {
+    const double Jx[6] = {0.0, p[2], -p[1], 1.0, 0.0, 0.0}, Jy[6] = {-p[2], 0.0, p[0], 0.0, 1.0, 0.0},
+                 Jz[6] = {p[1], -p[0], 0.0, 0.0, 0.0, 1.0};
+    gn_add_row(s, Jx, e[0], w), gn_add_row(s, Jy, e[1], w), gn_add_row(s, Jz, e[2], w);
+}
+
+// point-to-plane: the row J = (p x n, n) with residual n . e, weighted by that residual
+__device__ __forceinline__ void gn_plane_row(double (&s)[GN_NSUM], const double (&p)[3], const double (&n)[3],
+                                             const double (&e)[3], double kappa) {
+    const double r = (n[0] * e[0] + n[1] * e[1]) + n[2] * e[2];
+    const double J[6] = {p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0], n[0], n[1], n[2]};
+    gn_add_row(s, J, r, gn_weight(kappa, r * r));
+}
+
+// the sums of a block of 256 threads -> partial[blk * GN_NSUM_PAD + k]; lanes 1..3 of a quad hold zeros; all threads call it
+__device__ __forceinline__ void gn_block_reduce(const double (&s)[GN_NSUM], double *partial, int blk) {
+    __shared__ double sred[4][GN_NSUM];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < GN_NSUM; ++k) {
+        double v = s[k];
+#pragma unroll
+        for (int off = 32; off >= 4; off >>= 1) v += __shfl_xor(v, off, 64);
+        if (lane == 0) sred[w][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < GN_NSUM)
+        partial[(size_t)blk * GN_NSUM_PAD + threadIdx.x] =
+            (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
+}
+
+// the head of a solve kernel (one wave): S (in LDS) = the partials of blocks 0 .. nblk-1 added in that order, and row k of dbg_system
+__device__ __forceinline__ void gn_sum_partials(const double *partial, int nblk, double *S, double *dbg_system, size_t k) {
+    const int lane = threadIdx.x;
+    if (lane < GN_NSUM) {
+        double v = 0.0;
+        for (int b = 0; b < nblk; ++b) v += partial[(size_t)b * GN_NSUM_PAD + lane];
+        S[lane] = v;
+        if (dbg_system) dbg_system[k * GN_NSUM + lane] = v;
+    }
+    __syncthreads();
+}
+
+// problem k of a batch to its start values: pose <- init with the last row 0 0 0 1, the results; gn_zero_system: its debug row
+__device__ __forceinline__ void gn_init_problem(size_t k, const double *init, double *pose, float *fitness, float *rmse,
+                                                int32_t *iterations, int32_t *status) {
+    for (int i = 0; i < 12; ++i) pose[k * 16 + i] = init[k * 16 + i];
+    pose[k * 16 + 12] = 0.0, pose[k * 16 + 13] = 0.0, pose[k * 16 + 14] = 0.0, pose[k * 16 + 15] = 1.0;
+    fitness[k] = 0.f, rmse[k] = 0.f, iterations[k] = 0, status[k] = DPM_ICP_MAX_ITER;
+}
+
+__device__ __forceinline__ void gn_zero_system(size_t k, double *dbg_system) {
+    if (dbg_system)
+        for (int i = 0; i < GN_NSUM; ++i) dbg_system[k * GN_NSUM + i] = 0.0;
+}
 
 __device__ __forceinline__ bool finite_d(double v) { return fabs(v) < 1e300; }   // false for Inf and NaN
 

@@ -10,13 +10,12 @@
 // Per iteration, two launches for all pairs together and no host synchronisation:
 //   accumulate: four lanes per source point scan the cells around the transformed point; the winner is the smallest
 //               (distance bits, original index) key, as in nn1_match_kernel.  Lane 0 of the quad adds the match's
-//               Gauss-Newton rows to 29 fp64 running sums (21 of H, 6 of g, count, squared residuals).  Queries are walked
-//               in INDEX order, the lanes / waves of a block are summed in a fixed tree and every block leaves one partial:
-//               the sums do not depend on scheduling.  No floating-point atomics.
-//   solve:      one wave per pair adds the partials in block order, solves H x = -g by Cholesky with a pivot test, composes
-//               the step onto the pose and sets the pair's `done` flag; blocks of a done pair return at once.
-// The step x = (w, v) moves a transformed point p' to p' + w x p' + v; it is applied as pose <- [exp(w) | v] o pose
-// (Rodrigues rotation, the translation taken as it is).
+//               Gauss-Newton rows (unweighted) to the 29 fp64 running sums.  Queries are walked in INDEX order and every
+//               block leaves one partial.
+//   solve:      one wave per pair adds the partials in block order, takes the step and sets the pair's `done` flag; blocks
+//               of a done pair return at once.
+// The rows, the reduction, the solve and the step x = (w, v), which moves a transformed point p' to p' + w x p' + v, are
+// csrc/gn_solve.h, shared with csrc/local_map.hip.
 #include "block_scan.h"
 #include "cell_grid.h"
 #include "gn_solve.h"
@@ -24,8 +23,6 @@
 namespace {
 
 constexpr int GMAX = 512;   // grid cells per axis (upper bound)
-constexpr int NSUM = GN_NSUM;   // H upper triangle (21), g (6), matches, sum of squared residuals
-constexpr int NSUM_PAD = 32;
 
 struct IcpHdr {   // start of every pair's workspace slice (256 bytes reserved)
     float lox, loy, inv_cs;
@@ -46,7 +43,7 @@ struct IcpArgs {
     float *fitness, *rmse;
     int32_t *iterations, *status;
     int32_t *dbg_match;        // (P,N) or NULL
-    double *dbg_system;        // (P,NSUM) or NULL
+    double *dbg_system;        // (P,GN_NSUM) or NULL
 };
 
 __device__ __forceinline__ IcpHdr *hdr_of(const IcpArgs &a, int p) { return (IcpHdr *)(a.ws + (size_t)p * a.ws_stride); }
@@ -127,12 +124,8 @@ __global__ __launch_bounds__(1024) void icp_scan_kernel(IcpArgs A) {
 __global__ void icp_init_kernel(IcpArgs A, const double *init) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= A.n_pairs) return;
-    for (int k = 0; k < 12; ++k) A.pose[(size_t)p * 16 + k] = init[(size_t)p * 16 + k];
-    A.pose[(size_t)p * 16 + 12] = 0.0, A.pose[(size_t)p * 16 + 13] = 0.0, A.pose[(size_t)p * 16 + 14] = 0.0;
-    A.pose[(size_t)p * 16 + 15] = 1.0;
-    A.fitness[p] = 0.f, A.rmse[p] = 0.f, A.iterations[p] = 0, A.status[p] = DPM_ICP_MAX_ITER;
-    if (A.dbg_system)
-        for (int k = 0; k < NSUM; ++k) A.dbg_system[(size_t)p * NSUM + k] = 0.0;
+    gn_init_problem(p, init, A.pose, A.fitness, A.rmse, A.iterations, A.status);
+    gn_zero_system(p, A.dbg_system);
 }
 
 // a new stage of the schedule: every pair runs again from where it stands
@@ -141,18 +134,6 @@ __global__ void icp_stage_kernel(IcpArgs A) {
     if (p >= A.n_pairs) return;
     hdr_of(A, p)->done = 0;
     A.status[p] = DPM_ICP_MAX_ITER;
-}
-
-// one match's row J (6) and residual e into the running sums
-__device__ __forceinline__ void add_row(double (&s)[NSUM], const double (&J)[6], double e) {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) s[k] = fma(J[i], J[j], s[k]), ++k;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) s[21 + i] = fma(J[i], e, s[21 + i]);
-    s[28] = fma(e, e, s[28]);
 }
 
 template <int PLANE>
@@ -169,14 +150,16 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(IcpArgs A, float r2
     const float4 *sorted = sorted_of(A, pair);
     const int gx = hdr->gx, gy = hdr->gy, H = hdr->H;
     const float inv_cs = hdr->inv_cs, lox = hdr->lox, loy = hdr->loy;
+    // The search runs in fp32, like the information matrix's: gn_load_pose / gn_xform with no origin, written out because
+    // through them the point kernel timed above this form in both runs (profiles/gn_shared_isa.md).
     const double *pose = A.pose + (size_t)pair * 16;
     float Rt[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) Rt[k] = (float)pose[k];   // the search runs in fp32, like the information matrix's
+    for (int k = 0; k < 12; ++k) Rt[k] = (float)pose[k];
     const int quad = threadIdx.x >> 2, ql = threadIdx.x & 3;
-    double s[NSUM];
+    double s[GN_NSUM];
 #pragma unroll
-    for (int k = 0; k < NSUM; ++k) s[k] = 0.0;
+    for (int k = 0; k < GN_NSUM; ++k) s[k] = 0.0;
     for (int j = 0; j < 4; ++j) {
         const int i = blk * 256 + j * 64 + quad;   // uniform inside a quad
         if (i >= n1) {
@@ -184,10 +167,9 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(IcpArgs A, float r2
             continue;
         }
         const float x = p1[i], y = p1[(size_t)N + i], z = p1[2 * (size_t)N + i];
-        const float qx = fmaf(Rt[2], z, fmaf(Rt[1], y, Rt[0] * x)) + Rt[3];
-        const float qy = fmaf(Rt[6], z, fmaf(Rt[5], y, Rt[4] * x)) + Rt[7];
-        const float qz = fmaf(Rt[10], z, fmaf(Rt[9], y, Rt[8] * x)) + Rt[11];
-        const float flx = floorf((qx - lox) * inv_cs), fly = floorf((qy - loy) * inv_cs);
+        const float q[3] = {fmaf(Rt[2], z, fmaf(Rt[1], y, Rt[0] * x)) + Rt[3], fmaf(Rt[6], z, fmaf(Rt[5], y, Rt[4] * x)) + Rt[7],
+                            fmaf(Rt[10], z, fmaf(Rt[9], y, Rt[8] * x)) + Rt[11]};
+        const float flx = floorf((q[0] - lox) * inv_cs), fly = floorf((q[1] - loy) * inv_cs);
         const int cx = (int)fmaxf(fminf(flx, 1e6f), -1e6f), cy = (int)fmaxf(fminf(fly, 1e6f), -1e6f);
         const int xa = min(max(cx - H, 0), gx), xb = min(max(cx + H + 1, 0), gx);
         unsigned long long best = ~0ull;
@@ -201,63 +183,39 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(IcpArgs A, float r2
             rlo[r] = in ? cells[yc * gx + xa] : 0, rhi[r] = in ? cells[yc * gx + xb] : 0;
         }
 #pragma unroll
-        for (int r = 0; r < 5; ++r) quad_scan_range(sorted, rlo[r], rhi[r], ql, qx, qy, qz, best);
+        for (int r = 0; r < 5; ++r) quad_scan_range(sorted, rlo[r], rhi[r], ql, q[0], q[1], q[2], best);
         best = quad_min_key(best);
         const bool hit = best != ~0ull && __uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
         const int win = hit ? (int)(unsigned)best : -1;
         if (ql != 0) continue;
         if (A.dbg_match) A.dbg_match[(size_t)pair * N + i] = win;
         if (!hit) continue;
-        const double px = qx, py = qy, pz = qz;
-        const double ex = px - (double)p2[win], ey = py - (double)p2[(size_t)N + win], ez = pz - (double)p2[2 * (size_t)N + win];
+        const double p[3] = {q[0], q[1], q[2]};
+        const double e[3] = {p[0] - (double)p2[win], p[1] - (double)p2[(size_t)N + win], p[2] - (double)p2[2 * (size_t)N + win]};
         s[27] += 1.0;
         if (PLANE) {
-            const double nx = nrm[3 * (size_t)win], ny = nrm[3 * (size_t)win + 1], nz = nrm[3 * (size_t)win + 2];
-            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            add_row(s, J, (nx * ex + ny * ey) + nz * ez);
+            const double n[3] = {nrm[3 * (size_t)win], nrm[3 * (size_t)win + 1], nrm[3 * (size_t)win + 2]};
+            gn_plane_row(s, p, n, e, 0.0);
         } else {
-            const double Jx[6] = {0.0, pz, -py, 1.0, 0.0, 0.0}, Jy[6] = {-pz, 0.0, px, 0.0, 1.0, 0.0},
-                         Jz[6] = {py, -px, 0.0, 0.0, 0.0, 1.0};
-            add_row(s, Jx, ex), add_row(s, Jy, ey), add_row(s, Jz, ez);
+            gn_point_rows(s, p, e, 1.0);
         }
     }
-    // lanes, then waves, in a fixed tree; one partial per block
-    __shared__ double sred[4][NSUM];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int off = 32; off >= 4; off >>= 1) v += __shfl_xor(v, off, 64);   // lanes 1..3 of a quad hold zeros
-        if (lane == 0) sred[w][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSUM)
-        partial_of(A, pair)[(size_t)blk * NSUM_PAD + threadIdx.x] =
-            (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
+    gn_block_reduce(s, partial_of(A, pair), blk);
 }
 
 __global__ __launch_bounds__(64) void icp_solve_kernel(IcpArgs A, double tol_rot, double tol_trans) {
     const int pair = blockIdx.x, lane = threadIdx.x;
     IcpHdr *hdr = hdr_of(A, pair);
     if (hdr->done) return;
-    __shared__ double S[NSUM_PAD];
-    if (lane < NSUM) {
-        const double *part = partial_of(A, pair);
-        const int nblk = (A.N + 255) / 256;
-        double v = 0.0;
-        for (int b = 0; b < nblk; ++b) v += part[(size_t)b * NSUM_PAD + lane];   // block order
-        S[lane] = v;
-        if (A.dbg_system) A.dbg_system[(size_t)pair * NSUM + lane] = v;
-    }
-    __syncthreads();
+    __shared__ double S[GN_NSUM_PAD];
+    gn_sum_partials(partial_of(A, pair), (A.N + 255) / 256, S, A.dbg_system, pair);
     if (lane != 0) return;
     gn_solve_step(S, hdr->n1, A.pose + (size_t)pair * 16, A.fitness, A.rmse, A.iterations, A.status, pair, &hdr->done, tol_rot, tol_trans);
 }
 
 size_t slice_bytes(int N) {
     const size_t b = 256 + sizeof(int) * (size_t)(GMAX * GMAX + 4) + sizeof(float4) * (size_t)N +
-                     sizeof(double) * NSUM_PAD * (size_t)dpm_cdiv(N, 256);
+                     sizeof(double) * GN_NSUM_PAD * (size_t)dpm_cdiv(N, 256);
     return (b + 255) & ~(size_t)255;
 }
 

@@ -34,6 +34,7 @@
 //    back to a full scan for its nearest point.
 #include "block_scan.h"
 #include "filter_dc.h"
+#include "sym3_jacobi.h"
 #include "topk_emulate.h"
 #include <type_traits>
 
@@ -1329,8 +1330,8 @@ __global__ __launch_bounds__(WPB * 64) void knn_self_kernel(const float *__restr
 // ---------------------------------------------------------------------------------------------
 // Point normals for LowPassFilter (reference dataloader/transforms.py:268-271: open3d 0.16
 // PointCloud.estimate_normals(KDTreeSearchParamRadius(r))): covariance of the points within r of the point
-// (itself included) from fp64 cumulants, normal = unit eigenvector of its smallest eigenvalue (cyclic Jacobi in
-// fp64; the sign is arbitrary -- the caller only uses |n_i . n_j|); fewer than 3 points in range -> (0,0,1).
+// (itself included) from fp64 cumulants, normal = unit eigenvector of its smallest eigenvalue (sym3_jacobi.h;
+// the sign is arbitrary -- the caller only uses |n_i . n_j|); fewer than 3 points in range -> (0,0,1).
 // One wave per point over the 3x3 cells of a grid with cell edge >= r.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -1382,27 +1383,7 @@ __global__ __launch_bounds__(WPB * 64) void point_normals_kernel(const float *__
                           {0, 0, m[9] / n - mz * mz}};
         A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
         double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        for (int sweep = 0; sweep < 12; ++sweep) {
-            const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-            if (off <= 1e-300 || off <= 1e-18 * (fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]))) break;
-            for (int p = 0; p < 2; ++p)
-                for (int r = p + 1; r < 3; ++r) {
-                    if (A[p][r] == 0.0) continue;
-                    const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double cs_ = 1.0 / sqrt(t * t + 1.0), sn = t * cs_;
-                    for (int k = 0; k < 3; ++k) {  // A <- A J
-                        const double akp = A[k][p], akr = A[k][r];
-                        A[k][p] = cs_ * akp - sn * akr, A[k][r] = sn * akp + cs_ * akr;
-                    }
-                    for (int k = 0; k < 3; ++k) {  // A <- J^T A,  V <- V J
-                        const double apk = A[p][k], ark = A[r][k];
-                        A[p][k] = cs_ * apk - sn * ark, A[r][k] = sn * apk + cs_ * ark;
-                        const double vkp = V[k][p], vkr = V[k][r];
-                        V[k][p] = cs_ * vkp - sn * vkr, V[k][r] = sn * vkp + cs_ * vkr;
-                    }
-                }
-        }
+        sym3_jacobi(A, V);
         int e = 0;
         if (A[1][1] < A[e][e]) e = 1;
         if (A[2][2] < A[e][e]) e = 2;

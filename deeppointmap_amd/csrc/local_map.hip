@@ -35,10 +35,11 @@
 //               (distance bits, n * 32 + sub-cell): ties are broken by geometry alone.  A hit needs d2 <= (float)(max_dist^2);
 //               max_dist <= v (checked on the host), so in exact arithmetic no nearer point lies outside the 27 voxels.
 //               Lane 0 adds the point-to-point rows, weighted w = (kappa / (kappa + e.e))^2 (Geman-McClure, kappa =
-//               kernel_scale^2, 0 = unweighted), to the 29 fp64 sums of csrc/icp.hip: H and g weighted, the match count and
-//               the squared residuals not.  Lanes, then waves, in a fixed tree; one partial per block.
-//   solve:      one wave adds the partials in block order; the step is csrc/gn_solve.h, taken on the pose in the map frame
-//               (where the rows were formed) and shifted back; a step not taken leaves the pose's bytes alone.
+//               kernel_scale^2, 0 = unweighted), to the 29 fp64 sums of csrc/gn_solve.h: H and g weighted, the match count
+//               and the squared residuals not.  One partial per block.
+//   solve:      one wave adds the partials in block order; the step is taken on the pose in the map frame (where the rows
+//               were formed) and shifted back; a step not taken leaves the pose's bytes alone.
+// The search pose is csrc/gn_solve.h's; the rows, the reduction, the solve and the start values are shared with csrc/icp.hip there.
 //
 // Voxel planes (dpm_local_map_planes): a cache derived from the map, one float4 (normal, w) and one count per SLOT of the
 // current half, in caller-owned buffers.  One launch, four lanes a slot.  The centre of a held voxel is
@@ -47,23 +48,23 @@
 // Lane l adds the ten cumulants of d (n, 3 first, 6 second moments) in fp64 over the neighbours n = l, l + 4, ... ascending,
 // sub-cells ascending; the four lanes are added as (l0 + l1) + (l2 + l3).  So a voxel's plane is a function of the map's
 // content alone.  Lane 0 forms the scatter matrix n * S_ab - S_a * S_b (the covariance times n^2: exactly zero where the
-// points' coordinates are, which a quotient by n would not keep), runs the cyclic Jacobi of csrc/knn.hip's
-// point_normals_kernel in fp64 and orders the eigenvalues ascending, the smaller axis first among equals.  The normal is
+// points' coordinates are, which a quotient by n would not keep), runs the cyclic Jacobi of csrc/sym3_jacobi.h in
+// fp64 and orders the eigenvalues ascending, the smaller axis first among equals.  The normal is
 // the unit eigenvector of the smallest, rounded to fp32, its sign such that the component of largest magnitude (of the fp32
 // values; the first axis among equals) is positive; w = (float)(max(l0, 0) / l1).  Fewer than 3 members, or a line, l1 <= 1e-8 l2
 // (which includes l1 <= 0; see LINE_RATIO): (0, 0, 0, -1).  An empty slot: (0, 0, 0, -1) and count 0.
 //
 // Plane rows (dpm_local_map_register_planes): lm_accumulate_kernel<true>.  Search, tie-break and key as above; the matched
 // point's voxel (its slot) gives a row only when counts >= min_points and 0 <= w <= (float)max_ratio:
-// e = (nx*ex + ny*ey) + nz*ez, J = (p x n, n) -- csrc/icp.hip's plane row -- weighted (kappa / (kappa + e*e))^2.  A match
-// whose voxel has no such plane contributes nothing and is not counted.
+// e = (nx*ex + ny*ey) + nz*ez, J = (p x n, n) -- gn_plane_row, the batched ICP's too -- weighted (kappa / (kappa + e*e))^2.
+// A match whose voxel has no such plane contributes nothing and is not counted.
 #include "cell_grid.h"
 #include "gn_solve.h"
+#include "sym3_jacobi.h"
 
 namespace {
 
 constexpr unsigned long long EMPTY = ~0ull;
-constexpr int NSUM = GN_NSUM, NSUM_PAD = 32;
 constexpr int LM_BLOCK = 256;
 
 struct MapHdr {   // 256 bytes
@@ -82,34 +83,6 @@ struct Map {
     __host__ __device__ MapHdr *hdr() const { return (MapHdr *)base; }
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {   // splitmix64 finaliser, as voxel_map.hip
-    k ^= k >> 30;
-    k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27;
-    k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
-// the fp32 pose of the map frame: 9 rotation entries row-major, then the translation minus the origin
-struct Pose32 {
-    float R[9], t[3];
-};
-
-__device__ __forceinline__ Pose32 load_pose(const double *pose, const Map &M) {
-    Pose32 P;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) P.R[3 * i + j] = (float)pose[4 * i + j];
-    P.t[0] = (float)(pose[3] - M.ox), P.t[1] = (float)(pose[7] - M.oy), P.t[2] = (float)(pose[11] - M.oz);
-    return P;
-}
-
-__device__ __forceinline__ void xform(const Pose32 &P, float x, float y, float z, float q[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) q[a] = fmaf(P.R[3 * a + 2], z, fmaf(P.R[3 * a + 1], y, P.R[3 * a] * x)) + P.t[a];
-}
-
 // voxel coordinate (biased by 2^20) and sub-cell coordinate of one axis; 0 when the 21 bits cannot hold it (or NaN)
 __device__ __forceinline__ int axis_cell(float p, float v, int s, int &vox, int &sub) {
     const float f = __fdiv_rn(p, v), fl = floorf(f);
@@ -121,6 +94,14 @@ __device__ __forceinline__ int axis_cell(float p, float v, int s, int &vox, int 
 
 __device__ __forceinline__ unsigned long long pack_key(int x, int y, int z) {
     return (unsigned long long)x | ((unsigned long long)y << 21) | ((unsigned long long)z << 42);
+}
+
+__device__ __forceinline__ int key_axis(unsigned long long key, int a) { return (int)((key >> (21 * a)) & 0x1FFFFF); }
+
+// the centre of a held voxel, per axis c = ((float)index + 0.5f) * v
+__device__ __forceinline__ void voxel_centre(unsigned long long key, float v, float c[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = ((float)(key_axis(key, a) - 1048576) + 0.5f) * v;
 }
 
 // slot of `key` in a table nobody is writing, or -1
@@ -147,6 +128,23 @@ __device__ __forceinline__ int claim_slot(unsigned long long *keys, int cap_vox,
     return -1;
 }
 
+// Lane ql of a quad visits the neighbours n = ql, ql + 4, ... (n = ((dz+1) * 3 + (dy+1)) * 3 + (dx+1)) of the 27 voxels around
+// (vx, vy, vz) and offers every occupied sub-cell, ascending, to f(n, slot, c, point).  own_slot >= 0: the slot of n = 13, if known.
+template <typename Fn>
+__device__ __forceinline__ void quad_visit27(const unsigned long long *keys, const unsigned long long *owner, const float4 *pts,
+                                             int cap_vox, int S, int vx, int vy, int vz, int ql, int own_slot, Fn f) {
+    for (int n = ql; n < 27; n += 4) {
+        const int x = vx + n % 3 - 1, y = vy + (n / 3) % 3 - 1, z = vz + n / 9 - 1;
+        if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) continue;
+        const int slot = n == 13 && own_slot >= 0 ? own_slot : find_slot(keys, cap_vox, pack_key(x, y, z));
+        if (slot < 0) continue;
+        for (int c = 0; c < S; ++c) {
+            if (owner[(size_t)slot * S + c] == EMPTY) continue;
+            f(n, slot, c, pts[(size_t)slot * S + c]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(LM_BLOCK) void lm_clear_kernel(Map M, int h, bool header) {
     const size_t tid = (size_t)blockIdx.x * LM_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * LM_BLOCK;
     if (header && tid < 64) ((unsigned *)M.base)[tid] = 0u;
@@ -163,13 +161,13 @@ struct Frame {
 };
 
 // what claim and commit compute alike for row i; false when the row offers nothing
-__device__ __forceinline__ bool row_cell(const Map &M, const Frame &F, const Pose32 &P, int i, float lo2, float hi2,
+__device__ __forceinline__ bool row_cell(const Map &M, const Frame &F, const GnPose32 &P, int i, float lo2, float hi2,
                                          unsigned long long &key, int &sub, float q[3], bool &outside) {
     const float x = F.xyz[3 * (size_t)i], y = F.xyz[3 * (size_t)i + 1], z = F.xyz[3 * (size_t)i + 2];
     const float r2 = (x * x + y * y) + z * z;
     outside = false;
     if (!(r2 >= lo2 && r2 <= hi2)) return false;
-    xform(P, x, y, z, q);
+    gn_xform(P, x, y, z, q);
     int vx, vy, vz, sx, sy, sz;
     if (!(axis_cell(q[0], M.v, M.s, vx, sx) & axis_cell(q[1], M.v, M.s, vy, sy) & axis_cell(q[2], M.v, M.s, vz, sz))) {
         outside = true;
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_insert_kernel(Map M, Frame F, con
     const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
     const int n = min(max(F.count[0], 0), F.cap);
     if (i >= n) return;
-    const Pose32 P = load_pose(pose, M);
+    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
     unsigned long long key;
     int sub;
     float q[3];
@@ -217,10 +215,9 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_prune_kernel(Map M, const double 
     const unsigned long long key = M.keys(M.half)[slot];
     if (key == EMPTY) return;
     const float tx = (float)(pose[3] - M.ox), ty = (float)(pose[7] - M.oy), tz = (float)(pose[11] - M.oz);
-    const float cx = ((float)((int)(key & 0x1FFFFF) - 1048576) + 0.5f) * M.v;
-    const float cy = ((float)((int)((key >> 21) & 0x1FFFFF) - 1048576) + 0.5f) * M.v;
-    const float cz = ((float)((int)((key >> 42) & 0x1FFFFF) - 1048576) + 0.5f) * M.v;
-    const float dx = cx - tx, dy = cy - ty, dz = cz - tz;
+    float c[3];
+    voxel_centre(key, M.v, c);
+    const float dx = c[0] - tx, dy = c[1] - ty, dz = c[2] - tz;
     if (!((dx * dx + dy * dy) + dz * dz <= r2)) return;
     const int to = claim_slot(M.keys(1 - M.half), M.cap_vox, key);   // never full: no more keys than the old half held
     if (to < 0) {
@@ -256,32 +253,6 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_export_kernel(Map M, unsigned lon
 }
 
 // ------------------------------------------------------------------------------------------------------------- voxel planes
-// cyclic Jacobi of a symmetric 3 x 3 matrix in fp64, the loop of csrc/knn.hip's point_normals_kernel: A becomes diagonal
-// (the eigenvalues), the columns of V the eigenvectors
-__device__ __forceinline__ void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-        if (off <= 1e-300 || off <= 1e-18 * (fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]))) break;
-        for (int p = 0; p < 2; ++p)
-            for (int r = p + 1; r < 3; ++r) {
-                if (A[p][r] == 0.0) continue;
-                const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs_ = 1.0 / sqrt(t * t + 1.0), sn = t * cs_;
-                for (int k = 0; k < 3; ++k) {  // A <- A J
-                    const double akp = A[k][p], akr = A[k][r];
-                    A[k][p] = cs_ * akp - sn * akr, A[k][r] = sn * akp + cs_ * akr;
-                }
-                for (int k = 0; k < 3; ++k) {  // A <- J^T A,  V <- V J
-                    const double apk = A[p][k], ark = A[r][k];
-                    A[p][k] = cs_ * apk - sn * ark, A[r][k] = sn * apk + cs_ * ark;
-                    const double vkp = V[k][p], vkr = V[k][r];
-                    V[k][p] = cs_ * vkp - sn * vkr, V[k][r] = sn * vkp + cs_ * vkr;
-                }
-            }
-    }
-}
-
 // A point set whose middle eigenvalue is at most this fraction of its largest is a LINE: it has no plane.  In exact arithmetic
 // that is l1 = 0 (a ring of a spinning sensor on a flat wall), but the map's coordinates are fp32: a line a metre long comes
 // back 2^-24 |p| thick, l1 / l2 near 1e-11 at |p| = 50 m instead of 0, and the eigenvector of l0 is then whatever that rounding
@@ -300,25 +271,17 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_planes_kernel(Map M, float r2, fl
         if (ql == 0) planes[slot] = make_float4(0.f, 0.f, 0.f, -1.f), counts[slot] = 0;
         return;
     }
-    const int vx = (int)(key & 0x1FFFFF), vy = (int)((key >> 21) & 0x1FFFFF), vz = (int)((key >> 42) & 0x1FFFFF);
-    const float cx = ((float)(vx - 1048576) + 0.5f) * M.v, cy = ((float)(vy - 1048576) + 0.5f) * M.v,
-                cz = ((float)(vz - 1048576) + 0.5f) * M.v;
+    float ctr[3];
+    voxel_centre(key, M.v, ctr);
     double m[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // n, x, y, z, xx, xy, xz, yy, yz, zz
-    for (int n = ql; n < 27; n += 4) {
-        const int x = vx + n % 3 - 1, y = vy + (n / 3) % 3 - 1, z = vz + n / 9 - 1;
-        if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) continue;
-        const int nb = n == 13 ? slot : find_slot(keys, M.cap_vox, pack_key(x, y, z));
-        if (nb < 0) continue;
-        for (int c = 0; c < M.S; ++c) {
-            if (owner[(size_t)nb * M.S + c] == EMPTY) continue;
-            const float4 t = pts[(size_t)nb * M.S + c];
-            const float dx = t.x - cx, dy = t.y - cy, dz = t.z - cz;
-            if (!((dx * dx + dy * dy) + dz * dz <= r2)) continue;
-            const double X = dx, Y = dy, Z = dz;
-            m[0] += 1.0, m[1] += X, m[2] += Y, m[3] += Z;
-            m[4] += X * X, m[5] += X * Y, m[6] += X * Z, m[7] += Y * Y, m[8] += Y * Z, m[9] += Z * Z;
-        }
-    }
+    quad_visit27(keys, owner, pts, M.cap_vox, M.S, key_axis(key, 0), key_axis(key, 1), key_axis(key, 2), ql, slot,
+                 [&](int, int, int, const float4 &t) {
+        const float dx = t.x - ctr[0], dy = t.y - ctr[1], dz = t.z - ctr[2];
+        if (!((dx * dx + dy * dy) + dz * dz <= r2)) return;
+        const double X = dx, Y = dy, Z = dz;
+        m[0] += 1.0, m[1] += X, m[2] += Y, m[3] += Z;
+        m[4] += X * X, m[5] += X * Y, m[6] += X * Z, m[7] += Y * Y, m[8] += Y * Z, m[9] += Z * Z;
+    });
 #pragma unroll
     for (int k = 0; k < 10; ++k) {   // (l0 + l1) + (l2 + l3)
         m[k] += __shfl_xor(m[k], 1, 64);
@@ -333,7 +296,7 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_planes_kernel(Map M, float r2, fl
                           {0, 0, n * m[9] - m[3] * m[3]}};
         A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
         double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        jacobi3(A, V);
+        sym3_jacobi(A, V);
         // ascending, the smaller axis first among equals: e0 the smallest, e1 the smaller of the other two
         int e0 = 0;
         if (A[1][1] < A[e0][e0]) e0 = 1;
@@ -354,7 +317,7 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_planes_kernel(Map M, float r2, fl
 }
 
 // ------------------------------------------------------------------------------------------------------------ registration
-struct RegHdr {   // start of the workspace (256 bytes), then one partial of NSUM_PAD doubles per block
+struct RegHdr {   // start of the workspace (256 bytes), then one partial of GN_NSUM_PAD doubles per block
     int done, n1;
 };
 
@@ -368,36 +331,20 @@ struct RegArgs {
     int32_t *iterations, *status;
     long long *dbg_key;     // (cap,) or NULL
     int32_t *dbg_sub;       // (cap,) or NULL
-    double *dbg_system;     // (NSUM,) or NULL
+    double *dbg_system;     // (GN_NSUM,) or NULL
 };
 
 __global__ void lm_reg_init_kernel(RegArgs A, const double *init) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    for (int k = 0; k < 12; ++k) A.pose[k] = init[k];
-    A.pose[12] = 0.0, A.pose[13] = 0.0, A.pose[14] = 0.0, A.pose[15] = 1.0;
-    *A.fitness = 0.f, *A.rmse = 0.f, *A.iterations = 0, *A.status = DPM_ICP_MAX_ITER;
+    gn_init_problem(0, init, A.pose, A.fitness, A.rmse, A.iterations, A.status);
     A.hdr->done = 0, A.hdr->n1 = min(max(A.F.count[0], 0), A.F.cap);
-    if (A.dbg_system)
-        for (int k = 0; k < NSUM; ++k) A.dbg_system[k] = 0.0;
+    gn_zero_system(0, A.dbg_system);
 }
 
 __global__ void lm_reg_stage_kernel(RegArgs A) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     A.hdr->done = 0;
     *A.status = DPM_ICP_MAX_ITER;
-}
-
-// one weighted row: H += w J^T J, g += w J^T e, squared residuals += e e
-__device__ __forceinline__ void add_row_w(double (&s)[NSUM], const double (&J)[6], double e, double w) {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const double wj = w * J[i];
-#pragma unroll
-        for (int j = i; j < 6; ++j) s[k] = fma(wj, J[j], s[k]), ++k;
-        s[21 + i] = fma(wj, e, s[21 + i]);
-    }
-    s[28] = fma(e, e, s[28]);
 }
 
 // the plane cache of the current half and the gate a voxel's plane passes to give a row (all unused when !PLANE)
@@ -413,13 +360,13 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, floa
     if (A.hdr->done) return;
     const Map &M = A.M;
     const int blk = blockIdx.x, n1 = A.hdr->n1, cap = A.F.cap;
-    const Pose32 P = load_pose(A.pose, M);
+    const GnPose32 P = gn_load_pose(A.pose, M.ox, M.oy, M.oz);
     const unsigned long long *keys = M.keys(M.half), *owner = M.owner(M.half);
     const float4 *pts = M.pts(M.half);
     const int quad = threadIdx.x >> 2, ql = threadIdx.x & 3;
-    double s[NSUM];
+    double s[GN_NSUM];
 #pragma unroll
-    for (int k = 0; k < NSUM; ++k) s[k] = 0.0;
+    for (int k = 0; k < GN_NSUM; ++k) s[k] = 0.0;
     for (int j = 0; j < 4; ++j) {
         const int i = blk * 256 + j * 64 + quad;   // uniform inside a quad
         if (i >= n1) {
@@ -430,27 +377,18 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, floa
             continue;
         }
         float q[3];
-        xform(P, A.F.xyz[3 * (size_t)i], A.F.xyz[3 * (size_t)i + 1], A.F.xyz[3 * (size_t)i + 2], q);
+        gn_xform(P, A.F.xyz[3 * (size_t)i], A.F.xyz[3 * (size_t)i + 1], A.F.xyz[3 * (size_t)i + 2], q);
         int vx, vy, vz, sx, sy, sz;
         const bool inside = axis_cell(q[0], M.v, M.s, vx, sx) & axis_cell(q[1], M.v, M.s, vy, sy) & axis_cell(q[2], M.v, M.s, vz, sz);
         unsigned long long best = ~0ull;
         int best_slot = -1;
-        if (inside) {
-            for (int n = ql; n < 27; n += 4) {
-                const int x = vx + n % 3 - 1, y = vy + (n / 3) % 3 - 1, z = vz + n / 9 - 1;
-                if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) continue;
-                const int slot = find_slot(keys, M.cap_vox, pack_key(x, y, z));
-                if (slot < 0) continue;
-                for (int c = 0; c < M.S; ++c) {
-                    if (owner[(size_t)slot * M.S + c] == EMPTY) continue;
-                    const float4 t = pts[(size_t)slot * M.S + c];
-                    const float dx = q[0] - t.x, dy = q[1] - t.y, dz = q[2] - t.z;
-                    const unsigned long long key =
-                        ((unsigned long long)__float_as_uint((dx * dx + dy * dy) + dz * dz) << 32) | (unsigned)(n * 32 + c);
-                    if (key < best) best = key, best_slot = slot;
-                }
-            }
-        }
+        if (inside)
+            quad_visit27(keys, owner, pts, M.cap_vox, M.S, vx, vy, vz, ql, -1, [&](int n, int slot, int c, const float4 &t) {
+                const float dx = q[0] - t.x, dy = q[1] - t.y, dz = q[2] - t.z;
+                const unsigned long long key =
+                    ((unsigned long long)__float_as_uint((dx * dx + dy * dy) + dz * dz) << 32) | (unsigned)(n * 32 + c);
+                if (key < best) best = key, best_slot = slot;
+            });
         const unsigned long long mine = best;
         best = quad_min_key(best);
         bool hit = best != ~0ull &&__uint_as_float((unsigned)(best >> 32)) <= r2;   // a NaN distance is no hit
@@ -469,58 +407,37 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, floa
         if (A.dbg_sub) A.dbg_sub[i] = hit ? c : -1;
         if (!hit) continue;
         const float4 t = pts[(size_t)win_slot * M.S + c];
-        const double px = q[0], py = q[1], pz = q[2];
-        const double ex = px - (double)t.x, ey = py - (double)t.y, ez = pz - (double)t.z;
+        const double p[3] = {q[0], q[1], q[2]};
+        const double e[3] = {p[0] - (double)t.x, p[1] - (double)t.y, p[2] - (double)t.z};
         s[27] += 1.0;
         if (PLANE) {
-            const double nx = pl.x, ny = pl.y, nz = pl.z;
-            const double e = (nx * ex + ny * ey) + nz * ez;
-            double w = 1.0;
-            if (kappa > 0.0) {
-                const double r = kappa / (kappa + e * e);
-                w = r * r;
-            }
-            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            add_row_w(s, J, e, w);
+            const double n[3] = {pl.x, pl.y, pl.z};
+            gn_plane_row(s, p, n, e, kappa);
         } else {
-            double w = 1.0;
-            if (kappa > 0.0) {
-                const double r = kappa / (kappa + ((ex * ex + ey * ey) + ez * ez));
-                w = r * r;
-            }
-            const double Jx[6] = {0.0, pz, -py, 1.0, 0.0, 0.0}, Jy[6] = {-pz, 0.0, px, 0.0, 1.0, 0.0},
-                         Jz[6] = {py, -px, 0.0, 0.0, 0.0, 1.0};
-            add_row_w(s, Jx, ex, w), add_row_w(s, Jy, ey, w), add_row_w(s, Jz, ez, w);
+            gn_point_rows(s, p, e, gn_weight(kappa, (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]));
         }
     }
-    // lanes, then waves, in a fixed tree; one partial per block
-    __shared__ double sred[4][NSUM];
+    // gn_block_reduce written out: through it the point-row kernel timed 3 to 4 % slower (profiles/gn_shared_isa.md)
+    __shared__ double sred[4][GN_NSUM];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < NSUM; ++k) {
+    for (int k = 0; k < GN_NSUM; ++k) {
         double v = s[k];
 #pragma unroll
         for (int off = 32; off >= 4; off >>= 1) v += __shfl_xor(v, off, 64);   // lanes 1..3 of a quad hold zeros
         if (lane == 0) sred[wv][k] = v;
     }
     __syncthreads();
-    if (threadIdx.x < NSUM)
-        A.partial[(size_t)blk * NSUM_PAD + threadIdx.x] =
+    if (threadIdx.x < GN_NSUM)
+        A.partial[(size_t)blk * GN_NSUM_PAD + threadIdx.x] =
             (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
 }
 
 __global__ __launch_bounds__(64) void lm_solve_kernel(RegArgs A, double tol_rot, double tol_trans) {
     const int lane = threadIdx.x;
     if (A.hdr->done) return;
-    __shared__ double S[NSUM_PAD];
-    if (lane < NSUM) {
-        const int nblk = (A.F.cap + 255) / 256;
-        double v = 0.0;
-        for (int b = 0; b < nblk; ++b) v += A.partial[(size_t)b * NSUM_PAD + lane];   // block order
-        S[lane] = v;
-        if (A.dbg_system) A.dbg_system[lane] = v;
-    }
-    __syncthreads();
+    __shared__ double S[GN_NSUM_PAD];
+    gn_sum_partials(A.partial, (A.F.cap + 255) / 256, S, A.dbg_system, 0);
     if (lane != 0) return;
     // the rows were formed in the map frame, so the step acts on the pose there; a step that was not taken leaves the
     // world pose's bytes alone

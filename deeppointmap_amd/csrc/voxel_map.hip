@@ -162,14 +162,6 @@ __global__ __launch_bounds__(VM_BLOCK) void vm_bounds_kernel(const float *const 
     }
 }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {   // splitmix64 finaliser
-    k ^= k >> 30;
-    k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27;
-    k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
 struct Run {
     unsigned long long key;
     long long q[3];

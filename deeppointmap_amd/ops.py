@@ -1008,6 +1008,21 @@ def icp_target_normals(pcd: torch.Tensor, lengths: torch.Tensor, dst_frame: torc
     return normals
 
 
+def _schedule_arrays(schedule):
+    """schedule = [(max_dist, max_iter), ...] -> (ctypes double array of the distances, int32 array of the limits, their number)"""
+    stages = [(float(d), int(n)) for d, n in schedule]
+    if not stages:
+        raise ValueError("schedule: at least one (max_dist, max_iter) stage")
+    dist, iters = zip(*stages)
+    return (ctypes.c_double * len(stages))(*dist), (ctypes.c_int32 * len(stages))(*iters), len(stages)
+
+
+def _registration_results(n: int, dev):
+    """the results of n registration problems: pose (n,4,4) fp64, fitness, rmse (n,) fp32, iterations, status (n,) int32"""
+    new = lambda dtype, *shape: torch.empty(n, *shape, device=dev, dtype=dtype)
+    return new(torch.float64, 4, 4), new(torch.float32), new(torch.float32), new(torch.int32), new(torch.int32)
+
+
 def icp_refine(pcd: torch.Tensor, lengths: torch.Tensor, src_frame: torch.Tensor, dst_frame: torch.Tensor, init: torch.Tensor,
                schedule, metric: int = ICP_PLANE, tol_rot: float = 1e-7, tol_trans: float = 1e-6,
                normals: Optional[torch.Tensor] = None, debug: bool = False):
@@ -1029,21 +1044,15 @@ def icp_refine(pcd: torch.Tensor, lengths: torch.Tensor, src_frame: torch.Tensor
             raise ValueError("normals: expected (F,N,3)")
     else:
         normals = None
-    stages = [(float(d), int(n)) for d, n in schedule]
-    dist = (ctypes.c_double * len(stages))(*[d for d, _ in stages])
-    iters = (ctypes.c_int32 * len(stages))(*[n for _, n in stages])
+    dist, iters, n_stages = _schedule_arrays(schedule)
     dev = pcd.device
     lib = _lib.load()
-    pose = torch.empty(P_, 4, 4, device=dev, dtype=torch.float64)
-    fitness = torch.empty(P_, device=dev, dtype=torch.float32)
-    rmse = torch.empty(P_, device=dev, dtype=torch.float32)
-    iterations = torch.empty(P_, device=dev, dtype=torch.int32)
-    status = torch.empty(P_, device=dev, dtype=torch.int32)
+    pose, fitness, rmse, iterations, status = _registration_results(P_, dev)
     match = torch.full((P_, N), -1, device=dev, dtype=torch.int32) if debug else None
     system = torch.zeros(P_, ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
     ws = torch.empty(lib.dpm_icp_workspace_bytes(P_, N), device=dev, dtype=torch.uint8)
     _lib.check(lib.dpm_icp_refine_batched(_ptr(pcd), F, N, _ptr(lengths), _ptr(normals), _ptr(src_frame), _ptr(dst_frame), P_,
-                                          _ptr(init), int(metric), ctypes.addressof(dist), ctypes.addressof(iters), len(stages),
+                                          _ptr(init), int(metric), ctypes.addressof(dist), ctypes.addressof(iters), n_stages,
                                           float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse),
                                           _ptr(iterations), _ptr(status), _ptr(match), _ptr(system), _ptr(ws), _stream(pcd)),
                "dpm_icp_refine_batched")
@@ -2253,24 +2262,17 @@ def local_map_register(table, cap_vox, subdiv, half, voxel, origin, xyz, count, 
     _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(init, torch.float64, "init")
     if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1 or count.numel() != 1 or tuple(init.shape) != (4, 4):
         raise ValueError("local_map_register: xyz (cap,3) with cap >= 1, count (1,), init (4,4)")
-    stages = [(float(d), int(n)) for d, n in schedule]
-    if not stages:
-        raise ValueError("schedule: at least one (max_dist, max_iter) stage")
-    dist = (ctypes.c_double * len(stages))(*[d for d, _ in stages])
-    iters = (ctypes.c_int32 * len(stages))(*[n for _, n in stages])
+    dist, iters, n_stages = _schedule_arrays(schedule)
     dev, cap = table.device, xyz.shape[0]
     with torch.cuda.device(dev):
-        pose = torch.empty(4, 4, device=dev, dtype=torch.float64)
-        fitness = torch.empty(1, device=dev, dtype=torch.float32)
-        rmse = torch.empty(1, device=dev, dtype=torch.float32)
-        iterations = torch.empty(1, device=dev, dtype=torch.int32)
-        status = torch.empty(1, device=dev, dtype=torch.int32)
+        pose, fitness, rmse, iterations, status = _registration_results(1, dev)
+        pose = pose[0]
         key = torch.full((cap,), -1, device=dev, dtype=torch.int64) if debug else None
         sub = torch.full((cap,), -1, device=dev, dtype=torch.int32) if debug else None
         system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
         ws = torch.empty(512 + 256 * ((cap + 255) // 256), device=dev, dtype=torch.uint8)
         head = (_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o))
-        tail = (_ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), len(stages),
+        tail = (_ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), n_stages,
                 float(kernel_scale), float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations),
                 _ptr(status), _ptr(key), _ptr(sub), _ptr(system), _ptr(ws), _stream(table))
         if _plane is None:

@@ -2,6 +2,8 @@
 neighbour with ties to the smaller index, radius cut, Gauss-Newton rows, fp64 Cholesky solve with the pivot test,
 exponential-map update, stop rule, status codes.  This restatement is the yardstick of tests/test_gpu_icp.py: the reference
 has no ICP (its refined_SE3.pkl was made offline by a third-party one), so there is no golden file to compare against.
+The Gauss-Newton part (csrc/gn_solve.h: weights, system, system_floor, solve, update, iterate) also serves the restatements of
+the registration against the local map (tests/lidar_odometry_restated.py, tests/lidar_plane_restated.py).
 
 `dtype` is the precision of everything up to the summed system (transform, distances, rows, sums); the solve and the pose
 are float64 in both, as on the GPU.  Also here: the synthetic room scenes the tests register.
@@ -100,22 +102,38 @@ def rows(q, win, tgt, normals, metric, dtype):
 IU = np.triu_indices(6)
 
 
-def system(J, e, count, dtype):
-    """the 29 sums: H upper triangle row-major (21), g (6), matches, squared residuals -- summed in dtype"""
-    H = (J[:, :, None] * J[:, None, :]).sum(axis=0, dtype=dtype)
-    g = (J * e[:, None]).sum(axis=0, dtype=dtype)
+def weights(E, kernel_scale, dtype):
+    """E (m,) squared residuals of the matches -> Geman-McClure w = (k / (k + E))^2 with k = kernel_scale^2; 0: ones"""
+    if not kernel_scale > 0:
+        return np.ones(len(E), dtype)
+    k = dtype(kernel_scale * kernel_scale)
+    r = k / (k + E)
+    return (r * r).astype(dtype)
+
+
+def system(J, e, count, dtype, w=None):
+    """the 29 sums: H upper triangle row-major (21), g (6), matches, squared residuals -- summed in dtype.  w (rows,): H and
+    g weighted, the count and the squared residuals not"""
+    wJ = J if w is None else w[:, None] * J
+    H = (wJ[:, :, None] * J[:, None, :]).sum(axis=0, dtype=dtype)
+    g = (wJ * e[:, None]).sum(axis=0, dtype=dtype)
     return np.concatenate([H[IU], g, [count], [(e * e).sum(dtype=dtype)]]).astype(np.float64)
 
 
-def system_floor(J, e, delta):
+def system_floor(J, e, delta, w=None, dw=None):
     """What an error of up to `delta` in every coordinate of the transformed source can move each sum by: the rotation
-    entries of a row are linear in that point with coefficients of 1-norm <= 2, the residual moves by <= 2 delta."""
+    entries of a row are linear in that point with coefficients of 1-norm <= 2, the residual moves by <= 2 delta.  With
+    weights w (rows,) that this error moves by up to dw, a term w J J moves by w d(J J) + |J J| dw."""
     aJ, ae = np.abs(J).astype(np.float64), np.abs(e).astype(np.float64)
     dJ = np.zeros(6)
     dJ[:3] = 2 * delta
-    H = (aJ[:, :, None] * dJ[None, None, :] + aJ[:, None, :] * dJ[None, :, None]).sum(axis=0)
-    g = (aJ * (2 * delta) + ae[:, None] * dJ[None, :]).sum(axis=0)
-    return np.concatenate([H[IU], g, [0.0], [(2 * ae * 2 * delta).sum()]])
+    H = aJ[:, :, None] * dJ[None, None, :] + aJ[:, None, :] * dJ[None, :, None]
+    g = aJ * (2 * delta) + ae[:, None] * dJ[None, :]
+    if w is not None:
+        w = w.astype(np.float64)
+        H = w[:, None, None] * H + dw[:, None, None] * aJ[:, :, None] * aJ[:, None, :]
+        g = w[:, None] * g + dw[:, None] * aJ * ae[:, None]
+    return np.concatenate([H.sum(axis=0)[IU], g.sum(axis=0), [0.0], [(2 * ae * 2 * delta).sum()]])
 
 
 def solve(S):
@@ -166,29 +184,50 @@ def update(pose, x):
     return out
 
 
-def icp(src, tgt, normals, init, max_dist=1.0, max_iter=30, metric=PLANE, tol_rot=1e-7, tol_trans=1e-6, dtype=np.float64):
-    """-> dict(pose, fitness, rmse, iterations, status)"""
+def _shifted(pose, origin, sign):
+    """the pose with sign * origin added to its translation, float64; origin None: the pose itself"""
+    if origin is None:
+        return pose
+    P = np.array(pose, np.float64)
+    P[:3, 3] += sign * np.asarray(origin, np.float64)
+    return P
+
+
+def iterate(system_of, n_src, init, schedule, tol_rot=1e-7, tol_trans=1e-6, origin=None):
+    """The loop of every registration over schedule = [(max_dist, max_iter), ...] -> dict(pose, fitness, rmse, iterations,
+    status).  system_of(pose, max_dist) -> S (29,) is the search and the rows; its pose, and the step, are in the frame
+    shifted by -origin (the local map's frame), the pose kept is the world's."""
     pose = np.array(init, np.float64)
     fitness = rmse = 0.0
     iterations, status = 0, MAX_ITER
-    for _ in range(max_iter):
+    for max_dist, max_iter in schedule:
+        status = MAX_ITER
+        for _ in range(max_iter):
+            local = _shifted(pose, origin, -1)
+            S = system_of(local, max_dist)
+            x, bad = solve(S)
+            if bad == NO_MATCH:
+                fitness, rmse, status = 0.0, 0.0, NO_MATCH
+                break
+            fitness, rmse = S[27] / max(n_src, 1), float(np.sqrt(S[28] / S[27]))
+            if bad is not None:
+                status = bad
+                break
+            pose = _shifted(update(local, x), origin, 1)
+            iterations += 1
+            if np.linalg.norm(x[:3]) < tol_rot and np.linalg.norm(x[3:]) < tol_trans:
+                status = CONVERGED
+                break
+    return dict(pose=pose, fitness=fitness, rmse=rmse, iterations=iterations, status=status)
+
+
+def icp(src, tgt, normals, init, max_dist=1.0, max_iter=30, metric=PLANE, tol_rot=1e-7, tol_trans=1e-6, dtype=np.float64):
+    """-> dict(pose, fitness, rmse, iterations, status)"""
+    def system_of(pose, max_dist):
         q, win, _, _ = match(pose, src, tgt, max_dist, dtype)
         J, e = rows(q, win, tgt, normals, metric, dtype)
-        S = system(J, e, int((win >= 0).sum()), dtype)
-        x, bad = solve(S)
-        if bad == NO_MATCH:
-            fitness, rmse, status = 0.0, 0.0, NO_MATCH
-            break
-        fitness, rmse = S[27] / max(len(src), 1), float(np.sqrt(S[28] / S[27]))
-        if bad is not None:
-            status = bad
-            break
-        pose = update(pose, x)
-        iterations += 1
-        if np.linalg.norm(x[:3]) < tol_rot and np.linalg.norm(x[3:]) < tol_trans:
-            status = CONVERGED
-            break
-    return dict(pose=pose, fitness=fitness, rmse=rmse, iterations=iterations, status=status)
+        return system(J, e, int((win >= 0).sum()), dtype)
+    return iterate(system_of, len(src), init, [(max_dist, max_iter)], tol_rot, tol_trans)
 
 
 # ------------------------------------------------------------------------------------------------------------------- scenes

@@ -5,7 +5,7 @@ tests/test_gpu_local_map.py and tests/test_gpu_lidar_odometry.py.
 
 `dtype` float32 mirrors the kernels' operation order (transform by the rounded map-frame pose, fp32 division, floor,
 sub-cell, distances); float64 is the independent form: nothing is rounded to fp32 on the way.  The solve and the pose are
-float64 in both, as on the GPU (icp_restated.solve / update are reused: it is the same csrc/gn_solve.h).
+float64 in both, as on the GPU; the Gauss-Newton part is icp_restated's: it is the same csrc/gn_solve.h.
 """
 import os
 import sys
@@ -218,33 +218,19 @@ def search_fast(q, exported, voxel, s, max_dist, dtype, tree=None, k=8):
 
 
 # --------------------------------------------------------------------------------------------------------------- Gauss-Newton
-def weights(e3, kernel_scale, dtype):
-    """e3 (m,3) residual vectors -> Geman-McClure w = (k / (k + e.e))^2 with k = kernel_scale^2; 0: ones"""
-    if not kernel_scale > 0:
-        return np.ones(len(e3), dtype)
-    k = dtype(kernel_scale * kernel_scale)
-    r = k / (k + ((e3[:, 0] * e3[:, 0] + e3[:, 1] * e3[:, 1]) + e3[:, 2] * e3[:, 2]))
-    return (r * r).astype(dtype)
-
-
 def system(q, win, xyz, kernel_scale, dtype):
-    """the 29 sums on given matches: H and g weighted, count and squared residuals not; also J, e, w for the bounds"""
+    """the 29 sums of the point rows on given matches, weighted by the match's e.e; also J, e, w for the bounds"""
     m = int((win >= 0).sum())
     J, e = I.rows(q, win, xyz, None, I.POINT, dtype)
-    w = weights(e.reshape(3, m).T, kernel_scale, dtype)
-    w3 = np.tile(w, 3)
-    H = ((w3[:, None] * J)[:, :, None] * J[:, None, :]).sum(axis=0, dtype=dtype)
-    g = ((w3[:, None] * J) * e[:, None]).sum(axis=0, dtype=dtype)
-    S = np.concatenate([H[I.IU], g, [m], [(e * e).sum(dtype=dtype)]]).astype(np.float64)
-    return S, J, e, w3
+    e3 = e.reshape(3, m).T
+    w3 = np.tile(I.weights((e3[:, 0] * e3[:, 0] + e3[:, 1] * e3[:, 1]) + e3[:, 2] * e3[:, 2], kernel_scale, dtype), 3)
+    return I.system(J, e, m, dtype, w3), J, e, w3
 
 
 def system_floor(J, e, w3, kernel_scale, delta):
-    """icp_restated.system_floor with weights: what an error of `delta` in every coordinate of the transformed query can move
-    each sum by.  A weighted term w J J moves by w d(J J) + |J J| dw; with E = e.e of the match, |dE| <= sum_a 2 |e_a| 2 delta
-    and dw = 2 sqrt(w) k / (k + E)^2 dE <= 2 w / (k + E) dE."""
-    aJ, ae = np.abs(J).astype(np.float64), np.abs(e).astype(np.float64)
-    w3 = w3.astype(np.float64)
+    """icp_restated.system_floor with the weights of point rows: with E = e.e of the match, |dE| <= sum_a 2 |e_a| 2 delta and
+    dw = 2 sqrt(w) k / (k + E)^2 dE <= 2 w / (k + E) dE."""
+    ae, w3 = np.abs(e).astype(np.float64), w3.astype(np.float64)
     m = len(e) // 3
     dw = np.zeros(len(e))
     if kernel_scale > 0:
@@ -252,45 +238,21 @@ def system_floor(J, e, w3, kernel_scale, delta):
         E = (ae.reshape(3, m) ** 2).sum(axis=0)
         dE = (2 * ae.reshape(3, m) * 2 * delta).sum(axis=0)
         dw = np.tile(2 * w3[:m] / (k + E) * dE, 3)
-    dJ = np.zeros(6)
-    dJ[:3] = 2 * delta
-    H = (w3[:, None, None] * (aJ[:, :, None] * dJ[None, None, :] + aJ[:, None, :] * dJ[None, :, None])
-         + dw[:, None, None] * aJ[:, :, None] * aJ[:, None, :]).sum(axis=0)
-    g = (w3[:, None] * (aJ * (2 * delta) + ae[:, None] * dJ[None, :]) + dw[:, None] * aJ * ae[:, None]).sum(axis=0)
-    return np.concatenate([H[I.IU], g, [0.0], [(2 * ae * 2 * delta).sum()]])
+    return I.system_floor(J, e, delta, w3, dw)
 
 
 def register(src, exported, voxel, s, origin, init, schedule, kernel_scale=0.0, tol_rot=1e-7, tol_trans=1e-6,
              dtype=np.float64, search=search_fast):
-    """-> dict(pose, fitness, rmse, iterations, status) of the valid rows src (n,3) float32 against an exported map"""
+    """-> dict(pose, fitness, rmse, iterations, status) of the valid rows src (n,3) float32 against an exported map; the step
+    acts in the map frame, where the rows were formed"""
     from scipy.spatial import cKDTree
-    pose = np.array(init, np.float64)
-    fitness = rmse = 0.0
-    iterations, status = 0, MAX_ITER
     xyz = exported[3]
     extra = dict(tree=cKDTree(xyz.astype(np.float64))) if search is search_fast and len(xyz) else {}
-    for max_dist, max_iter in schedule:
-        status = MAX_ITER
-        for _ in range(max_iter):
-            q = I.transform(map_pose(pose, origin), src, dtype)
-            win = search(q, exported, voxel, s, max_dist, dtype, **extra)
-            S = system(q, win, xyz, kernel_scale, dtype)[0]
-            x, bad = I.solve(S)
-            if bad == NO_MATCH:
-                fitness, rmse, status = 0.0, 0.0, NO_MATCH
-                break
-            fitness, rmse = S[27] / max(len(src), 1), float(np.sqrt(S[28] / S[27]))
-            if bad is not None:
-                status = bad
-                break
-            step = I.update(map_pose(pose, origin), x)   # the step acts in the map frame, where the rows were formed
-            step[:3, 3] += np.asarray(origin, np.float64)
-            pose = step
-            iterations += 1
-            if np.linalg.norm(x[:3]) < tol_rot and np.linalg.norm(x[3:]) < tol_trans:
-                status = CONVERGED
-                break
-    return dict(pose=pose, fitness=fitness, rmse=rmse, iterations=iterations, status=status)
+
+    def system_of(pose, max_dist):
+        q = I.transform(pose, src, dtype)
+        return system(q, search(q, exported, voxel, s, max_dist, dtype, **extra), xyz, kernel_scale, dtype)[0]
+    return I.iterate(system_of, len(src), init, schedule, tol_rot, tol_trans, origin)
 
 
 # ------------------------------------------------------------------------------------------------------------------- odometry

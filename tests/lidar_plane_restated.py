@@ -57,7 +57,7 @@ def members(exported, voxel, plane_radius, dtype):
 
 
 def jacobi(A):
-    """csrc/local_map.hip's jacobi3 on a batch (V,3,3) float64 -> (eigenvalues (V,3) = the diagonal, eigenvectors in columns)"""
+    """csrc/sym3_jacobi.h's sym3_jacobi on a batch (V,3,3) float64 -> (eigenvalues (V,3) = the diagonal, eigenvectors in columns)"""
     A = A.copy()
     V = np.broadcast_to(np.eye(3), A.shape).copy()
     live = np.ones(len(A), bool)
@@ -153,43 +153,25 @@ def per_row(exported, P, min_points=5, max_ratio=0.1):
     return P.normal[at], gate(P.counts, P.w, min_points, max_ratio)[at]
 
 
-def weights(e, kernel_scale, dtype):
-    """e (m,) plane residuals -> Geman-McClure w = (k / (k + e e))^2 with k = kernel_scale^2; 0: ones"""
-    if not kernel_scale > 0:
-        return np.ones(len(e), dtype)
-    k = dtype(kernel_scale * kernel_scale)
-    r = k / (k + e * e)
-    return (r * r).astype(dtype)
-
-
 def system(q, win, xyz, normals, rows_ok, kernel_scale, dtype):
     """the 29 sums of the plane rows on given matches (-1: none); a match whose voxel gives no row drops out, count included.
     -> S, J, e, w and the matches that gave rows"""
     win = np.where((win >= 0) & rows_ok[np.maximum(win, 0)], win, -1)
     J, e = I.rows(q, win, xyz, normals, I.PLANE, dtype)
-    w = weights(e, kernel_scale, dtype)
-    H = ((w[:, None] * J)[:, :, None] * J[:, None, :]).sum(axis=0, dtype=dtype)
-    g = ((w[:, None] * J) * e[:, None]).sum(axis=0, dtype=dtype)
-    S = np.concatenate([H[I.IU], g, [int((win >= 0).sum())], [(e * e).sum(dtype=dtype)]]).astype(np.float64)
-    return S, J, e, w, win
+    w = I.weights(e * e, kernel_scale, dtype)
+    return I.system(J, e, int((win >= 0).sum()), dtype, w), J, e, w, win
 
 
 def system_floor(J, e, w, kernel_scale, delta):
-    """lidar_odometry_restated.system_floor for plane rows: what an error of `delta` in every coordinate of the transformed
-    query can move each sum by.  The rotation entries p x n are linear in the point with coefficients of 1-norm <= 2
-    (|n| = 1), the entries n do not move, the residual n.(p - q) moves by <= 2 delta; with E = e e, |dE| <= 2 |e| 2 delta
-    and dw <= 2 w / (k + E) dE."""
-    aJ, ae, w = np.abs(J).astype(np.float64), np.abs(e).astype(np.float64), w.astype(np.float64)
+    """icp_restated.system_floor with the weights of plane rows.  The rotation entries p x n are linear in the point with
+    coefficients of 1-norm <= 2 (|n| = 1), the entries n do not move, the residual n.(p - q) moves by <= 2 delta; with
+    E = e e, |dE| <= 2 |e| 2 delta and dw <= 2 w / (k + E) dE."""
+    ae, w = np.abs(e).astype(np.float64), w.astype(np.float64)
     dw = np.zeros(len(e))
     if kernel_scale > 0:
         k = kernel_scale * kernel_scale
         dw = 2 * w / (k + ae * ae) * (2 * ae * 2 * delta)
-    dJ = np.zeros(6)
-    dJ[:3] = 2 * delta
-    H = (w[:, None, None] * (aJ[:, :, None] * dJ[None, None, :] + aJ[:, None, :] * dJ[None, :, None])
-         + dw[:, None, None] * aJ[:, :, None] * aJ[:, None, :]).sum(axis=0)
-    g = (w[:, None] * (aJ * (2 * delta) + ae[:, None] * dJ[None, :]) + dw[:, None] * aJ * ae[:, None]).sum(axis=0)
-    return np.concatenate([H[I.IU], g, [0.0], [(2 * ae * 2 * delta).sum()]])
+    return I.system_floor(J, e, delta, w, dw)
 
 
 # --------------------------------------------------------------------------------------------------------------- registration
@@ -201,9 +183,6 @@ def register(src, exported, voxel, s, origin, init, schedule, kernel_scale=0.0, 
         return L.register(src, exported, voxel, s, origin, init, schedule, kernel_scale, tol_rot, tol_trans, dtype)
     assert metric == "plane", metric
     from scipy.spatial import cKDTree
-    pose = np.array(init, np.float64)
-    fitness = rmse = 0.0
-    iterations, status = 0, MAX_ITER
     xyz = exported[3]
     if len(xyz):
         P = planes(exported, voxel, 1.5 * voxel if plane_radius is None else plane_radius, dtype) if P is None else P
@@ -211,28 +190,12 @@ def register(src, exported, voxel, s, origin, init, schedule, kernel_scale=0.0, 
     else:
         normals, rows_ok = np.zeros((0, 3), np.float32), np.zeros(0, bool)
     extra = dict(tree=cKDTree(xyz.astype(np.float64))) if len(xyz) else {}
-    for max_dist, max_iter in schedule:
-        status = MAX_ITER
-        for _ in range(max_iter):
-            q = I.transform(L.map_pose(pose, origin), src, dtype)
-            win = L.search_fast(q, exported, voxel, s, max_dist, dtype, **extra)
-            S = system(q, win, xyz, normals, rows_ok, kernel_scale, dtype)[0]
-            x, bad = I.solve(S)
-            if bad == NO_MATCH:
-                fitness, rmse, status = 0.0, 0.0, NO_MATCH
-                break
-            fitness, rmse = S[27] / max(len(src), 1), float(np.sqrt(S[28] / S[27]))
-            if bad is not None:
-                status = bad
-                break
-            step = I.update(L.map_pose(pose, origin), x)
-            step[:3, 3] += np.asarray(origin, np.float64)
-            pose = step
-            iterations += 1
-            if np.linalg.norm(x[:3]) < tol_rot and np.linalg.norm(x[3:]) < tol_trans:
-                status = CONVERGED
-                break
-    return dict(pose=pose, fitness=fitness, rmse=rmse, iterations=iterations, status=status)
+
+    def system_of(pose, max_dist):
+        q = I.transform(pose, src, dtype)
+        win = L.search_fast(q, exported, voxel, s, max_dist, dtype, **extra)
+        return system(q, win, xyz, normals, rows_ok, kernel_scale, dtype)[0]
+    return I.iterate(system_of, len(src), init, schedule, tol_rot, tol_trans, origin)
 
 
 # -------------------------------------------------------------------------------------------------------------- adaptive gate
