@@ -165,6 +165,10 @@ SIGNATURES = {
     "dpm_local_map_planes": (I, [P, I, I, I, D, P, D, P, P, P]),
     "dpm_local_map_register_planes": (I, [P, I, I, I, D, P, P, P, I, D, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P,
                                           P]),
+    "dpm_scan_context_build": (I, [P, P, I, I, I, D, D, D, P, P, P, P, P, P]),
+    "dpm_scan_context_build_batched": (I, [P, P, I, I, I, I, D, D, D, P, P, P, P, P, P]),
+    "dpm_scan_context_search_workspace_bytes": (c_size_t, [I, I, I]),
+    "dpm_scan_context_search": (I, [P, P, I, P, P, I, P, I, I, I, P, P, P, P, P]),
 }
 
 

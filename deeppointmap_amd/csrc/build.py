@@ -60,6 +60,7 @@ SOURCES = {
     "map_eval.hip": [],
     "deskew.hip": [],
     "local_map.hip": [],
+    "scan_context.hip": [],
 }
 
 

@@ -986,25 +986,30 @@ ICP_CONVERGED, ICP_MAX_ITER, ICP_NO_MATCH, ICP_SINGULAR = 0, 1, 2, 3
 ICP_NSUM = 29   # debug_system: H upper triangle (21), g (6), matches, squared residuals
 
 
-def icp_target_normals(pcd: torch.Tensor, lengths: torch.Tensor, dst_frame: torch.Tensor, radius: float = 1.0) -> torch.Tensor:
+def icp_target_normals(pcd: torch.Tensor, lengths: torch.Tensor, dst_frame: torch.Tensor, radius: float = 1.0, host=None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(F,N,3) fp32: dpm_point_normals of the valid points of every distinct frame in dst_frame, zeros elsewhere -- the
-    `normals` of icp_refine(metric="plane").  Reads lengths and dst_frame on the host (one synchronisation)."""
+    `normals` of icp_refine(metric="plane").  Reads lengths and dst_frame on the host (one synchronisation), unless the caller
+    knows them already: host = (the frames to compute, the lengths of all F frames) as python ints, and nothing is read.
+    out: an (F,N,3) tensor to write those frames' rows into (the other rows keep what they hold)."""
     _chk(pcd, torch.float32, "pcd"), _chk(lengths, torch.int32, "lengths"), _chk(dst_frame, torch.int32, "dst_frame")
     F, _, N = pcd.shape
     lib = _lib.load()
-    normals = torch.zeros(F, N, 3, device=pcd.device, dtype=torch.float32)
+    normals = torch.zeros(F, N, 3, device=pcd.device, dtype=torch.float32) if out is None else _chk(out, torch.float32, "out")
+    if tuple(normals.shape) != (F, N, 3):
+        raise ValueError("out: expected (F,N,3)")
     ws = torch.empty(lib.dpm_knn_self_workspace_bytes(N), device=pcd.device, dtype=torch.uint8)
-    counts = lengths.tolist()
-    for f in sorted(set(dst_frame.tolist())):
+    frames, counts = (dst_frame.tolist(), lengths.tolist()) if host is None else host
+    for f in sorted(set(int(f) for f in frames)):
         if not 0 <= f < F:
             raise ValueError(f"dst_frame: frame {f} outside [0, {F})")
         n = min(max(int(counts[f]), 0), N)
         if n == 0:
             continue
         xyz = pcd[f, :, :n].t().contiguous()
-        out = torch.empty(n, 3, device=pcd.device, dtype=torch.float32)
-        _lib.check(lib.dpm_point_normals(_ptr(xyz), n, float(radius), _ptr(out), _ptr(ws), _stream(pcd)), "dpm_point_normals")
-        normals[f, :n] = out
+        rows = torch.empty(n, 3, device=pcd.device, dtype=torch.float32)
+        _lib.check(lib.dpm_point_normals(_ptr(xyz), n, float(radius), _ptr(rows), _ptr(ws), _stream(pcd)), "dpm_point_normals")
+        normals[f, :n] = rows
     return normals
 
 
@@ -2313,3 +2318,98 @@ def local_map_export(table, cap_vox, subdiv, half, max_out=None):
     count, keys, sub, owner, xyz = call(int(max_out))
     n = min(int(count.item()), int(max_out))
     return keys[:n], sub[:n], owner[:n], xyz[:n]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Scan Context descriptors and their exhaustive search (csrc/scan_context.hip; loop_closure.py is the caller)
+# ------------------------------------------------------------------------------------------------------------
+SC_MAX_RINGS, SC_MAX_SECTORS, SC_MAX_K = 32, 64, 8
+
+
+def scan_context_tables(rings: int, sectors: int, max_range: float):
+    """the host tables of dpm_scan_context_build, formed in float64 and rounded once: ring_e2 (rings,) float32 = the squared
+    ring edges e_1 .. e_rings, sector_cs (sectors/2 - 1, 2) float32 = (cos, sin) of 2 pi m / sectors, m = 1 .. sectors/2 - 1"""
+    import numpy as np
+    rings, sectors = int(rings), int(sectors)
+    if not (1 <= rings <= SC_MAX_RINGS and 4 <= sectors <= SC_MAX_SECTORS and sectors % 2 == 0):
+        raise ValueError(f"rings in 1..{SC_MAX_RINGS}, sectors even in 4..{SC_MAX_SECTORS}")
+    m = np.arange(1, rings + 1, dtype=np.float64)
+    ring_e2 = ((m * float(max_range) / rings) ** 2).astype(np.float32)
+    a = 2.0 * np.pi * np.arange(1, sectors // 2, dtype=np.float64) / sectors
+    sector_cs = np.stack([np.cos(a), np.sin(a)], axis=1).astype(np.float32)
+    return np.ascontiguousarray(ring_e2), np.ascontiguousarray(sector_cs)
+
+
+def _sc_outputs(out, F: int, rings: int, sectors: int, dev):
+    if out is None:
+        return (torch.empty(F, rings, sectors, device=dev, dtype=torch.float32),
+                torch.empty(F, rings, sectors, device=dev, dtype=torch.float32), torch.empty(F, device=dev, dtype=torch.int64))
+    raw, norm, mask = out
+    _chk(raw, torch.float32, "raw"), _chk(norm, torch.float32, "norm"), _chk(mask, torch.int64, "mask")
+    if raw.numel() != F * rings * sectors or norm.numel() != F * rings * sectors or mask.numel() != F:
+        raise ValueError("scan context outputs: raw / norm (F,rings,sectors) fp32 and mask (F,) int64 (the mask's bits)")
+    return raw, norm, mask
+
+
+def scan_context_build(xyz: torch.Tensor, count: torch.Tensor, rings: int, sectors: int, max_range: float, min_range: float,
+                       z_offset: float, tables=None, out=None):
+    """dpm_scan_context_build: xyz (cap,3) fp32, count (1,) int32 on the GPU -> (raw (1,rings,sectors), norm (1,rings,sectors)
+    fp32, mask (1,) int64 holding the 64 mask bits); `out` = (raw, norm, mask) views of one database row to write into.
+    Three launches, no host synchronisation."""
+    _lidar_arg(xyz, torch.float32, "xyz", xyz.dim() == 2 and xyz.shape[1] == 3, "(cap,3)")
+    _lidar_arg(count, torch.int32, "count", count.numel() == 1, "(1,)")
+    _lidar_dev(xyz=xyz, count=count)
+    ring_e2, sector_cs = scan_context_tables(rings, sectors, max_range) if tables is None else tables
+    dev = xyz.device
+    with torch.cuda.device(dev):
+        raw, norm, mask = _sc_outputs(out, 1, int(rings), int(sectors), dev)
+        _lib.check(_lib.load().dpm_scan_context_build(_ptr(xyz) if xyz.shape[0] else None, _ptr(count), xyz.shape[0], int(rings),
+                                                      int(sectors), float(max_range), float(min_range), float(z_offset),
+                                                      ring_e2.ctypes.data, sector_cs.ctypes.data, _ptr(raw), _ptr(norm), _ptr(mask),
+                                                      _stream(xyz)), "dpm_scan_context_build")
+    return raw, norm, mask
+
+
+def scan_context_build_batched(pcd: torch.Tensor, lengths: torch.Tensor, rings: int, sectors: int, max_range: float,
+                               min_range: float, z_offset: float, tables=None, out=None):
+    """dpm_scan_context_build_batched: pcd (F,3,N) fp32, lengths (F,) int32 -> (raw, norm (F,rings,sectors), mask (F,) int64)"""
+    _lidar_arg(pcd, torch.float32, "pcd", pcd.dim() == 3 and pcd.shape[1] == 3 and pcd.shape[0] >= 1, "(F,3,N), F >= 1")
+    _lidar_arg(lengths, torch.int32, "lengths", lengths.dim() == 1 and lengths.shape[0] == pcd.shape[0], "(F,)")
+    _lidar_dev(pcd=pcd, lengths=lengths)
+    ring_e2, sector_cs = scan_context_tables(rings, sectors, max_range) if tables is None else tables
+    dev, (F, _, N) = pcd.device, pcd.shape
+    with torch.cuda.device(dev):
+        raw, norm, mask = _sc_outputs(out, F, int(rings), int(sectors), dev)
+        _lib.check(_lib.load().dpm_scan_context_build_batched(_ptr(pcd) if N else None, _ptr(lengths), F, N, int(rings), int(sectors),
+                                                              float(max_range), float(min_range), float(z_offset),
+                                                              ring_e2.ctypes.data, sector_cs.ctypes.data, _ptr(raw), _ptr(norm),
+                                                              _ptr(mask), _stream(pcd)), "dpm_scan_context_build_batched")
+    return raw, norm, mask
+
+
+def scan_context_search(q_norm: torch.Tensor, q_mask: torch.Tensor, db_norm: torch.Tensor, db_mask: torch.Tensor,
+                        limit: torch.Tensor, k: int, rows: Optional[int] = None):
+    """dpm_scan_context_search: queries (Q,rings,sectors) fp32 / (Q,) int64 against rows 0 .. limit[q]-1 of the first `rows`
+    (default all) database rows (D,rings,sectors) / (D,) -> dist (Q,k) fp32, row (Q,k) int32, shift (Q,k) int32, ascending,
+    padded with (inf, -1, -1).  Two launches, no host synchronisation."""
+    _chk(q_norm, torch.float32, "q_norm"), _chk(q_mask, torch.int64, "q_mask"), _chk(limit, torch.int32, "limit")
+    _chk(db_norm, torch.float32, "db_norm"), _chk(db_mask, torch.int64, "db_mask")
+    if q_norm.dim() != 3 or db_norm.dim() != 3 or q_norm.shape[1:] != db_norm.shape[1:]:
+        raise ValueError("scan_context_search: q_norm (Q,rings,sectors) and db_norm (D,rings,sectors)")
+    Q, rings, sectors = q_norm.shape
+    D = db_norm.shape[0] if rows is None else int(rows)
+    if not 1 <= D <= db_norm.shape[0] or Q < 1 or q_mask.numel() != Q or limit.numel() != Q or db_mask.numel() != db_norm.shape[0]:
+        raise ValueError("scan_context_search: Q >= 1, 1 <= rows <= D, q_mask / limit (Q,), db_mask (D,)")
+    if not 1 <= int(k) <= SC_MAX_K:
+        raise ValueError(f"k in 1..{SC_MAX_K}")
+    dev = q_norm.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        dist = torch.empty(Q, int(k), device=dev, dtype=torch.float32)
+        row = torch.empty(Q, int(k), device=dev, dtype=torch.int32)
+        shift = torch.empty(Q, int(k), device=dev, dtype=torch.int32)
+        ws = torch.empty(lib.dpm_scan_context_search_workspace_bytes(Q, D, int(k)), device=dev, dtype=torch.uint8)
+        _lib.check(lib.dpm_scan_context_search(_ptr(q_norm), _ptr(q_mask), Q, _ptr(db_norm), _ptr(db_mask), D, _ptr(limit), rings,
+                                               sectors, int(k), _ptr(dist), _ptr(row), _ptr(shift), _ptr(ws), _stream(q_norm)),
+                   "dpm_scan_context_search")
+    return dist, row, shift

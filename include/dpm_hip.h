@@ -1068,6 +1068,48 @@ int dpm_local_map_register_planes(const void *map, int cap_vox, int subdiv, int 
                                   float *rmse, int32_t *iterations, int32_t *status, long long *debug_key, int32_t *debug_sub,
                                   double *debug_system, void *workspace, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- geometric loop closure ---- */
+
+/* Scan Context place descriptors (Kim & Kim, IROS 2018) and the exhaustive search over a database of them
+ * (csrc/scan_context.hip; deeppointmap_amd/loop_closure.py is the caller).  No counterpart in the reference, which
+ * recognises places with its learned loop head only.  DESIGN §7k is the definition; in short:
+ *
+ * A descriptor is a polar grid of rings (1..32) x sectors (even, 4..64) cells; three outputs per frame: raw heights
+ * (rings, sectors) fp32, column-normalised heights (rings, sectors) fp32 and a 64-bit column occupancy mask.  Tables ON THE
+ * HOST, read before the launch: ring_e2 (rings,) fp32 = e_1 .. e_rings, the squared ring edges (float)((m max_range /
+ * rings)^2); sector_cs (sectors/2 - 1, 2) fp32 = (cos, sin) of 2 pi m / sectors, m = 1 .. sectors/2 - 1.  A row of xyz with
+ * a non-finite coordinate or r2 = x*x + y*y == 0 is skipped; it counts iff (float)(min_range^2) <= r2 < e_rings; its ring is
+ * the number of m in 1..rings-1 with r2 >= e_m; half = 0 if y > 0 || (y == 0 && x > 0), else 1 and (x, y) is negated; its
+ * sector is half * sectors/2 + the number of m with cos_m * y - sin_m * x >= 0.  h = z + (float)z_offset counts when > 0 and
+ * the cell keeps the greatest h (integer atomicMax on its bits); an empty cell is 0.  Per column j: n2 = sum_r h*h (r
+ * ascending, sequential fp32), norm = sqrtf(n2), normalised = h / norm where norm > 0 else 0, mask bit j = norm > 0.
+ * Three launches (clear, bin, finish), no host synchronisation, capturable; the same bytes whatever the order of the rows.
+ * DPM_EINVAL: rings / sectors outside their limits, min_range > max_range. */
+/* one frame: xyz (cap,3) fp32 row-major, count (1,) int32 on the device (rows at and past it are never read); raw / norm /
+ * mask point at the frame's row of the database tensors */
+int dpm_scan_context_build(const float *xyz, const int32_t *count, int cap, int rings, int sectors, double max_range,
+                           double min_range, double z_offset, const float *ring_e2, const float *sector_cs, float *raw,
+                           float *norm, unsigned long long *mask, dpm_stream_t stream);
+/* F <= 65535 frames: pcd (F,3,N) fp32 channel-first, lengths (F,) int32 valid leading points; raw / norm (F,rings,sectors),
+ * mask (F,) */
+int dpm_scan_context_build_batched(const float *pcd, const int32_t *lengths, int F, int N, int rings, int sectors,
+                                   double max_range, double min_range, double z_offset, const float *ring_e2,
+                                   const float *sector_cs, float *raw, float *norm, unsigned long long *mask,
+                                   dpm_stream_t stream);
+/* Query q (Q <= 65535; normalised descriptors q_norm (Q,rings,sectors) and masks q_mask (Q,)) against rows
+ * 0 .. limit[q]-1 of the database (db_norm (D,rings,sectors), db_mask (D,); limit (Q,) int32 on the device, clamped to
+ * [0, D]).  For a pair and a shift s in 0..sectors-1: used(s) = popcount_j(mq[j] & mc[(j+s) % sectors]), S(s) = sum_j
+ * <Aq[:,j], Ac[:,(j+s) % sectors]> (the dot product a ring-ascending fp32 fma chain, the sum j ascending), d(s) = used ?
+ * max(1 - S / used, 0) : 1.  The pair's result is its smallest key (bits of d, s); the query's result the K (1..8) smallest
+ * keys (bits of d, row), ascending: dist (Q,K) fp32, row (Q,K) int32, shift (Q,K) int32, padded with (inf, -1, -1).  Query
+ * column j matches candidate column j + s: the query frame's yaw in the candidate's frame is s * 2 pi / sectors.  Exact
+ * selection, fixed summation orders, no atomics: the same bytes on every run.  Two launches, no host synchronisation;
+ * nothing of size (Q, D) is stored: workspace holds one K-list per block of database rows. */
+size_t dpm_scan_context_search_workspace_bytes(int Q, int D, int K);
+int dpm_scan_context_search(const float *q_norm, const unsigned long long *q_mask, int Q, const float *db_norm,
+                            const unsigned long long *db_mask, int D, const int32_t *limit, int rings, int sectors, int K,
+                            float *dist, int32_t *row, int32_t *shift, void *workspace, dpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
