@@ -24,6 +24,7 @@
 // 2 i + g: conflict-free), a tile read as A[row 4 g + q][column i] has rows 36 apart (bank 16 g + i: conflict-free); a tile
 // read both ways is kept in both images (at most 4 x 64 rows: 35 KB).
 #include "dpm_common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -267,13 +268,15 @@ bool rows_ok(const float *p, int ld, long long s) { return p && aligned16(p) && 
 
 bool shape_ok(int B, int M, int N, int heads) { return B >= 1 && M >= 1 && N >= 1 && heads >= 1 && B <= 65535 && heads <= 65535; }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+float *layout(WsCursor &c, int B, int M, int heads) { return c.take256<float>((size_t)B * heads * M); }   // delta: one float per query row
 
 }  // namespace
 
 extern "C" size_t dpm_attention_train_workspace_bytes(int B, int M, int N, int heads) {
     if (!shape_ok(B, M, N, heads)) return 0;
-    return 256 + align256(4 * (size_t)B * heads * M);
+    WsCursor c(nullptr);
+    layout(c, B, M, heads);
+    return c.bytes();
 }
 
 extern "C" int dpm_attention_train_forward(const float *Q, int ldq, long long sq, const float *K, int ldk, long long sk,
@@ -299,7 +302,8 @@ extern "C" int dpm_attention_train_backward(const float *Q, int ldq, long long s
                   rows_ok(dout, ldd, sd));
     DPM_CHECK_ARG(dQ && dK && dV && aligned16(dQ) && aligned16(dK) && aligned16(dV));
     hipStream_t st = (hipStream_t)stream;
-    float *delta = (float *)align256((size_t)(uintptr_t)workspace);
+    WsCursor c(workspace);
+    float *delta = layout(c, B, M, heads);
     const float scale = 1.0f / sqrtf((float)head_dim);
     const Rows q{Q, ldq, sq}, k{K, ldk, sk}, v{V, ldv, sv}, d{dout, ldd, sd};
     hipLaunchKernelGGL(at_delta_kernel, dim3(dpm_cdiv(M, AT_T), heads, B), dim3(AT_T), 0, st, out, ldo, so, dout, ldd, sd, M, heads,

@@ -14,6 +14,8 @@
 // No kernel waits on another workgroup; the only atomics are integer atomics (the ground filter's cell table on
 // order-preserving images of z, the voxel grid's minima), which are associative: two runs give identical bytes.
 #include "block_scan.h"
+#include "workspace.h"
+#include <algorithm>
 
 namespace {
 
@@ -355,14 +357,42 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackArgs a, int s0, int
     padding[(size_t)(s0 + s) * P + j] = j >= n;
 }
 
-inline uintptr_t align256(void *p) { return ((uintptr_t)p + 255) & ~(uintptr_t)255; }
+// One buffer serves the three selections in turn, each with a layout of its own from the aligned base on.
+struct GroundWs { unsigned *table; int *bcount; };   // 16 bytes a cell, then the block counts
+GroundWs ground_layout(WsCursor &c, int capacity, long long ncell) {
+    GroundWs w;
+    w.table = c.take<unsigned>(4 * (size_t)ncell);
+    w.bcount = c.take<int>((size_t)dpm_cdiv(capacity, CH));
+    return w;
+}
+struct VoxelWs {
+    VoxHdr *hdr;
+    unsigned long long *dist;   // 8 + 4 bytes a cell
+    int *grid, *bcount;
+};
+VoxelWs voxel_layout(WsCursor &c, long long max_cells) {
+    VoxelWs w;
+    w.hdr = c.take<VoxHdr>(1);
+    c.align256();
+    w.dist = c.take<unsigned long long>((size_t)max_cells);
+    w.grid = c.take<int>((size_t)max_cells);
+    w.bcount = c.take<int>((size_t)(max_cells / CH + 1));
+    return w;
+}
+int *mask_layout(WsCursor &c, int capacity) { return c.take<int>((size_t)dpm_cdiv(capacity, CH)); }
 
 }  // namespace
 
 extern "C" size_t dpm_augment_workspace_bytes(int capacity, long long cells) {
-    // header + the ground table (16 bytes a cell) or the voxel grids (12 bytes a cell) + the block counts of either domain
+    // header + the ground table (16 bytes a cell) or the voxel grids (12 bytes a cell) + the block counts of either domain:
+    // a bound on the three layouts above rather than the largest of them, kept to the byte (callers size one buffer for the
+    // whole chain by it).  The one size that is a formula of its own; the layouts are measured next to it so that a slice
+    // added to one of them cannot outgrow it unnoticed.
     if (capacity < 0 || cells < 0) return 0;
-    return 1024 + 16 * (size_t)cells + sizeof(int) * ((size_t)cells / CH + (size_t)capacity / CH + 4);
+    WsCursor ground(nullptr), voxel(nullptr), mask(nullptr);
+    ground_layout(ground, capacity, cells), voxel_layout(voxel, cells), mask_layout(mask, capacity);
+    const size_t bound = 1024 + 16 * (size_t)cells + sizeof(int) * ((size_t)cells / CH + (size_t)capacity / CH + 4);
+    return std::max(bound, std::max(ground.bytes(), std::max(voxel.bytes(), mask.bytes())));
 }
 
 extern "C" int dpm_ground_filter(const float *xyz, const int32_t *idx_in, const int32_t *count, int capacity, int img_len,
@@ -372,8 +402,8 @@ extern "C" int dpm_ground_filter(const float *xyz, const int32_t *idx_in, const 
     DPM_CHECK_ARG(grid_width > 0.0 && (long long)img_len * img_width <= (1 << 26) && out_xyz != xyz && out_count != count);
     hipStream_t st = (hipStream_t)stream;
     const int ncell = img_len * img_width, max_blocks = (int)dpm_cdiv(capacity, CH);
-    unsigned *table = (unsigned *)align256(workspace);
-    int *bcount = (int *)(table + 4 * (size_t)ncell);
+    WsCursor c(workspace);
+    const auto [table, bcount] = ground_layout(c, capacity, ncell);
     GroundKeep k;
     k.xyz = xyz, k.count = count, k.cap = capacity, k.L = img_len, k.W = img_width, k.preserve = preserve_sparse_ground != 0;
     k.identity = !(ground_height > 0.0);   // transforms.py:186
@@ -392,12 +422,9 @@ extern "C" int dpm_voxel_select(const float *xyz, const int32_t *idx_in, const i
     DPM_CHECK_ARG(xyz && count && out_xyz && status && workspace && capacity >= 1 && voxel_size > 0.0);
     DPM_CHECK_ARG(max_cells >= CH && max_cells <= 0x7fffffffLL && (retention == 0 || retention == 1) && out_xyz != xyz);
     hipStream_t st = (hipStream_t)stream;
-    uintptr_t p = align256(workspace);
-    VoxHdr *hdr = (VoxHdr *)p;
-    unsigned long long *dist = (unsigned long long *)(p + 256);
-    int *grid = (int *)(dist + max_cells);
+    WsCursor c(workspace);
+    const auto [hdr, dist, grid, bcount] = voxel_layout(c, max_cells);
     const int max_blocks = (int)(max_cells / CH + 1);
-    int *bcount = grid + max_cells;
     const float vs = (float)voxel_size;
     hipLaunchKernelGGL(vox_bbox_kernel, dim3(1), dim3(1024), 0, st, xyz, count, capacity, vs, max_cells, hdr);
     hipLaunchKernelGGL(vox_fill_kernel, dim3(2048), dim3(256), 0, st, hdr, grid, retention ? dist : nullptr);
@@ -426,7 +453,8 @@ extern "C" int dpm_mask_select(const float *xyz, const int32_t *idx_in, const in
     k.dmin = (float)min_dis, k.dmax = (float)max_dis, k.ratio = (float)drop_ratio, k.u = u;
     for (int i = 0; i < MAX_WEDGES; ++i)
         for (int j = 0; j < 4; ++j) k.w[i][j] = i < n_wedges ? wedges[4 * i + j] : 0.f;   // `wedges` is HOST memory
-    return compact(k, (int)dpm_cdiv(capacity, CH), (int *)align256(workspace), xyz, idx_in, out_xyz, out_idx, capacity, out_count,
+    WsCursor c(workspace);
+    return compact(k, (int)dpm_cdiv(capacity, CH), mask_layout(c, capacity), xyz, idx_in, out_xyz, out_idx, capacity, out_count,
                    (hipStream_t)stream);
 }
 

@@ -4,6 +4,7 @@
 // Compiled with -ffp-contract=off: every fused multiply-add is an explicit fmaf().
 #include "dpm_common.h"
 #include "topk_emulate.h"
+#include "workspace.h"
 #include <algorithm>
 
 namespace {
@@ -1458,9 +1459,19 @@ extern "C" int dpm_attention_planes(const float *Q, int ldq, long long sq, const
 
 // Key-split form (few queries, many keys; see attention_kernel<SPLIT>): same arguments as dpm_attention_shifted plus the
 // number of key ranges and a workspace of dpm_attention_split_workspace_bytes(B, M, heads, head_dim, nsplit) bytes.
+struct SplitWs { float *part_o, *part_ml; };   // per key range: the unnormalised outputs, then (max, sum) per query and head
+static SplitWs split_layout(WsCursor &c, int B, int M, int heads, int head_dim, int nsplit) {
+    const size_t rows = (size_t)nsplit * B * M;
+    SplitWs w;
+    w.part_o = c.take<float>(rows * heads * head_dim);
+    w.part_ml = c.take<float>(rows * 2 * heads);
+    return w;
+}
 extern "C" size_t dpm_attention_split_workspace_bytes(int B, int M, int heads, int head_dim, int nsplit) {
     if (B <= 0 || M <= 0 || heads <= 0 || head_dim <= 0 || nsplit <= 0) return 0;
-    return sizeof(float) * (size_t)nsplit * B * M * ((size_t)heads * head_dim + 2 * (size_t)heads) + 256;
+    WsCursor c(nullptr);
+    split_layout(c, B, M, heads, head_dim, nsplit);
+    return c.bytes();
 }
 
 extern "C" int dpm_attention_split(const float *Q, int ldq, long long sq, const float *K, int ldk, long long sk,
@@ -1475,8 +1486,8 @@ extern "C" int dpm_attention_split(const float *Q, int ldq, long long sq, const 
     const int chunk = ((N + 64 * nsplit - 1) / (64 * nsplit)) * 64;
     DPM_CHECK_ARG((long long)(nsplit - 1) * chunk < N);
     hipStream_t st = (hipStream_t)stream;
-    float *part_o = (float *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    float *part_ml = part_o + (size_t)nsplit * B * M * heads * HD;
+    WsCursor c(workspace);
+    const auto [part_o, part_ml] = split_layout(c, B, M, heads, HD, nsplit);
     const bool vec = ldk % 4 == 0 && ldv % 4 == 0 && sk % 4 == 0 && sv % 4 == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)V & 15) == 0;
     const float scale = (float)(1.0 / sqrt((double)head_dim));
     const dim3 grid(dpm_cdiv(M, 64) * nsplit, heads, B);
@@ -1518,12 +1529,42 @@ constexpr long long TOPK_BIG = 1LL << 18;  // elements per problem above which t
 // row slabs of the column statistics: none up to 512 rows (the batched 256 x 256 hot path keeps its one-kernel form)
 static int col_splits(int M) { return M <= 512 ? 1 : std::min(64, (M + 127) / 128); }
 
+struct PairingWs {
+    float *rmax, *rsum, *cmax, *csum;   // row and column statistics, from the caller's pointer on
+    TopkState *state;                   // grid-wide top-k (M N >= TOPK_BIG): state, the entries above the threshold, the ties
+    float *gt_v;
+    int *gt_i, *eq_i;
+    float *pmax, *psum;                 // column statistics per row slab (col_splits(M) > 1)
+};
+static PairingWs pairing_layout(WsCursor &c, int batch, int M, int N) {
+    const size_t BM = (size_t)batch * M, BN = (size_t)batch * N, splits = (size_t)col_splits(M);
+    PairingWs w = {};
+    w.rmax = c.take<float>(BM), w.rsum = c.take<float>(BM), w.cmax = c.take<float>(BN), w.csum = c.take<float>(BN);
+    // The two optional regions start at the running size rounded up, and the running size grows by what they hold plus
+    // 256 bytes without being rounded itself: they are carved from a rounded copy of the cursor.
+    if ((long long)M * N >= TOPK_BIG) {
+        WsCursor r = c;
+        r.align256();
+        const size_t at = r.bytes();
+        w.state = r.take<TopkState>((size_t)batch);
+        w.gt_v = r.take<float>((size_t)batch * TK_MAXK);
+        w.gt_i = r.take<int>((size_t)batch * TK_MAXK), w.eq_i = r.take<int>((size_t)batch * TK_MAXK);
+        c.skip(256 + r.bytes() - at);
+    }
+    c.skip(256);   // the 256 bytes the size has always counted behind the statistics; the slabs live behind everything else
+    if (splits > 1) {
+        WsCursor r = c;
+        r.align256();
+        const size_t at = r.bytes();
+        w.pmax = r.take<float>(BN * splits), w.psum = r.take<float>(BN * splits);
+        c.skip(256 + r.bytes() - at);
+    }
+    return w;
+}
 extern "C" size_t dpm_pairing_workspace_bytes(int batch, int M, int N) {
-    size_t b = sizeof(float) * 2 * (size_t)batch * ((size_t)M + (size_t)N) + 256;
-    if ((long long)M * N >= TOPK_BIG)
-        b += 256 + (size_t)batch * (sizeof(TopkState) + (size_t)TK_MAXK * (sizeof(float) + 2 * sizeof(int)));
-    if (col_splits(M) > 1) b += 256 + sizeof(float) * 2 * (size_t)batch * col_splits(M) * (size_t)N;
-    return b;
+    WsCursor c(nullptr, false);
+    pairing_layout(c, batch, M, N);
+    return c.bytes();
 }
 
 extern "C" int dpm_dual_softmax_topk(float *S, int batch, int M, int N, double tau, int k, float *out_val,
@@ -1532,18 +1573,15 @@ extern "C" int dpm_dual_softmax_topk(float *S, int batch, int M, int N, double t
     DPM_CHECK_ARG(k >= 1 && (long long)k <= (long long)M * N);
     if (k > TK_MAXK || (long long)M * N > 0x7fffffffLL) return DPM_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const size_t BM = (size_t)batch * M, BN = (size_t)batch * N;
-    float *rmax = (float *)workspace, *rsum = rmax + BM, *cmax = rsum + BM, *csum = cmax + BN;
+    const size_t BM = (size_t)batch * M;
+    WsCursor c(workspace, false);
+    const auto [rmax, rsum, cmax, csum, state, gt_v, gt_i, eq_i, pmax, psum] = pairing_layout(c, batch, M, N);
     const float itau = 1.0f / (float)tau;  // torch divides by the scalar as a multiplication by 1/tau
     hipLaunchKernelGGL(row_stats_kernel, dim3(dpm_cdiv((long long)BM, 4)), dim3(256), 0, st, S, (int)BM, N, itau, rmax, rsum);
     const int splits = col_splits(M);
     if (splits == 1) {
         hipLaunchKernelGGL(col_stats_kernel, dim3(dpm_cdiv(N, 64), batch), dim3(256), 0, st, S, M, N, itau, cmax, csum);
-    } else {  // slabs live behind everything else in the workspace
-        size_t off = sizeof(float) * 2 * (BM + BN) + 256;
-        if ((long long)M * N >= TOPK_BIG)
-            off += 256 + (size_t)batch * (sizeof(TopkState) + (size_t)TK_MAXK * (sizeof(float) + 2 * sizeof(int)));
-        float *pmax = (float *)((((uintptr_t)workspace + off) + 255) & ~(uintptr_t)255), *psum = pmax + (size_t)batch * splits * N;
+    } else {
         for (int phase = 0; phase < 2; ++phase)
             hipLaunchKernelGGL(col_slab_kernel, dim3(dpm_cdiv(N, 64), batch * splits), dim3(256), 0, st, S, M, N, itau, splits,
                                pmax, psum, phase);
@@ -1565,11 +1603,6 @@ extern "C" int dpm_dual_softmax_topk(float *S, int batch, int M, int N, double t
     // grid-wide radix select.  Exact ties at the threshold beyond TK_MAXK entries (degenerate inputs) would
     // overflow the tie list; they cannot occur for k <= TK_MAXK distinct-valued softmax products in practice and
     // are clamped (the one-workgroup kernel above has the fully general path).
-    uintptr_t wp = ((uintptr_t)(csum + BN) + 255) & ~(uintptr_t)255;
-    TopkState *state = (TopkState *)wp;
-    float *gt_v = (float *)(state + batch);
-    int *gt_i = (int *)(gt_v + (size_t)batch * TK_MAXK);
-    int *eq_i = gt_i + (size_t)batch * TK_MAXK;
     hipError_t e = hipMemsetAsync(state, 0, sizeof(TopkState) * (size_t)batch, st);
     if (e != hipSuccess) return (int)e;
     const unsigned G = (unsigned)std::min<long long>(2048 / batch + 1, (n + 1023) / 1024);
@@ -1597,8 +1630,16 @@ extern "C" int dpm_mean_rows(const float *x, int B, int R, int C, float *out, in
     return dpm_launch_status();
 }
 
+// nine floats per weight, 2k weights per problem, from the caller's pointer on
+static float *kabsch_layout(WsCursor &c, int batch, int k) {
+    float *ws = c.take<float>((size_t)batch * (size_t)(2 * k) * 9);
+    c.skip(256);   // slack the size has always carried
+    return ws;
+}
 extern "C" size_t dpm_kabsch_workspace_bytes(int batch, int k) {
-    return (size_t)batch * (size_t)(2 * k) * 9 * sizeof(float) + 256;
+    WsCursor c(nullptr, false);
+    kabsch_layout(c, batch, k);
+    return c.bytes();
 }
 
 extern "C" int dpm_corr_kabsch(const float *offsets, const float *src_xyz, int ld_src, long long stride_src,
@@ -1622,9 +1663,10 @@ extern "C" int dpm_corr_kabsch(const float *offsets, const float *src_xyz, int l
         hipError_t e = hipFuncSetAttribute((const void *)corr_kabsch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kabsch_lds);
         if (e != hipSuccess) return (int)e;
     }
+    WsCursor c(workspace, false);
     hipLaunchKernelGGL(corr_kabsch_kernel, dim3(batch), dim3(KB), kabsch_lds, (hipStream_t)stream, offsets, src_xyz, ld_src,
                        stride_src, dst_xyz, ld_dst, stride_dst, src_idx, dst_idx, conf, k,
-                       (float)(eps_offset * eps_offset), num_iter, (float)std_ratio, (float *)workspace, result, header,
+                       (float)(eps_offset * eps_offset), num_iter, (float)std_ratio, kabsch_layout(c, batch, k), result, header,
                        header_stride);
     return dpm_launch_status();
 }

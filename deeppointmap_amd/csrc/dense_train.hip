@@ -30,6 +30,7 @@
 // 16-byte aligned (ld % 4 != 0 or a misaligned base: W[:, :Cin] of a (Cout, Cin + 3) weight) are staged with scalar loads, as
 // the VEC switch of gemm.hip does.
 #include "dpm_common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -338,7 +339,12 @@ int slices(long long R, int most = DT_SPLITS) {
     return nt < most ? nt : most;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// one slice both backward calls start at: the dW partials, and room for the row kernel's column partials: all DT_CSPLITS of
+// them as soon as the rows exceed DT_SPLITS tiles, so that the size is constant from there on
+float *layout(WsCursor &c, long long R, int Cin, int Cout) {
+    const size_t S = (size_t)slices(R), S2 = row_tiles(R) > DT_SPLITS ? (size_t)DT_CSPLITS : S;
+    return c.take256<float>(S * ((size_t)Cout * Cin + Cout) + S2 * 2 * (size_t)Cout);
+}
 
 int zero_async(float *p, size_t n, hipStream_t st) {
     const hipError_t e = p ? hipMemsetAsync(p, 0, 4 * n, st) : hipSuccess;
@@ -359,10 +365,9 @@ void launch_ln(hipStream_t st, unsigned tiles, const float *x, int ldx, const fl
 
 extern "C" size_t dpm_dense_train_workspace_bytes(long long R, int Cin, int Cout) {
     if (!shape_ok(R, Cin, Cout)) return 0;
-    // the dW partials, and room for the row kernel's column partials: all DT_CSPLITS of them as soon as the rows exceed
-    // DT_SPLITS tiles, so that the size is constant from there on
-    const size_t S = (size_t)slices(R), S2 = row_tiles(R) > DT_SPLITS ? (size_t)DT_CSPLITS : S;
-    return 256 + align256(4 * S * ((size_t)Cout * Cin + Cout) + 4 * S2 * 2 * (size_t)Cout);
+    WsCursor c(nullptr);
+    layout(c, R, Cin, Cout);
+    return c.bytes();
 }
 
 extern "C" int dpm_dense_train_forward(const float *x, int ldx, const float *W, int ldw, const float *bias, const float *residual,
@@ -408,7 +413,8 @@ extern "C" int dpm_dense_train_backward_rows(const float *dy, const float *out, 
     if (!out) out = dy;   // never read for ACT_NONE
     hipLaunchKernelGGL(dt_bwd_rows_kernel, dim3(dpm_cdiv(R, 4)), dim3(DT_T), 0, st, dy, out, h, stats, gamma, R, Cout, act, g, dh);
     if (dgamma) {
-        float *ws = (float *)align256((size_t)(uintptr_t)workspace);
+        WsCursor c(workspace);
+        float *ws = layout(c, R, 1, Cout);
         const int nt = row_tiles(R), S = slices(R, DT_CSPLITS);
         hipLaunchKernelGGL(dt_colsum_kernel, dim3(dpm_cdiv(Cout, 64), S), dim3(DT_T), 0, st, dy, out, h, stats, R, Cout, act, nt, S, ws);
         hipLaunchKernelGGL(dt_reduce_kernel, dim3(dpm_cdiv(2 * (long long)Cout, DT_T)), dim3(DT_T), 0, st, ws, S, 2 * (size_t)Cout,
@@ -433,7 +439,8 @@ extern "C" int dpm_dense_train_backward_gemm(const float *dh, const float *x, in
                            (const float *)nullptr, R, Cout, Cin, DPM_ACT_NONE, (int)vec_ok(dh, Cout), (int)vec_ok(W, ldw), dx,
                            (float *)nullptr, (float *)nullptr);
     if (dW) {
-        float *ws = (float *)align256((size_t)(uintptr_t)workspace);
+        WsCursor c(workspace);
+        float *ws = layout(c, R, Cin, Cout);
         const int S = slices(R);
         const size_t n = (size_t)Cout * Cin + Cout;
         hipLaunchKernelGGL(dt_dw_kernel, dim3(dpm_cdiv(Cin, 64), dpm_cdiv(Cout, 64), S), dim3(DT_T), 0, st, dh, (int)vec_ok(dh, Cout), x,

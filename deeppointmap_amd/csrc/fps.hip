@@ -465,16 +465,26 @@ int launch(const float *xyz, const int32_t *lengths, int B, int N, int K, int32_
 }  // namespace
 
 // fps_tree.hip
-size_t dpm_fps_str_bucket_workspace_bytes(int B, int N);
-int dpm_fps_str_bucket_sort(const float *xyz, const int32_t *lengths, int B, int N, float4 *pts, float *closest, float4 *tmp,
-                            hipStream_t st);
+FpsStrWs dpm_fps_str_bucket_layout(WsCursor &c, int B, int N);
+int dpm_fps_str_bucket_sort(const float *xyz, const int32_t *lengths, int B, int N, const FpsStrWs &w, hipStream_t st);
+
+// bucket algorithm over Z-ordered cells: float4 sorted points + closest, per frame.  (The plain kernel beyond 65 536 points
+// keeps its B * N `closest` at the caller's pointer: less than this.)
+struct BucketWs { float4 *pts; float *closest; };
+static BucketWs bucket_layout(WsCursor &c, int B, int N) {
+    BucketWs w;
+    c.skip(256);   // 256 B of debug counters in front
+    w.pts = c.take<float4>((size_t)B * (size_t)N);
+    w.closest = c.take<float>((size_t)B * (size_t)N);
+    return w;
+}
 
 extern "C" size_t dpm_fps_workspace_bytes(int B, int N, int K) {
     (void)K;
-    // bucket algorithms: float4 sorted points + closest, per frame (Sort-Tile-Recursive packing: see fps_tree.hip)
-    const size_t bucket = (size_t)B * (size_t)N * (sizeof(float4) + sizeof(int32_t)) + 512;
-    const size_t strb = N > 16384 && N <= 65536 ? dpm_fps_str_bucket_workspace_bytes(B, N) : 0;
-    return bucket > strb ? bucket : strb;
+    WsCursor bucket(nullptr), strb(nullptr);
+    bucket_layout(bucket, B, N);
+    if (N > 16384 && N <= 65536) dpm_fps_str_bucket_layout(strb, B, N);   // Sort-Tile-Recursive packing: see fps_tree.hip
+    return bucket.bytes() > strb.bytes() ? bucket.bytes() : strb.bytes();
 }
 
 // algo: 0 = by size; 1 = plain kernel (any N); 2 = bucket kernel over Z-ordered grid cells (N <= 65 536); 5 = bucket kernel
@@ -495,11 +505,11 @@ static int fps_dispatch(const float *xyz, const int32_t *lengths, const int32_t 
         DPM_CHECK_ARG(workspace != nullptr);
         if (N <= 16384 || N > 65536) return DPM_EUNSUPPORTED;
         const int slots = 65536;
-        uintptr_t p = (((uintptr_t)workspace + 255) & ~(uintptr_t)255) + 256;
-        float4 *pts = (float4 *)p;
-        float *closest = (float *)(pts + (size_t)B * slots);
-        float4 *tmp = (float4 *)(((uintptr_t)(closest + (size_t)B * slots) + 255) & ~(uintptr_t)255);
-        const int rc = dpm_fps_str_bucket_sort(xyz, lengths, B, N, pts, closest, tmp, st);
+        WsCursor c(workspace);
+        const FpsStrWs w = dpm_fps_str_bucket_layout(c, B, N);
+        float4 *pts = w.pts;
+        float *closest = w.closest;
+        const int rc = dpm_fps_str_bucket_sort(xyz, lengths, B, N, w, st);
         if (rc != DPM_OK) return rc;
         if (dpm_knob("DPM_ABLATE_FPS_ROUNDS", 0)) return dpm_launch_status();  // -DDPM_EXPERIMENT builds only: the packing without the rounds (scripts/step_model.py)
 #ifdef DPM_EXPERIMENT
@@ -521,12 +531,11 @@ static int fps_dispatch(const float *xyz, const int32_t *lengths, const int32_t 
     if (algo >= 2) {
         if (N > 64 * MAXBUCKETS) return DPM_EUNSUPPORTED;
         DPM_CHECK_ARG(workspace != nullptr);
-        uintptr_t p = (((uintptr_t)workspace + 255) & ~(uintptr_t)255) + 256;  // 256 B of debug counters in front
-        float4 *pts = (float4 *)p;
+        WsCursor c(workspace);
+        const auto [pts, closest] = bucket_layout(c, B, N);
 #ifdef DPM_FPS_STATS
-        (void)hipMemsetAsync((void *)(p - 256), 0, 256, st);
+        (void)hipMemsetAsync((char *)pts - 256, 0, 256, st);
 #endif
-        float *closest = (float *)(pts + (size_t)B * N);
         hipLaunchKernelGGL(fps_bucket_sort_kernel, dim3(B), dim3(FB), 0, st, xyz, lengths, N, pts, closest);
         hipLaunchKernelGGL(fps_bucket_kernel<false>, dim3(B), dim3(FB), 0, st, xyz, lengths, N, K, pts, closest, idx,
                            new_xyz, new_lengths, 0, start, 0, 0);

@@ -52,7 +52,7 @@ struct StrAux {       // per frame, behind the sort's scratch array
 };
 __host__ __device__ inline size_t str_aux_bytes(int N) {
     const size_t chunks = (size_t)(N + SC_CHUNK - 1) / SC_CHUNK;
-    return (chunks * 4 * sizeof(float) + chunks * XB * sizeof(int) + 255) & ~(size_t)255;
+    return ws_align256(chunks * 4 * sizeof(float) + chunks * XB * sizeof(int));
 }
 __device__ __forceinline__ StrAux str_aux(char *aux, int b, int N) {
     char *p = aux + (size_t)b * str_aux_bytes(N);
@@ -253,16 +253,30 @@ __global__ __launch_bounds__(SC_T) void str_ysort_kernel(const int32_t *__restri
 }  // namespace
 
 // algo 5: the Sort-Tile-Recursive packing for fps.hip's bucket kernel (bucket = leaf; a 4 x 4 block of neighbouring
-// leaves lands on 16 different waves).  Workspace: TL * LEAF float4 + TL * LEAF float per frame, then N float4 scratch.
-size_t dpm_fps_str_bucket_workspace_bytes(int B, int N) {
-    return (size_t)B * ((size_t)TL * LEAF * (sizeof(float4) + sizeof(float)) + (size_t)N * sizeof(float4) + str_aux_bytes(N)) + 1536;
+// leaves lands on 16 different waves).  Workspace: behind the bucket kernel's counters TL * LEAF float4 + TL * LEAF float
+// per frame, then B * N float4 of scratch, followed (256-byte aligned) by B * str_aux_bytes(N) bytes for the chunk passes.
+FpsStrWs dpm_fps_str_bucket_layout(WsCursor &c, int B, int N) {
+    FpsStrWs w;
+    c.skip(256);   // the bucket kernel's debug counters
+    w.pts = c.take<float4>((size_t)B * TL * LEAF);
+    w.closest = c.take<float>((size_t)B * TL * LEAF);
+    c.align256();
+    w.tmp = c.take<float4>((size_t)B * N);
+    // aux starts rounded up, but the size has always counted the scratch before it unrounded (the slack below covers the
+    // padding): it is carved from a rounded copy of the cursor
+    WsCursor r = c;
+    r.align256();
+    w.aux = r.take<char>((size_t)B * str_aux_bytes(N));
+    c.skip((size_t)B * str_aux_bytes(N));
+    c.skip(1024);  // slack the size has always carried
+    return w;
 }
-// tmp: B * N float4 of scratch, followed (256-byte aligned) by B * str_aux_bytes(N) bytes for the chunk passes
-int dpm_fps_str_bucket_sort(const float *xyz, const int32_t *lengths, int B, int N, float4 *pts, float *closest, float4 *tmp,
-                            hipStream_t st) {
+int dpm_fps_str_bucket_sort(const float *xyz, const int32_t *lengths, int B, int N, const FpsStrWs &w, hipStream_t st) {
     if (N > TL * LEAF) return DPM_EUNSUPPORTED;
     const int extra = dpm_knob("DPM_PRICE_FPS_SORT", 0);   // -DDPM_EXPERIMENT builds only: the (idempotent) sort n more times = its price inside the pipelined step
-    char *aux = (char *)(((uintptr_t)(tmp + (size_t)B * N) + 255) & ~(uintptr_t)255);
+    float4 *pts = w.pts, *tmp = w.tmp;
+    float *closest = w.closest;
+    char *aux = w.aux;
     const int chunks = (N + SC_CHUNK - 1) / SC_CHUNK;
     for (int rep = 0; rep <= extra; ++rep) {
         hipLaunchKernelGGL(str_chunk_kernel<0>, dim3(chunks, B), dim3(SC_T), 0, st, xyz, lengths, N, pts, closest, tmp, aux);

@@ -1,8 +1,16 @@
 // Wave-level helpers shared by the farthest-point-sampling kernels (fps.hip, fps_tree.hip).
 #pragma once
 #include "dpm_common.h"
+#include "workspace.h"
 
 #pragma clang fp contract(off)
+
+struct FpsStrWs {   // workspace of the Sort-Tile-Recursive bucket path (fps_tree.hip lays it out, fps.hip runs the rounds on it)
+    float4 *pts;
+    float *closest;
+    float4 *tmp;
+    char *aux;
+};
 
 namespace {
 

@@ -20,6 +20,7 @@
 // reduce_kernel adds the partials in wave order.  Which points a wave owns depends on the shapes only, so two runs give identical
 // bytes.
 #include "dpm_common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -340,12 +341,13 @@ __global__ __launch_bounds__(256) void group_train_reduce_kernel(const float *__
 
 struct Plan {
     int rpw, ppw, waves;
-    size_t off_mask, off_cursor, off_offsets, off_lists, off_entries, off_partial, bytes;
+    uint32_t *mask;
+    int32_t *cursor, *offsets, *lists, *entries;
+    float *partial;
 };
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-bool make_plan(int B, int N, int S, int K, int Cout, Plan &p) {
+// the launch plan and, through the cursor, the workspace layout (the base is taken as given: the caller's 16-byte alignment)
+bool make_plan(WsCursor &c, int B, int N, int S, int K, int Cout, Plan &p) {
     if (!(Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512) || !(K == 16 || K == 32)) return false;
     const long long points = (long long)B * N, rows = (long long)B * S * K;
     if (B < 1 || N < 1 || S < 1 || points >= (1LL << 30) || rows >= (1LL << 31) || (long long)S * K >= (1LL << 31)) return false;
@@ -355,14 +357,12 @@ bool make_plan(int B, int N, int S, int K, int Cout, Plan &p) {
     const long long cap = 131072 / Cout > 256 ? 131072 / Cout : 256;   // the partials stay at 2.5 MiB whatever the width
     p.ppw = (int)((groups + cap - 1) / cap);
     p.waves = (int)((groups + p.ppw - 1) / p.ppw);
-    size_t o = 0;
-    p.off_mask = o, o = align256(o + sizeof(uint32_t) * (size_t)B * S);
-    p.off_cursor = o, o = align256(o + sizeof(int32_t) * (size_t)points);
-    p.off_offsets = o, o = align256(o + sizeof(int32_t) * ((size_t)points + 1));
-    p.off_lists = o, o = align256(o + sizeof(int32_t) * (size_t)rows);
-    p.off_entries = o, o = align256(o + sizeof(int32_t) * (size_t)rows);
-    p.off_partial = o, o = align256(o + sizeof(float) * (size_t)p.waves * 5 * Cout);
-    p.bytes = o;
+    p.mask = c.take256<uint32_t>((size_t)B * S);
+    p.cursor = c.take256<int32_t>((size_t)points);
+    p.offsets = c.take256<int32_t>((size_t)points + 1);
+    p.lists = c.take256<int32_t>((size_t)rows);
+    p.entries = c.take256<int32_t>((size_t)rows);
+    p.partial = c.take256<float>((size_t)p.waves * 5 * Cout);
     return true;
 }
 
@@ -375,7 +375,8 @@ extern "C" int dpm_group_train_forward(const float *P, const float *xyz, const f
     DPM_CHECK_ARG(B >= 1 && N >= 1 && S >= 1 && K >= 1 && ldw_rel >= 3 && radius > 0.0);
     DPM_CHECK_ARG(((uintptr_t)P & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)slots & 3) == 0);
     Plan pl;
-    if (!make_plan(B, N, S, K, Cout, pl)) return DPM_EUNSUPPORTED;
+    WsCursor none(nullptr, false);   // the forward has no workspace: the plan only says whether the shape is supported
+    if (!make_plan(none, B, N, S, K, Cout, pl)) return DPM_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)B * S;
     const float inv_r = 1.0f / (float)radius;
@@ -396,7 +397,8 @@ extern "C" int dpm_group_train_forward(const float *P, const float *xyz, const f
 
 extern "C" size_t dpm_group_train_workspace_bytes(int B, int N, int S, int K, int Cout) {
     Plan pl;
-    return make_plan(B, N, S, K, Cout, pl) ? pl.bytes : 0;
+    WsCursor c(nullptr, false);
+    return make_plan(c, B, N, S, K, Cout, pl) ? c.bytes() : 0;
 }
 
 extern "C" int dpm_group_train_backward(const float *P, const float *xyz, const float *centers, const int32_t *idx,
@@ -408,13 +410,12 @@ extern "C" int dpm_group_train_backward(const float *P, const float *xyz, const 
     DPM_CHECK_ARG(((uintptr_t)P & 15) == 0 && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)dP & 15) == 0 &&
                   ((uintptr_t)slots & 3) == 0 && ((uintptr_t)workspace & 15) == 0);
     Plan pl;
-    if (!make_plan(B, N, S, K, Cout, pl)) return DPM_EUNSUPPORTED;
+    WsCursor c(workspace, false);
+    if (!make_plan(c, B, N, S, K, Cout, pl)) return DPM_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    uint32_t *mask = reinterpret_cast<uint32_t *>(ws + pl.off_mask);
-    int32_t *cursor = reinterpret_cast<int32_t *>(ws + pl.off_cursor), *offsets = reinterpret_cast<int32_t *>(ws + pl.off_offsets);
-    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *entries = reinterpret_cast<int32_t *>(ws + pl.off_entries);
-    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
+    uint32_t *mask = pl.mask;
+    int32_t *cursor = pl.cursor, *offsets = pl.offsets, *lists = pl.lists, *entries = pl.entries;
+    float *partial = pl.partial;
     const long long total = (long long)B * S, points = (long long)B * N, rows = total * K;
     const int kshift = K == 16 ? 4 : 5;
     const float inv_r = 1.0f / (float)radius;

@@ -19,6 +19,7 @@
 #include "block_scan.h"
 #include "cell_grid.h"
 #include "gn_solve.h"
+#include "workspace.h"
 
 namespace {
 
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(IcpArgs A, double tol_rot
 size_t slice_bytes(int N) {
     const size_t b = 256 + sizeof(int) * (size_t)(GMAX * GMAX + 4) + sizeof(float4) * (size_t)N +
                      sizeof(double) * GN_NSUM_PAD * (size_t)dpm_cdiv(N, 256);
-    return (b + 255) & ~(size_t)255;
+    return ws_align256(b);
 }
 
 }  // namespace
@@ -247,7 +248,7 @@ extern "C" int dpm_icp_refine_batched(const float *pcd, int F, int N, const int3
     IcpArgs A{};
     A.pcd = pcd, A.normals = normals, A.lengths = lengths, A.src = src_frame, A.dst = dst_frame;
     A.F = F, A.N = N, A.n_pairs = n_pairs;
-    A.ws = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), A.ws_stride = slice_bytes(N);
+    A.ws = (char *)ws_align256((uintptr_t)workspace), A.ws_stride = slice_bytes(N);
     A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
     A.dbg_match = debug_match, A.dbg_system = debug_system;
     const dim3 per_point(dpm_cdiv(N, 256), n_pairs);

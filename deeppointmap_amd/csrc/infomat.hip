@@ -10,6 +10,7 @@
 // products gives a matrix that depends on ten moments (n, sum x, y, z, xx, yy, zz, xy, xz, yz);
 // they are accumulated in fp64 and rounded once to the fp32 6x6 the reference returns.
 #include "cell_grid.h"
+#include "workspace.h"
 #include <type_traits>
 
 namespace {
@@ -526,7 +527,7 @@ static size_t ws_slice_bytes(int N1, int N2) {
     size_t b = 256 + sizeof(int) * (size_t)(GMAX * GMAX + 1) + 12 + sizeof(float4) * (size_t)N2 +
                10 * sizeof(long long) * (size_t)dpm_cdiv(N1, 256) +
                sizeof(float4) * (size_t)N2 + sizeof(int) * ((size_t)dpm_cdiv(N2, GB_CHUNK) * (GMAX + 8) + GMAX + 4);  // row-sorted copy, row histograms, row starts, chunk bounds
-    return (b + 255) & ~(size_t)255;
+    return ws_align256(b);
 }
 
 extern "C" size_t dpm_infomat_workspace_bytes(int n_pairs, int N1, int N2) {
@@ -564,7 +565,7 @@ static PairArgs batched_args(const float *pcd, int N, const int32_t *src_frame, 
                              void *workspace) {
     PairArgs A{};
     A.pcd1 = pcd, A.pcd2 = pcd, A.f1 = src_frame, A.f2 = dst_frame, A.stride1 = 3LL * N, A.stride2 = 3LL * N;
-    A.ws = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), A.ws_stride = ws_slice_bytes(N, N);
+    A.ws = (char *)ws_align256((uintptr_t)workspace), A.ws_stride = ws_slice_bytes(N, N);
     A.N1 = N, A.N2 = N;
     return A;
 }
@@ -575,7 +576,7 @@ extern "C" int dpm_information_matrix(const float *pcd1, int N1, const float *pc
     PairArgs A{};
     A.pcd1 = pcd1, A.pcd2 = pcd2, A.f1 = nullptr, A.f2 = nullptr, A.stride1 = 0, A.stride2 = 0;
     A.Rt = Rt, A.rt_stride = 0, A.out = out6x6, A.out_stride = 0;
-    A.ws = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), A.ws_stride = ws_slice_bytes(N1, N2);
+    A.ws = (char *)ws_align256((uintptr_t)workspace), A.ws_stride = ws_slice_bytes(N1, N2);
     A.N1 = N1, A.N2 = N2;
     return launch_infomat(A, 1, radius, (hipStream_t)stream);
 }

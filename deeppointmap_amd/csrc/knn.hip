@@ -34,6 +34,7 @@
 //    back to a full scan for its nearest point.
 #include "block_scan.h"
 #include "filter_dc.h"
+#include "workspace.h"
 #include "sym3_jacobi.h"
 #include "topk_emulate.h"
 #include <type_traits>
@@ -1441,36 +1442,49 @@ extern "C" int dpm_ball_query(const float *points, const int32_t *lengths, const
     return dpm_launch_status();
 }
 
-extern "C" size_t dpm_knn_workspace_bytes(int B, int N) {
-    if (N < GRID_MIN_N) return 0;
-    return 1024 + sizeof(KnnGrid) * (size_t)B + sizeof(int) * (size_t)B * (GDIM * GDIM + 1) +
-           (size_t)B * (size_t)N * sizeof(float4) + 256 + sizeof(int32_t) * (size_t)TIE_CAP + sizeof(int32_t) * (size_t)B * (size_t)N;
-}
-
 namespace {
 struct KnnWs {  // layout of the grid workspace (dpm_knn_workspace_bytes)
     KnnGrid *hdr;
     int *start;
     float4 *sorted;
     int *tie_count;  // [0] = queued tie rows, [1] = rows the fast search left to the full one; the lists follow
+    int32_t *len_dev;  // the self grid's one frame length (inside the 64-byte counter header)
     int32_t *tie_rows;
     int32_t *todo_rows;
     int todo_cap;
 };
-KnnWs carve(void *workspace, int B, int N) {
+KnnWs knn_layout(WsCursor &c, int B, int N) {
     KnnWs w;
-    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    w.hdr = (KnnGrid *)p;
-    p = (p + sizeof(KnnGrid) * (size_t)B + 255) & ~(uintptr_t)255;
-    w.start = (int *)p;
-    p = (p + sizeof(int) * (size_t)B * (GDIM * GDIM + 1) + 255) & ~(uintptr_t)255;
-    w.sorted = (float4 *)p;
-    p = (p + sizeof(float4) * (size_t)B * (size_t)N + 255) & ~(uintptr_t)255;
-    w.tie_count = (int *)p;
-    w.tie_rows = (int32_t *)(p + 64);
-    w.todo_rows = w.tie_rows + TIE_CAP;
+    w.hdr = c.take256<KnnGrid>((size_t)B);
+    w.start = c.take256<int>((size_t)B * (GDIM * GDIM + 1));
+    w.sorted = c.take256<float4>((size_t)B * (size_t)N);
+    w.tie_count = c.take<int>(8);
+    w.len_dev = c.take<int32_t>(8);
+    w.tie_rows = c.take<int32_t>(TIE_CAP);
+    w.todo_rows = c.take<int32_t>((size_t)B * (size_t)N);
     w.todo_cap = (size_t)B * (size_t)N < (size_t)0x7fffffff ? (int)((size_t)B * (size_t)N) : 0x7fffffff;
     return w;
+}
+KnnWs carve(void *workspace, int B, int N) {
+    WsCursor c(workspace);
+    return knn_layout(c, B, N);
+}
+// the self grid: one "frame" of N points; the cursor ends no earlier than behind a grid of GRID_MIN_N points, the least this
+// workspace has ever been (dpm_knn_self_workspace_bytes)
+KnnWs self_layout(WsCursor &c, int N) {
+    WsCursor floor = c;
+    const KnnWs w = knn_layout(c, 1, N);
+    knn_layout(floor, 1, GRID_MIN_N);
+    if (floor.bytes() > c.bytes()) c = floor;
+    return w;
+}
+// one frame of N points, all valid: the length lives in the workspace's counter header, written by the device itself (a
+// fill, not a copy from the caller's stack: the runtime may stage a pageable source after we have returned, and a fill is
+// capturable in a HIP graph)
+hipError_t carve_self(void *workspace, int N, KnnWs &w, hipStream_t st) {
+    WsCursor c(workspace);
+    w = self_layout(c, N);
+    return hipMemsetD32Async((hipDeviceptr_t)w.len_dev, N, 1, st);
 }
 void launch_grid_build(const float *points, const int32_t *lengths, int B, int N, double radius, const KnnWs &w,
                        hipStream_t st) {
@@ -1515,6 +1529,13 @@ int launch_grid_search(const float *points, const int32_t *lengths, const float 
     return dpm_launch_status();
 }
 }  // namespace
+
+extern "C" size_t dpm_knn_workspace_bytes(int B, int N) {
+    if (N < GRID_MIN_N) return 0;
+    WsCursor c(nullptr);
+    knn_layout(c, B, N);
+    return c.bytes();
+}
 
 extern "C" int dpm_knn_hybrid_reuse(const float *points, const int32_t *lengths, const float *centers, int B, int N,
                                     int S, int K, double radius, int32_t *idx, void *workspace,
@@ -1576,31 +1597,24 @@ extern "C" int dpm_knn_hybrid(const float *points, const int32_t *lengths, const
 }
 
 // ---- self kNN (pre-processing filters) ------------------------------------------------------------------
-extern "C" size_t dpm_knn_self_workspace_bytes(int N) { return dpm_knn_workspace_bytes(1, N > GRID_MIN_N ? N : GRID_MIN_N); }
+extern "C" size_t dpm_knn_self_workspace_bytes(int N) {
+    WsCursor c(nullptr);
+    self_layout(c, N);
+    return c.bytes();
+}
 
 extern "C" int dpm_knn_self(const float *xyz, int N, int K, double cell, int32_t *idx, float *dist2, float *mean_dist,
                             void *workspace, dpm_stream_t stream) {
     DPM_CHECK_ARG(xyz && workspace && N >= 1 && K >= 1 && cell > 0.0 && (idx || dist2 || mean_dist));
     if (K + 1 > KMAX) return DPM_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    KnnGrid *hdr = (KnnGrid *)p;
-    p = (p + sizeof(KnnGrid) + 255) & ~(uintptr_t)255;
-    int *start = (int *)p;
-    p = (p + sizeof(int) * (size_t)(GDIM * GDIM + 1) + 255) & ~(uintptr_t)255;
-    float4 *sorted = (float4 *)p;
-    p = (p + sizeof(float4) * (size_t)N + 255) & ~(uintptr_t)255;
-    int *tie_count = (int *)p;
-    // one "frame" of N points, all valid: the length lives in the workspace header area
-    int32_t *len_dev = (int32_t *)(tie_count + 8);
-    // written by the device itself (a fill, not a copy from this function's stack: the runtime may stage a pageable
-    // source after we have returned, and a fill is capturable in a HIP graph)
-    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)len_dev, N, 1, st);
+    KnnWs w;
+    hipError_t e = carve_self(workspace, N, w, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, len_dev, N, (float)cell, 0.f, hdr, start, sorted,
-                       tie_count);
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, w.len_dev, N, (float)cell, 0.f, w.hdr, w.start,
+                       w.sorted, w.tie_count);
     hipLaunchKernelGGL(knn_self_kernel<false>, dim3(dpm_cdiv(N, WPB)), dim3(WPB * 64), 0, st, xyz, N, K,
-                       (const int32_t *)nullptr, 0, hdr, start, sorted, idx, dist2, mean_dist);
+                       (const int32_t *)nullptr, 0, w.hdr, w.start, w.sorted, idx, dist2, mean_dist);
     return dpm_launch_status();
 }
 
@@ -1608,24 +1622,14 @@ extern "C" int dpm_point_normals(const float *xyz, int N, double radius, float *
                                  dpm_stream_t stream) {
     DPM_CHECK_ARG(xyz && normals && workspace && N >= 1 && radius > 0.0);
     hipStream_t st = (hipStream_t)stream;
-    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    KnnGrid *hdr = (KnnGrid *)p;
-    p = (p + sizeof(KnnGrid) + 255) & ~(uintptr_t)255;
-    int *start = (int *)p;
-    p = (p + sizeof(int) * (size_t)(GDIM * GDIM + 1) + 255) & ~(uintptr_t)255;
-    float4 *sorted = (float4 *)p;
-    p = (p + sizeof(float4) * (size_t)N + 255) & ~(uintptr_t)255;
-    int *tie_count = (int *)p;
-    int32_t *len_dev = (int32_t *)(tie_count + 8);
-    // written by the device itself (a fill, not a copy from this function's stack: the runtime may stage a pageable
-    // source after we have returned, and a fill is capturable in a HIP graph)
-    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)len_dev, N, 1, st);
+    KnnWs w;
+    hipError_t e = carve_self(workspace, N, w, st);
     if (e != hipSuccess) return (int)e;
     // cell edge slightly above the radius: the 3x3 block then contains every point strictly within it
-    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, len_dev, N, (float)(radius * 1.001), 0.f, hdr, start,
-                       sorted, tie_count);
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, w.len_dev, N, (float)(radius * 1.001), 0.f, w.hdr,
+                       w.start, w.sorted, w.tie_count);
     hipLaunchKernelGGL(point_normals_kernel<false>, dim3(dpm_cdiv(N, WPB)), dim3(WPB * 64), 0, st, xyz, N,
-                       (float)(radius * radius), (const int32_t *)nullptr, 0, hdr, start, sorted, normals);
+                       (float)(radius * radius), (const int32_t *)nullptr, 0, w.hdr, w.start, w.sorted, normals);
     return dpm_launch_status();
 }
 
@@ -1636,46 +1640,36 @@ extern "C" int dpm_point_normals(const float *xyz, int N, double radius, float *
 // arithmetic, same order, same bytes as those four entry points on xyz[:count].
 namespace {
 struct FilterWs {  // layout of dpm_filter_dc_workspace_bytes: the self-kNN grid, then the per-point arrays
-    KnnGrid *hdr;
-    int *start;
-    float4 *sorted;
-    int *tie_count;
+    KnnWs g;
     float *stat;       // (cap)     mean neighbour distance / similarity
     float *normals;    // (cap,3)   LowPassFilter only
     int32_t *nn;       // (cap,K)   LowPassFilter only
 };
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-FilterWs carve_filter(void *workspace, int cap) {
+FilterWs filter_layout(WsCursor &c, int cap, int K) {
     FilterWs w;
-    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const uintptr_t base = p;
-    w.hdr = (KnnGrid *)p;
-    p = (p + sizeof(KnnGrid) + 255) & ~(uintptr_t)255;
-    w.start = (int *)p;
-    p = (p + sizeof(int) * (size_t)(GDIM * GDIM + 1) + 255) & ~(uintptr_t)255;
-    w.sorted = (float4 *)p;
-    p = (p + sizeof(float4) * (size_t)cap + 255) & ~(uintptr_t)255;
-    w.tie_count = (int *)p;
-    p = base + align256(dpm_knn_self_workspace_bytes(cap));
-    w.stat = (float *)p;
-    p += align256(sizeof(float) * (size_t)cap);
-    w.normals = (float *)p;
-    p += align256(sizeof(float) * 3 * (size_t)cap);
-    w.nn = (int32_t *)p;
+    w.g = self_layout(c, cap);
+    w.stat = c.take256<float>((size_t)cap);
+    w.normals = c.take256<float>(3 * (size_t)cap);
+    w.nn = c.take256<int32_t>((size_t)cap * (size_t)K);
     return w;
+}
+FilterWs carve_filter(void *workspace, int cap, int K) {
+    WsCursor c(workspace);
+    return filter_layout(c, cap, K);
 }
 // one frame of at most `cap` points whose length is count[0]: the build clamps it to [0, cap] itself
 void launch_self_grid_dc(const float *xyz, const int32_t *count, int cap, float cell, const FilterWs &w, hipStream_t st) {
-    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, count, cap, cell, 0.f, w.hdr, w.start, w.sorted,
-                       w.tie_count);
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(1), dim3(1024), 0, st, xyz, count, cap, cell, 0.f, w.g.hdr, w.g.start, w.g.sorted,
+                       w.g.tie_count);
 }
 }  // namespace
 
 extern "C" size_t dpm_filter_dc_workspace_bytes(int cap, int K) {
     if (cap < 0) cap = 0;
     if (K < 0) K = 0;
-    return 256 + align256(dpm_knn_self_workspace_bytes(cap)) + align256(sizeof(float) * (size_t)cap) +
-           align256(sizeof(float) * 3 * (size_t)cap) + align256(sizeof(int32_t) * (size_t)cap * (size_t)K);
+    WsCursor c(nullptr);
+    filter_layout(c, cap, K);
+    return c.bytes();
 }
 
 extern "C" int dpm_outlier_filter_dc(const float *xyz, const int32_t *idx, const int32_t *count, int cap, int nb_neighbors,
@@ -1686,10 +1680,10 @@ extern "C" int dpm_outlier_filter_dc(const float *xyz, const int32_t *idx, const
     if (cap == 0) return DPM_OK;
     DPM_CHECK_ARG(xyz && count && xyz_out && count_out && workspace);
     hipStream_t st = (hipStream_t)stream;
-    const FilterWs w = carve_filter(workspace, cap);
+    const FilterWs w = carve_filter(workspace, cap, nb_neighbors);
     launch_self_grid_dc(xyz, count, cap, (float)cell, w, st);
     hipLaunchKernelGGL(knn_self_kernel<true>, dim3(dpm_cdiv(cap, WPB)), dim3(WPB * 64), 0, st, xyz, cap, nb_neighbors, count,
-                       nb_neighbors, w.hdr, w.start, w.sorted, (int32_t *)nullptr, (float *)nullptr, w.stat);
+                       nb_neighbors, w.g.hdr, w.g.start, w.g.sorted, (int32_t *)nullptr, (float *)nullptr, w.stat);
     dpm_detail::launch_stat_filter_dc(w.stat, count, cap, nb_neighbors, (float)std_ratio, 0, (float)ratio, xyz, idx, xyz_out,
                                       idx_out, count_out, st);
     return dpm_launch_status();
@@ -1705,15 +1699,15 @@ extern "C" int dpm_lowpass_filter_dc(const float *xyz, const int32_t *idx, const
     if (cap == 0) return DPM_OK;
     DPM_CHECK_ARG(xyz && count && xyz_out && count_out && workspace);
     hipStream_t st = (hipStream_t)stream;
-    const FilterWs w = carve_filter(workspace, cap);
+    const FilterWs w = carve_filter(workspace, cap, normals_num);
     // two grids, as in the synchronous path: edge slightly above the radius for the normals (the 3x3 block then holds every
     // point strictly within it), `cell` for the neighbour search; the second build overwrites the first in stream order
     launch_self_grid_dc(xyz, count, cap, (float)(normals_radius * 1.001), w, st);
     hipLaunchKernelGGL(point_normals_kernel<true>, dim3(dpm_cdiv(cap, WPB)), dim3(WPB * 64), 0, st, xyz, cap,
-                       (float)(normals_radius * normals_radius), count, normals_num, w.hdr, w.start, w.sorted, w.normals);
+                       (float)(normals_radius * normals_radius), count, normals_num, w.g.hdr, w.g.start, w.g.sorted, w.normals);
     launch_self_grid_dc(xyz, count, cap, (float)cell, w, st);
     hipLaunchKernelGGL(knn_self_kernel<true>, dim3(dpm_cdiv(cap, WPB)), dim3(WPB * 64), 0, st, xyz, cap, normals_num, count,
-                       normals_num, w.hdr, w.start, w.sorted, w.nn, (float *)nullptr, (float *)nullptr);
+                       normals_num, w.g.hdr, w.g.start, w.g.sorted, w.nn, (float *)nullptr, (float *)nullptr);
     dpm_detail::launch_lowpass_sim_dc(w.normals, w.nn, count, cap, normals_num, flux, w.stat, st);
     dpm_detail::launch_stat_filter_dc(w.stat, count, cap, normals_num, (float)filter_std, 1, (float)ratio, xyz, idx, xyz_out,
                                       idx_out, count_out, st);

@@ -61,6 +61,7 @@
 #include "cell_grid.h"
 #include "gn_solve.h"
 #include "sym3_jacobi.h"
+#include "workspace.h"
 
 namespace {
 
@@ -524,6 +525,14 @@ extern "C" int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half,
 
 namespace {
 
+// the registration's workspace: the register header in a 256-byte slice of its own, then the accumulate blocks' partials
+// (512 + 256 bytes per 256 points of capacity: the size the callers compute)
+void reg_layout(WsCursor &c, int cap, RegArgs &A) {
+    static_assert(sizeof(RegHdr) <= 256, "the header has a 256-byte slice");
+    A.hdr = c.take256<RegHdr>(1);
+    A.partial = c.take<double>((size_t)dpm_cdiv(cap, 256) * GN_NSUM_PAD);
+}
+
 // both registrations: PA = nullptr is point-to-point
 int register_impl(const PlaneArgs *PA, const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
                   const float *xyz, const int32_t *count, int cap, const double *init_pose, const double *stage_max_dist,
@@ -540,8 +549,8 @@ int register_impl(const PlaneArgs *PA, const void *map, int cap_vox, int subdiv,
     RegArgs A{};
     A.M = make_map((void *)map, cap_vox, subdiv, half, voxel, origin);
     A.F = Frame{xyz, nullptr, count, cap};
-    unsigned char *ws = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    A.hdr = (RegHdr *)ws, A.partial = (double *)(ws + 256);
+    WsCursor c(workspace);
+    reg_layout(c, cap, A);
     A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
     A.dbg_key = debug_key, A.dbg_sub = debug_sub, A.dbg_system = debug_system;
     const double kappa = kernel_scale * kernel_scale;

@@ -26,6 +26,7 @@
 // 2 i + g: conflict-free), a tile read as [row g][column i] has rows 80 apart (bank 16 g + i: conflict-free).  W1 is 256 KiB:
 // it passes through LDS in tiles of 64 channels x 64 k.
 #include "dpm_common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -235,16 +236,21 @@ bool shape_ok(int B, int L) { return B >= 1 && L >= 1 && B <= 65535 && dpm_cdiv(
 
 int row_tiles(int B, int L) { return (int)(((long long)B * L + LP_R - 1) / LP_R); }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// one slice for either call: the forward's per-tile column sums or the backward's partial dW1, whichever is larger
+float *layout(WsCursor &c, int B, int L) {
+    const size_t fwd = (size_t)B * dpm_cdiv(L, LP_R) * LP_E;
+    const int nt = row_tiles(B, L);
+    const size_t bwd = (size_t)(nt < LP_SPLITS ? nt : LP_SPLITS) * (LP_E * LP_E + LP_E);
+    return c.take256<float>(fwd > bwd ? fwd : bwd);
+}
 
 }  // namespace
 
 extern "C" size_t dpm_loop_pool_workspace_bytes(int B, int L, int E) {
     if (!shape_ok(B, L) || E != LP_E) return 0;
-    const size_t fwd = 4 * (size_t)B * dpm_cdiv(L, LP_R) * LP_E;
-    const int nt = row_tiles(B, L);
-    const size_t bwd = 4 * (size_t)(nt < LP_SPLITS ? nt : LP_SPLITS) * (LP_E * LP_E + LP_E);
-    return 256 + align256(fwd > bwd ? fwd : bwd);
+    WsCursor c(nullptr);
+    layout(c, B, L);
+    return c.bytes();
 }
 
 extern "C" int dpm_loop_pool_forward(const float *x, int ldx, const float *W1, const float *b1, int B, int L, int E, float *m,
@@ -253,7 +259,8 @@ extern "C" int dpm_loop_pool_forward(const float *x, int ldx, const float *W1, c
     if (E != LP_E) return DPM_EUNSUPPORTED;
     DPM_CHECK_ARG(aligned16(x) && aligned16(W1) && ldx >= LP_E && ldx % 4 == 0);
     hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)align256((size_t)(uintptr_t)workspace);
+    WsCursor c(workspace);
+    float *ws = layout(c, B, L);
     const int tiles = (int)dpm_cdiv(L, LP_R);
     hipLaunchKernelGGL(lp_forward_kernel, dim3(LP_E / LP_C, tiles, B), dim3(LP_T), 0, st, x, (long long)ldx, W1, b1, L, tiles, ws);
     hipLaunchKernelGGL(lp_mean_kernel, dim3(dpm_cdiv((long long)B * LP_E, LP_T)), dim3(LP_T), 0, st, ws, tiles, L, B * LP_E, m);
@@ -266,7 +273,8 @@ extern "C" int dpm_loop_pool_backward(const float *x, int ldx, const float *W1, 
     if (E != LP_E) return DPM_EUNSUPPORTED;
     DPM_CHECK_ARG(aligned16(x) && aligned16(W1) && ldx >= LP_E && ldx % 4 == 0);
     hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)align256((size_t)(uintptr_t)workspace);
+    WsCursor c(workspace);
+    float *ws = layout(c, B, L);
     const int ntiles = row_tiles(B, L), S = ntiles < LP_SPLITS ? ntiles : LP_SPLITS;
     hipLaunchKernelGGL(lp_backward_kernel, dim3(LP_E / LP_C, S), dim3(LP_T), 0, st, x, (long long)ldx, W1, b1, g, L,
                        (long long)B * L, ntiles, S, ws);

@@ -21,6 +21,7 @@
 
 #include "block_scan.h"
 #include "cell_grid.h"
+#include "workspace.h"
 
 namespace {
 
@@ -315,7 +316,7 @@ extern "C" int dpm_cloud_nn(const float *query, int Nq, const float *target, int
     hipStream_t st = (hipStream_t)stream;
     NnArgs A{};
     A.qry = query, A.tgt = target, A.Nq = Nq, A.Nt = Nt, A.ox = origin_x, A.oy = origin_y, A.oz = origin_z;
-    A.ws = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    A.ws = (char *)ws_align256((uintptr_t)workspace);
     hipLaunchKernelGGL(nn_setup_kernel, dim3(1), dim3(1024), 0, st, A, (float)max_dist);
     if (Nt > 0) {
         hipLaunchKernelGGL(nn_grid_kernel<false>, dim3(dpm_cdiv(Nt, 256)), dim3(256), 0, st, A);
@@ -326,9 +327,14 @@ extern "C" int dpm_cloud_nn(const float *query, int Nq, const float *target, int
     return dpm_launch_status();
 }
 
+// the blocks' partials: one row of SCOL + T columns per block and class (and one for all classes)
+static double *stats_layout(WsCursor &c, int M, int C, int T) { return c.take<double>((size_t)stat_blocks(M) * (C + 1) * (SCOL + T)); }
+
 extern "C" size_t dpm_distance_stats_workspace_bytes(int M, int C, int T) {
     if (M < 0 || C < 0 || C > DPM_STATS_MAX_CLASSES || T < 0 || T > DPM_STATS_MAX_THRESHOLDS) return 0;
-    return sizeof(double) * (size_t)stat_blocks(M) * (C + 1) * (SCOL + T) + 256;
+    WsCursor c(nullptr);
+    stats_layout(c, M, C, T);
+    return c.bytes();
 }
 
 extern "C" int dpm_distance_stats(const float *dist, int M, const int32_t *surf, const int32_t *class_id, int n_surf, int C,
@@ -341,7 +347,8 @@ extern "C" int dpm_distance_stats(const float *dist, int M, const int32_t *surf,
     StatThr thr{};
     for (int k = 0; k < T; ++k) thr.v[k] = thresholds[k];
     hipStream_t st = (hipStream_t)stream;
-    double *partial = (double *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    WsCursor c(workspace);
+    double *partial = stats_layout(c, M, C, T);
     const int blocks = stat_blocks(M), chunk = M == 0 ? 1 : (int)dpm_cdiv(M, blocks), cols = SCOL + T;
     hipLaunchKernelGGL(stats_partial_kernel, dim3(blocks, C + 1), dim3(256), 0, st, dist, M, chunk, surf, class_id, n_surf, C, thr,
                        T, (float)max_dist, partial);

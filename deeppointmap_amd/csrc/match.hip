@@ -14,6 +14,7 @@
 // S is bit-identical to gemm_nt_mfma_kernel's (same instruction, same k order); the column sums are folded as
 // sum_s psum_s * exp(pmax_s - cmax) instead of one pass against the final maximum (last-bit differences).
 #include "dpm_common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -512,20 +513,17 @@ __global__ __launch_bounds__(MT_T) void match_topk_kernel(const float *__restric
     for (int e = t; e < k; e += MT_T) out_v[(size_t)pair * k + e] = sv[e], out_i[(size_t)pair * k + e] = si[e];
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-MatchWs carve(void *workspace, int batch, int M, int N, int k) {
-    const int strips = (M + MT_ROWS - 1) / MT_ROWS;
+MatchWs layout(WsCursor &c, int batch, int M, int N, int k) {
+    const size_t strips = (size_t)(M + MT_ROWS - 1) / MT_ROWS;
     const size_t kcap = (size_t)std::min<long long>(k, (long long)MT_ROWS * N);
-    char *p = (char *)align256((size_t)(uintptr_t)workspace);
     MatchWs w;
-    w.rmax = (float *)p, p += align256(sizeof(float) * (size_t)batch * M);
-    w.rsum = (float *)p, p += align256(sizeof(float) * (size_t)batch * M);
-    w.pmax = (float *)p, p += align256(sizeof(float) * (size_t)batch * strips * N);
-    w.psum = (float *)p, p += align256(sizeof(float) * (size_t)batch * strips * N);
-    w.ticket = (int *)p, p += align256(sizeof(int) * (size_t)batch);
-    w.cand_v = (float *)p, p += align256(sizeof(float) * (size_t)batch * strips * kcap);
-    w.cand_i = (int *)p;
+    w.rmax = c.take256<float>((size_t)batch * M);
+    w.rsum = c.take256<float>((size_t)batch * M);
+    w.pmax = c.take256<float>((size_t)batch * strips * N);
+    w.psum = c.take256<float>((size_t)batch * strips * N);
+    w.ticket = c.take256<int>((size_t)batch);
+    w.cand_v = c.take256<float>((size_t)batch * strips * kcap);
+    w.cand_i = c.take256<int>((size_t)batch * strips * kcap);
     return w;
 }
 
@@ -539,10 +537,9 @@ extern "C" int dpm_debug_match_trace(long long *host_out, int n) {
 
 extern "C" size_t dpm_match_workspace_bytes(int batch, int M, int N, int k) {
     if (batch < 1 || M < 1 || N < 1 || k < 1) return 0;
-    const size_t strips = (size_t)(M + MT_ROWS - 1) / MT_ROWS;
-    const size_t kcap = (size_t)std::min<long long>(k, (long long)MT_ROWS * N);
-    return 256 + 2 * align256(sizeof(float) * (size_t)batch * M) + 2 * align256(sizeof(float) * (size_t)batch * strips * N) +
-           align256(sizeof(int) * (size_t)batch) + 2 * align256(4 * (size_t)batch * strips * kcap);
+    WsCursor c(nullptr);
+    layout(c, batch, M, N, k);
+    return c.bytes();
 }
 
 extern "C" int dpm_match_topk(const float *a, const float *b, int batch, int M, int N, int C, double tau, int k, float *out_val,
@@ -553,7 +550,8 @@ extern "C" int dpm_match_topk(const float *a, const float *b, int batch, int M, 
     if (N > MT_COLS || k > MT_KCAP || C % MT_KT != 0 || strips > 65535 || batch > 65535 || (long long)M * N > 0x7fffffffLL ||
         ((uintptr_t)a & 15) != 0 || ((uintptr_t)b & 15) != 0)
         return DPM_EUNSUPPORTED;
-    const MatchWs ws = carve(workspace, batch, M, N, k);
+    WsCursor c(workspace);
+    const MatchWs ws = layout(c, batch, M, N, k);
     const float itau = 1.0f / (float)tau;  // torch divides by the scalar as a multiplication by 1/tau
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(match_stats_kernel, dim3(strips, batch), dim3(MT_T), 0, st, a, b, M, N, C, itau, ws);

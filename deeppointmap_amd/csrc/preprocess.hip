@@ -11,6 +11,7 @@
 // true division for the normalisation (torch's in-place `/=` on CPU tensors).
 #include "block_scan.h"
 #include "filter_dc.h"
+#include "workspace.h"
 
 namespace {
 
@@ -264,8 +265,26 @@ __global__ __launch_bounds__(1024) void stat_filter_kernel(const float *__restri
 
 }  // namespace
 
+namespace {
+struct PreWs {
+    PreHdr *hdr;
+    int *grid, *bcount;
+};
+PreWs pre_layout(WsCursor &c, long long max_cells) {
+    PreWs w;
+    w.hdr = c.take<PreHdr>(1);
+    c.align256();
+    w.grid = c.take<int>((size_t)max_cells);
+    w.bcount = c.take<int>((size_t)(max_cells / CH + 2));   // one count per chunk, and a spare the size has always had
+    c.skip(512);   // slack the size has always carried
+    return w;
+}
+}  // namespace
+
 extern "C" size_t dpm_preprocess_workspace_bytes(long long max_cells) {
-    return 1024 + sizeof(int) * (size_t)max_cells + sizeof(int) * (size_t)(max_cells / CH + 2);
+    WsCursor c(nullptr);
+    pre_layout(c, max_cells);
+    return c.bytes();
 }
 
 extern "C" int dpm_preprocess_scan(const float *xyz, int N, int stride, double voxel_size, double min_dis, double max_dis,
@@ -274,11 +293,9 @@ extern "C" int dpm_preprocess_scan(const float *xyz, int N, int stride, double v
     DPM_CHECK_ARG(xyz && out_xyz && status && workspace && N >= 1 && stride >= 3 && voxel_size > 0.0 && ratio != 0.0);
     DPM_CHECK_ARG(max_cells >= CH && out_capacity >= 1);
     hipStream_t st = (hipStream_t)stream;
-    uintptr_t p = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    PreHdr *hdr = (PreHdr *)p;
-    int *grid = (int *)(p + 256);
+    WsCursor c(workspace);
+    const auto [hdr, grid, bcount] = pre_layout(c, max_cells);
     const int max_blocks = (int)(max_cells / CH + 1);
-    int *bcount = grid + max_cells;
     const float vs = (float)voxel_size;
     hipLaunchKernelGGL(pre_bbox_kernel, dim3(1), dim3(1024), 0, st, xyz, N, stride, vs, max_cells, hdr);
     hipLaunchKernelGGL(pre_fill_kernel, dim3(2048), dim3(256), 0, st, hdr, grid);

@@ -17,6 +17,7 @@
 // would be (B, S / 64, D) pairs of floats of workspace (128 MiB per feature pair at B = 2, S = D = 16384) against twice the
 // MFMA work.  The partial-statistics variant was not built or measured.
 #include "dpm_common.h"
+#include "workspace.h"
 
 #include <type_traits>
 
@@ -479,32 +480,24 @@ __global__ __launch_bounds__(RL_T) void rl_backward_kernel(SideIn a, SideIn bs, 
     }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Ws {
     float *hat_a, *hat_b, *norm_a, *norm_b, *lse_a, *lse_b, *term_a, *term_b;
     int *flags_a, *flags_b;
     Partials part;
 };
 
-Ws carve(void *workspace, int B, int M, int N, int C) {
-    char *p = (char *)align256((size_t)(uintptr_t)workspace);
-    auto take = [&](size_t bytes) {
-        char *q = p;
-        p += align256(bytes);
-        return q;
-    };
+Ws layout(WsCursor &c, int B, int M, int N, int C) {
+    const size_t ra = (size_t)B * M, rb = (size_t)B * N;
     Ws w;
-    w.hat_a = (float *)take(4 * (size_t)B * M * C), w.hat_b = (float *)take(4 * (size_t)B * N * C);
-    w.norm_a = (float *)take(4 * (size_t)B * M), w.norm_b = (float *)take(4 * (size_t)B * N);
-    w.lse_a = (float *)take(4 * (size_t)B * M), w.lse_b = (float *)take(4 * (size_t)B * N);
-    w.term_a = (float *)take(4 * (size_t)B * M), w.term_b = (float *)take(4 * (size_t)B * N);
-    w.flags_a = (int *)take(4 * (size_t)B * M), w.flags_b = (int *)take(4 * (size_t)B * N);
-    w.part.v = (double *)take(8 * 2 * RL_PARTS), w.part.n = (long long *)take(8 * 2 * RL_PARTS);
-    w.part.h = (long long *)take(8 * 2 * RL_PARTS);
+    w.hat_a = c.take256<float>(ra * C), w.hat_b = c.take256<float>(rb * C);
+    w.norm_a = c.take256<float>(ra), w.norm_b = c.take256<float>(rb);
+    w.lse_a = c.take256<float>(ra), w.lse_b = c.take256<float>(rb);
+    w.term_a = c.take256<float>(ra), w.term_b = c.take256<float>(rb);
+    w.flags_a = c.take256<int>(ra), w.flags_b = c.take256<int>(rb);
+    w.part.v = c.take256<double>(2 * RL_PARTS), w.part.n = c.take256<long long>(2 * RL_PARTS);
+    w.part.h = c.take256<long long>(2 * RL_PARTS);
     return w;
 }
-
 bool shape_ok(int B, int M, int N, int C) { return B >= 1 && M >= 1 && N >= 1 && C >= 1 && B <= 65535; }
 
 float threshold(double eps) { return (float)(eps * eps); }   // torch compares an fp32 tensor with the scalar rounded to fp32
@@ -523,8 +516,9 @@ extern "C" int dpm_reg_loss_pairs(const float *xyz_a, const float *xyz_b, int B,
 
 extern "C" size_t dpm_reg_loss_workspace_bytes(int B, int M, int N, int C) {
     if (!shape_ok(B, M, N, C)) return 0;
-    return 256 + align256(4 * (size_t)B * M * C) + align256(4 * (size_t)B * N * C) +
-           4 * (align256(4 * (size_t)B * M) + align256(4 * (size_t)B * N)) + 3 * align256(8 * 2 * RL_PARTS);
+    WsCursor c(nullptr);
+    layout(c, B, M, N, C);
+    return c.bytes();
 }
 
 static bool reg_loss_channels(int C) { return C == 64 || C == 128 || C == 192 || C == 256; }
@@ -536,7 +530,8 @@ extern "C" int dpm_reg_loss_forward(const float *fea_a, const float *fea_b, cons
     DPM_CHECK_ARG(fea_a && fea_b && pad_a && pad_b && nn_a && nn_b && loss && stats && workspace && shape_ok(B, M, N, C));
     DPM_CHECK_ARG(tau > 0.0 && eps >= 0.0 && (!neutral || (xyz_a && xyz_b)));
     if (!reg_loss_channels(C)) return DPM_EUNSUPPORTED;
-    const Ws ws = carve(workspace, B, M, N, C);
+    WsCursor c(workspace);
+    const Ws ws = layout(c, B, M, N, C);
     hipStream_t st = (hipStream_t)stream;
     const float itau = 1.0f / (float)tau, e2 = threshold(eps);
     hipLaunchKernelGGL(rl_prep_kernel, dim3(dpm_cdiv(M, 64), B), dim3(RL_T), 0, st, fea_a, M, C, ws.hat_a, ws.norm_a);
@@ -577,7 +572,8 @@ extern "C" int dpm_reg_loss_backward(const float *xyz_a, const float *xyz_b, con
     DPM_CHECK_ARG(nn_a && nn_b && grad_loss && stats && workspace && grad_a && grad_b && shape_ok(B, M, N, C));
     DPM_CHECK_ARG(tau > 0.0 && eps >= 0.0 && (!neutral || (xyz_a && xyz_b)));
     if (!reg_loss_channels(C)) return DPM_EUNSUPPORTED;
-    const Ws ws = carve(const_cast<void *>(workspace), B, M, N, C);
+    WsCursor c(const_cast<void *>(workspace));
+    const Ws ws = layout(c, B, M, N, C);
     hipStream_t st = (hipStream_t)stream;
     const float itau = 1.0f / (float)tau, e2 = threshold(eps);
     const SideIn sa{ws.hat_a, xyz_a, ws.norm_a, ws.lse_a, nn_a, ws.flags_a}, sb{ws.hat_b, xyz_b, ws.norm_b, ws.lse_b, nn_b, ws.flags_b};

@@ -26,6 +26,7 @@
 // column lane & 31) for lane half h: with rows 72 floats apart the two halves of a store land 4 * 72 = 288 = 32 (mod 64) banks
 // apart and a store is conflict free; a diagonal read takes at most `sectors` <= 64 consecutive floats of one row.
 #include "dpm_common.h"
+#include "workspace.h"
 
 #include <cmath>
 
@@ -311,9 +312,24 @@ extern "C" int dpm_scan_context_build_batched(const float *pcd, const int32_t *l
                     mask, (hipStream_t)stream);
 }
 
+struct SearchWs {   // the blocks' K best per query: packed (distance, row) keys, then the shifts
+    unsigned long long *part_key;
+    int32_t *part_shift;
+};
+// from the caller's pointer on (no base rounding, no allowance)
+static SearchWs search_layout(WsCursor &c, int Q, int D, int K) {
+    const size_t n = (size_t)Q * dpm_cdiv(D, sc_rows_per_block(Q, D)) * K;
+    SearchWs w;
+    w.part_key = c.take<unsigned long long>(n);
+    w.part_shift = c.take<int32_t>(n);
+    return w;
+}
+
 extern "C" size_t dpm_scan_context_search_workspace_bytes(int Q, int D, int K) {
     if (Q < 1 || D < 1 || K < 1 || K > SC_MAX_K) return 0;
-    return (size_t)Q * dpm_cdiv(D, sc_rows_per_block(Q, D)) * K * 12;
+    WsCursor c(nullptr, false);
+    search_layout(c, Q, D, K);
+    return c.bytes();
 }
 
 extern "C" int dpm_scan_context_search(const float *q_norm, const unsigned long long *q_mask, int Q, const float *db_norm,
@@ -322,8 +338,8 @@ extern "C" int dpm_scan_context_search(const float *q_norm, const unsigned long 
     DPM_CHECK_ARG(q_norm && q_mask && db_norm && db_mask && limit && dist && row && shift && workspace);
     DPM_CHECK_ARG(Q >= 1 && Q <= 65535 && D >= 1 && K >= 1 && K <= SC_MAX_K && sc_check(rings, sectors));
     const int rpb = sc_rows_per_block(Q, D), nblk = (int)dpm_cdiv(D, rpb);
-    unsigned long long *part_key = (unsigned long long *)workspace;
-    int32_t *part_shift = (int32_t *)(part_key + (size_t)Q * nblk * K);
+    WsCursor c(workspace, false);
+    const auto [part_key, part_shift] = search_layout(c, Q, D, K);
     const dim3 grid(nblk, Q), block(64 * SC_WAVES);
 #define SC_LAUNCH(NT, STEPS)                                                                                                       \
     hipLaunchKernelGGL((sc_search_kernel<NT, STEPS>), grid, block, 0, (hipStream_t)stream, q_norm, q_mask, db_norm, db_mask, D, limit, \

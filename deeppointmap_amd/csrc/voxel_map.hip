@@ -32,6 +32,7 @@
 // Memory: header 256 B + per slot 40 B (key 8, sums 24, first 4, count 4) with N + N/4 (+64) slots, + N/4 bytes of
 // bitmask / prefix: <= 51 B per input point (+ 8 KB).
 #include "dpm_common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -59,7 +60,7 @@ __host__ __device__ inline Layout vm_layout(long long N) {
     L.off_bits = o;   o += (size_t)L.W * 4;
     L.off_wpre = o;   o += (size_t)L.W * 4;
     L.off_chunks = o; o += (size_t)(L.NCH + 1) * 4;
-    L.total = (o + 255) & ~(size_t)255;
+    L.total = ws_align256(o);
     return L;
 }
 

@@ -20,6 +20,7 @@
 
 #include "block_scan.h"
 #include "topk_emulate.h"
+#include "workspace.h"
 
 namespace {
 
@@ -245,14 +246,31 @@ int dpm_voxel_sampler_bounds(const float *points, const uint8_t *padding, int B,
     return dpm_launch_status();
 }
 
-static size_t vox_align(size_t x) { return (x + 255) & ~(size_t)255; }
+struct VoxSampleWs {
+    unsigned long long *keys;
+    unsigned *cnt;
+    int32_t *ufirst, *ucnt;
+    VI *scratch;
+    int *bcount;
+};
+// from the caller's pointer on (no base rounding, no allowance)
+static VoxSampleWs vox_sample_layout(WsCursor &c, int B, int N, long long max_cells) {
+    const size_t cells = (size_t)B * (size_t)(max_cells + 1), rows = (size_t)B * N;
+    const size_t nchunk = (size_t)((max_cells + 1 + CH - 1) / CH);
+    VoxSampleWs w;
+    w.keys = c.take256<unsigned long long>(cells);
+    w.cnt = c.take256<unsigned>(cells);
+    w.ufirst = c.take256<int32_t>(rows), w.ucnt = c.take256<int32_t>(rows);
+    w.scratch = c.take256<VI>(rows);
+    w.bcount = c.take256<int>((size_t)B * nchunk);
+    return w;
+}
 
 size_t dpm_voxel_sampler_workspace_bytes(int B, int N, long long max_cells) {
     if (B <= 0 || N <= 0 || max_cells <= 0) return 0;
-    const size_t cells = (size_t)B * (size_t)(max_cells + 1), rows = (size_t)B * N;
-    const size_t nchunk = (size_t)((max_cells + 1 + CH - 1) / CH);
-    return vox_align(cells * 8) + vox_align(cells * 4) + 2 * vox_align(rows * 4) + vox_align(rows * sizeof(VI)) +
-           vox_align((size_t)B * nchunk * 4);
+    WsCursor c(nullptr, false);
+    vox_sample_layout(c, B, N, max_cells);
+    return c.bytes();
 }
 
 int dpm_voxel_sampler_select(const float *points, const uint8_t *padding, int B, int N, int D, double voxel_size,
@@ -262,20 +280,10 @@ int dpm_voxel_sampler_select(const float *points, const uint8_t *padding, int B,
     DPM_CHECK_ARG(voxel_size > 0 && sample_range > 0 && max_cells > 0 && max_cells < 0x7fffffffLL && N <= (1 << 24));
     DPM_CHECK_ARG(K < 0 ? cap == N : (K >= 1 && cap == K));
     hipStream_t st = (hipStream_t)stream;
-    const size_t cells = (size_t)B * (size_t)(max_cells + 1), rows = (size_t)B * N;
+    const size_t cells = (size_t)B * (size_t)(max_cells + 1);
     const int nchunk = (int)((max_cells + 1 + CH - 1) / CH);
-    char *w = (char *)workspace;
-    unsigned long long *keys = (unsigned long long *)w;
-    w += vox_align(cells * 8);
-    unsigned *cnt = (unsigned *)w;
-    w += vox_align(cells * 4);
-    int32_t *ufirst = (int32_t *)w;
-    w += vox_align(rows * 4);
-    int32_t *ucnt = (int32_t *)w;
-    w += vox_align(rows * 4);
-    VI *scratch = (VI *)w;
-    w += vox_align(rows * sizeof(VI));
-    int *bcount = (int *)w;
+    WsCursor c(workspace, false);
+    const auto [keys, cnt, ufirst, ucnt, scratch, bcount] = vox_sample_layout(c, B, N, max_cells);
     hipError_t e = hipMemsetAsync(keys, 0xff, cells * 8, st);
     if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, cells * 4, st);
     if (e != hipSuccess) return (int)e;

@@ -9,7 +9,8 @@
  *
  * Conventions
  *  - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller, the
- *    library never allocates, frees or retains it; scratch is passed in as `workspace`.
+ *    library never allocates, frees or retains it; scratch is passed in as `workspace`
+ *    (sized by the entry point's dpm_*_workspace_bytes; DESIGN.md section 3 has the layout rules).
  *  - all tensors are fp32, dense, "point-major": xyz (B,N,3), features (B,N,C); index
  *    tensors are int32; `lengths[b]` = number of valid (leading) points of frame b.
  *  - every call is asynchronous on `stream` (a hipStream_t passed as void*), re-entrant and
