@@ -160,6 +160,7 @@ SIGNATURES = {
     "dpm_local_map_init": (I, [P, I, I, P]),
     "dpm_local_map_insert": (I, [P, I, I, I, D, P, P, P, P, I, P, c_uint, D, D, P]),
     "dpm_local_map_prune": (I, [P, I, I, I, D, P, P, D, P]),
+    "dpm_local_map_insert_frames": (I, [P, I, I, I, D, P, P, P, I, I, P, P, P, I, P, D, D, D, P]),
     "dpm_local_map_register": (I, [P, I, I, I, D, P, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P, P]),
     "dpm_local_map_export": (I, [P, I, I, I, P, P, P, P, P, I, P]),
     "dpm_local_map_planes": (I, [P, I, I, I, D, P, D, P, P, P]),

@@ -27,6 +27,12 @@
 //            has (dx*dx + dy*dy) + dz*dz <= (float)(radius^2) from the pose's translation is claimed there and its S
 //            sub-cells are copied.  A voxel is one key: the copy has one writer.
 //   export   (key, sub-cell, owner, xyz) of every occupied sub-cell in arrival order + their number; Python sorts.
+//   frames   (dpm_local_map_insert_frames) claim and commit over a LIST of stored frames in two launches, blockIdx.y the list
+//            entry, x over the P columns of a channel-major store (capacity,3,P): entry f offers column i of row frames[f]
+//            under poses[f] by the claim's rule, owner word (stamps[f] << 32) | i.  With a centre, a row is offered only when
+//            its voxel passes prune's test around it: the content is that of the inserts, in any order, followed by the
+//            prune, and the voxels the prune would drop never ask for a slot.  `outside` counts before the filter, `overflow`
+//            after it.
 //
 // Registration: per iteration two launches, no host synchronisation, capturable on one stream.
 //   accumulate: four lanes per query, queries in ROW order.  The query is moved by the device pose rounded to fp32; lane l
@@ -154,6 +160,15 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_clear_kernel(Map M, int h, bool h
     for (size_t i = tid; i < n; i += stride) w[i] = EMPTY;
 }
 
+// prune's test: the centre of voxel `key` lies within sqrt(r2) of the pose's map-frame translation
+__device__ __forceinline__ bool voxel_within(const Map &M, unsigned long long key, const double *pose, float r2) {
+    const float tx = (float)(pose[3] - M.ox), ty = (float)(pose[7] - M.oy), tz = (float)(pose[11] - M.oz);
+    float c[3];
+    voxel_centre(key, M.v, c);
+    const float dx = c[0] - tx, dy = c[1] - ty, dz = c[2] - tz;
+    return (dx * dx + dy * dy) + dz * dz <= r2;
+}
+
 struct Frame {
     const float *xyz;        // (cap,3)
     const int32_t *idx;      // (cap,) original row numbers
@@ -161,10 +176,9 @@ struct Frame {
     int cap;
 };
 
-// what claim and commit compute alike for row i; false when the row offers nothing
-__device__ __forceinline__ bool row_cell(const Map &M, const Frame &F, const GnPose32 &P, int i, float lo2, float hi2,
+// what claim and commit compute alike for the sensor-frame point (x, y, z); false when it offers nothing
+__device__ __forceinline__ bool row_cell(const Map &M, const GnPose32 &P, float x, float y, float z, float lo2, float hi2,
                                          unsigned long long &key, int &sub, float q[3], bool &outside) {
-    const float x = F.xyz[3 * (size_t)i], y = F.xyz[3 * (size_t)i + 1], z = F.xyz[3 * (size_t)i + 2];
     const float r2 = (x * x + y * y) + z * z;
     outside = false;
     if (!(r2 >= lo2 && r2 <= hi2)) return false;
@@ -189,11 +203,59 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_insert_kernel(Map M, Frame F, con
     int sub;
     float q[3];
     bool outside;
-    if (!row_cell(M, F, P, i, lo2, hi2, key, sub, q, outside)) {
+    if (!row_cell(M, P, F.xyz[3 * (size_t)i], F.xyz[3 * (size_t)i + 1], F.xyz[3 * (size_t)i + 2], lo2, hi2, key, sub, q, outside)) {
         if (!COMMIT && outside) atomicAdd(&M.hdr()->outside, 1u);
         return;
     }
     const unsigned long long word = ((unsigned long long)stamp << 32) | (unsigned)F.idx[i];
+    if (!COMMIT) {
+        const int slot = claim_slot(M.keys(M.half), M.cap_vox, key);
+        if (slot < 0) {
+            atomicAdd(&M.hdr()->overflow, 1u);
+            return;
+        }
+        atomicMin(&M.owner(M.half)[(size_t)slot * M.S + sub], word);
+    } else {
+        const int slot = find_slot(M.keys(M.half), M.cap_vox, key);
+        if (slot < 0) return;   // counted as overflow by claim
+        const size_t c = (size_t)slot * M.S + sub;
+        if (M.owner(M.half)[c] == word) M.pts(M.half)[c] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+}
+
+// a list of stored frames: row frames[f] of a channel-major store under poses[f], stamped stamps[f]
+struct FrameList {
+    const float *store;        // (capacity,3,P)
+    const int32_t *lengths;    // (capacity,)
+    int capacity, P;
+    const int32_t *frames;     // (F,) rows of the store
+    const double *poses;       // (F,16)
+    const uint32_t *stamps;    // (F,)
+    const double *centre;      // (16,) or NULL: no filter
+};
+
+// lm_insert_kernel over a list: blockIdx.y the list entry, x over the columns.  Hundreds of entries offer points to the same
+// sub-cells; reading the owner word first and skipping an offer it already beats gave the same bytes and no time
+// (profiles/local_map_rebuild_bench.md), so every offer is one atomicMin.
+template <bool COMMIT>
+__global__ __launch_bounds__(LM_BLOCK) void lm_insert_frames_kernel(Map M, FrameList L, float lo2, float hi2, float r2) {
+    const int f = blockIdx.y, i = blockIdx.x * LM_BLOCK + threadIdx.x;
+    const int row = L.frames[f];
+    if ((unsigned)row >= (unsigned)L.capacity) return;   // checked on the host where the list is there; never read out of bounds
+    const int n = min(max(L.lengths[row], 0), L.P);
+    if (i >= n) return;
+    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
+    const float *p = L.store + (size_t)row * 3 * L.P + i;
+    unsigned long long key;
+    int sub;
+    float q[3];
+    bool outside;
+    if (!row_cell(M, P, p[0], p[L.P], p[2 * (size_t)L.P], lo2, hi2, key, sub, q, outside)) {
+        if (!COMMIT && outside) atomicAdd(&M.hdr()->outside, 1u);
+        return;
+    }
+    if (L.centre && !voxel_within(M, key, L.centre, r2)) return;
+    const unsigned long long word = ((unsigned long long)L.stamps[f] << 32) | (unsigned)i;
     if (!COMMIT) {
         const int slot = claim_slot(M.keys(M.half), M.cap_vox, key);
         if (slot < 0) {
@@ -215,11 +277,7 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_prune_kernel(Map M, const double 
     if (slot >= M.cap_vox) return;
     const unsigned long long key = M.keys(M.half)[slot];
     if (key == EMPTY) return;
-    const float tx = (float)(pose[3] - M.ox), ty = (float)(pose[7] - M.oy), tz = (float)(pose[11] - M.oz);
-    float c[3];
-    voxel_centre(key, M.v, c);
-    const float dx = c[0] - tx, dy = c[1] - ty, dz = c[2] - tz;
-    if (!((dx * dx + dy * dy) + dz * dz <= r2)) return;
+    if (!voxel_within(M, key, pose, r2)) return;
     const int to = claim_slot(M.keys(1 - M.half), M.cap_vox, key);   // never full: no more keys than the old half held
     if (to < 0) {
         atomicAdd(&M.hdr()->overflow, 1u);
@@ -520,6 +578,27 @@ extern "C" int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half,
                        (hipStream_t)stream, M, 1 - half, false);
     hipLaunchKernelGGL(lm_prune_kernel, dim3(dpm_cdiv(cap_vox, LM_BLOCK)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, pose,
                        (float)(radius * radius));
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_local_map_insert_frames(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                           const float *store, const int32_t *lengths, int capacity, int P,
+                                           const int32_t *frames, const double *poses, const uint32_t *stamps, int F,
+                                           const double *centre, double radius, double min_range, double max_range,
+                                           dpm_stream_t stream) {
+    DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
+    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    DPM_CHECK_ARG(min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
+    DPM_CHECK_ARG(!centre || (radius >= 0.0 && radius < 1e18));
+    if (F == 0) return DPM_OK;
+    DPM_CHECK_ARG(store && lengths && frames && poses && stamps);
+    const Map M = make_map(map, cap_vox, subdiv, half, voxel, origin);
+    const FrameList L{store, lengths, capacity, P, frames, poses, stamps, centre};
+    const float lo2 = (float)(min_range * min_range), hi2 = (float)(max_range * max_range);
+    const float r2 = centre ? (float)(radius * radius) : 0.f;
+    const dim3 grid(dpm_cdiv(P, LM_BLOCK), F);
+    hipLaunchKernelGGL(lm_insert_frames_kernel<false>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, L, lo2, hi2, r2);
+    hipLaunchKernelGGL(lm_insert_frames_kernel<true>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, L, lo2, hi2, r2);
     return dpm_launch_status();
 }
 

@@ -8,7 +8,8 @@ baseline, and refine.build_refined_table loop pairs that no ground truth picked 
 the exhaustive search over them.  `LoopCloser.add(pcd, pose)` takes a frame and its pose from ANY source (an odometry, a
 learned pipeline, ground truth with drift), looks for earlier frames of the same place, verifies them and grows a pose graph;
 `optimise()` returns the corrected trajectory.  `close_loops` is the offline form, `GeometricSlam` the odometry
-(odometry.LidarOdometry, composed, not changed) with the loop closer behind it.
+(odometry.LidarOdometry, composed) with the loop closer behind it; with rewrite_map a correction also reaches the map the next
+frame is registered against (LocalMap.rebuild from the stored frames, LidarOdometry.rebase).
 """
 from __future__ import annotations
 
@@ -280,6 +281,18 @@ class LoopCloser:
             self._take(accepted)
         return accepted
 
+    def keyframes_near(self, position, radius: float, poses=None, skip=()) -> List[int]:
+        """the stored rows whose pose's translation lies within `radius` of `position` (3,), the boundary included, ascending;
+        poses (n,4,4): the poses to judge by (a corrected trajectory, say; default: the ones `add` was given); skip: rows
+        left out.  Host arithmetic on host poses: no synchronisation."""
+        poses = self.poses if poses is None else poses
+        if len(poses) == 0:
+            return []
+        t = np.asarray(poses, np.float64).reshape(-1, 4, 4)[:len(self.poses), :3, 3]
+        near = np.linalg.norm(t - np.asarray(position, np.float64).reshape(3), axis=1) <= float(radius)
+        skip = set(int(s) for s in skip)
+        return [int(i) for i in np.nonzero(near)[0] if int(i) not in skip]
+
     # -- the graph
     def edges(self):
         """(source, target, X, information) of posegraph_optim.global_optimization: X takes source-scan coordinates into the
@@ -365,27 +378,64 @@ def close_loops(frames, poses, batch_pairs: int = 64, return_closer: bool = Fals
 class GeometricSlam:
     """LidarOdometry with a LoopCloser behind it: `step(pcd)` runs LidarOdometry.step, then LoopCloser.add with the pose it
     returned, and optimises the graph after an accepted loop.  `poses` is the corrected trajectory, `odometry.poses` the raw
-    one.  LIMIT: the local map is NOT rewritten after a correction -- it keeps running in the odometry's frame, so the
-    odometry neither gains nor loses from a loop; only the reported trajectory does.  odometry / loop: the keyword arguments
-    of LidarOdometry and LoopCloser."""
+    one.  odometry / loop: the keyword arguments of LidarOdometry and LoopCloser.
 
-    def __init__(self, odometry: Optional[dict] = None, loop: Optional[dict] = None):
+    rewrite_map=False: the local map keeps running in the odometry's frame, so the odometry neither gains nor loses from a
+    loop; only the reported trajectory does.  rewrite_map=True: after an accepted loop whose correction of the current pose
+    (the corrected pose Pc against the odometry's P) reaches rewrite_min_shift = (metres, radians) in translation OR in
+    rotation, the local map is rebuilt (LocalMap.rebuild) from the loop closer's stored frames within keyframe_radius
+    (default: the map's max_range) of Pc under their corrected poses, frames whose registration failed left out, and the
+    odometry is rebased by C = Pc P^-1 (LidarOdometry.rebase): the next frame is registered against the corrected geometry of
+    every earlier visit.  The loop closer never sees the jump: from the first rebase on it is handed the un-rebased chain
+    chain_k = chain_{k-1} P'_{k-1}^-1 P'_k (both P' in the odometry's current frame).  LIMIT: the rebuilt map consists of the
+    loop closer's thinned copies, at most points_per_frame a frame (and `sample`d), not of the odometry's own inserts; they
+    are not deskewed, so rewrite_map with the odometry's deskew raises ValueError."""
+
+    def __init__(self, odometry: Optional[dict] = None, loop: Optional[dict] = None, rewrite_map: bool = False,
+                 keyframe_radius: Optional[float] = None, rewrite_min_shift: Tuple[float, float] = (0.0, 0.0)):
+        if rewrite_map and (odometry or {}).get("deskew"):
+            raise ValueError("rewrite_map with deskew: the loop closer's stored frames are not deskewed")
         self.odometry = LidarOdometry(**(odometry or {}))
         self.loop_closer = LoopCloser(**(loop or {}))
+        self.rewrite_map, self.keyframe_radius = bool(rewrite_map), keyframe_radius
+        self.rewrite_min_shift = (float(rewrite_min_shift[0]), float(rewrite_min_shift[1]))
         self._corrected: List[np.ndarray] = []
         self._shifted = False       # a correction has happened: later poses follow it
+        self._chain: Optional[np.ndarray] = None     # the last pose handed to the loop closer, once the odometry was rebased
+
+    def _rewrite(self, pose: np.ndarray):
+        """the map rebuilt around the current frame's corrected pose and the odometry rebased, if the correction is large enough"""
+        Pc = self._corrected[-1]
+        C = Pc @ np.linalg.inv(pose)
+        shift = float(np.linalg.norm(Pc[:3, 3] - pose[:3, 3]))
+        turn = float(np.arccos(np.clip((np.trace(C[:3, :3]) - 1.0) / 2.0, -1.0, 1.0)))
+        if not (shift >= self.rewrite_min_shift[0] or turn >= self.rewrite_min_shift[1]):
+            return
+        lc, lm = self.loop_closer, self.odometry.local_map
+        failed = [i for i, st in enumerate(self.odometry.steps) if st.status not in (CONVERGED, MAX_ITER)]
+        corrected = np.stack(self._corrected)
+        rows = lc.keyframes_near(Pc[:3, 3], lm.max_range if self.keyframe_radius is None else self.keyframe_radius,
+                                 poses=corrected, skip=failed)
+        lm.rebuild(lc.store, lc.lengths, rows, corrected[rows], centre=Pc)
+        if self._chain is None:
+            self._chain = lc.poses[-1]
+        self.odometry.rebase(C)
 
     def step(self, pcd):
         """-> (odometry.OdometryStep, the loop edges accepted for this frame)"""
+        previous = self.odometry._pose(-1) if self.odometry.poses else None     # in the odometry's current frame, as st.pose
         st = self.odometry.step(pcd)
-        accepted = self.loop_closer.add(pcd, st.pose)
+        if self._chain is not None:
+            self._chain = self._chain @ (np.linalg.inv(previous) @ st.pose)
+        accepted = self.loop_closer.add(pcd, st.pose if self._chain is None else self._chain)
         if accepted:
             self._corrected = list(self.loop_closer.optimise())
             self._shifted = True
+            if self.rewrite_map:
+                self._rewrite(st.pose)
         elif self._shifted:
             # no new loop: the last correction carries on along the odometry's own motion
-            raw = self.odometry.poses
-            self._corrected.append(self._corrected[-1] @ (np.linalg.inv(raw[-2]) @ raw[-1]))
+            self._corrected.append(self._corrected[-1] @ (np.linalg.inv(previous) @ st.pose))
         else:
             self._corrected.append(st.pose.copy())     # nothing corrected yet: the odometry's pose, byte for byte
         return st, accepted

@@ -6,6 +6,7 @@ only.  Here it gives the evaluation tools (evaluate.py) a system to judge, the l
 
 `LocalMap` is the map: insert, prune, planes, register, read-back.  Its content is a function of the inserted points alone
 (DESIGN §7j): a sub-cell of a voxel keeps the point of the oldest frame, and within a frame of the smallest original row.
+`insert_frames` / `rebuild` make it from a list of stored frames with a pose each (after a loop correction).
 `LidarOdometry.step` is one frame: constant-velocity prediction on the host, optional deskew with that prediction, thinning
 with augment.voxel_sample, then register -> insert -> prune queued on the device pose, and ONE read-back.
 """
@@ -77,7 +78,7 @@ class LocalMap:
     def _args(self):
         return self.table, self.max_voxels, self.subdivisions, self.half, self.voxel_size, self.origin
 
-    # -- the three device operations: no host synchronisation
+    # -- the device operations: no host synchronisation
     def insert(self, pcd, pose):
         """the frame's valid rows under `pose` (4,4; numpy, or a tensor -- on the GPU it is read there, behind whatever wrote
         it); the rule sees the rows' `idx`.  Two launches."""
@@ -97,6 +98,56 @@ class LocalMap:
         self.half = 1 - self.half
         self._planes_stale = True
         return self
+
+    def insert_frames(self, store, lengths, frames, poses, stamps=None, centre=None, radius=None):
+        """stored frames under a pose each, in two launches for any number of them: row frames[f] of `store` (capacity,3,P)
+        fp32 channel-major / `lengths` (capacity,) int32 on the device (LoopCloser.store, .lengths) under poses[f] (F,4,4;
+        sensor -> world), stamped stamps[f] (host integers, pairwise distinct; None: the rows themselves); the rule sees the
+        COLUMN of a point as its row number.  frames / poses: host arrays (uploaded, nothing is read back) or device tensors;
+        frames on the device need `stamps`.  centre (4,4): only voxels that `prune(centre, radius)` would keep are offered
+        (radius None: max_range), so the result is that of `insert` of each frame with its stamp, in any order, and that
+        prune -- without the slots the dropped voxels would have taken first.  Adds to the current half."""
+        if stamps is None:
+            if isinstance(frames, torch.Tensor):
+                raise ValueError("insert_frames: frames on the device need stamps (host integers)")
+            stamps = frames
+        stamps = [int(s) for s in np.asarray(stamps).reshape(-1)]
+        if len(set(stamps)) != len(stamps) or any(not 0 <= s < 0xFFFFFFFF for s in stamps):
+            raise ValueError("insert_frames: stamps pairwise distinct, in [0, 2^32 - 1)")
+        dev = store.device
+        if isinstance(frames, torch.Tensor):
+            rows = frames.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            host = np.asarray(frames, np.int64).reshape(-1)
+            if host.size and not (0 <= host.min() and host.max() < store.shape[0]):
+                raise ValueError("insert_frames: frames are rows of the store")
+            rows = torch.from_numpy(host.astype(np.int32)).to(dev)
+        if len(stamps) != rows.numel():
+            raise ValueError("insert_frames: one stamp per frame")
+        if not isinstance(poses, torch.Tensor):
+            poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4))
+        if poses.numel() != 16 * rows.numel():
+            raise ValueError("insert_frames: poses (F,4,4)")
+        first = centre if centre is not None else (poses.reshape(-1, 4, 4)[0] if rows.numel() else None)
+        self._ready(dev, first)
+        if rows.numel() == 0:
+            return self
+        ops.local_map_insert_frames(*self._args(), store, lengths, rows, poses.to(device=self.device, dtype=torch.float64).contiguous(),
+                                    torch.from_numpy(np.array(stamps, np.uint32).view(np.int32)).to(self.device),
+                                    None if centre is None else _pose_tensor(centre, self.device),
+                                    self.max_range if radius is None else float(radius), self.min_range, self.max_range)
+        self.stamp = max(self.stamp, max(stamps) + 1)
+        self._planes_stale = True
+        return self
+
+    def rebuild(self, store, lengths, frames, poses, centre, radius=None):
+        """the map emptied (both halves, the header; `origin` is kept) and made anew from stored frames around `centre`:
+        `insert_frames` into half 0.  No host synchronisation."""
+        self._ready(store.device, centre)
+        ops.local_map_clear(self.table, self.max_voxels, self.subdivisions)
+        self.half = 0
+        self._planes_stale = True
+        return self.insert_frames(store, lengths, frames, poses, centre=centre, radius=radius)
 
     def planes(self):
         """(planes (max_voxels,4) float32 (normal, w), counts (max_voxels,) int32) on the device, per SLOT of the current
@@ -244,7 +295,8 @@ class LidarOdometry:
     `kernel_scale` every step registers with ONE stage (min(3 sigma, voxel_size), max_iter of the schedule's last stage) and
     kernel_scale sigma / 3, sigma = adaptive_sigma of the deviations between predicted and registered pose so far (those above
     min_motion; sigma0 before there is one).  The gate is clipped at voxel_size because the search looks into 27 voxels.
-    `gates` lists (schedule, kernel_scale) of every registered step.
+    `gates` lists (schedule, kernel_scale) of every registered step.  `rebase(C)` moves the odometry into another frame (after a
+    loop correction; loop_closure.GeometricSlam).
 
     One host synchronisation per step, counted in augment.host_syncs(): the read-back of the pose, the registration's
     results and the device-side error flags together.  The caller's frame keeps its bytes: the work is done on a copy."""
@@ -278,18 +330,34 @@ class LidarOdometry:
         self.initial_motion = np.eye(4) if initial_motion is None else np.array(initial_motion, np.float64).reshape(4, 4)
         self.poses: list = []
         self.steps: list = []
+        self.rebases: list = []      # (index of the first pose in the new frame, C) of every rebase
+        self._moved: dict = {}       # pose index -> that pose in the CURRENT frame, for the two poses a rebase moved
+
+    def rebase(self, C):
+        """from the next step on the odometry works in the frame C . old (C (4,4): a loop correction, say): the two poses the
+        prediction reads become C @ P, so the predicted motion stays what it was up to the product's rounding.  `poses`
+        recorded so far keep their bytes; `rebases` lists (len(poses), C).  The map is the caller's business
+        (LocalMap.rebuild)."""
+        C = np.array(C, np.float64).reshape(4, 4)
+        n = len(self.poses)
+        self._moved = {i: C @ self._pose(i) for i in range(max(n - 2, 0), n)}
+        self.rebases.append((n, C))
+
+    def _pose(self, i: int) -> np.ndarray:
+        """pose i (negative: from the end) in the odometry's current frame: `poses[i]` unless a rebase has moved it since"""
+        return self._moved.get(i % len(self.poses), self.poses[i])
 
     def predicted_motion(self, pcd=None) -> np.ndarray:
         """(4,4) float64: the motion predicted for the NEXT sweep, P_{k-2}^-1 P_{k-1} (`initial_motion` before two poses
         exist).  Takes and ignores a frame, so the bound method is a `motion` callable of augment.Deskew."""
         if len(self.poses) < 2:
             return self.initial_motion.copy()
-        return np.linalg.inv(self.poses[-2]) @ self.poses[-1]
+        return np.linalg.inv(self._pose(-2)) @ self._pose(-1)
 
     def predicted_pose(self) -> np.ndarray:
         if not self.poses:
             return self.first_pose.copy()
-        return self.poses[-1] @ self.predicted_motion()
+        return self._pose(-1) @ self.predicted_motion()
 
     def gate(self):
         """((max_dist, max_iter), ...) and kernel_scale of the next registration: the schedule and scale given, or with

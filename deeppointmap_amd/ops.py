@@ -2203,6 +2203,13 @@ def local_map_new(cap_vox: int, subdiv: int, device) -> torch.Tensor:
         raise ValueError("cap_vox: a power of two in [2, 2^24]; subdiv: 1, 2 or 3")
     with torch.cuda.device(device):
         table = torch.empty(n, device=device, dtype=torch.uint8)
+    return local_map_clear(table, cap_vox, subdiv)
+
+
+def local_map_clear(table, cap_vox, subdiv) -> torch.Tensor:
+    """dpm_local_map_init: the header zeroed, both halves empty"""
+    _local_map_args(table, cap_vox, subdiv)
+    with torch.cuda.device(table.device):
         _lib.check(_lib.load().dpm_local_map_init(_ptr(table), int(cap_vox), int(subdiv), _stream(table)), "dpm_local_map_init")
     return table
 
@@ -2228,6 +2235,30 @@ def local_map_prune(table, cap_vox, subdiv, half, voxel, origin, pose, radius):
     with torch.cuda.device(table.device):
         _lib.check(_lib.load().dpm_local_map_prune(_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o),
                                                    _ptr(pose), float(radius), _stream(table)), "dpm_local_map_prune")
+
+
+def local_map_insert_frames(table, cap_vox, subdiv, half, voxel, origin, store, lengths, frames, poses, stamps, centre, radius,
+                            min_range, max_range):
+    """dpm_local_map_insert_frames: store (capacity,3,P) fp32 channel-major, lengths (capacity,) int32, frames (F,) int32 rows
+    of the store, poses (F,4,4) fp64, stamps (F,) int32 holding the uint32 stamps' bits, centre (4,4) fp64 or None (then
+    radius is ignored), all on the GPU.  Two launches for any F, no host synchronisation, capturable in a graph."""
+    o = _local_map_args(table, cap_vox, subdiv, origin)
+    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
+    _chk(poses, torch.float64, "poses"), _chk(stamps, torch.int32, "stamps")
+    F = frames.numel()
+    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
+            or frames.dim() != 1 or poses.numel() != 16 * F or stamps.shape != frames.shape:
+        raise ValueError("local_map_insert_frames: store (capacity,3,P), lengths (capacity,), frames (F,), poses (F,4,4), stamps (F,)")
+    if centre is not None:
+        _chk(centre, torch.float64, "centre")
+        if centre.numel() != 16:
+            raise ValueError("local_map_insert_frames: centre (4,4)")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_local_map_insert_frames(
+            _ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths),
+            store.shape[0], store.shape[2], _ptr(frames), _ptr(poses), _ptr(stamps), F, _ptr(centre),
+            0.0 if centre is None else float(radius), float(min_range), float(max_range), _stream(table)),
+            "dpm_local_map_insert_frames")
 
 
 def local_map_planes(table, cap_vox, subdiv, half, voxel, origin, plane_radius, planes=None, counts=None):

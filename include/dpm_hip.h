@@ -1019,6 +1019,22 @@ int dpm_local_map_insert(void *map, int cap_vox, int subdiv, int half, double vo
  * axis has (dx*dx + dy*dy) + dz*dz <= (float)(radius^2) from the pose's map-frame translation; its sub-cells are copied. */
 int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin, const double *pose,
                         double radius, dpm_stream_t stream);
+/* A list of stored frames in two launches for any F (claim, commit; grid y = list entry), no workspace, capturable: what it
+ * takes to rebuild a map from keyframes.  store (capacity,3,P) fp32 CHANNEL-major and lengths (capacity,) int32 on the device
+ * (a length is clamped to [0, P], as dpm_local_map_insert clamps count); frames (F,) int32 rows of the store (a row outside
+ * [0, capacity) offers nothing), poses (F,16) fp64 sensor -> world, stamps (F,) uint32 pairwise distinct and < 2^32 - 1, all on
+ * the device; F in [0, 65535], F = 0 is a no-op.  Column i of entry f is offered under exactly dpm_local_map_insert's rule
+ * (range gate on the sensor-frame point, the transform, voxel, key and sub-cell) with the owner word (stamps[f] << 32) | i.
+ * centre: 16 doubles on the device (a pose; its translation is used) or NULL.  With a centre, a row is offered only when
+ * its voxel passes dpm_local_map_prune's test around it -- the same fp32 expression on the voxel's centre,
+ * (float)(centre_t - origin) and (float)(radius^2).  Header word 1 counts as dpm_local_map_insert counts it, before the
+ * filter; header word 0 counts rows that pass the filter and find no slot.  On a map that does not overflow, the sorted export
+ * equals that after dpm_local_map_insert of each entry with its stamp, in any order, followed by dpm_local_map_prune(centre,
+ * radius), byte for byte; voxels the prune would drop never take a slot. */
+int dpm_local_map_insert_frames(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
+                                const float *store, const int32_t *lengths, int capacity, int P, const int32_t *frames,
+                                const double *poses, const uint32_t *stamps, int F, const double *centre, double radius,
+                                double min_range, double max_range, dpm_stream_t stream);
 /* Robust point-to-point ICP of the frame's first count rows against the map, from init_pose (device), over the schedule
  * (stage_max_dist, stage_max_iter: n_stages <= 16 values ON THE HOST): two launches per iteration, capturable.  Every
  * stage_max_dist must be <= voxel: a query looks into the 3 x 3 x 3 voxels around its own.  The match is the occupied
