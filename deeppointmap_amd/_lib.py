@@ -166,6 +166,13 @@ SIGNATURES = {
     "dpm_local_map_planes": (I, [P, I, I, I, D, P, D, P, P, P]),
     "dpm_local_map_register_planes": (I, [P, I, I, I, D, P, P, P, I, D, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P,
                                           P]),
+    "dpm_tsdf_bytes": (c_size_t, [I]),
+    "dpm_tsdf_init": (I, [P, I, P]),
+    "dpm_tsdf_integrate": (I, [P, I, D, P, P, P, I, P, D, D, D, D, P]),
+    "dpm_tsdf_integrate_frames": (I, [P, I, D, P, P, P, I, I, P, P, I, D, D, D, D, P]),
+    "dpm_tsdf_export": (I, [P, I, P, P, P, P, I, P]),
+    "dpm_tsdf_surface": (I, [P, I, D, I, P, P, P, P, P, I, P]),
+    "dpm_tsdf_mesh": (I, [P, I, D, I, P, P, P, P, I, P]),
     "dpm_scan_context_build": (I, [P, P, I, I, I, D, D, D, P, P, P, P, P, P]),
     "dpm_scan_context_build_batched": (I, [P, P, I, I, I, I, D, D, D, P, P, P, P, P, P]),
     "dpm_scan_context_search_workspace_bytes": (c_size_t, [I, I, I]),

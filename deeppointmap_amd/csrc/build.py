@@ -61,6 +61,7 @@ SOURCES = {
     "deskew.hip": [],
     "local_map.hip": [],
     "scan_context.hip": [],
+    "tsdf_map.hip": [],
 }
 
 

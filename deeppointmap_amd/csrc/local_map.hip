@@ -67,11 +67,11 @@
 #include "cell_grid.h"
 #include "gn_solve.h"
 #include "sym3_jacobi.h"
+#include "voxel_hash.h"
 #include "workspace.h"
 
 namespace {
 
-constexpr unsigned long long EMPTY = ~0ull;
 constexpr int LM_BLOCK = 256;
 
 struct MapHdr {   // 256 bytes
@@ -89,51 +89,6 @@ struct Map {
     __host__ __device__ float4 *pts(int h) const { return (float4 *)(owner(h) + (size_t)cap_vox * S); }
     __host__ __device__ MapHdr *hdr() const { return (MapHdr *)base; }
 };
-
-// voxel coordinate (biased by 2^20) and sub-cell coordinate of one axis; 0 when the 21 bits cannot hold it (or NaN)
-__device__ __forceinline__ int axis_cell(float p, float v, int s, int &vox, int &sub) {
-    const float f = __fdiv_rn(p, v), fl = floorf(f);
-    if (!(fl >= -1048576.f && fl < 1048576.f)) return 0;
-    vox = (int)fl + 1048576;
-    sub = min((int)((f - fl) * (float)s), s - 1);
-    return 1;
-}
-
-__device__ __forceinline__ unsigned long long pack_key(int x, int y, int z) {
-    return (unsigned long long)x | ((unsigned long long)y << 21) | ((unsigned long long)z << 42);
-}
-
-__device__ __forceinline__ int key_axis(unsigned long long key, int a) { return (int)((key >> (21 * a)) & 0x1FFFFF); }
-
-// the centre of a held voxel, per axis c = ((float)index + 0.5f) * v
-__device__ __forceinline__ void voxel_centre(unsigned long long key, float v, float c[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = ((float)(key_axis(key, a) - 1048576) + 0.5f) * v;
-}
-
-// slot of `key` in a table nobody is writing, or -1
-__device__ __forceinline__ int find_slot(const unsigned long long *keys, int cap_vox, unsigned long long key) {
-    int slot = (int)(mix64(key) & (unsigned long long)(cap_vox - 1));
-    for (int probe = 0; probe < cap_vox; ++probe) {
-        const unsigned long long k = keys[slot];
-        if (k == key) return slot;
-        if (k == EMPTY) return -1;
-        slot = (slot + 1) & (cap_vox - 1);
-    }
-    return -1;
-}
-
-// slot of `key`, claimed if new, in a table other lanes are claiming in; -1 when no slot is free
-__device__ __forceinline__ int claim_slot(unsigned long long *keys, int cap_vox, unsigned long long key) {
-    int slot = (int)(mix64(key) & (unsigned long long)(cap_vox - 1));
-    for (int probe = 0; probe < cap_vox; ++probe) {
-        unsigned long long k = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == EMPTY) k = atomicCAS(&keys[slot], EMPTY, key);
-        if (k == EMPTY || k == key) return slot;
-        slot = (slot + 1) & (cap_vox - 1);
-    }
-    return -1;
-}
 
 // Lane ql of a quad visits the neighbours n = ql, ql + 4, ... (n = ((dz+1) * 3 + (dy+1)) * 3 + (dx+1)) of the 27 voxels around
 // (vx, vy, vz) and offers every occupied sub-cell, ascending, to f(n, slot, c, point).  own_slot >= 0: the slot of n = 13, if known.

@@ -1,0 +1,414 @@
+// A truncated signed distance field (TSDF) over hashed voxels, and a surface from it (deeppointmap_amd/tsdf.py is the caller).
+// The reference has no counterpart: its map is a cloud of points.  DESIGN §7l is the definition.
+//
+// Map: one buffer of 256 + 20 cap_vox bytes.  A 256-byte header (word 0: samples that found no slot, word 1: samples outside
+// the 21-bit key range), then an open-addressing table of cap_vox slots (csrc/voxel_hash.h: the keys, the probing and the
+// cutting of space are csrc/local_map.hip's) as three arrays: key u64, sum int64, count u32.  The map frame and the pose
+// handling are the local map's too: a float64 `origin` on the host, a pose of 16 doubles in device memory entering as (float)R
+// and (float)(t - origin) (gn_load_pose), a point as gn_xform's fma chain.
+//
+//   integrate  one lane per row, one launch.  Per row that passes the local map's range gate on the SENSOR-frame point, in fp32,
+//              every operation rounded once (the build has -ffp-contract=off; the division is __fdiv_rn, the square root sqrtf,
+//              which this build expands to the correctly rounded sequence -- __fsqrt_rn is the bare 1-ulp instruction here):
+//                  r = sqrt((x*x + y*y) + z*z),  q = the row in the map frame,  o = the pose's map-frame translation,
+//                  u = (q - o) / r per axis.
+//              For k = -n .. n ascending (n = ceil(tau / h), formed on the host): t = r + (float)k * h; the sample is skipped
+//              unless t > 0; p = o + u * t per axis; the voxel of p per axis by axis_cell (a sample outside the 21 bits adds one
+//              to header word 1 and is skipped); a sample whose key equals the key of this ray's previous keyed sample is skipped.
+//              With c the voxel's centre and e = q - c:  s = (ux*ex + uy*ey) + uz*ez clamped to [-(float)tau, (float)tau]:
+//              positive on the sensor's side of the return.  fixed = (long long)rintf(s * 2^24) (round half to even; |fixed| <=
+//              2^30 since tau <= 64).  The slot is found or claimed (atomicCAS on the key), then sum += fixed and count += 1 by
+//              integer atomics (equal keys of a wave merged first: integrate_ray).  No free slot: header word 0 counts the sample.
+//              Integer atomics only, and integer addition commutes: what a key leads to is the same whatever the order of rows,
+//              frames or launches.  Slot positions are not, and nothing reads them.
+//   frames     the same rule over a list of stored frames: blockIdx.y the list entry, x over the P columns of a channel-major
+//              store (capacity,3,P), as dpm_local_map_insert_frames reads it.
+//   export     (key, sum, count) of every occupied slot in arrival order + their number; Python sorts.
+//
+// Field: D(slot) = (float)((double)sum / ((double)count * 2^24)).  A voxel is QUALIFIED when count >= min_count (>= 1).
+//   surface    one lane per slot.  For a qualified voxel k0 and an axis a with k1 = k0 + e_a qualified and (D0 < 0) != (D1 < 0):
+//              f = D0 / (D0 - D1), the position is k0's centre with f * v added on axis a.  grad(k)_b from the qualified
+//              neighbours of k on axis b: both: D(k + e_b) - D(k - e_b); only +: 2 (D(k + e_b) - D(k)); only -: 2 (D(k) -
+//              D(k - e_b)); neither: 0.  The normal is g = grad(k0) + grad(k1), divided per axis by sqrt((gx*gx + gy*gy) + gz*gz)
+//              where that is > 0, else (0, 0, 0); it points to free space (D grows towards the sensor).
+//   mesh       marching tetrahedra, one lane per slot.  The cell anchored at a voxel centre is meshed only when its 8 corner
+//              voxels are qualified.  Corner number m = dx | dy << 1 | dz << 2.  The six tetrahedra of the Kuhn decomposition
+//              round the diagonal 0 - 7, one per permutation (a, b, c) of the axes in lexicographic order: corners 0, 1 << a,
+//              1 << a | 1 << b, 7.  Every edge of them runs from a corner p to a corner q that contains p's bits, so a vertex is
+//              named (key of p, direction): q ^ p = 1, 2, 4 (axes) -> 0, 1, 2; 3, 5, 6 (face diagonals) -> 3, 4, 5; 7 (the body
+//              diagonal) -> 6.  The faces of neighbouring cells carry the same diagonals.  A vertex exists where (Dp < 0) !=
+//              (Dq < 0): f = Dp / (Dp - Dq), the position is p's centre with f * v added on every axis of q ^ p.  One negative
+//              or one non-negative corner gives a triangle, two and two a quadrilateral cut into two triangles; they are wound
+//              so that the normal (b - a) x (c - a) points to the positive side.  A corner with D == 0 counts as positive, and
+//              the triangles of zero area it makes are kept.
+#include "gn_solve.h"
+#include "voxel_hash.h"
+
+namespace {
+
+constexpr int TS_BLOCK = 256;
+constexpr float FIX_ONE = 16777216.f;   // 2^24: |s| <= 64 m leaves 2^32 samples of headroom in the int64 sum
+constexpr int MAX_STEPS = 4096;         // n = ceil(tau / h) at most
+
+struct TsdfHdr {   // 256 bytes
+    unsigned overflow, outside, pad[62];
+};
+
+struct Tsdf {
+    unsigned char *base;
+    int cap_vox;
+    float v;
+    double ox, oy, oz;
+    __host__ __device__ unsigned long long *keys() const { return (unsigned long long *)(base + 256); }
+    __host__ __device__ long long *sum() const { return (long long *)(keys() + cap_vox); }
+    __host__ __device__ unsigned *count() const { return (unsigned *)(sum() + cap_vox); }
+    __host__ __device__ TsdfHdr *hdr() const { return (TsdfHdr *)base; }
+};
+
+struct Rays {
+    float lo2, hi2, tau, h;
+    int n;
+};
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_clear_kernel(Tsdf M) {
+    const size_t tid = (size_t)blockIdx.x * TS_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * TS_BLOCK;
+    if (tid < 64) ((unsigned *)M.base)[tid] = 0u;
+    for (size_t i = tid; i < (size_t)M.cap_vox; i += stride) M.keys()[i] = EMPTY, M.sum()[i] = 0, M.count()[i] = 0u;
+}
+
+// One return (x, y, z) in the sensor frame under pose P: the samples of its ray.  Neighbouring rows of a sweep are neighbouring
+// columns of one beam and fall into the same voxel at the same k, so equal keys are merged inside a wave before the atomics:
+// every lane of the wave walks the samples together (row = false: a lane without a return), runs of neighbouring lanes with one
+// key are summed by a segmented suffix sum over (count << 40) + fixed (|fixed| <= 2^30, 64 lanes), and the first lane of a run
+// adds the run's sum and count.  The same integers reach the table as with one pair of atomics a sample, which timed 2.4 times
+// slower on an HDL64E frame (profiles/tsdf_bench.md).  The callers keep the wave together: no lane returns before this.
+__device__ __forceinline__ void integrate_ray(const Tsdf &M, const GnPose32 &P, bool row, float x, float y, float z,
+                                              const Rays &R) {
+    const int lane = threadIdx.x & 63;
+    const float r2 = (x * x + y * y) + z * z;
+    const bool live = row && r2 >= R.lo2 && r2 <= R.hi2;
+    const float r = sqrtf(r2);
+    float q[3], u[3];
+    gn_xform(P, x, y, z, q);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) u[a] = __fdiv_rn(q[a] - P.t[a], r);
+    unsigned long long prev = EMPTY;
+    for (int k = -R.n; k <= R.n; ++k) {
+        const float t = r + (float)k * R.h;
+        bool valid = live && t > 0.f;
+        int vox[3] = {0, 0, 0}, sub;
+        int inside = 1;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) inside &= axis_cell(P.t[a] + u[a] * t, M.v, 1, vox[a], sub);
+        if (valid && !inside) atomicAdd(&M.hdr()->outside, 1u);
+        valid = valid && inside;
+        unsigned long long key = valid ? pack_key(vox[0], vox[1], vox[2]) : EMPTY;
+        if (valid && key == prev) valid = false, key = EMPTY;
+        else if (valid) prev = key;
+        float c[3];
+        voxel_centre(key, M.v, c);
+        const float ex = q[0] - c[0], ey = q[1] - c[1], ez = q[2] - c[2];
+        const float s = fminf(fmaxf((u[0] * ex + u[1] * ey) + u[2] * ez, -R.tau), R.tau);
+        long long acc = valid ? (1ll << 40) + (long long)rintf(s * FIX_ONE) : 0ll;
+        const unsigned long long before = __shfl_up(key, 1, 64);
+        const bool head = lane == 0 || before != key;
+        const unsigned long long heads = __ballot(head || !valid);
+        const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+        const int end = above ? lane + __ffsll((long long)above) : 64;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const long long other = __shfl_down(acc, off, 64);
+            if (lane + off < end) acc += other;
+        }
+        if (valid && head) {
+            const long long cnt = (acc + (1ll << 39)) >> 40, total = acc - (cnt << 40);
+            const int slot = claim_slot(M.keys(), M.cap_vox, key);
+            if (slot < 0) {
+                atomicAdd(&M.hdr()->overflow, (unsigned)cnt);
+            } else {
+                atomicAdd((unsigned long long *)&M.sum()[slot], (unsigned long long)total);
+                atomicAdd(&M.count()[slot], (unsigned)cnt);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_kernel(Tsdf M, const float *xyz, const int32_t *count, int cap,
+                                                                const double *pose, Rays R) {
+    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const int n = min(max(count[0], 0), cap);
+    const bool row = i < n;
+    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
+    integrate_ray(M, P, row, row ? xyz[3 * (size_t)i] : 0.f, row ? xyz[3 * (size_t)i + 1] : 0.f, row ? xyz[3 * (size_t)i + 2] : 0.f, R);
+}
+
+// a list of stored frames: row frames[f] of a channel-major store under poses[f]
+struct TsFrameList {
+    const float *store;        // (capacity,3,P)
+    const int32_t *lengths;    // (capacity,)
+    int capacity, P;
+    const int32_t *frames;     // (F,) rows of the store
+    const double *poses;       // (F,16)
+};
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_frames_kernel(Tsdf M, TsFrameList L, Rays R) {
+    const int f = blockIdx.y, i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const int row = L.frames[f];
+    if ((unsigned)row >= (unsigned)L.capacity) return;   // never read out of bounds; the whole block leaves
+    const int n = min(max(L.lengths[row], 0), L.P);
+    const bool has = i < n;
+    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
+    const float *p = L.store + (size_t)row * 3 * L.P + i;
+    integrate_ray(M, P, has, has ? p[0] : 0.f, has ? p[L.P] : 0.f, has ? p[2 * (size_t)L.P] : 0.f, R);
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_export_kernel(Tsdf M, unsigned long long *keys, long long *sums, uint32_t *counts,
+                                                             int32_t *count, int max_out) {
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long key = M.keys()[slot];
+    if (key == EMPTY) return;
+    const int pos = atomicAdd(count, 1);
+    if (pos < 0 || pos >= max_out) return;
+    keys[pos] = key, sums[pos] = M.sum()[slot], counts[pos] = M.count()[slot];
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the field
+// D of a slot; false when the slot is none (-1) or its voxel is not qualified
+__device__ __forceinline__ bool slot_value(const Tsdf &M, int slot, unsigned min_count, float &D) {
+    if (slot < 0) return false;
+    const unsigned n = M.count()[slot];
+    if (n < min_count) return false;
+    D = (float)__ddiv_rn((double)M.sum()[slot], (double)n * 16777216.0);
+    return true;
+}
+
+// D of the voxel with (biased) coordinates (x, y, z); false outside the 21 bits, without a slot or when not qualified
+__device__ __forceinline__ bool voxel_value(const Tsdf &M, int x, int y, int z, unsigned min_count, float &D) {
+    if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) return false;
+    return slot_value(M, find_slot(M.keys(), M.cap_vox, pack_key(x, y, z)), min_count, D);
+}
+
+// g += grad(k) of the qualified voxel k = (x[0], x[1], x[2]) with value D
+__device__ __forceinline__ void add_grad(const Tsdf &M, const int x[3], float D, unsigned min_count, float g[3]) {
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        float Dp = 0.f, Dm = 0.f;
+        const bool hp = voxel_value(M, x[0] + (b == 0), x[1] + (b == 1), x[2] + (b == 2), min_count, Dp);
+        const bool hm = voxel_value(M, x[0] - (b == 0), x[1] - (b == 1), x[2] - (b == 2), min_count, Dm);
+        g[b] += hp && hm ? Dp - Dm : hp ? 2.f * (Dp - D) : hm ? 2.f * (D - Dm) : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_surface_kernel(Tsdf M, unsigned min_count, unsigned long long *keys, int32_t *axes,
+                                                              float *xyz, float *normals, int32_t *count, int max_out) {
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long k0 = M.keys()[slot];
+    float D0;
+    if (k0 == EMPTY || !slot_value(M, slot, min_count, D0)) return;
+    const int x0[3] = {key_axis(k0, 0), key_axis(k0, 1), key_axis(k0, 2)};
+    float c[3];
+    voxel_centre(k0, M.v, c);
+    for (int a = 0; a < 3; ++a) {
+        const int x1[3] = {x0[0] + (a == 0), x0[1] + (a == 1), x0[2] + (a == 2)};
+        float D1;
+        if (!voxel_value(M, x1[0], x1[1], x1[2], min_count, D1) || (D0 < 0.f) == (D1 < 0.f)) continue;
+        const int pos = atomicAdd(count, 1);
+        if (pos < 0 || pos >= max_out) continue;
+        const float f = __fdiv_rn(D0, D0 - D1);
+        float g0[3] = {0.f, 0.f, 0.f}, g1[3] = {0.f, 0.f, 0.f};
+        add_grad(M, x0, D0, min_count, g0);
+        add_grad(M, x1, D1, min_count, g1);
+        const float gx = g0[0] + g1[0], gy = g0[1] + g1[1], gz = g0[2] + g1[2];
+        const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
+        const bool unit = len > 0.f;
+        keys[pos] = k0, axes[pos] = a;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) xyz[3 * (size_t)pos + b] = b == a ? c[b] + f * M.v : c[b];
+        normals[3 * (size_t)pos] = unit ? __fdiv_rn(gx, len) : 0.f;
+        normals[3 * (size_t)pos + 1] = unit ? __fdiv_rn(gy, len) : 0.f;
+        normals[3 * (size_t)pos + 2] = unit ? __fdiv_rn(gz, len) : 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- marching tetrahedra
+struct MeshOut {
+    unsigned long long *vkeys;   // (max_out,3)
+    int32_t *vdirs;              // (max_out,3)
+    float *xyz;                  // (max_out,3,3)
+    int32_t *count;
+    int max_out;
+};
+
+struct Cell {
+    int x[3];
+    float D[8], v;
+};
+
+// vertex j of triangle `pos`: on the edge between corners m[i0] and m[i1] of a tetrahedron whose corners are nested, m[0] c m[1] ...
+__device__ __forceinline__ void put_vertex(const MeshOut &O, const Cell &C, const int m[4], int i0, int i1, int pos, int j) {
+    const int p = m[min(i0, i1)], q = m[max(i0, i1)], d = q ^ p;
+    const unsigned long long key = pack_key(C.x[0] + (p & 1), C.x[1] + ((p >> 1) & 1), C.x[2] + (p >> 2));
+    const float f = __fdiv_rn(C.D[p], C.D[p] - C.D[q]);
+    float c[3];
+    voxel_centre(key, C.v, c);
+    const size_t at = 3 * (size_t)pos + j;
+    O.vkeys[at] = key;
+    O.vdirs[at] = d == 1 ? 0 : d == 2 ? 1 : d == 4 ? 2 : d == 3 ? 3 : d == 5 ? 4 : d == 6 ? 5 : 6;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) O.xyz[3 * at + b] = (d >> b) & 1 ? c[b] + f * C.v : c[b];
+}
+
+// the triangle on the edges (a0,a1), (b0,b1), (c0,c1); flip: the last two change places
+__device__ __forceinline__ void put_triangle(const MeshOut &O, const Cell &C, const int m[4], int a0, int a1, int b0, int b1,
+                                             int c0, int c1, bool flip) {
+    const int pos = atomicAdd(O.count, 1);
+    if (pos < 0 || pos >= O.max_out) return;
+    put_vertex(O, C, m, a0, a1, pos, 0);
+    put_vertex(O, C, m, flip ? c0 : b0, flip ? c1 : b1, pos, 1);
+    put_vertex(O, C, m, flip ? b0 : c0, flip ? b1 : c1, pos, 2);
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_mesh_kernel(Tsdf M, unsigned min_count, MeshOut O) {
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long k0 = M.keys()[slot];
+    Cell C;
+    C.v = M.v;
+    if (k0 == EMPTY || !slot_value(M, slot, min_count, C.D[0])) return;
+    for (int a = 0; a < 3; ++a) C.x[a] = key_axis(k0, a);
+    int neg = C.D[0] < 0.f;
+    for (int m = 1; m < 8; ++m) {
+        if (!voxel_value(M, C.x[0] + (m & 1), C.x[1] + ((m >> 1) & 1), C.x[2] + (m >> 2), min_count, C.D[m])) return;
+        neg |= (C.D[m] < 0.f) << m;
+    }
+    if (neg == 0 || neg == 255) return;
+    for (int t = 0; t < 6; ++t) {
+        // the t-th permutation (a, b, c) of the axes in lexicographic order; odd ones give a left-handed tetrahedron
+        const int a = t >> 1, b = (0x489 >> (2 * t)) & 3;   // b = 1, 2, 0, 2, 0, 1
+        const bool odd = (0x26 >> t) & 1;                    // t = 1, 2, 5
+        const int m[4] = {0, 1 << a, (1 << a) | (1 << b), 7};
+        int nm = 0;
+        for (int i = 0; i < 4; ++i) nm |= ((neg >> m[i]) & 1) << i;
+        const int cnt = __popc(nm);
+        if (cnt == 0 || cnt == 4) continue;
+        if (cnt != 2) {
+            // corner A alone on its side; (A, B, C, D) with B < C < D is an even permutation when A is even
+            const int A = __ffs(cnt == 1 ? nm : (~nm & 15)) - 1;
+            const int B = A == 0 ? 1 : 0, Cc = A <= 1 ? 2 : 1, Dd = A == 3 ? 2 : 3;
+            put_triangle(O, C, m, A, B, A, Cc, A, Dd, ((A & 1) != 0) ^ odd ^ (cnt == 3));
+        } else {
+            // A < B negative, Cc < Dd positive; the parity of (A, B, Cc, Dd) is that of its inversions
+            const int A = __ffs(nm) - 1, B = 31 - __clz(nm), pm = ~nm & 15, Cc = __ffs(pm) - 1, Dd = 31 - __clz(pm);
+            const int inv = (A > Cc) + (A > Dd) + (B > Cc) + (B > Dd);
+            const bool swap = ((inv & 1) != 0) ^ odd;
+            const int P = swap ? Dd : Cc, Q = swap ? Cc : Dd;
+            put_triangle(O, C, m, A, P, A, Q, B, Q, false);
+            put_triangle(O, C, m, A, P, B, Q, B, P, false);
+        }
+    }
+}
+
+inline bool tsdf_ok(const void *map, int cap_vox) {
+    return map && ((uintptr_t)map & 15) == 0 && cap_vox >= 2 && cap_vox <= (1 << 24) && (cap_vox & (cap_vox - 1)) == 0;
+}
+
+inline bool voxel_ok(double voxel) { return voxel > 0.0 && voxel < 1e18 && (float)voxel > 0.f; }
+
+inline bool origin_ok(const double *origin) {
+    if (!origin) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!(origin[a] > -1e300 && origin[a] < 1e300)) return false;
+    return true;
+}
+
+inline Tsdf make_tsdf(const void *map, int cap_vox, double voxel, const double *origin) {
+    Tsdf M;
+    M.base = (unsigned char *)map, M.cap_vox = cap_vox, M.v = (float)voxel;
+    M.ox = origin ? origin[0] : 0.0, M.oy = origin ? origin[1] : 0.0, M.oz = origin ? origin[2] : 0.0;
+    return M;
+}
+
+// the gate and the samples of a ray from the host's doubles; false when they are refused
+inline bool make_rays(double min_range, double max_range, double truncation, double step, Rays &R) {
+    if (!(min_range >= 0.0 && max_range >= min_range && max_range < 1e18)) return false;
+    if (!(truncation > 0.0 && truncation <= 64.0 && step > 0.0 && (float)step > 0.f && (float)truncation > 0.f)) return false;
+    const double n = ceil(truncation / step);
+    if (!(n <= (double)MAX_STEPS)) return false;
+    R.lo2 = (float)(min_range * min_range), R.hi2 = (float)(max_range * max_range);
+    R.tau = (float)truncation, R.h = (float)step, R.n = (int)n;
+    return true;
+}
+
+}  // namespace
+
+extern "C" size_t dpm_tsdf_bytes(int cap_vox) {
+    if (!tsdf_ok((const void *)16, cap_vox)) return 0;
+    return 256 + (size_t)cap_vox * 20;
+}
+
+extern "C" int dpm_tsdf_init(void *map, int cap_vox, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox));
+    const unsigned g = dpm_cdiv(cap_vox, TS_BLOCK);
+    hipLaunchKernelGGL(ts_clear_kernel, dim3(g > 8192 ? 8192 : g), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, 1.0, nullptr));
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_integrate(void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
+                                  const int32_t *count, int cap, const double *pose, double min_range, double max_range,
+                                  double truncation, double step, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(xyz && count && pose && cap >= 0);
+    Rays R;
+    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
+    if (cap == 0) return DPM_OK;
+    hipLaunchKernelGGL(ts_integrate_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), xyz, count, cap, pose, R);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_integrate_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
+                                         const int32_t *lengths, int capacity, int P, const int32_t *frames,
+                                         const double *poses, int F, double min_range, double max_range, double truncation,
+                                         double step, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    Rays R;
+    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
+    if (F == 0) return DPM_OK;
+    DPM_CHECK_ARG(store && lengths && frames && poses);
+    const TsFrameList L{store, lengths, capacity, P, frames, poses};
+    hipLaunchKernelGGL(ts_integrate_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), L, R);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long *keys, long long *sums, uint32_t *counts,
+                               int32_t *count, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && count && max_out >= 0);
+    DPM_CHECK_ARG(max_out == 0 || (keys && sums && counts));
+    hipLaunchKernelGGL(ts_export_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, 1.0, nullptr), keys, sums, counts, count, max_out);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *keys,
+                                int32_t *axes, float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
+    DPM_CHECK_ARG(max_out == 0 || (keys && axes && xyz && normals));
+    hipLaunchKernelGGL(ts_surface_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, keys, axes, xyz, normals, count, max_out);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
+                             int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
+    DPM_CHECK_ARG(max_out == 0 || (vertex_keys && vertex_dirs && xyz));
+    const MeshOut O{vertex_keys, vertex_dirs, xyz, count, max_out};
+    hipLaunchKernelGGL(ts_mesh_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, O);
+    return dpm_launch_status();
+}

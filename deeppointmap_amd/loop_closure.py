@@ -447,3 +447,19 @@ class GeometricSlam:
     @property
     def loops(self) -> List[LoopEdge]:
         return self.loop_closer.loops
+
+    def surface_rows(self) -> List[int]:
+        """the stored frames `surface_map` fuses: all but those whose registration failed (as `_rewrite` leaves them out)"""
+        steps = self.odometry.steps
+        return [i for i in range(len(self._corrected)) if i >= len(steps) or steps[i].status in (CONVERGED, MAX_ITER)]
+
+    def surface_map(self, voxel_size: float = 0.2, **kw):
+        """-> tsdf.TsdfMap(voxel_size, **kw) holding the loop closer's stored frames fused under the corrected `poses`, in one
+        TsdfMap.integrate_frames call and without a host synchronisation.  LIMIT: these are the loop closer's thinned
+        copies, at most points_per_frame a frame (and `sample`d), not the frames `step` was given."""
+        from .tsdf import TsdfMap
+        out = TsdfMap(voxel_size=voxel_size, **kw)
+        rows = self.surface_rows()
+        if rows:
+            out.integrate_frames(self.loop_closer.store, self.loop_closer.lengths, rows, self.poses[rows])
+        return out

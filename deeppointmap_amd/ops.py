@@ -2351,6 +2351,151 @@ def local_map_export(table, cap_vox, subdiv, half, max_out=None):
     return keys[:n], sub[:n], owner[:n], xyz[:n]
 
 
+# -- the TSDF surface map (csrc/tsdf_map.hip; orchestration in tsdf.py) --------------------------------------------------------
+TSDF_MAX_TRUNCATION = 64.0  # metres: tau 2^24 2^32 < 2^63
+TSDF_MAX_STEPS = 4096       # ceil(truncation / step) at most
+
+
+def tsdf_rays(truncation: float, step: float, min_range: float, max_range: float):
+    """the ray parameters every integrate call takes, checked as the entry points check them -> four floats"""
+    tau, h, lo, hi = float(truncation), float(step), float(min_range), float(max_range)
+    if not (0.0 < tau <= TSDF_MAX_TRUNCATION and h > 0.0 and tau / h <= TSDF_MAX_STEPS):
+        raise ValueError(f"0 < truncation <= {TSDF_MAX_TRUNCATION}, step > 0 and ceil(truncation / step) <= {TSDF_MAX_STEPS}")
+    if not 0.0 <= lo <= hi < 1e18:
+        raise ValueError("0 <= min_range <= max_range")
+    return lo, hi, tau, h
+
+
+def _tsdf_args(table: torch.Tensor, cap_vox: int, origin=None):
+    _chk(table, torch.uint8, "table")
+    if table.numel() != _lib.load().dpm_tsdf_bytes(int(cap_vox)) or table.numel() == 0:
+        raise ValueError("table: dpm_tsdf_bytes(cap_vox) bytes, cap_vox a power of two in [2, 2^24]")
+    return None if origin is None else (ctypes.c_double * 3)(*_origin3(origin))
+
+
+def tsdf_new(cap_vox: int, device) -> torch.Tensor:
+    """an empty map: the uint8 buffer every other tsdf_* call takes"""
+    n = _lib.load().dpm_tsdf_bytes(int(cap_vox))
+    if n == 0:
+        raise ValueError("cap_vox: a power of two in [2, 2^24]")
+    with torch.cuda.device(device):
+        table = torch.empty(n, device=device, dtype=torch.uint8)
+    return tsdf_clear(table, cap_vox)
+
+
+def tsdf_clear(table, cap_vox) -> torch.Tensor:
+    """dpm_tsdf_init: the header zeroed, the table empty"""
+    _tsdf_args(table, cap_vox)
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_init(_ptr(table), int(cap_vox), _stream(table)), "dpm_tsdf_init")
+    return table
+
+
+def tsdf_integrate(table, cap_vox, voxel, origin, xyz, count, pose, min_range, max_range, truncation, step):
+    """dpm_tsdf_integrate: xyz (cap,3) fp32, count (1,) int32, pose (4,4) fp64, all on the GPU.  One launch, no host
+    synchronisation, capturable in a graph."""
+    rays = tsdf_rays(truncation, step, min_range, max_range)
+    o = _tsdf_args(table, cap_vox, origin)
+    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or count.numel() != 1 or pose.numel() != 16:
+        raise ValueError("tsdf_integrate: xyz (cap,3), count (1,), pose (4,4)")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_integrate(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz),
+                                                  _ptr(count), xyz.shape[0], _ptr(pose), *rays, _stream(table)),
+                   "dpm_tsdf_integrate")
+
+
+def tsdf_integrate_frames(table, cap_vox, voxel, origin, store, lengths, frames, poses, min_range, max_range, truncation, step):
+    """dpm_tsdf_integrate_frames: store (capacity,3,P) fp32 channel-major, lengths (capacity,) int32, frames (F,) int32 rows of
+    the store, poses (F,4,4) fp64, all on the GPU.  One launch for any F, no host synchronisation, capturable in a graph."""
+    rays = tsdf_rays(truncation, step, min_range, max_range)
+    o = _tsdf_args(table, cap_vox, origin)
+    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
+    _chk(poses, torch.float64, "poses")
+    F = frames.numel()
+    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
+            or frames.dim() != 1 or poses.numel() != 16 * F or F > 65535:
+        raise ValueError("tsdf_integrate_frames: store (capacity,3,P), lengths (capacity,), frames (F,) with F <= 65535, poses (F,4,4)")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_integrate_frames(
+            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
+            store.shape[2], _ptr(frames), _ptr(poses), F, *rays, _stream(table)), "dpm_tsdf_integrate_frames")
+
+
+def _counted(call, max_out):
+    """the `count may exceed max_out` contract of the export-style entry points: call(n) -> (count (1,) int32, *outputs of n
+    rows).  max_out None: counted first, then written whole (the map has not changed in between, so the count is not read
+    again); max_out = 0 -> the count alone, as an int; otherwise -> (count as an int, *outputs cut to min(count, max_out)
+    rows).  One read of the count, a host synchronisation, in every case."""
+    if max_out is None or int(max_out) == 0:
+        n = int(call(0)[0].item())
+        return n if max_out is not None else (n, *call(n)[1:])
+    count, *out = call(int(max_out))
+    total = int(count.item())
+    return (total, *[t[:min(total, int(max_out))] for t in out])
+
+
+def tsdf_export(table, cap_vox, max_out=None):
+    """dpm_tsdf_export -> (count, keys (n,) int64 holding the uint64 keys' bits, sums (n,) int64, counts (n,) int32 holding
+    the uint32 counts' bits) in no defined order; max_out as in _counted"""
+    _tsdf_args(table, cap_vox)
+    dev, lib = table.device, _lib.load()
+
+    def call(n):
+        with torch.cuda.device(dev):
+            count = torch.zeros(1, device=dev, dtype=torch.int32)
+            keys = torch.empty(n, device=dev, dtype=torch.int64)
+            sums = torch.empty(n, device=dev, dtype=torch.int64)
+            counts = torch.empty(n, device=dev, dtype=torch.int32)
+            _lib.check(lib.dpm_tsdf_export(_ptr(table), int(cap_vox), _ptr(keys) if n else None, _ptr(sums) if n else None,
+                                           _ptr(counts) if n else None, _ptr(count), n, _stream(table)), "dpm_tsdf_export")
+        return count, keys, sums, counts
+    return _counted(call, max_out)
+
+
+def tsdf_surface(table, cap_vox, voxel, min_count=1, max_out=None):
+    """dpm_tsdf_surface -> (count, keys (n,) int64, axes (n,) int32, xyz (n,3) fp32 map-frame, normals (n,3) fp32) in no
+    defined order; max_out as in _counted"""
+    _tsdf_args(table, cap_vox)
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    dev, lib = table.device, _lib.load()
+
+    def call(n):
+        with torch.cuda.device(dev):
+            count = torch.zeros(1, device=dev, dtype=torch.int32)
+            keys = torch.empty(n, device=dev, dtype=torch.int64)
+            axes = torch.empty(n, device=dev, dtype=torch.int32)
+            xyz = torch.empty(n, 3, device=dev, dtype=torch.float32)
+            normals = torch.empty(n, 3, device=dev, dtype=torch.float32)
+            _lib.check(lib.dpm_tsdf_surface(_ptr(table), int(cap_vox), float(voxel), int(min_count), _ptr(keys) if n else None,
+                                            _ptr(axes) if n else None, _ptr(xyz) if n else None, _ptr(normals) if n else None,
+                                            _ptr(count), n, _stream(table)), "dpm_tsdf_surface")
+        return count, keys, axes, xyz, normals
+    return _counted(call, max_out)
+
+
+def tsdf_mesh(table, cap_vox, voxel, min_count=1, max_out=None):
+    """dpm_tsdf_mesh -> (count, vertex_keys (n,3) int64, vertex_dirs (n,3) int32, xyz (n,3,3) fp32 map-frame): one triangle a
+    row, in no defined order; max_out as in _counted"""
+    _tsdf_args(table, cap_vox)
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    dev, lib = table.device, _lib.load()
+
+    def call(n):
+        with torch.cuda.device(dev):
+            count = torch.zeros(1, device=dev, dtype=torch.int32)
+            vkeys = torch.empty(n, 3, device=dev, dtype=torch.int64)
+            vdirs = torch.empty(n, 3, device=dev, dtype=torch.int32)
+            xyz = torch.empty(n, 3, 3, device=dev, dtype=torch.float32)
+            _lib.check(lib.dpm_tsdf_mesh(_ptr(table), int(cap_vox), float(voxel), int(min_count), _ptr(vkeys) if n else None,
+                                         _ptr(vdirs) if n else None, _ptr(xyz) if n else None, _ptr(count), n, _stream(table)),
+                       "dpm_tsdf_mesh")
+        return count, vkeys, vdirs, xyz
+    return _counted(call, max_out)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Scan Context descriptors and their exhaustive search (csrc/scan_context.hip; loop_closure.py is the caller)
 # ------------------------------------------------------------------------------------------------------------

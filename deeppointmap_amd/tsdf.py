@@ -1,0 +1,258 @@
+"""A fused surface on the GPU: a truncated signed distance field (TSDF) over hashed voxels (csrc/tsdf_map.hip), its zero
+crossings as surface points with normals, and a triangle mesh from marching tetrahedra.  The reference has no counterpart:
+its map is a cloud of points.  DESIGN §7l is the definition.
+
+`TsdfMap.integrate` fuses one frame under its pose: every return is a ray from the pose's translation, sampled every `step`
+metres within `truncation` of the return; each sample adds the signed distance to the return along the ray, as seen from
+the centre of the voxel it falls into, to that voxel's integer sum.  Integer atomics only, so the map is a function of the
+frames alone: the sorted export has the same bytes whatever the order of rows, frames or launches.
+`integrate_frames` does the same for a list of stored frames in one launch (LoopCloser.store), which is how
+`GeometricSlam.surface_map` fuses a run under its corrected poses.
+
+LIMITS: no free-space carving along the whole ray (a surface that moved away stays); no weight cap or decay; the frame's
+pose is the origin of every ray (no per-point origins for sweeps that are not deskewed); no weighting by incidence angle;
+marching tetrahedra, not marching cubes; the voxels live on the device (nothing is streamed to the host).
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import augment, ops
+from .odometry import _pose_tensor
+
+OVERFLOW = "the TSDF map is full (max_voxels={}): samples found no free slot and the map is undefined; raise max_voxels"
+FIX_ONE = 16777216.0    # 2^24: a sum is in units of 2^-24 m
+
+
+class TsdfSurface(NamedTuple):
+    """zero crossings along the axes, sorted by (key, axis), on the device.  xyz is in WORLD coordinates, (float)((double)xyz_map
+    + origin), so that evaluate.map_accuracy(s.xyz, scene, origin=s.origin) takes it as it is; xyz_map is what the kernel wrote,
+    relative to `origin`."""
+    xyz: torch.Tensor        # (3,M) float32, world
+    normals: torch.Tensor    # (3,M) float32, towards free space; (0,0,0) where the field has no gradient
+    keys: torch.Tensor       # (M,) int64: the voxel k0 of the crossing between k0 and k0 + e_axis
+    axes: torch.Tensor       # (M,) int32
+    origin: np.ndarray       # (3,) float64
+    xyz_map: torch.Tensor    # (3,M) float32, map frame
+
+
+def field_values(sums, counts) -> np.ndarray:
+    """D = (float)((double)sum / ((double)count * 2^24)) of exported slots, as the kernels form it"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (np.asarray(sums, np.int64).astype(np.float64)
+                / (np.asarray(counts).astype(np.uint32).astype(np.float64) * FIX_ONE)).astype(np.float32)
+
+
+def weld(vertex_keys, vertex_dirs, xyz):
+    """triangles as (n,3) vertex names (key, direction) + (n,3,3) positions -> (vertices (V,3) float32 sorted by name, faces
+    (F,3) int32, each rotated so that its smallest vertex comes first, sorted by row).  A name has one position."""
+    k, d = np.asarray(vertex_keys, np.int64).reshape(-1), np.asarray(vertex_dirs, np.int32).reshape(-1)
+    p = np.asarray(xyz, np.float32).reshape(-1, 3)
+    if k.size == 0:
+        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+    order = np.lexsort((d, k))
+    ks, ds = k[order], d[order]
+    first = np.concatenate([[True], (ks[1:] != ks[:-1]) | (ds[1:] != ds[:-1])])
+    index = np.empty(k.size, np.int64)
+    index[order] = np.cumsum(first) - 1
+    vertices = p[order][first]
+    faces = index.reshape(-1, 3)
+    lead = faces.argmin(axis=1)
+    faces = np.stack([faces[np.arange(len(faces)), (lead + j) % 3] for j in range(3)], axis=1)
+    faces = faces[np.lexsort((faces[:, 2], faces[:, 1], faces[:, 0]))]
+    return np.ascontiguousarray(vertices), np.ascontiguousarray(faces.astype(np.int32))
+
+
+def write_ply(path, vertices, faces=None, normals=None) -> None:
+    """a binary little-endian PLY: vertices (V,3) float32 [with normals (V,3)], faces (F,3) int32 as uchar-counted lists"""
+    v = np.ascontiguousarray(np.asarray(vertices, "<f4").reshape(-1, 3))
+    cols, props = [v], ["x", "y", "z"]
+    if normals is not None:
+        n = np.asarray(normals, "<f4").reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError("write_ply: one normal per vertex")
+        cols.append(n)
+        props += ["nx", "ny", "nz"]
+    f = np.zeros((0, 3), "<i4") if faces is None else np.asarray(faces, "<i4").reshape(-1, 3)
+    if f.size and not (0 <= f.min() and f.max() < len(v)):
+        raise ValueError("write_ply: faces index the vertices")
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"] + [f"property float {p}" for p in props]
+    if faces is not None:
+        head += [f"element face {len(f)}", "property list uchar int vertex_indices"]
+    head.append("end_header")
+    with open(path, "wb") as out:
+        out.write(("\n".join(head) + "\n").encode("ascii"))
+        out.write(np.ascontiguousarray(np.concatenate(cols, axis=1)).tobytes())
+        if faces is not None:
+            rec = np.zeros(len(f), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+            rec["n"], rec["v"] = 3, f
+            out.write(rec.tobytes())
+
+
+class TsdfMap:
+    """A TSDF of `max_voxels` slots (a power of two) with voxels of `voxel_size` metres.  truncation (default 3 voxel_size, at
+    most 64 m): how far before and behind a return its ray is sampled, and the clamp of the distance; step (default
+    voxel_size / 2): the spacing of the samples.  Coordinates are fp32 relative to `origin` (three float64; default: the
+    translation of the first pose), so work far from the world's zero keeps fp32 accuracy.  A return counts when min_range
+    <= |p| <= max_range in the sensor frame.  A map that ran out of slots is undefined: `overflow()` is then non-zero and
+    `check()` raises ValueError.  The extractions synchronise once each and do not look at that word: call `check()` first."""
+
+    def __init__(self, voxel_size: float = 0.2, truncation: Optional[float] = None, step: Optional[float] = None,
+                 max_voxels: int = 1 << 22, min_range: float = 0.0, max_range: float = 100.0, origin=None, device=None):
+        if not (voxel_size > 0 and float(np.float32(voxel_size)) > 0):
+            raise ValueError("voxel_size > 0")
+        if max_voxels < 2 or max_voxels > 1 << 24 or max_voxels & (max_voxels - 1):
+            raise ValueError("max_voxels: a power of two in [2, 2^24]")
+        self.voxel_size, self.max_voxels = float(voxel_size), int(max_voxels)
+        self.truncation = 3.0 * self.voxel_size if truncation is None else float(truncation)
+        self.step = self.voxel_size / 2.0 if step is None else float(step)
+        self.min_range, self.max_range = float(min_range), float(max_range)
+        ops.tsdf_rays(self.truncation, self.step, self.min_range, self.max_range)
+        self.origin = None if origin is None else np.asarray(origin, np.float64).reshape(3).copy()
+        self.device = device
+        self.table: Optional[torch.Tensor] = None
+
+    # -- plumbing
+    def _ready(self, dev, pose=None):
+        if self.table is None:
+            self.device = dev if self.device is None else torch.device(self.device)
+            self.table = ops.tsdf_new(self.max_voxels, self.device)
+        if self.origin is None:
+            if pose is None:
+                self.origin = np.zeros(3)
+            else:
+                if isinstance(pose, torch.Tensor) and pose.is_cuda:   # only here: give `origin` to keep the pose on the device
+                    augment._SYNCS[0] += 1
+                    pose = pose.detach().cpu().numpy()
+                self.origin = np.asarray(pose, np.float64).reshape(4, 4)[:3, 3].copy()
+
+    def _rays(self):
+        return self.min_range, self.max_range, self.truncation, self.step
+
+    # -- fusion: no host synchronisation
+    def integrate(self, pcd, pose, length=None):
+        """one frame under `pose` (4,4 sensor -> world; numpy, or a tensor -- on the GPU it is read there): an
+        augment.PointCloud, or xyz (N,3) float32 on the GPU with `length` (an int, or a (1,) int32 tensor on the GPU; None:
+        N).  One launch."""
+        if isinstance(pcd, torch.Tensor):
+            xyz = pcd
+            if xyz.dim() != 2 or xyz.shape[1] != 3:
+                raise ValueError("integrate: xyz (N,3)")
+            if isinstance(length, torch.Tensor):
+                count = length.reshape(1)
+            else:
+                n = xyz.shape[0] if length is None else int(length)
+                if not 0 <= n <= xyz.shape[0]:
+                    raise ValueError("integrate: 0 <= length <= N")
+                count = torch.full((1,), n, dtype=torch.int32).to(xyz.device)
+        else:
+            if length is not None:
+                raise ValueError("integrate: a PointCloud carries its own length")
+            xyz, count = pcd.xyz, pcd.count
+        if tuple(np.shape(pose)) != (4, 4):
+            raise ValueError("pose: (4,4)")
+        self._ready(xyz.device, pose)
+        if xyz.shape[0] == 0:
+            return self
+        ops.tsdf_integrate(self.table, self.max_voxels, self.voxel_size, self.origin, xyz, count,
+                           _pose_tensor(pose, self.device), *self._rays())
+        return self
+
+    def integrate_frames(self, store, lengths, frames, poses):
+        """stored frames under a pose each, in one launch for any number of them: row frames[f] of `store` (capacity,3,P) fp32
+        channel-major / `lengths` (capacity,) int32 on the device (LoopCloser.store, .lengths) under poses[f] (F,4,4; sensor
+        -> world).  frames / poses: host arrays (uploaded, nothing is read back) or device tensors.  The result is that of
+        `integrate` of each entry, byte for byte."""
+        dev = store.device
+        if isinstance(frames, torch.Tensor):
+            rows = frames.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            host = np.asarray(frames, np.int64).reshape(-1)
+            if host.size and not (0 <= host.min() and host.max() < store.shape[0]):
+                raise ValueError("integrate_frames: frames are rows of the store")
+            rows = torch.from_numpy(host.astype(np.int32)).to(dev)
+        if not isinstance(poses, torch.Tensor):
+            poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4))
+        if poses.numel() != 16 * rows.numel() or rows.numel() > 65535:
+            raise ValueError("integrate_frames: poses (F,4,4), F <= 65535")
+        self._ready(dev, poses.reshape(-1, 4, 4)[0] if rows.numel() else None)
+        if rows.numel() == 0:
+            return self
+        ops.tsdf_integrate_frames(self.table, self.max_voxels, self.voxel_size, self.origin, store, lengths, rows,
+                                  poses.to(device=self.device, dtype=torch.float64).contiguous(), *self._rays())
+        return self
+
+    # -- read-back: one host synchronisation each
+    def _header(self, word: int) -> int:
+        if self.table is None:
+            return 0
+        augment._SYNCS[0] += 1
+        return int(self.table[4 * word:4 * word + 4].view(torch.int32).item()) & 0xFFFFFFFF
+
+    def overflow(self) -> int:
+        """samples that found no free slot so far (0: the map is defined)"""
+        return self._header(0)
+
+    def outside(self) -> int:
+        """samples that fell outside the 21-bit key range so far (they are left out)"""
+        return self._header(1)
+
+    def check(self):
+        n = self.overflow()
+        if n:
+            raise ValueError(OVERFLOW.format(self.max_voxels) + f" ({n} samples)")
+        return self
+
+    def _extract(self, fn, *args):
+        """fn(table, max_voxels, *args) without its count: the one read of that count is the extraction's synchronisation"""
+        augment._SYNCS[0] += 1
+        return fn(self.table, self.max_voxels, *args)[1:]
+
+    def export(self):
+        """(keys (n,) int64, sums (n,) int64 in units of 2^-24 m, counts (n,) uint32) numpy, sorted by key: the same bytes
+        whatever the order the frames arrived in"""
+        if self.table is None:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.uint32)
+        keys, sums, counts = [t.cpu().numpy() for t in self._extract(ops.tsdf_export)]
+        order = np.argsort(keys, kind="stable")
+        return keys[order], sums[order], counts[order].view(np.uint32)
+
+    def field(self, min_count: int = 1):
+        """(keys (m,) int64, D (m,) float32 metres) of the qualified voxels (count >= min_count), sorted by key; D > 0 on the
+        sensor's side of the surface"""
+        if int(min_count) < 1:
+            raise ValueError("min_count >= 1")
+        keys, sums, counts = self.export()
+        ok = counts >= np.uint32(min_count)
+        return keys[ok], field_values(sums[ok], counts[ok])
+
+    def surface(self, min_count: int = 1) -> TsdfSurface:
+        """the zero crossings of the field along the axes between qualified voxels, with normals from the field's gradient"""
+        if int(min_count) < 1:
+            raise ValueError("min_count >= 1")
+        if self.table is None:
+            dev = self.device if self.device is not None else "cpu"
+            z = torch.zeros(3, 0, dtype=torch.float32, device=dev)
+            return TsdfSurface(z, z.clone(), torch.zeros(0, dtype=torch.int64, device=dev),
+                               torch.zeros(0, dtype=torch.int32, device=dev), np.zeros(3) if self.origin is None else self.origin, z.clone())
+        keys, axes, xyz, normals = self._extract(ops.tsdf_surface, self.voxel_size, int(min_count))
+        order = torch.sort(axes, stable=True).indices
+        order = order[torch.sort(keys[order], stable=True).indices]
+        local = xyz[order].t().contiguous()
+        world = (local.double() + torch.from_numpy(self.origin).to(local.device)[:, None]).float()
+        return TsdfSurface(world, normals[order].t().contiguous(), keys[order], axes[order], self.origin.copy(), local)
+
+    def mesh(self, min_count: int = 1):
+        """(vertices (V,3) float32 in the map frame -- world = vertices + origin --, faces (F,3) int32) from marching
+        tetrahedra over the cells whose 8 corner voxels are qualified; welded by vertex name and sorted (`weld`); a face's
+        normal (b - a) x (c - a) points to free space"""
+        if int(min_count) < 1:
+            raise ValueError("min_count >= 1")
+        if self.table is None:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+        return weld(*[t.cpu().numpy() for t in self._extract(ops.tsdf_mesh, self.voxel_size, int(min_count))])
+
+    write_ply = staticmethod(write_ply)

@@ -1085,6 +1085,76 @@ int dpm_local_map_register_planes(const void *map, int cap_vox, int subdiv, int 
                                   float *rmse, int32_t *iterations, int32_t *status, long long *debug_key, int32_t *debug_sub,
                                   double *debug_system, void *workspace, dpm_stream_t stream);
 
+/* ---------------------------------------------------------------- TSDF surface map ---------- */
+
+/* A truncated signed distance field over hashed voxels and a surface from it (csrc/tsdf_map.hip; deeppointmap_amd/tsdf.py is
+ * the caller).  No counterpart in the reference, whose map is a cloud of points.  DESIGN §7l is the definition.
+ *
+ * The map is one device buffer of dpm_tsdf_bytes(cap_vox) = 256 + 20 cap_vox bytes, 16-byte aligned: a 256-byte header (word
+ * 0: samples that found no free slot, word 1: samples outside the key range) and one open-addressing table of cap_vox slots
+ * (a power of two in [2, 2^24], linear probing from splitmix64(key) & (cap_vox - 1), empty key ~0) as three arrays: key
+ * uint64, sum int64, count uint32.  Keys, the map frame and the pose handling are dpm_local_map_insert's: `voxel` and `origin`
+ * (three doubles ON THE HOST) the same in every call on one map, a pose 16 doubles IN DEVICE MEMORY entering as (float)R and
+ * (float)(t - origin), a point q = fma(R2, z, fma(R1, y, R0 * x)) + t, per axis the voxel floor(q / voxel) from the correctly
+ * rounded fp32 quotient, kept in [-2^20, 2^20), the 3 x 21-bit key, the centre c = ((float)voxel_index + 0.5f) * voxel.
+ *
+ * FUSION.  A row (x, y, z) of a frame is a return seen from the pose's translation.  It is taken when (float)(min_range^2) <=
+ * r2 <= (float)(max_range^2) with r2 = (x*x + y*y) + z*z (a NaN fails).  In fp32, every operation rounded once, no fused
+ * multiply-add outside q's chain, division and square root correctly rounded:
+ *     r = sqrt(r2),  o = (float)(t - origin),  u = (q - o) / r per axis;
+ *     n = ceil(truncation / step) on the host in double (at most 4096), tau = (float)truncation, h = (float)step;
+ *     for k = -n .. n ascending:  t = r + (float)k * h;  skipped unless t > 0;  p = o + u * t per axis;  the voxel of p (a
+ *     sample outside the 21 bits adds one to header word 1 and is skipped);  skipped when its key equals the key of this
+ *     ray's previous keyed sample;  e = q - c;  s = (ux*ex + uy*ey) + uz*ez clamped to [-tau, tau], positive on the sensor's
+ *     side of the return;  fixed = (long long)rintf(s * 16777216.f), round half to even;  the slot found or claimed, then
+ *     sum += fixed and count += 1 (integer atomics).  No free slot: header word 0 counts the sample.
+ * 0 < truncation <= 64 (metres): tau 2^24 2^32 < 2^63, so 2^32 samples cannot overflow a sum.  Integer addition commutes: what
+ * a key leads to is the same whatever the order of rows, frames or launches (slot positions are not); two runs export
+ * identical bytes once sorted.  The map is defined only while header word 0 is zero.  A return at range 0 has no direction:
+ * u is NaN and its samples with t > 0 count in header word 1.  Every call runs on `stream` without a host synchronisation.
+ *
+ * FIELD.  D = (float)((double)sum / ((double)count * 16777216.0)) of a slot.  A voxel is QUALIFIED when count >= min_count
+ * (min_count >= 1); a voxel without a slot, or outside the 21 bits, is not. */
+size_t dpm_tsdf_bytes(int cap_vox);
+/* header zeroed, table empty */
+int dpm_tsdf_init(void *map, int cap_vox, dpm_stream_t stream);
+/* One frame in one launch, one lane per row, capturable.  xyz (cap,3) fp32 row-major, count (1,) int32 on the device: rows at
+ * and past it are never read.  DPM_EINVAL: truncation outside (0, 64], step <= 0, ceil(truncation / step) > 4096. */
+int dpm_tsdf_integrate(void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const int32_t *count,
+                       int cap, const double *pose, double min_range, double max_range, double truncation, double step,
+                       dpm_stream_t stream);
+/* The same rule over a list of stored frames in one launch for any F (grid y = list entry), capturable.  store (capacity,3,P)
+ * fp32 CHANNEL-major and lengths (capacity,) int32 (a length is clamped to [0, P]), frames (F,) int32 rows of the store (a
+ * row outside [0, capacity) offers nothing), poses (F,16) fp64, all on the device; F in [0, 65535], F = 0 is a no-op.  The
+ * sorted export equals that after dpm_tsdf_integrate of each entry, byte for byte. */
+int dpm_tsdf_integrate_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
+                              const int32_t *lengths, int capacity, int P, const int32_t *frames, const double *poses, int F,
+                              double min_range, double max_range, double truncation, double step, dpm_stream_t stream);
+/* Every occupied slot in no defined order: keys (max_out,) uint64, sums (max_out,) int64, counts (max_out,) uint32.  count
+ * (1,) int32, ZEROED BY THE CALLER, receives their number, which may exceed max_out (the rest is not written; max_out = 0
+ * only counts). */
+int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long *keys, long long *sums, uint32_t *counts, int32_t *count,
+                    int max_out, dpm_stream_t stream);
+/* Zero crossings along the axes, one lane per slot, in no defined order, count / max_out as above.  A record is written for
+ * a qualified voxel k0 and an axis a when k1 = k0 + e_a is qualified and (D0 < 0) != (D1 < 0): keys = k0, axes = a, xyz
+ * (max_out,3) = k0's centre with f * voxel added on axis a, f = D0 / (D0 - D1) (fp32, correctly rounded; map frame).
+ * grad(k)_b from the qualified neighbours of k on axis b: both: D(k + e_b) - D(k - e_b); only k + e_b: 2 (D(k + e_b) - D(k));
+ * only k - e_b: 2 (D(k) - D(k - e_b)); neither: 0.  normals (max_out,3) = g / sqrt((gx*gx + gy*gy) + gz*gz) per axis with
+ * g = grad(k0) + grad(k1), (0, 0, 0) when the root is 0; it points to free space. */
+int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *keys, int32_t *axes,
+                     float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream);
+/* Marching tetrahedra, one lane per slot: triangles in no defined order, count / max_out as above.  The cell anchored at a
+ * voxel's centre is meshed only when its 8 corner voxels (corner m = dx | dy << 1 | dz << 2) are qualified.  Its six
+ * tetrahedra are the Kuhn decomposition round the diagonal 0 - 7, one per permutation (a, b, c) of the axes: corners 0,
+ * 1 << a, 1 << a | 1 << b, 7; neighbouring cells then agree on every face diagonal.  An edge runs from a corner p to a corner q
+ * containing p's bits; it carries a vertex when (Dp < 0) != (Dq < 0), named by vertex_keys = the key of p and vertex_dirs =
+ * 0, 1, 2 for q ^ p = 1, 2, 4 (axes), 3, 4, 5 for 3, 5, 6 (face diagonals), 6 for 7 (the body diagonal), at p's centre with
+ * f * voxel added on every axis of q ^ p, f = Dp / (Dp - Dq).  vertex_keys / vertex_dirs (max_out,3), xyz (max_out,3,3): a
+ * triangle's three vertices, wound so that (b - a) x (c - a) points to the positive side (free space).  A corner with D == 0
+ * counts as positive; the triangles of zero area it makes are kept. */
+int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
+                  int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream);
+
 /* ---------------------------------------------------------------- geometric loop closure ---- */
 
 /* Scan Context place descriptors (Kim & Kim, IROS 2018) and the exhaustive search over a database of them
