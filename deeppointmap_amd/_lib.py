@@ -170,6 +170,10 @@ SIGNATURES = {
     "dpm_tsdf_init": (I, [P, I, P]),
     "dpm_tsdf_integrate": (I, [P, I, D, P, P, P, I, P, D, D, D, D, P]),
     "dpm_tsdf_integrate_frames": (I, [P, I, D, P, P, P, I, I, P, P, I, D, D, D, D, P]),
+    "dpm_tsdf_integrate_planes": (I, [P, I, D, P, P, P, P, I, P, D, D, D, D, D, P]),
+    "dpm_tsdf_integrate_planes_frames": (I, [P, I, D, P, P, P, P, I, I, P, P, I, D, D, D, D, D, P]),
+    "dpm_tsdf_carve": (I, [P, I, D, P, P, P, I, P, D, D, D, D, I, D, P]),
+    "dpm_tsdf_carve_frames": (I, [P, I, D, P, P, P, I, I, P, P, I, D, D, D, D, I, D, P]),
     "dpm_tsdf_export": (I, [P, I, P, P, P, P, I, P]),
     "dpm_tsdf_surface": (I, [P, I, D, I, P, P, P, P, P, I, P]),
     "dpm_tsdf_mesh": (I, [P, I, D, I, P, P, P, P, I, P]),

@@ -2,7 +2,7 @@
 // The reference has no counterpart: its map is a cloud of points.  DESIGN §7l is the definition.
 //
 // Map: one buffer of 256 + 20 cap_vox bytes.  A 256-byte header (word 0: samples that found no slot, word 1: samples outside
-// the 21-bit key range), then an open-addressing table of cap_vox slots (csrc/voxel_hash.h: the keys, the probing and the
+// the 21-bit key range, word 2: rows of the plane form without a usable normal), then an open-addressing table of cap_vox slots (csrc/voxel_hash.h: the keys, the probing and the
 // cutting of space are csrc/local_map.hip's) as three arrays: key u64, sum int64, count u32.  The map frame and the pose
 // handling are the local map's too: a float64 `origin` on the host, a pose of 16 doubles in device memory entering as (float)R
 // and (float)(t - origin) (gn_load_pose), a point as gn_xform's fma chain.
@@ -23,6 +23,23 @@
 //              frames or launches.  Slot positions are not, and nothing reads them.
 //   frames     the same rule over a list of stored frames: blockIdx.y the list entry, x over the P columns of a channel-major
 //              store (capacity,3,P), as dpm_local_map_insert_frames reads it.
+//   planes     integrate / frames with the distance to the TANGENT PLANE at the return in place of the distance along the ray
+//              (wrong by about d tan(incidence) for a centre d beside a slanted ray), weighted by the cosine of the incidence.
+//              A normal per row in the SENSOR frame, unit length expected, not renormalised, either sign: (cap,3) beside xyz, or
+//              a store (capacity,P,3).  Gate, r, q, o, u, the samples, the voxels, header word 1 and the skip are the rule above.
+//              Per row, once: n_m[a] = fma(R[a][2], nz, fma(R[a][1], ny, R[a][0] * nx)) (gn_xform's chain without t);
+//              a0 = (n_m.x*u.x + n_m.y*u.y) + n_m.z*u.z; m = a0 >= 0 ? n_m : -n_m (away from the sensor, as u); a = |a0|;
+//              wq = (int)rintf(a * 256.f).  The row is USABLE when wq >= 1 and a >= (float)cos_min (a zero or NaN normal fails by
+//              comparison); a row that passed the range gate and is not usable adds one to header word 2 and offers nothing.
+//              Per kept sample: s = (m.x*ex + m.y*ey) + m.z*ez clamped to [-tau, tau], fixed = rintf(s * 2^24), sum += wq *
+//              fixed, count += wq.  D = sum / (count * 2^24) is the weighted mean; a full-weight sample counts 256.  With |n| <=
+//              1: wq * |fixed| <= 2^38, and a count wraps after 2^24 full-weight samples of one voxel.
+//   carve      lookups only (find_slot; no slot is claimed, the key set stays).  Per row that passes the range gate, for k = 1,
+//              2, ... while t = (float)k * h < r - (float)margin: the voxel of o + u * t (outside the 21 bits: skipped silently);
+//              skipped when its key equals the key of this ray's previous keyed sample; if the table holds the key: sum += weight
+//              * rintf(tau * 2^24), count += weight ("free, at the truncation distance").  weight in [1, 65535] count units;
+//              max_range / step <= 65536.  A function of (the map before, the set of frames); meant to run after the
+//              integrations, and a later integrate adds to what is there.
 //   export     (key, sum, count) of every occupied slot in arrival order + their number; Python sorts.
 //
 // Field: D(slot) = (float)((double)sum / ((double)count * 2^24)).  A voxel is QUALIFIED when count >= min_count (>= 1).
@@ -51,7 +68,7 @@ constexpr float FIX_ONE = 16777216.f;   // 2^24: |s| <= 64 m leaves 2^32 samples
 constexpr int MAX_STEPS = 4096;         // n = ceil(tau / h) at most
 
 struct TsdfHdr {   // 256 bytes
-    unsigned overflow, outside, pad[62];
+    unsigned overflow, outside, unusable, pad[61];
 };
 
 struct Tsdf {
@@ -82,16 +99,36 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_clear_kernel(Tsdf M) {
 // key are summed by a segmented suffix sum over (count << 40) + fixed (|fixed| <= 2^30, 64 lanes), and the first lane of a run
 // adds the run's sum and count.  The same integers reach the table as with one pair of atomics a sample, which timed 2.4 times
 // slower on an HDL64E frame (profiles/tsdf_bench.md).  The callers keep the wave together: no lane returns before this.
+// PLANE: the distance to the tangent plane at the return instead of the distance along the ray.  (nx, ny, nz) is the return's
+// normal in the sensor frame; the row gate, the weight wq and the direction m are formed once a row, before the samples.  A run
+// is summed in two words, sum (wq * fixed, at most 64 * 2^38) and count (wq): a packed word would tie the rule to |n| <= 1.
+template <bool PLANE>
 __device__ __forceinline__ void integrate_ray(const Tsdf &M, const GnPose32 &P, bool row, float x, float y, float z,
-                                              const Rays &R) {
+                                              const Rays &R, float nx = 0.f, float ny = 0.f, float nz = 0.f,
+                                              float cos_min = 0.f) {
     const int lane = threadIdx.x & 63;
     const float r2 = (x * x + y * y) + z * z;
-    const bool live = row && r2 >= R.lo2 && r2 <= R.hi2;
+    bool live = row && r2 >= R.lo2 && r2 <= R.hi2;
     const float r = sqrtf(r2);
     float q[3], u[3];
     gn_xform(P, x, y, z, q);
 #pragma unroll
     for (int a = 0; a < 3; ++a) u[a] = __fdiv_rn(q[a] - P.t[a], r);
+    float m[3] = {0.f, 0.f, 0.f};
+    unsigned wq = 0u;
+    if constexpr (PLANE) {
+        float nm[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) nm[a] = fmaf(P.R[3 * a + 2], nz, fmaf(P.R[3 * a + 1], ny, P.R[3 * a] * nx));
+        const float a0 = (nm[0] * u[0] + nm[1] * u[1]) + nm[2] * u[2], aa = fabsf(a0), wf = rintf(aa * 256.f);
+        const bool usable = wf >= 1.f && aa >= cos_min;   // a NaN fails both
+        if (live && !usable) atomicAdd(&M.hdr()->unusable, 1u);
+        live = live && usable;
+        wq = live ? (unsigned)wf : 0u;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) m[a] = a0 >= 0.f ? nm[a] : -nm[a];
+    }
+    const float *d = PLANE ? m : u;
     unsigned long long prev = EMPTY;
     for (int k = -R.n; k <= R.n; ++k) {
         const float t = r + (float)k * R.h;
@@ -108,26 +145,45 @@ __device__ __forceinline__ void integrate_ray(const Tsdf &M, const GnPose32 &P, 
         float c[3];
         voxel_centre(key, M.v, c);
         const float ex = q[0] - c[0], ey = q[1] - c[1], ez = q[2] - c[2];
-        const float s = fminf(fmaxf((u[0] * ex + u[1] * ey) + u[2] * ez, -R.tau), R.tau);
-        long long acc = valid ? (1ll << 40) + (long long)rintf(s * FIX_ONE) : 0ll;
+        const float s = fminf(fmaxf((d[0] * ex + d[1] * ey) + d[2] * ez, -R.tau), R.tau);
+        long long acc = valid ? (PLANE ? (long long)wq * (long long)rintf(s * FIX_ONE) : (1ll << 40) + (long long)rintf(s * FIX_ONE)) : 0ll;
         const unsigned long long before = __shfl_up(key, 1, 64);
         const bool head = lane == 0 || before != key;
         const unsigned long long heads = __ballot(head || !valid);
         const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
         const int end = above ? lane + __ffsll((long long)above) : 64;
+        if constexpr (PLANE) {
+            unsigned cnt = valid ? wq : 0u;
 #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long other = __shfl_down(acc, off, 64);
-            if (lane + off < end) acc += other;
-        }
-        if (valid && head) {
-            const long long cnt = (acc + (1ll << 39)) >> 40, total = acc - (cnt << 40);
-            const int slot = claim_slot(M.keys(), M.cap_vox, key);
-            if (slot < 0) {
-                atomicAdd(&M.hdr()->overflow, (unsigned)cnt);
-            } else {
-                atomicAdd((unsigned long long *)&M.sum()[slot], (unsigned long long)total);
-                atomicAdd(&M.count()[slot], (unsigned)cnt);
+            for (int off = 1; off < 64; off <<= 1) {
+                const long long other = __shfl_down(acc, off, 64);
+                const unsigned others = __shfl_down(cnt, off, 64);
+                if (lane + off < end) acc += other, cnt += others;
+            }
+            if (valid && head) {
+                const int slot = claim_slot(M.keys(), M.cap_vox, key);
+                if (slot < 0) {
+                    atomicAdd(&M.hdr()->overflow, cnt);
+                } else {
+                    atomicAdd((unsigned long long *)&M.sum()[slot], (unsigned long long)acc);
+                    atomicAdd(&M.count()[slot], cnt);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const long long other = __shfl_down(acc, off, 64);
+                if (lane + off < end) acc += other;
+            }
+            if (valid && head) {
+                const long long cnt = (acc + (1ll << 39)) >> 40, total = acc - (cnt << 40);
+                const int slot = claim_slot(M.keys(), M.cap_vox, key);
+                if (slot < 0) {
+                    atomicAdd(&M.hdr()->overflow, (unsigned)cnt);
+                } else {
+                    atomicAdd((unsigned long long *)&M.sum()[slot], (unsigned long long)total);
+                    atomicAdd(&M.count()[slot], (unsigned)cnt);
+                }
             }
         }
     }
@@ -139,7 +195,7 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_integrate_kernel(Tsdf M, const fl
     const int n = min(max(count[0], 0), cap);
     const bool row = i < n;
     const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
-    integrate_ray(M, P, row, row ? xyz[3 * (size_t)i] : 0.f, row ? xyz[3 * (size_t)i + 1] : 0.f, row ? xyz[3 * (size_t)i + 2] : 0.f, R);
+    integrate_ray<false>(M, P, row, row ? xyz[3 * (size_t)i] : 0.f, row ? xyz[3 * (size_t)i + 1] : 0.f, row ? xyz[3 * (size_t)i + 2] : 0.f, R);
 }
 
 // a list of stored frames: row frames[f] of a channel-major store under poses[f]
@@ -159,7 +215,93 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_integrate_frames_kernel(Tsdf M, T
     const bool has = i < n;
     const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
     const float *p = L.store + (size_t)row * 3 * L.P + i;
-    integrate_ray(M, P, has, has ? p[0] : 0.f, has ? p[L.P] : 0.f, has ? p[2 * (size_t)L.P] : 0.f, R);
+    integrate_ray<false>(M, P, has, has ? p[0] : 0.f, has ? p[L.P] : 0.f, has ? p[2 * (size_t)L.P] : 0.f, R);
+}
+
+// the plane-distance forms: normals (cap,3) beside xyz, or a store (capacity,P,3) beside the frame store
+__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_planes_kernel(Tsdf M, const float *xyz, const float *normals,
+                                                                       const int32_t *count, int cap, const double *pose, Rays R,
+                                                                       float cos_min) {
+    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const int n = min(max(count[0], 0), cap);
+    const bool row = i < n;
+    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
+    const float *p = xyz + 3 * (size_t)i, *nr = normals + 3 * (size_t)i;
+    integrate_ray<true>(M, P, row, row ? p[0] : 0.f, row ? p[1] : 0.f, row ? p[2] : 0.f, R, row ? nr[0] : 0.f, row ? nr[1] : 0.f,
+                        row ? nr[2] : 0.f, cos_min);
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_planes_frames_kernel(Tsdf M, TsFrameList L, const float *normals, Rays R,
+                                                                              float cos_min) {
+    const int f = blockIdx.y, i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const int row = L.frames[f];
+    if ((unsigned)row >= (unsigned)L.capacity) return;   // never read out of bounds; the whole block leaves
+    const int n = min(max(L.lengths[row], 0), L.P);
+    const bool has = i < n;
+    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
+    const float *p = L.store + (size_t)row * 3 * L.P + i, *nr = normals + ((size_t)row * L.P + i) * 3;
+    integrate_ray<true>(M, P, has, has ? p[0] : 0.f, has ? p[L.P] : 0.f, has ? p[2 * (size_t)L.P] : 0.f, R, has ? nr[0] : 0.f,
+                        has ? nr[1] : 0.f, has ? nr[2] : 0.f, cos_min);
+}
+
+// ---------------------------------------------------------------------------------------------------------- free-space carving
+// One return: every voxel its ray crosses before `margin` short of the return, IF THE TABLE HOLDS IT, is told "free, at the
+// truncation distance".  Lookups only (find_slot: nobody writes a key while a carve runs), so the key set stays and what a key
+// receives depends on the key set and the frames alone, not on their order.  A lane on its own, leaving when its ray ends: the
+// form that merges equal keys of a wave before the lookup, as integrate_ray does, was built and timed 1.14 times slower on an
+// HDL64E frame and 1.21 times slower on 50 stored frames (profiles/tsdf_bench.md).  Supposed, not measured: lookups of one key by
+// neighbouring lanes are one cache line, few lookups hit, and the merged wave walks to its longest ray.
+// The loop ends: t = (float)k * h grows without bound and lim <= r <= sqrt(hi2) is finite (k <= max_range / step + 1 <= 65537).
+struct Carve {
+    long long add;     // weight * rintf(tau * 2^24)
+    unsigned weight;
+    float margin;
+};
+
+__device__ __forceinline__ void carve_ray(const Tsdf &M, const GnPose32 &P, float x, float y, float z, const Rays &R,
+                                          const Carve &C) {
+    const float r2 = (x * x + y * y) + z * z;
+    if (!(r2 >= R.lo2 && r2 <= R.hi2)) return;
+    const float r = sqrtf(r2), lim = r - C.margin;
+    float q[3], u[3];
+    gn_xform(P, x, y, z, q);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) u[a] = __fdiv_rn(q[a] - P.t[a], r);
+    unsigned long long prev = EMPTY;
+    for (int k = 1;; ++k) {
+        const float t = (float)k * R.h;
+        if (!(t < lim)) break;
+        int vox[3] = {0, 0, 0}, sub;
+        int inside = 1;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) inside &= axis_cell(P.t[a] + u[a] * t, M.v, 1, vox[a], sub);
+        if (!inside) continue;
+        const unsigned long long key = pack_key(vox[0], vox[1], vox[2]);
+        if (key == prev) continue;
+        prev = key;
+        const int slot = find_slot(M.keys(), M.cap_vox, key);
+        if (slot < 0) continue;
+        atomicAdd((unsigned long long *)&M.sum()[slot], (unsigned long long)C.add);
+        atomicAdd(&M.count()[slot], C.weight);
+    }
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_carve_kernel(Tsdf M, const float *xyz, const int32_t *count, int cap,
+                                                            const double *pose, Rays R, Carve C) {
+    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (i >= min(max(count[0], 0), cap)) return;
+    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
+    carve_ray(M, P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], R, C);
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_carve_frames_kernel(Tsdf M, TsFrameList L, Rays R, Carve C) {
+    const int f = blockIdx.y, i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const int row = L.frames[f];
+    if ((unsigned)row >= (unsigned)L.capacity) return;   // never read out of bounds
+    if (i >= min(max(L.lengths[row], 0), L.P)) return;
+    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
+    const float *p = L.store + (size_t)row * 3 * L.P + i;
+    carve_ray(M, P, p[0], p[L.P], p[2 * (size_t)L.P], R, C);
 }
 
 __global__ __launch_bounds__(TS_BLOCK) void ts_export_kernel(Tsdf M, unsigned long long *keys, long long *sums, uint32_t *counts,
@@ -382,6 +524,76 @@ extern "C" int dpm_tsdf_integrate_frames(void *map, int cap_vox, double voxel, c
     const TsFrameList L{store, lengths, capacity, P, frames, poses};
     hipLaunchKernelGGL(ts_integrate_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, voxel, origin), L, R);
+    return dpm_launch_status();
+}
+
+inline bool cos_ok(double cos_min) { return cos_min >= 0.0 && cos_min <= 1.0; }
+
+extern "C" int dpm_tsdf_integrate_planes(void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
+                                         const float *normals, const int32_t *count, int cap, const double *pose, double min_range,
+                                         double max_range, double truncation, double step, double cos_min, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(xyz && normals && count && pose && cap >= 0 && cos_ok(cos_min));
+    Rays R;
+    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
+    if (cap == 0) return DPM_OK;
+    hipLaunchKernelGGL(ts_integrate_planes_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), xyz, normals, count, cap, pose, R, (float)cos_min);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_integrate_planes_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
+                                                const float *normals, const int32_t *lengths, int capacity, int P,
+                                                const int32_t *frames, const double *poses, int F, double min_range,
+                                                double max_range, double truncation, double step, double cos_min,
+                                                dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin) && cos_ok(cos_min));
+    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    Rays R;
+    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
+    if (F == 0) return DPM_OK;
+    DPM_CHECK_ARG(store && normals && lengths && frames && poses);
+    const TsFrameList L{store, lengths, capacity, P, frames, poses};
+    hipLaunchKernelGGL(ts_integrate_planes_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), L, normals, R, (float)cos_min);
+    return dpm_launch_status();
+}
+
+// the carve's constants from the host's arguments; false when they are refused
+inline bool make_carve(const Rays &R, double max_range, double step, int weight, double margin, Carve &C) {
+    if (!(weight >= 1 && weight <= 65535 && margin >= 0.0 && margin < 1e18 && max_range / step <= 65536.0)) return false;
+    C.add = (long long)weight * (long long)rintf(R.tau * FIX_ONE), C.weight = (unsigned)weight, C.margin = (float)margin;
+    return true;
+}
+
+extern "C" int dpm_tsdf_carve(void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const int32_t *count,
+                              int cap, const double *pose, double min_range, double max_range, double truncation, double step,
+                              int weight, double margin, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(xyz && count && pose && cap >= 0);
+    Rays R;
+    Carve C;
+    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R) && make_carve(R, max_range, step, weight, margin, C));
+    if (cap == 0) return DPM_OK;
+    hipLaunchKernelGGL(ts_carve_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), xyz, count, cap, pose, R, C);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_carve_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
+                                     const int32_t *lengths, int capacity, int P, const int32_t *frames, const double *poses, int F,
+                                     double min_range, double max_range, double truncation, double step, int weight, double margin,
+                                     dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    Rays R;
+    Carve C;
+    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R) && make_carve(R, max_range, step, weight, margin, C));
+    if (F == 0) return DPM_OK;
+    DPM_CHECK_ARG(store && lengths && frames && poses);
+    const TsFrameList L{store, lengths, capacity, P, frames, poses};
+    hipLaunchKernelGGL(ts_carve_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), L, R, C);
     return dpm_launch_status();
 }
 

@@ -215,10 +215,13 @@ class LoopCloser:
             return torch.zeros(6, 6, device=self.device, dtype=torch.float32)
         return ops.information_matrix(a, b, _Rt(X, self.device), self.info_radius)
 
-    def _normals_for(self, frames):
-        """the normals of the stored frames that become ICP targets, once each; no host read (the lengths are known)"""
+    def _normals_for(self, frames, force: bool = False):
+        """the normals of the stored frames that become ICP targets, once each; no host read (the lengths are known).  force:
+        also under the point metric, whose closer holds no normals until somebody asks (GeometricSlam.surface_map)"""
         new = sorted(set(int(f) for f in frames) - self._has_normals)
-        if self.metric == "plane" and new:
+        if force and new and self.normals is None:
+            self.normals = torch.zeros(self.capacity, self.P, 3, device=self.device, dtype=torch.float32)
+        if (self.metric == "plane" or force) and new:
             counts = self.counts + [0] * (self.capacity - len(self.counts))
             ops.icp_target_normals(self.store, self.lengths, self.lengths[:0], self.normals_radius, host=(new, counts), out=self.normals)
             self._has_normals.update(new)
@@ -453,13 +456,24 @@ class GeometricSlam:
         steps = self.odometry.steps
         return [i for i in range(len(self._corrected)) if i >= len(steps) or steps[i].status in (CONVERGED, MAX_ITER)]
 
-    def surface_map(self, voxel_size: float = 0.2, **kw):
-        """-> tsdf.TsdfMap(voxel_size, **kw) holding the loop closer's stored frames fused under the corrected `poses`, in one
-        TsdfMap.integrate_frames call and without a host synchronisation.  LIMIT: these are the loop closer's thinned
-        copies, at most points_per_frame a frame (and `sample`d), not the frames `step` was given."""
+    def surface_map(self, voxel_size: float = 0.2, distance: str = "ray", carve: float = 0.0, **kw):
+        """-> tsdf.TsdfMap(voxel_size, distance=distance, **kw) holding the loop closer's stored frames fused under the
+        corrected `poses`, in one TsdfMap.integrate_frames call and without a host synchronisation.  distance="plane": the
+        distance to the tangent plane at each return, with the loop closer's normals of the stored frames (dpm_point_normals
+        at its normals_radius; computed here, one launch a frame, for the rows that have none yet).  carve > 0: afterwards one
+        TsdfMap.carve_frames call over the same rows with that weight (in full-weight samples).  LIMIT: these are the loop
+        closer's thinned copies, at most points_per_frame a frame (and `sample`d), not the frames `step` was given."""
         from .tsdf import TsdfMap
-        out = TsdfMap(voxel_size=voxel_size, **kw)
-        rows = self.surface_rows()
+        out = TsdfMap(voxel_size=voxel_size, distance=distance, **kw)
+        if not carve >= 0:
+            raise ValueError("carve >= 0")
+        rows, lc = self.surface_rows(), self.loop_closer
         if rows:
-            out.integrate_frames(self.loop_closer.store, self.loop_closer.lengths, rows, self.poses[rows])
+            normals = None
+            if distance == "plane":
+                lc._normals_for(rows, force=True)
+                normals = lc.normals
+            out.integrate_frames(lc.store, lc.lengths, rows, self.poses[rows], normals=normals)
+            if carve > 0:
+                out.carve_frames(lc.store, lc.lengths, rows, self.poses[rows], weight=carve)
         return out

@@ -2354,6 +2354,8 @@ def local_map_export(table, cap_vox, subdiv, half, max_out=None):
 # -- the TSDF surface map (csrc/tsdf_map.hip; orchestration in tsdf.py) --------------------------------------------------------
 TSDF_MAX_TRUNCATION = 64.0  # metres: tau 2^24 2^32 < 2^63
 TSDF_MAX_STEPS = 4096       # ceil(truncation / step) at most
+TSDF_MAX_CARVE_WEIGHT = 65535   # count units a carve may add per crossed voxel
+TSDF_MAX_CARVE_STEPS = 65536    # max_range / step at most for a carve
 
 
 def tsdf_rays(truncation: float, step: float, min_range: float, max_range: float):
@@ -2420,6 +2422,93 @@ def tsdf_integrate_frames(table, cap_vox, voxel, origin, store, lengths, frames,
         _lib.check(_lib.load().dpm_tsdf_integrate_frames(
             _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
             store.shape[2], _ptr(frames), _ptr(poses), F, *rays, _stream(table)), "dpm_tsdf_integrate_frames")
+
+
+def _tsdf_frame_args(what, xyz, count, pose):
+    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or count.numel() != 1 or pose.numel() != 16:
+        raise ValueError(f"{what}: xyz (cap,3), count (1,), pose (4,4)")
+
+
+def _tsdf_list_args(what, store, lengths, frames, poses) -> int:
+    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
+    _chk(poses, torch.float64, "poses")
+    F = frames.numel()
+    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
+            or frames.dim() != 1 or poses.numel() != 16 * F or F > 65535:
+        raise ValueError(f"{what}: store (capacity,3,P), lengths (capacity,), frames (F,) with F <= 65535, poses (F,4,4)")
+    return F
+
+
+def _tsdf_cos(cos_min) -> float:
+    if not 0.0 <= float(cos_min) <= 1.0:
+        raise ValueError("0 <= cos_min <= 1")
+    return float(cos_min)
+
+
+def tsdf_carve_args(weight, margin, step: float, max_range: float):
+    """the carve's own arguments, checked as the entry points check them -> (int weight, float margin)"""
+    w, g = int(weight), float(margin)
+    if not (1 <= w <= TSDF_MAX_CARVE_WEIGHT and 0.0 <= g < 1e18):
+        raise ValueError(f"carve: weight in [1, {TSDF_MAX_CARVE_WEIGHT}] count units, margin >= 0")
+    if not float(max_range) / float(step) <= TSDF_MAX_CARVE_STEPS:
+        raise ValueError(f"carve: max_range / step <= {TSDF_MAX_CARVE_STEPS}")
+    return w, g
+
+
+def tsdf_integrate_planes(table, cap_vox, voxel, origin, xyz, normals, count, pose, min_range, max_range, truncation, step,
+                          cos_min=0.0):
+    """dpm_tsdf_integrate_planes: tsdf_integrate's arguments and normals (cap,3) fp32 in the sensor frame.  One launch, no host
+    synchronisation, capturable in a graph."""
+    rays = tsdf_rays(truncation, step, min_range, max_range)
+    o = _tsdf_args(table, cap_vox, origin)
+    _tsdf_frame_args("tsdf_integrate_planes", xyz, count, pose)
+    if _chk(normals, torch.float32, "normals").shape != xyz.shape:
+        raise ValueError("tsdf_integrate_planes: normals (cap,3), one per row of xyz")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_integrate_planes(
+            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(normals), _ptr(count), xyz.shape[0],
+            _ptr(pose), *rays, _tsdf_cos(cos_min), _stream(table)), "dpm_tsdf_integrate_planes")
+
+
+def tsdf_integrate_planes_frames(table, cap_vox, voxel, origin, store, normals, lengths, frames, poses, min_range, max_range,
+                                 truncation, step, cos_min=0.0):
+    """dpm_tsdf_integrate_planes_frames: tsdf_integrate_frames' arguments and a normals store (capacity,P,3) fp32"""
+    rays = tsdf_rays(truncation, step, min_range, max_range)
+    o = _tsdf_args(table, cap_vox, origin)
+    F = _tsdf_list_args("tsdf_integrate_planes_frames", store, lengths, frames, poses)
+    if tuple(_chk(normals, torch.float32, "normals").shape) != (store.shape[0], store.shape[2], 3):
+        raise ValueError("tsdf_integrate_planes_frames: normals (capacity,P,3)")
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_integrate_planes_frames(
+            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(normals), _ptr(lengths), store.shape[0],
+            store.shape[2], _ptr(frames), _ptr(poses), F, *rays, _tsdf_cos(cos_min), _stream(table)),
+            "dpm_tsdf_integrate_planes_frames")
+
+
+def tsdf_carve(table, cap_vox, voxel, origin, xyz, count, pose, min_range, max_range, truncation, step, weight, margin):
+    """dpm_tsdf_carve: tsdf_integrate's arguments, weight (count units) and margin (metres).  Lookups only; one launch, no
+    host synchronisation, capturable in a graph."""
+    rays = tsdf_rays(truncation, step, min_range, max_range)
+    w, g = tsdf_carve_args(weight, margin, step, max_range)
+    o = _tsdf_args(table, cap_vox, origin)
+    _tsdf_frame_args("tsdf_carve", xyz, count, pose)
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_carve(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(count),
+                                              xyz.shape[0], _ptr(pose), *rays, w, g, _stream(table)), "dpm_tsdf_carve")
+
+
+def tsdf_carve_frames(table, cap_vox, voxel, origin, store, lengths, frames, poses, min_range, max_range, truncation, step, weight,
+                      margin):
+    """dpm_tsdf_carve_frames: tsdf_integrate_frames' arguments, weight and margin"""
+    rays = tsdf_rays(truncation, step, min_range, max_range)
+    w, g = tsdf_carve_args(weight, margin, step, max_range)
+    o = _tsdf_args(table, cap_vox, origin)
+    F = _tsdf_list_args("tsdf_carve_frames", store, lengths, frames, poses)
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_carve_frames(
+            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
+            store.shape[2], _ptr(frames), _ptr(poses), F, *rays, w, g, _stream(table)), "dpm_tsdf_carve_frames")
 
 
 def _counted(call, max_out):

@@ -9,9 +9,18 @@ frames alone: the sorted export has the same bytes whatever the order of rows, f
 `integrate_frames` does the same for a list of stored frames in one launch (LoopCloser.store), which is how
 `GeometricSlam.surface_map` fuses a run under its corrected poses.
 
-LIMITS: no free-space carving along the whole ray (a surface that moved away stays); no weight cap or decay; the frame's
-pose is the origin of every ray (no per-point origins for sweeps that are not deskewed); no weighting by incidence angle;
-marching tetrahedra, not marching cubes; the voxels live on the device (nothing is streamed to the host).
+`TsdfMap(distance="plane")` fuses the distance of the voxel's centre to the TANGENT PLANE at the return instead (the distance
+along the ray is wrong by about d tan(incidence) for a centre d beside a slanted ray), each sample weighted by the cosine of
+the incidence in 1/256ths; it needs a normal per return, in the sensor frame.  A map keeps one form from its construction:
+`unit` is the count of one full-weight sample, 1 or 256, and every `min_count` and carve weight is given in full-weight samples.
+`carve` / `carve_frames` tell every voxel THE MAP ALREADY HOLDS that a ray crosses well before its return "free, at the
+truncation distance": lookups only, so the key set stays, and what was seen through is forgotten once the free observations
+outweigh it.  Carving is meant to run after the integrations; a later integrate simply adds to what is there.
+
+LIMITS: carving reaches only voxels that exist and claims none; no weight cap or decay; the frame's pose is the origin of every
+ray (no per-point origins for sweeps that are not deskewed); the normals of the plane form are the caller's (or dpm_point_normals
+of the frame alone, `normals=<radius>`); marching tetrahedra, not marching cubes; the voxels live on the device (nothing is
+streamed to the host).
 """
 from __future__ import annotations
 
@@ -98,10 +107,19 @@ class TsdfMap:
     voxel_size / 2): the spacing of the samples.  Coordinates are fp32 relative to `origin` (three float64; default: the
     translation of the first pose), so work far from the world's zero keeps fp32 accuracy.  A return counts when min_range
     <= |p| <= max_range in the sensor frame.  A map that ran out of slots is undefined: `overflow()` is then non-zero and
-    `check()` raises ValueError.  The extractions synchronise once each and do not look at that word: call `check()` first."""
+    `check()` raises ValueError.  The extractions synchronise once each and do not look at that word: call `check()` first.
+    distance: "ray" (along the ray; the default) or "plane" (to the tangent plane at the return: `integrate` then needs
+    normals), fixed for the map's life; cos_min in [0, 1]: in plane mode a return whose |cos(incidence)| is below it is left
+    out and counted in `unusable()`."""
 
     def __init__(self, voxel_size: float = 0.2, truncation: Optional[float] = None, step: Optional[float] = None,
-                 max_voxels: int = 1 << 22, min_range: float = 0.0, max_range: float = 100.0, origin=None, device=None):
+                 max_voxels: int = 1 << 22, min_range: float = 0.0, max_range: float = 100.0, origin=None, device=None,
+                 distance: str = "ray", cos_min: float = 0.0):
+        if distance not in ("ray", "plane"):
+            raise ValueError("distance is 'ray' or 'plane'")
+        if not 0.0 <= float(cos_min) <= 1.0:
+            raise ValueError("0 <= cos_min <= 1")
+        self.distance, self.cos_min, self.unit = distance, float(cos_min), 256 if distance == "plane" else 1
         if not (voxel_size > 0 and float(np.float32(voxel_size)) > 0):
             raise ValueError("voxel_size > 0")
         if max_voxels < 2 or max_voxels > 1 << 24 or max_voxels & (max_voxels - 1):
@@ -132,57 +150,124 @@ class TsdfMap:
     def _rays(self):
         return self.min_range, self.max_range, self.truncation, self.step
 
-    # -- fusion: no host synchronisation
-    def integrate(self, pcd, pose, length=None):
-        """one frame under `pose` (4,4 sensor -> world; numpy, or a tensor -- on the GPU it is read there): an
-        augment.PointCloud, or xyz (N,3) float32 on the GPU with `length` (an int, or a (1,) int32 tensor on the GPU; None:
-        N).  One launch."""
+    def _map(self):
+        return self.table, self.max_voxels, self.voxel_size, self.origin
+
+    @staticmethod
+    def _frame(what, pcd, pose, length):
+        """-> (xyz (N,3), count (1,) int32 on the device) of an augment.PointCloud or of xyz with `length`"""
         if isinstance(pcd, torch.Tensor):
             xyz = pcd
             if xyz.dim() != 2 or xyz.shape[1] != 3:
-                raise ValueError("integrate: xyz (N,3)")
+                raise ValueError(f"{what}: xyz (N,3)")
             if isinstance(length, torch.Tensor):
                 count = length.reshape(1)
             else:
                 n = xyz.shape[0] if length is None else int(length)
                 if not 0 <= n <= xyz.shape[0]:
-                    raise ValueError("integrate: 0 <= length <= N")
+                    raise ValueError(f"{what}: 0 <= length <= N")
                 count = torch.full((1,), n, dtype=torch.int32).to(xyz.device)
         else:
             if length is not None:
-                raise ValueError("integrate: a PointCloud carries its own length")
+                raise ValueError(f"{what}: a PointCloud carries its own length")
             xyz, count = pcd.xyz, pcd.count
         if tuple(np.shape(pose)) != (4, 4):
             raise ValueError("pose: (4,4)")
-        self._ready(xyz.device, pose)
-        if xyz.shape[0] == 0:
-            return self
-        ops.tsdf_integrate(self.table, self.max_voxels, self.voxel_size, self.origin, xyz, count,
-                           _pose_tensor(pose, self.device), *self._rays())
-        return self
+        return xyz, count
 
-    def integrate_frames(self, store, lengths, frames, poses):
-        """stored frames under a pose each, in one launch for any number of them: row frames[f] of `store` (capacity,3,P) fp32
-        channel-major / `lengths` (capacity,) int32 on the device (LoopCloser.store, .lengths) under poses[f] (F,4,4; sensor
-        -> world).  frames / poses: host arrays (uploaded, nothing is read back) or device tensors.  The result is that of
-        `integrate` of each entry, byte for byte."""
+    def _list(self, what, store, frames, poses):
+        """-> (rows (F,) int32 on the device, poses (F,4,4)) of a list of stored frames, checked"""
         dev = store.device
         if isinstance(frames, torch.Tensor):
             rows = frames.to(device=dev, dtype=torch.int32).contiguous()
         else:
             host = np.asarray(frames, np.int64).reshape(-1)
             if host.size and not (0 <= host.min() and host.max() < store.shape[0]):
-                raise ValueError("integrate_frames: frames are rows of the store")
+                raise ValueError(f"{what}: frames are rows of the store")
             rows = torch.from_numpy(host.astype(np.int32)).to(dev)
         if not isinstance(poses, torch.Tensor):
             poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4))
         if poses.numel() != 16 * rows.numel() or rows.numel() > 65535:
-            raise ValueError("integrate_frames: poses (F,4,4), F <= 65535")
-        self._ready(dev, poses.reshape(-1, 4, 4)[0] if rows.numel() else None)
+            raise ValueError(f"{what}: poses (F,4,4), F <= 65535")
+        return rows, poses
+
+    def _estimated(self, xyz, count, radius):
+        """dpm_point_normals of the frame's valid rows alone -> (N,3), zeros past them.  Reads the length: one synchronisation."""
+        augment._SYNCS[0] += 1
+        n = min(max(int(count.item()), 0), xyz.shape[0])
+        out = torch.zeros_like(xyz)
+        if n:
+            lengths = torch.full((1,), n, dtype=torch.int32, device=xyz.device)
+            out[:n] = ops.icp_target_normals(xyz[:n].t().contiguous()[None], lengths, lengths[:0], float(radius), host=([0], [n]))[0]
+        return out
+
+    # -- fusion: no host synchronisation
+    def integrate(self, pcd, pose, length=None, normals=None):
+        """one frame under `pose` (4,4 sensor -> world; numpy, or a tensor -- on the GPU it is read there): an
+        augment.PointCloud, or xyz (N,3) float32 on the GPU with `length` (an int, or a (1,) int32 tensor on the GPU; None:
+        N).  One launch.  distance="plane": `normals` is required -- (N,3) float32 on the GPU, in the SENSOR frame, unit length,
+        either sign; or a radius in metres to estimate them from the frame alone (dpm_point_normals), which costs the host read
+        of the length, the only synchronisation here.  distance="ray": normals must be None."""
+        xyz, count = self._frame("integrate", pcd, pose, length)
+        if (normals is None) != (self.distance == "ray"):
+            raise ValueError("integrate: normals are required by distance='plane' and refused by distance='ray'")
+        if isinstance(normals, torch.Tensor) and normals.shape != xyz.shape:
+            raise ValueError("integrate: normals (N,3), one per row")
+        self._ready(xyz.device, pose)
+        if xyz.shape[0] == 0:
+            return self
+        if self.distance == "ray":
+            ops.tsdf_integrate(*self._map(), xyz, count, _pose_tensor(pose, self.device), *self._rays())
+        else:
+            if not isinstance(normals, torch.Tensor):
+                normals = self._estimated(xyz, count, normals)
+            ops.tsdf_integrate_planes(*self._map(), xyz, normals, count, _pose_tensor(pose, self.device), *self._rays(), self.cos_min)
+        return self
+
+    def integrate_frames(self, store, lengths, frames, poses, normals=None):
+        """stored frames under a pose each, in one launch for any number of them: row frames[f] of `store` (capacity,3,P) fp32
+        channel-major / `lengths` (capacity,) int32 on the device (LoopCloser.store, .lengths) under poses[f] (F,4,4; sensor
+        -> world).  frames / poses: host arrays (uploaded, nothing is read back) or device tensors.  The result is that of
+        `integrate` of each entry, byte for byte.  distance="plane": normals (capacity,P,3) float32, the store's normals in
+        each frame's own sensor frame (LoopCloser.normals), is required; distance="ray": it must be None."""
+        if (normals is None) != (self.distance == "ray"):
+            raise ValueError("integrate_frames: normals are required by distance='plane' and refused by distance='ray'")
+        rows, poses = self._list("integrate_frames", store, frames, poses)
+        self._ready(store.device, poses.reshape(-1, 4, 4)[0] if rows.numel() else None)
         if rows.numel() == 0:
             return self
-        ops.tsdf_integrate_frames(self.table, self.max_voxels, self.voxel_size, self.origin, store, lengths, rows,
-                                  poses.to(device=self.device, dtype=torch.float64).contiguous(), *self._rays())
+        poses = poses.to(device=self.device, dtype=torch.float64).contiguous()
+        if self.distance == "ray":
+            ops.tsdf_integrate_frames(*self._map(), store, lengths, rows, poses, *self._rays())
+        else:
+            ops.tsdf_integrate_planes_frames(*self._map(), store, normals, lengths, rows, poses, *self._rays(), self.cos_min)
+        return self
+
+    # -- carving: no host synchronisation either
+    def _carve_args(self, weight, margin):
+        margin = self.truncation + self.voxel_size if margin is None else float(margin)
+        return ops.tsdf_carve_args(max(1, int(round(float(weight) * self.unit))) if weight > 0 else 0, margin, self.step, self.max_range)
+
+    def carve(self, pcd, pose, length=None, weight: float = 1.0, margin: Optional[float] = None):
+        """the free space of one frame (the arguments of `integrate`): every voxel the map holds that a ray crosses before
+        `margin` metres (default truncation + voxel_size) short of its return receives `weight` full-weight samples (times
+        `unit`, at most 65535 count units) of "free, at the truncation distance".  Lookups only: no voxel is added.  Run it
+        after the integrations.  Needs max_range / step <= 65536.  One launch."""
+        xyz, count = self._frame("carve", pcd, pose, length)
+        w, g = self._carve_args(weight, margin)
+        if self.table is None or xyz.shape[0] == 0:      # an empty map holds nothing to carve
+            return self
+        ops.tsdf_carve(*self._map(), xyz, count, _pose_tensor(pose, self.device), *self._rays(), w, g)
+        return self
+
+    def carve_frames(self, store, lengths, frames, poses, weight: float = 1.0, margin: Optional[float] = None):
+        """`carve` of a list of stored frames (the arguments of `integrate_frames`) in one launch"""
+        rows, poses = self._list("carve_frames", store, frames, poses)
+        w, g = self._carve_args(weight, margin)
+        if self.table is None or rows.numel() == 0:
+            return self
+        ops.tsdf_carve_frames(*self._map(), store, lengths, rows, poses.to(device=self.device, dtype=torch.float64).contiguous(),
+                              *self._rays(), w, g)
         return self
 
     # -- read-back: one host synchronisation each
@@ -199,6 +284,17 @@ class TsdfMap:
     def outside(self) -> int:
         """samples that fell outside the 21-bit key range so far (they are left out)"""
         return self._header(1)
+
+    def unusable(self) -> int:
+        """plane mode: returns that passed the range gate so far and were left out for their normal -- zero, NaN, or with
+        |cos(incidence)| below 1/512 or below cos_min"""
+        return self._header(2)
+
+    def _min_count(self, min_count) -> int:
+        """min_count in full-weight samples -> the kernel's count units"""
+        if not float(min_count) > 0:
+            raise ValueError("min_count > 0")
+        return max(1, int(round(float(min_count) * self.unit)))
 
     def check(self):
         n = self.overflow()
@@ -220,39 +316,37 @@ class TsdfMap:
         order = np.argsort(keys, kind="stable")
         return keys[order], sums[order], counts[order].view(np.uint32)
 
-    def field(self, min_count: int = 1):
+    def field(self, min_count: float = 1):
         """(keys (m,) int64, D (m,) float32 metres) of the qualified voxels (count >= min_count), sorted by key; D > 0 on the
-        sensor's side of the surface"""
-        if int(min_count) < 1:
-            raise ValueError("min_count >= 1")
+        sensor's side of the surface.  min_count, here and below, is in full-weight samples: max(1, round(min_count * unit))
+        is what the count is compared with."""
+        min_count = self._min_count(min_count)
         keys, sums, counts = self.export()
         ok = counts >= np.uint32(min_count)
         return keys[ok], field_values(sums[ok], counts[ok])
 
-    def surface(self, min_count: int = 1) -> TsdfSurface:
+    def surface(self, min_count: float = 1) -> TsdfSurface:
         """the zero crossings of the field along the axes between qualified voxels, with normals from the field's gradient"""
-        if int(min_count) < 1:
-            raise ValueError("min_count >= 1")
+        min_count = self._min_count(min_count)
         if self.table is None:
             dev = self.device if self.device is not None else "cpu"
             z = torch.zeros(3, 0, dtype=torch.float32, device=dev)
             return TsdfSurface(z, z.clone(), torch.zeros(0, dtype=torch.int64, device=dev),
                                torch.zeros(0, dtype=torch.int32, device=dev), np.zeros(3) if self.origin is None else self.origin, z.clone())
-        keys, axes, xyz, normals = self._extract(ops.tsdf_surface, self.voxel_size, int(min_count))
+        keys, axes, xyz, normals = self._extract(ops.tsdf_surface, self.voxel_size, min_count)
         order = torch.sort(axes, stable=True).indices
         order = order[torch.sort(keys[order], stable=True).indices]
         local = xyz[order].t().contiguous()
         world = (local.double() + torch.from_numpy(self.origin).to(local.device)[:, None]).float()
         return TsdfSurface(world, normals[order].t().contiguous(), keys[order], axes[order], self.origin.copy(), local)
 
-    def mesh(self, min_count: int = 1):
+    def mesh(self, min_count: float = 1):
         """(vertices (V,3) float32 in the map frame -- world = vertices + origin --, faces (F,3) int32) from marching
         tetrahedra over the cells whose 8 corner voxels are qualified; welded by vertex name and sorted (`weld`); a face's
         normal (b - a) x (c - a) points to free space"""
-        if int(min_count) < 1:
-            raise ValueError("min_count >= 1")
+        min_count = self._min_count(min_count)
         if self.table is None:
             return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
-        return weld(*[t.cpu().numpy() for t in self._extract(ops.tsdf_mesh, self.voxel_size, int(min_count))])
+        return weld(*[t.cpu().numpy() for t in self._extract(ops.tsdf_mesh, self.voxel_size, min_count)])
 
     write_ply = staticmethod(write_ply)

@@ -1091,7 +1091,8 @@ int dpm_local_map_register_planes(const void *map, int cap_vox, int subdiv, int 
  * the caller).  No counterpart in the reference, whose map is a cloud of points.  DESIGN §7l is the definition.
  *
  * The map is one device buffer of dpm_tsdf_bytes(cap_vox) = 256 + 20 cap_vox bytes, 16-byte aligned: a 256-byte header (word
- * 0: samples that found no free slot, word 1: samples outside the key range) and one open-addressing table of cap_vox slots
+ * 0: samples that found no free slot, word 1: samples outside the key range, word 2: rows without a usable normal -- the
+ * plane-distance form below) and one open-addressing table of cap_vox slots
  * (a power of two in [2, 2^24], linear probing from splitmix64(key) & (cap_vox - 1), empty key ~0) as three arrays: key
  * uint64, sum int64, count uint32.  Keys, the map frame and the pose handling are dpm_local_map_insert's: `voxel` and `origin`
  * (three doubles ON THE HOST) the same in every call on one map, a pose 16 doubles IN DEVICE MEMORY entering as (float)R and
@@ -1130,6 +1131,47 @@ int dpm_tsdf_integrate(void *map, int cap_vox, double voxel, const double *origi
 int dpm_tsdf_integrate_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
                               const int32_t *lengths, int capacity, int P, const int32_t *frames, const double *poses, int F,
                               double min_range, double max_range, double truncation, double step, dpm_stream_t stream);
+/* PLANE-DISTANCE FUSION.  dpm_tsdf_integrate / _frames with one change: the distance of the voxel's centre to the TANGENT PLANE
+ * at the return replaces its distance along the ray (which is wrong by about d tan(incidence) for a centre d beside the ray),
+ * and a sample is weighted by the cosine of the incidence.  normals: fp32 IN THE SENSOR FRAME, one per row, unit length
+ * expected and not renormalised (either sign); (cap,3) row-major beside xyz, or for the list form a store (capacity,P,3) beside
+ * `store` (what ops.icp_target_normals writes).  0 <= cos_min <= 1.  The range gate, r, q, o, u, n, the samples t = r + (float)k
+ * * h, the t > 0 test, the voxel of o + u * t, header word 1 and the skip of a repeated key are the rule above, untouched.  Per
+ * row, once, in fp32 (R the (float) rotation of the pose, as q's chain uses it):
+ *     n_m[a] = fma(R[a][2], nz, fma(R[a][1], ny, R[a][0] * nx));   a0 = (n_m.x*u.x + n_m.y*u.y) + n_m.z*u.z;
+ *     m = a0 >= 0 ? n_m : -n_m (away from the sensor, as u);   a = |a0|;   wq = (int)rintf(a * 256.f), round half to even.
+ * The row is USABLE when wq >= 1 and a >= (float)cos_min; a zero or NaN normal (or a return at range 0) fails by comparison.  A
+ * row that passed the range gate and is not usable adds one to header word 2 -- one per row -- and offers no sample (nor
+ * anything to header word 1).  Per kept sample of a usable row, with e = q - c:
+ *     s = (m.x*ex + m.y*ey) + m.z*ez clamped to [-tau, tau], positive on the sensor's side;  fixed = (long long)rintf(s *
+ *     16777216.f);  sum += wq * fixed and count += wq (integer atomics).  No free slot: header word 0 grows by wq.
+ * D = sum / (count * 2^24) is then the weighted mean and the extractions below read it unchanged; a full-weight sample counts
+ * 256, and min_count is in those units.  Headroom (|n| <= 1): wq <= 256 and |fixed| <= 2^30, so wq * |fixed| <= 2^38 and a sum
+ * holds 2^24 such samples; a count (uint32) wraps after 2^24 full-weight samples of one voxel.  A map is fused in ONE of the two
+ * forms: their counts have different units.  Order independence and the equality of the list form with the per-frame calls hold
+ * as above. */
+int dpm_tsdf_integrate_planes(void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const float *normals,
+                              const int32_t *count, int cap, const double *pose, double min_range, double max_range,
+                              double truncation, double step, double cos_min, dpm_stream_t stream);
+int dpm_tsdf_integrate_planes_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
+                                     const float *normals, const int32_t *lengths, int capacity, int P, const int32_t *frames,
+                                     const double *poses, int F, double min_range, double max_range, double truncation,
+                                     double step, double cos_min, dpm_stream_t stream);
+/* FREE-SPACE CARVING, lookups only: no slot is claimed, the key set stays as it is.  The frame and list arguments of
+ * dpm_tsdf_integrate / _frames; weight in [1, 65535] in the map's count units (1 a sample of a ray-distance map, 256 of a
+ * plane-distance map); margin >= 0 metres.  DPM_EINVAL also when max_range / step > 65536.  Per row that passes the range gate,
+ * with r, q, o, u as above, for k = 1, 2, ... while t = (float)k * h < r - (float)margin:  the voxel of o + u * t (outside the
+ * 21 bits: skipped silently);  skipped when its key equals the key of this ray's previous keyed sample;  if the table holds the
+ * key:  sum += weight * tau_fixed with tau_fixed = (long long)rintf(tau * 16777216.f), and count += weight -- the observation
+ * "free, at the truncation distance".  The result is a function of (the map before the call, the set of frames), not of their
+ * order.  Carving is meant to run AFTER the integrations (it reaches only voxels that exist); a later integrate adds to what
+ * is there. */
+int dpm_tsdf_carve(void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const int32_t *count, int cap,
+                   const double *pose, double min_range, double max_range, double truncation, double step, int weight,
+                   double margin, dpm_stream_t stream);
+int dpm_tsdf_carve_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store, const int32_t *lengths,
+                          int capacity, int P, const int32_t *frames, const double *poses, int F, double min_range,
+                          double max_range, double truncation, double step, int weight, double margin, dpm_stream_t stream);
 /* Every occupied slot in no defined order: keys (max_out,) uint64, sums (max_out,) int64, counts (max_out,) uint32.  count
  * (1,) int32, ZEROED BY THE CALLER, receives their number, which may exceed max_out (the rest is not written; max_out = 0
  * only counts). */
