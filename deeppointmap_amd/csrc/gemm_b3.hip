@@ -18,6 +18,7 @@
 // bytes whose 16-byte chunks (a lane's 8 consecutive k: one ds_read_b128 per fragment) are swizzled against bank conflicts
 // (b3_col, dpm_common.h), 24 576 B per workgroup.
 #include "dpm_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -440,6 +441,292 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_ln_b3_kernel(const float 
     }
 }
 
+// The tail of a decoder block (descriptor_attention.py:41-48) as ONE kernel for C = 256:
+//     z2  = LN2(a Wo^T + bo + pre)                  cross attention's out-projection, residual z1 = pre, norm2
+//     h   = relu(z2 W0^T + b0)                      mlp.0
+//     out = LN3(h W2^T + b2 + z2) [+ post]          mlp.2, residual, norm3, the next block's position embedding
+// which dpm_linear_layernorm_bf16x3, dpm_linear_bf16x3 and dpm_linear_layernorm_bf16x3 compute in three launches over the same
+// 64-row tiles: z2 written, read as X and read again as pre, h written and read.  A row of `out` depends on the same row of a,
+// pre and post only, so a workgroup carries its 64 rows through all three products.  BIT-IDENTICAL to the three launches:
+//   * tile, wave layout and main loop are gemm_ln_b3_kernel<64, 256, 2, 4>'s in all three stages (512 threads, wave tile 32 x 64,
+//     K-tile 32): every output element sees the same six-product sequence in the same K order -- also the one the 64 x 128
+//     gemm_b3_kernel gives mlp.0 today (an element's bits do not depend on the tile shape);
+//   * the intermediate stays in registers in the STAGING layout: after a stage's accumulators have gone through the LDS tile ct,
+//     thread t reads back row t / 8, columns 32 kt + 4 (t % 8) .. + 3 for kt = 0 .. 7 -- exactly the four values it splits into
+//     the X planes of K-tile kt in the next stage.  Same fp32 values through the same split3: same planes;
+//   * LayerNorm in that layout has the association of the row-wise epilogue above.  There a lane sums (x + y) + (z + w) of four
+//     consecutive columns and an xor-butterfly runs over the 64 column groups g = col / 4 with offsets 1, 2, 4, 8, 16, 32.  Here
+//     g = 8 kt + (t % 8): offsets 1, 2, 4 are exchanges among the eight lanes of a row (per kt), offsets 8, 16, 32 are additions
+//     between a thread's kt registers, ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)).  Every level adds the same two partial
+//     sums as the butterfly does, and a + b = b + a in floating point, so every lane of the butterfly holds these bits;
+//   * bias, ReLU, rsqrtf(.. + 1e-5f), fmaf(v * rs, gamma, beta) and `post` after LN3: the existing expressions in their order.
+// Resources (kernel-resource-usage at gfx950: 128 registers, no scratch, 77 824 B of LDS): four waves per SIMD and two workgroups
+// per CU, as gemm_ln_b3_kernel<64, 256, 2, 4>.  The main loop alone takes 104 registers there, so the intermediate's 32 do not
+// all fit next to it: its last two K-tiles (8 registers) wait in LDS behind the operand planes (dt_stash: 16 KB, which two resident
+// workgroups still have room for), the products walk one column block at a time (fewer W fragments live), and the addresses
+// are scalar bases + one offset register.  z2, which LN3 needs again, cannot stay resident as well (ZREG = true spills 200
+// registers): it goes to `out` after LN2 and the thread that wrote a piece reads that piece back during the last K-tile of the
+// third product (an L2 hit), before the result overwrites it.  The epilogue operands (pre, z2, post) and every weight's first
+// K-tile are requested where registers are free AND their latency is covered: during the last K-tile / the previous epilogue.
+// Alone at 32 768 rows 83 us against 99-111 us for the three launches; in the step's registration stage 92 against 119 us
+// (profiles/decoder_tail_bench.md).
+struct TailArgs {
+    const float *a, *pre, *post;
+    float *out;
+    const uint16_t *w[3];   // planes of out_proj | mlp.0 | mlp.2
+    long long plane[3];
+    const float *bias[3];
+    const float *g2, *be2, *g3, *be3;
+    int R;
+};
+constexpr int DT_BM = 64, DT_C = 256, DT_T = 512, DT_NK = DT_C / B3_KT, DT_LDC = DT_C + 4;
+#ifndef DPM_TAIL_STASH
+#define DPM_TAIL_STASH 2
+#endif
+// the last DT_NS K-tiles of the intermediate wait in LDS behind the operand planes (16 bytes per thread and tile) instead of in registers
+constexpr int DT_NS = DPM_TAIL_STASH, DT_OPER = 3 * (DT_BM + DT_C) * B3_LD;   // (uint16 elements of the operand planes)
+__device__ __forceinline__ f32x4 *dt_stash(uint16_t *smem, int kt) {
+    return reinterpret_cast<f32x4 *>(smem + DT_OPER) + (kt - (DT_NK - DT_NS)) * DT_T + threadIdx.x;
+}
+// after the epilogue arithmetic, and after dt_restage's second barrier (the slots lie over the tail of ct)
+__device__ __forceinline__ void dt_stash_put(uint16_t *smem, const f32x4 (&v)[DT_NK]) {
+#pragma unroll
+    for (int kt = DT_NK - DT_NS; kt < DT_NK; ++kt) *dt_stash(smem, kt) = v[kt];
+}
+
+// uniform pointer + this thread's 32-bit BYTE offset: the scalar-base addressing form, one address register for all pieces
+template <typename V, typename P>
+__device__ __forceinline__ V *dt_at(P *uniform, unsigned bytes) {
+    using B = std::conditional_t<std::is_const<P>::value, const char, char>;
+    return reinterpret_cast<V *>(reinterpret_cast<B *>(uniform) + bytes);
+}
+// ... and a uniform element offset pinned to scalar registers (left alone the compiler adds the plane strides per lane: a register
+// pair per piece)
+__device__ __forceinline__ long long dt_uniform(long long o) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)o), hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)o >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+template <int CTRL>
+__device__ __forceinline__ float dt_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+// sum over a row's 64 column groups: s[kt] of the eight lanes t % 8 (the lanes of one row are eight consecutive lanes)
+__device__ __forceinline__ float dt_row_sum(float (&s)[DT_NK]) {
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) {
+        s[kt] += dt_dpp<0xB1>(s[kt]);    // lane ^ 1
+        s[kt] += dt_dpp<0x4E>(s[kt]);    // lane ^ 2
+        s[kt] += dt_dpp<0x141>(s[kt]);   // the other quad of the eight (all four of its lanes hold the same sum): lane ^ 4
+    }
+    return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+}
+// v (+ bias, by the caller) -> LN(v) * gamma + beta, this thread's 32 values of its row
+__device__ __forceinline__ void dt_layernorm(f32x4 (&v)[DT_NK], const float *__restrict__ gamma, const float *__restrict__ beta, int sk) {
+    float s[DT_NK];
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) s[kt] = (v[kt][0] + v[kt][1]) + (v[kt][2] + v[kt][3]);
+    const float mu = dt_row_sum(s) / (float)DT_C;
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) {
+        v[kt][0] -= mu, v[kt][1] -= mu, v[kt][2] -= mu, v[kt][3] -= mu;
+        s[kt] = fmaf(v[kt][0], v[kt][0], fmaf(v[kt][1], v[kt][1], fmaf(v[kt][2], v[kt][2], v[kt][3] * v[kt][3])));
+    }
+    const float rs = rsqrtf(dt_row_sum(s) / (float)DT_C + 1e-5f);
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4 *>(gamma + kt * B3_KT + sk), b4 = *reinterpret_cast<const f32x4 *>(beta + kt * B3_KT + sk);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[kt][q] = fmaf(v[kt][q] * rs, g4[q], b4[q]);
+    }
+}
+
+// piece p (rows t / 4 + 128 p, 8 consecutive k from k0) of plane pl of a weight's K-tile: uniform base, per-thread byte offset
+__device__ __forceinline__ const u32x4 *dt_wsrc(const uint16_t *__restrict__ Wp, long long plane, int p, int pl, int k0, unsigned wo) {
+    return dt_at<const u32x4>(Wp + dt_uniform(pl * plane + p * (DT_T / 4) * DT_C) + k0, wo);
+}
+__device__ __forceinline__ unsigned dt_woff() { return (unsigned)((threadIdx.x >> 2) * DT_C + (threadIdx.x & 3) * 8) * 2u; }
+// K-tile 0 of a weight -> registers: requested by the caller ahead of the product (during the previous product's epilogue)
+__device__ __forceinline__ void dt_wtile0(const uint16_t *__restrict__ Wp, long long plane, u32x4 (&wv)[2][3]) {
+    const unsigned wo = dt_woff();
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) wv[p][pl] = *dt_wsrc(Wp, plane, p, pl, 0, wo);
+}
+
+// one product of the tail: acc = X W^T over K = 256, X from global memory (xg + xo: this thread's row, column sk; one K-tile ahead in
+// registers, as gemm_ln_b3_kernel) or from the registers xr (XREG); W planes one K-tile ahead in the registers wv (K-tile 0: dt_wtile0).  MID(kt) runs after
+// K-tile kt's loads have been requested (the caller's own prefetches).
+template <bool XREG, typename Mid>
+__device__ __forceinline__ void dt_product(uint16_t *smem, const float *xg, unsigned xo, const f32x4 (&xr)[DT_NK], const uint16_t *__restrict__ Wp,
+                                           long long plane, u32x4 (&wv)[2][3], f32x4 (&acc)[2][4], Mid mid) {
+    constexpr int WM = 32, WN = 64, MB = 2, NB = 4, PW = 2;
+    uint16_t (*Xs)[DT_BM][B3_LD] = reinterpret_cast<uint16_t (*)[DT_BM][B3_LD]>(smem);
+    uint16_t (*Ws)[DT_C][B3_LD] = reinterpret_cast<uint16_t (*)[DT_C][B3_LD]>(smem + 3 * DT_BM * B3_LD);
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 2, wn = w & 3;
+    const int sr = t >> 3, sk = (t & 7) * 4, wk = (t & 3) * 8, fr = lane & 15, fk = (lane >> 4) * 8;
+    const int wrow = t >> 2;
+    const unsigned wo = dt_woff();
+    f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!XREG) xv = *dt_at<const f32x4>(xg, xo);
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) {
+        {
+            const f32x4 x = !XREG ? xv : kt >= DT_NK - DT_NS ? *dt_stash(smem, kt) : xr[kt];
+            unsigned h0, m0, l0, h1, m1, l1, h2, m2, l2, h3, m3, l3;
+            split3(x[0], h0, m0, l0), split3(x[1], h1, m1, l1), split3(x[2], h2, m2, l2), split3(x[3], h3, m3, l3);
+            *reinterpret_cast<u32x2 *>(&Xs[0][sr][b3_col(sr, sk)]) = u32x2{pack2(h0, h1), pack2(h2, h3)};
+            *reinterpret_cast<u32x2 *>(&Xs[1][sr][b3_col(sr, sk)]) = u32x2{pack2(m0, m1), pack2(m2, m3)};
+            *reinterpret_cast<u32x2 *>(&Xs[2][sr][b3_col(sr, sk)]) = u32x2{pack2(l0, l1), pack2(l2, l3)};
+        }
+#pragma unroll
+        for (int p = 0; p < PW; ++p)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4 *>(&Ws[pl][p * (DT_T / 4) + wrow][b3_col(wrow, wk)]) = wv[p][pl];
+        __syncthreads();
+        if (kt + 1 < DT_NK) {   // (static: the loop is unrolled)
+            const int kn = (kt + 1) * B3_KT;
+            // (the offset made opaque per K-tile: otherwise the six piece addresses are formed once, as six register pairs that
+            // live through the whole product)
+            unsigned wok = wo;
+            asm volatile("" : "+v"(wok));
+            if (!XREG) xv = *dt_at<const f32x4>(xg + kn, xo);
+#pragma unroll
+            for (int p = 0; p < PW; ++p)
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) wv[p][pl] = *dt_wsrc(Wp, plane, p, pl, kn, wok);
+        }
+        mid(kt);
+        // an accumulator takes its six products in the order of the other bf16x3 kernels -- smallest terms first; (plane of W,
+        // plane of X): (1,1) (2,0) (0,2) (1,0) (0,1) (0,0) -- but here one column block at a time: only that block's W fragments
+        // are live next to the X fragments (the accumulators of a block are independent chains; the order across them is free)
+        bf16x8 b[3][MB];
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int i = 0; i < MB; ++i) b[pl][i] = *reinterpret_cast<const bf16x8 *>(&Xs[pl][wm * WM + i * 16 + fr][b3_col(fr, fk)]);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            bf16x8 a[3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) a[pl] = *reinterpret_cast<const bf16x8 *>(&Ws[pl][wn * WN + j * 16 + fr][b3_col(fr, fk)]);
+#define DPM_B3(PWQ, PXQ) \
+    _Pragma("unroll") for (int i = 0; i < MB; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[PWQ], b[PXQ][i], acc[i][j], 0, 0, 0)
+            DPM_B3(1, 1);
+            DPM_B3(2, 0);
+            DPM_B3(0, 2);
+            DPM_B3(1, 0);
+            DPM_B3(0, 1);
+            DPM_B3(0, 0);
+#undef DPM_B3
+        }
+        __syncthreads();
+    }
+}
+
+// accumulators -> LDS tile ct (over the operand planes, which the last K-tile has finished with) -> v in the staging layout
+template <typename Mid>
+__device__ __forceinline__ void dt_restage(uint16_t *smem, const f32x4 (&acc)[2][4], f32x4 (&v)[DT_NK], Mid mid) {
+    float *ct = reinterpret_cast<float *>(smem);
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));   // the tile addresses are formed again here rather than kept in registers through a product
+    const int lane = t & 63, w = t >> 6, wm = w >> 2, wn = w & 3, sr = t >> 3, sk = (t & 7) * 4;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            *reinterpret_cast<f32x4 *>(&ct[(wm * 32 + i * 16 + (lane & 15)) * DT_LDC + wn * 64 + j * 16 + (lane >> 4) * 4]) = acc[i][j];
+    mid();   // (the accumulators' registers are free from here on: the caller's epilogue loads)
+    __syncthreads();
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) v[kt] = *reinterpret_cast<const f32x4 *>(&ct[sr * DT_LDC + kt * B3_KT + sk]);
+    __syncthreads();   // the next product's staging writes over ct
+}
+
+__device__ __forceinline__ void dt_add_bias(f32x4 (&v)[DT_NK], const float *__restrict__ bias, int sk) {
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) {
+        const f32x4 bv = bias ? *reinterpret_cast<const f32x4 *>(bias + kt * B3_KT + sk) : f32x4{0.f, 0.f, 0.f, 0.f};   // (+ 0.f without one, as the row-wise epilogues)
+        v[kt] += bv;
+    }
+}
+
+template <bool ZREG>
+__global__ __launch_bounds__(DT_T) __attribute__((amdgpu_waves_per_eu(4, 4))) void decoder_tail_b3_kernel(TailArgs A) {
+    constexpr int SM0 = DT_OPER + DT_NS * DT_T * 8, SM1 = 2 * DT_BM * DT_LDC, SM = SM0 > SM1 ? SM0 : SM1;   // operand planes + stash | staged tile
+    __shared__ __attribute__((aligned(16))) uint16_t smem[SM];
+    const int t = threadIdx.x, sr = t >> 3, sk = (t & 7) * 4;
+    const int row0 = blockIdx.x * DT_BM, r = row0 + sr;
+    const long long base = dt_uniform((long long)row0 * DT_C);
+    const unsigned ro = (unsigned)(min(sr, A.R - 1 - row0) * DT_C + sk) * 4u;   // (bytes) rows past the end: the last row again, never stored
+    const float *ga = A.a + base, *gpre = A.pre + base, *gpost = (A.post ? A.post : A.pre) + base;
+    float *gout = A.out + base;
+    f32x4 acc[2][4], v[DT_NK], z[DT_NK];
+    u32x4 wv[2][3];
+    dt_wtile0(A.w[0], A.plane[0], wv);
+    // ---- z2 = LN2(a Wo^T + bo + pre)
+    // (epilogue operands are requested during the LAST K-tile, when the registers of the one-ahead W / X tiles are free: earlier
+    // they would not fit next to the main loop at four waves per SIMD)
+    dt_product<false>(smem, ga, ro, v, A.w[0], A.plane[0], wv, acc, [&](int kt) {
+        if (kt == DT_NK - 1) {
+#pragma unroll
+            for (int k2 = 0; k2 < DT_NK; ++k2) z[k2] = *dt_at<const f32x4>(gpre + k2 * B3_KT, ro);
+        }
+    });
+    dt_restage(smem, acc, v, [&] { dt_wtile0(A.w[1], A.plane[1], wv); });
+    dt_add_bias(v, A.bias[0], sk);
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) v[kt] += z[kt];
+    dt_layernorm(v, A.g2, A.be2, sk);
+    if (ZREG) {
+#pragma unroll
+        for (int kt = 0; kt < DT_NK; ++kt) z[kt] = v[kt];
+    } else if (r < A.R) {
+#pragma unroll
+        for (int kt = 0; kt < DT_NK; ++kt) *dt_at<f32x4>(gout + kt * B3_KT, ro) = v[kt];
+    }
+    dt_stash_put(smem, v);
+    // ---- h = relu(z2 W0^T + b0)
+    dt_product<true>(smem, nullptr, 0u, v, A.w[1], A.plane[1], wv, acc, [](int) {});
+    dt_restage(smem, acc, v, [&] { dt_wtile0(A.w[2], A.plane[2], wv); });
+    dt_add_bias(v, A.bias[1], sk);
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[kt][q] = fmaxf(v[kt][q], 0.f);
+    dt_stash_put(smem, v);
+    // ---- out = LN3(h W2^T + b2 + z2) + post
+    dt_product<true>(smem, nullptr, 0u, v, A.w[2], A.plane[2], wv, acc, [&](int kt) {
+        if (!ZREG && kt == DT_NK - 1) {   // z2 back from `out`
+#pragma unroll
+            for (int k2 = 0; k2 < DT_NK; ++k2) z[k2] = *dt_at<const f32x4>(gout + k2 * B3_KT, ro);
+        }
+    });
+    f32x4 pv[DT_NK];
+    dt_restage(smem, acc, v, [&] {
+        if (A.post) {
+#pragma unroll
+            for (int kt = 0; kt < DT_NK; ++kt) pv[kt] = *dt_at<const f32x4>(gpost + kt * B3_KT, ro);
+        }
+    });
+    dt_add_bias(v, A.bias[2], sk);
+#pragma unroll
+    for (int kt = 0; kt < DT_NK; ++kt) v[kt] += z[kt];
+    dt_layernorm(v, A.g3, A.be3, sk);
+    if (A.post) {
+#pragma unroll
+        for (int kt = 0; kt < DT_NK; ++kt) v[kt] += pv[kt];
+    }
+    if (r < A.R) {
+#pragma unroll
+        for (int kt = 0; kt < DT_NK; ++kt) *dt_at<f32x4>(gout + kt * B3_KT, ro) = v[kt];
+    }
+}
+
 
 // InvResMLP's point-wise pair (network/encoder/pointnext.py:118-138: pw_conv = Conv1d(C, 4C) -> LayerNorm -> ReLU -> Conv1d(4C, C)
 // -> LayerNorm, then + residual and ReLU) as ONE kernel for C = 32 (the first level: 262 144 rows per 64-frame batch, where the
@@ -731,6 +1018,31 @@ extern "C" int dpm_linear_layernorm_bf16x3(const float *x, int ldx, const void *
     else if (Cout == 32) DPM_GLN3(64, 32, 2, 2);
     else return DPM_EUNSUPPORTED;
 #undef DPM_GLN3
+    return dpm_launch_status();
+}
+
+// A decoder block's tail in one kernel (decoder_tail_b3_kernel): out = LN3(relu(LN2(a Wo^T + bo + pre) W0^T + b0) W2^T + b2 + z2)
+// [+ post], z2 the LN2 result.  a, pre, post (may be NULL), out packed (R, C) fp32, out distinct from a (it may be pre's storage:
+// a workgroup has read its rows of pre before it writes them); the three weights (C, C) packed as the planes of
+// dpm_split_bf16x3; biases may be NULL.  C = 256 only.  DPM_EUNSUPPORTED for other widths or unaligned operands: the caller runs
+// dpm_linear_layernorm_bf16x3, dpm_linear_bf16x3 (ReLU), dpm_linear_layernorm_bf16x3 -- the same rows bit for bit.
+#ifndef DPM_TAIL_ZREG
+#define DPM_TAIL_ZREG 0   // 1: z2 held in registers across mlp.0 and mlp.2 (spills at four waves per SIMD: measurement builds only)
+#endif
+extern "C" int dpm_decoder_tail_bf16x3(const float *a, const float *pre, const float *post, float *out, int R, int C,
+                                       const void *wo_planes, long long plane_o, const float *bo, const float *g2, const float *be2,
+                                       const void *w0_planes, long long plane_0, const float *b0, const void *w2_planes,
+                                       long long plane_2, const float *b2, const float *g3, const float *be3, dpm_stream_t stream) {
+    DPM_CHECK_ARG(a && pre && out && wo_planes && w0_planes && w2_planes && g2 && be2 && g3 && be3 && R >= 1 && C >= 1 && a != out);
+    const long long cc = (long long)C * C;
+    DPM_CHECK_ARG(plane_o >= cc && plane_0 >= cc && plane_2 >= cc);
+    auto al = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
+    if (C != DT_C || plane_o % 8 != 0 || plane_0 % 8 != 0 || plane_2 % 8 != 0 || !al(a) || !al(pre) || !al(post) || !al(out) ||
+        !al(wo_planes) || !al(w0_planes) || !al(w2_planes) || !al(bo) || !al(b0) || !al(b2) || !al(g2) || !al(be2) || !al(g3) || !al(be3))
+        return DPM_EUNSUPPORTED;
+    const TailArgs A{a, pre, post, out, {(const uint16_t *)wo_planes, (const uint16_t *)w0_planes, (const uint16_t *)w2_planes},
+                     {plane_o, plane_0, plane_2}, {bo, b0, b2}, g2, be2, g3, be3, R};
+    hipLaunchKernelGGL(decoder_tail_b3_kernel<DPM_TAIL_ZREG != 0>, dim3(dpm_cdiv(R, DT_BM)), dim3(DT_T), 0, (hipStream_t)stream, A);
     return dpm_launch_status();
 }
 

@@ -108,6 +108,19 @@ class Decoder(ParamTree):
         return ops.linear_layernorm(x, self.p(lin + ".weight"), self.p(lin + ".bias"), self.p(ln + ".weight"),
                                     self.p(ln + ".bias"), pre=residual, post=post)
 
+    def _block_tail(self, pre: str, a, z1, post=None):
+        """The tail of block `pre` (descriptor_attention.py:41-48) from the cross attention's output `a` and its query rows z1:
+        z2 = LN2(a Wo^T + bo + z1), then LN3(mlp(z2) + z2) (+ post, the next block's position embedding) -- one kernel where
+        ops.decoder_tail applies, otherwise its three launches (the same rows bit for bit)"""
+        ca, n2, m0, m2, n3 = pre + ".cross_attn.out_proj", pre + ".norm2", pre + ".mlp.0", pre + ".mlp.2", pre + ".norm3"
+        out = ops.decoder_tail(a, z1, self.p(ca + ".weight"), self.p(ca + ".bias"), self.p(n2 + ".weight"), self.p(n2 + ".bias"),
+                               self.p(m0 + ".weight"), self.p(m0 + ".bias"), self.p(m2 + ".weight"), self.p(m2 + ".bias"),
+                               self.p(n3 + ".weight"), self.p(n3 + ".bias"), post)
+        if out is not None:
+            return out
+        z2 = self._lin_ln(ca, n2, a, z1)
+        return self._lin_ln(m2, n3, self._lin(m0, z2, ops.ACT_RELU), z2, post)
+
     def _stage(self, desc: torch.Tensor, dev) -> Tuple[torch.Tensor, torch.Tensor, int, int]:
         """(B,131,M) any device -> token-major rows (B*M,131) on the GPU.  The rows are 132 floats apart: the 128 feature
         columns of every token start 16-byte aligned, which the projection GEMM's vector loads need (with rows of 131
@@ -131,13 +144,16 @@ class Decoder(ParamTree):
             return self._lin_ln(pre + ".out_proj", norm, a, xp, post)
         return ops.linear(a, self.p(pre + ".out_proj.weight"), self.p(pre + ".out_proj.bias"), residual=xp)
 
-    def _cross_attn(self, pre: str, xq, xkv, B, M, N, norm: str = None, mask=None):
-        """mask (B,N) uint8: key_padding_mask of the key / value side"""
+    def _cross_attn(self, pre: str, xq, xkv, B, M, N, norm: str = None, mask=None, tail=None):
+        """mask (B,N) uint8: key_padding_mask of the key / value side; tail = (block prefix, post): the result goes through the
+        rest of the block as well (`_block_tail`)"""
         E = self.model_channel
         w, b = self.p(pre + ".in_proj_weight"), self.p(pre + ".in_proj_bias")
         q = ops.linear(xq, w[:E], b[:E])
         kv = ops.linear(xkv, w[E:], b[E:])
         a = ops.attention(q, kv[:, :E], kv[:, E:], B, M, N, HEADS, key_mask=mask)
+        if tail is not None:
+            return self._block_tail(tail[0], a, xq, tail[1])
         if norm is not None:
             return self._lin_ln(pre + ".out_proj", norm, a, xq)
         return ops.linear(a, self.p(pre + ".out_proj.weight"), self.p(pre + ".out_proj.bias"), residual=xq)
@@ -182,13 +198,9 @@ class Decoder(ParamTree):
             x1 = self._self_attn(pre + ".self_attn", xp, B, M, norm=pre + ".norm1", post=ps, mask=ms)
             y1 = self._self_attn(pre + ".self_attn", yp, B, N, norm=pre + ".norm1", post=pd, mask=md)
             # cross attention, both directions read the pre-update tensors      (descriptor_attention.py:41-44)
-            x2 = self._cross_attn(pre + ".cross_attn", x1, y1, B, M, N, norm=pre + ".norm2", mask=md)
-            y2 = self._cross_attn(pre + ".cross_attn", y1, x1, B, N, M, norm=pre + ".norm2", mask=ms)
-            # MLP: LN3(mlp(x) + x); the next layer starts with + pos            (descriptor_attention.py:47-48)
-            xp = self._lin_ln(pre + ".mlp.2", pre + ".norm3", self._lin(pre + ".mlp.0", x2, ops.ACT_RELU), x2,
-                              None if last else ps)
-            yp = self._lin_ln(pre + ".mlp.2", pre + ".norm3", self._lin(pre + ".mlp.0", y2, ops.ACT_RELU), y2,
-                              None if last else pd)
+            # ... LN2, then the MLP: LN3(mlp(x) + x); the next layer starts with + pos   (descriptor_attention.py:47-48)
+            xp = self._cross_attn(pre + ".cross_attn", x1, y1, B, M, N, mask=md, tail=(pre, None if last else ps))
+            yp = self._cross_attn(pre + ".cross_attn", y1, x1, B, N, M, mask=ms, tail=(pre, None if last else pd))
         return xp, xyz_s, yp, xyz_d, B, M, N
 
     def _attention_layers_stacked(self, ts, td, B, M, N, ms=None, md=None):
@@ -217,9 +229,7 @@ class Decoder(ParamTree):
             # both directions read the pre-update tensors (descriptor_attention.py:41-44)
             ops.attention(qkv[:R1, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, M, N, HEADS, out=a[:R1], key_mask=md)
             ops.attention(qkv[R1:, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, N, M, HEADS, out=a[R1:], key_mask=ms)
-            z2 = self._lin_ln(ca + ".out_proj", pre + ".norm2", a, z1)
-            zp = self._lin_ln(pre + ".mlp.2", pre + ".norm3", self._lin(pre + ".mlp.0", z2, ops.ACT_RELU), z2,
-                              None if last else pos)
+            zp = self._block_tail(pre, a, z1, None if last else pos)
         return zp[:R1], zp[R1:]
 
     def _attention_layers_joint(self, ts, td, B, M, frames=None, mask=None):
@@ -283,9 +293,7 @@ class Decoder(ParamTree):
                 if a is None:
                     qkv = ops.linear(z1, self.p(ca + ".in_proj_weight"), self.p(ca + ".in_proj_bias"))  # q | k | v of every token
                     a = ops.attention(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], 2 * B, M, M, HEADS, kv_shift=B, key_mask=mask)
-            z2 = self._lin_ln(ca + ".out_proj", pre + ".norm2", a, z1)
-            zp = self._lin_ln(pre + ".mlp.2", pre + ".norm3", self._lin(pre + ".mlp.0", z2, ops.ACT_RELU), z2,
-                              None if last else pos)
+            zp = self._block_tail(pre, a, z1, None if last else pos)
         return zp[:R], zp[R:]
 
     # -- public API ----------------------------------------------------------------------------

@@ -47,10 +47,14 @@ FUSED_MATCH = True     # similarity -> dual softmax -> top-k as one operator (cs
 # csrc/decoder_ops.hip attention_kernel<PRE>): split once by the projection's epilogue instead of by every query block that reads
 # a key tile.  Bit-identical to the fp32 hand-over (False).
 KV_PLANES = True
+# the tail of every decoder block (cross attention's out-projection + norm2, mlp.0 + ReLU, mlp.2 + norm3) as ONE kernel (csrc/gemm_b3.hip,
+# decoder_tail_b3_kernel): the (rows, 256) intermediates z2 and h never leave the workgroup.  Bit-identical to the three launches
+# (False); applies where ops.linear_layernorm takes its fused bf16x3 kernel.  profiles/decoder_tail_bench.md has the numbers.
+DECODER_TAIL_FUSED = True
 DEDUP_FRAMES = True    # False: per-frame decoder work once per pair side instead of once per frame (new Decoder objects)
 
 _ENV = {"DPM_FOLD_MIN_RADIUS": ("FOLD_MIN_RADIUS", float), "DPM_KV_PLANES": ("KV_PLANES", lambda v: v != "0"), "DPM_CENTRED_GATHER": ("CENTRED_GATHER", lambda v: v != "0"), "DPM_FPS_ALGO": ("FPS_ALGO", int), "DPM_NO_FUSED_LN": ("FUSED_LN", lambda v: v != "1"),
-        "DPM_DEDUP_FRAMES": ("DEDUP_FRAMES", lambda v: v != "0"), "DPM_GEMM_BF16X3": ("GEMM_BF16X3", lambda v: v == "1"), "DPM_BF16X3_MAX_K": ("BF16X3_MAX_K", int), "DPM_BF16X3_LN_MIN_K": ("BF16X3_LN_MIN_K", int), "DPM_FUSED_LN_SMALL_ROWS": ("FUSED_LN_SMALL_ROWS", int), "DPM_GEMM_LN_BF16X3": ("GEMM_LN_BF16X3", lambda v: v == "1"),
+        "DPM_DEDUP_FRAMES": ("DEDUP_FRAMES", lambda v: v != "0"), "DPM_DECODER_TAIL": ("DECODER_TAIL_FUSED", lambda v: v != "0"), "DPM_GEMM_BF16X3": ("GEMM_BF16X3", lambda v: v == "1"), "DPM_BF16X3_MAX_K": ("BF16X3_MAX_K", int), "DPM_BF16X3_LN_MIN_K": ("BF16X3_LN_MIN_K", int), "DPM_FUSED_LN_SMALL_ROWS": ("FUSED_LN_SMALL_ROWS", int), "DPM_GEMM_LN_BF16X3": ("GEMM_LN_BF16X3", lambda v: v == "1"),
         "DPM_FUSED_MATCH": ("FUSED_MATCH", lambda v: v != "0"), "DPM_FUSED_PWCONV": ("FUSED_PWCONV", lambda v: v != "0"), "DPM_FOLD_GATHER": ("FOLD_GATHER", lambda v: v != "0")}
 
 

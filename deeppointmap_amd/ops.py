@@ -666,6 +666,45 @@ def pwconv_pair(x: torch.Tensor, W1, b1, g1, be1, W2, b2, g2, be2, post: Optiona
     return out
 
 
+def decoder_tail(a: torch.Tensor, z1: torch.Tensor, Wo, bo, g2, be2, W0, b0, W2, b2, g3, be3,
+                 post: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """LN3(relu(z2 W0^T + b0) W2^T + b2 + z2) [+ post] with z2 = LN2(a Wo^T + bo + z1): the tail of a decoder block in one kernel
+    (csrc/gemm_b3.hip, decoder_tail_b3_kernel; C = 256).  None when the layers / layouts are not covered or the knobs route the
+    three layers elsewhere: the caller runs linear_layernorm, linear (ReLU), linear_layernorm -- the same rows bit for bit.  The
+    conditions are linear_layernorm's for its fused bf16x3 kernel (the row window included), so the tail replaces exactly the
+    launches that kernel would have made."""
+    C = a.shape[-1]
+    if not (knobs.DECODER_TAIL_FUSED and knobs.GEMM_BF16X3 and knobs.GEMM_LN_BF16X3 and knobs.FUSED_LN and C == 256
+            and knobs.BF16X3_LN_MIN_K <= C <= knobs.BF16X3_MAX_K and a.is_cuda and a.dtype == torch.float32 and a.dim() == 2
+            and a.is_contiguous()):
+        return None
+    R = a.shape[0]
+    if not (R >= FUSED_LN_MIN_ROWS or 1 <= R <= knobs.FUSED_LN_SMALL_ROWS):
+        return None
+    for t_ in (z1, post):
+        if t_ is not None and not (t_.dtype == torch.float32 and t_.is_cuda and t_.is_contiguous() and tuple(t_.shape) == (R, C)):
+            return None
+    planes = []
+    for W, b in ((Wo, bo), (W0, b0), (W2, b2)):
+        if tuple(W.shape[:2]) != (C, C) or W.numel() != C * C or (b is not None and b.data_ptr() % 16):
+            return None
+        wp = _weight_planes(W)
+        if wp is None:
+            return None
+        planes.append(wp)
+    for n, t_ in (("gamma2", g2), ("beta2", be2), ("gamma3", g3), ("beta3", be3)):
+        _chk(t_, torch.float32, n)
+    out = torch.empty(R, C, device=a.device, dtype=torch.float32)
+    (po, oo, no), (p0, o0, n0), (p2, o2, n2) = planes
+    st = _lib.load().dpm_decoder_tail_bf16x3(_ptr(a), _ptr(z1), _ptr(post), _ptr(out), R, C, po.data_ptr() + 2 * oo, no, _ptr(bo),
+                                             _ptr(g2), _ptr(be2), p0.data_ptr() + 2 * o0, n0, _ptr(b0), p2.data_ptr() + 2 * o2, n2,
+                                             _ptr(b2), _ptr(g3), _ptr(be3), _stream(a))
+    if st == -2:
+        return None
+    _lib.check(st, "dpm_decoder_tail_bf16x3")
+    return out
+
+
 def three_interp_cat(xyz1, xyz2, lengths2, fea1, fea2) -> torch.Tensor:
     """fine xyz1 (B,N,3)/fea1 (B,N,D1), coarse xyz2 (B,S,3)/fea2 (B,S,D2) -> (B,N,D1+D2)."""
     for n, t in (("xyz1", xyz1), ("xyz2", xyz2), ("fea1", fea1), ("fea2", fea2)):

@@ -375,6 +375,18 @@ int dpm_linear_layernorm_bf16x3(const float *x, int ldx, const void *w_planes, i
                                 const float *bias, const float *pre, const float *gamma, const float *beta, const float *post,
                                 float *out, int ldo, int R, int Cin, int Cout, int act, dpm_stream_t stream);
 
+/* The tail of a decoder block (descriptor_attention.py:41-48: cross attention's out-projection + residual + norm2, then the MLP +
+ * residual + norm3) as ONE kernel for C = 256: out = LN3(relu(z2 W0^T + b0) W2^T + b2 + z2) [+ post] with
+ * z2 = LN2(a Wo^T + bo + pre).  a, pre, post (may be NULL), out packed (R, C) fp32; out must not be a (it may be pre's storage);
+ * the weights (C, C) packed as bf16x3 planes of dpm_split_bf16x3 (plane p of element i at planes[p * plane_stride + i]); the
+ * biases may be NULL.  Rows identical, bit for bit, to dpm_linear_layernorm_bf16x3 (pre), dpm_linear_bf16x3 (ReLU),
+ * dpm_linear_layernorm_bf16x3 (pre = z2, post).  DPM_EUNSUPPORTED for C != 256 or operands that are not 16-byte aligned. */
+int dpm_decoder_tail_bf16x3(const float *a, const float *pre, const float *post, float *out, int R, int C, const void *wo_planes,
+                            long long plane_stride_o, const float *bo, const float *gamma2, const float *beta2,
+                            const void *w0_planes, long long plane_stride_0, const float *b0, const void *w2_planes,
+                            long long plane_stride_2, const float *b2, const float *gamma3, const float *beta3,
+                            dpm_stream_t stream);
+
 /* InvResMLP's point-wise pair (network/encoder/pointnext.py:118-138: pw_conv = Conv1d(C, 4C, 1) -> LayerNorm1d -> ReLU ->
  * Conv1d(4C, C, 1) -> LayerNorm1d, then the residual and ReLU) as ONE kernel for C = 32, H = 4C = 128 (the first level, whose
  * 4C-wide intermediate is otherwise written to and read back from HBM): out = relu(LN2(relu(LN1(x W1^T + b1)) W2^T + b2) + post).
