@@ -73,6 +73,14 @@ __device__ __forceinline__ void gn_plane_row(double (&s)[GN_NSUM], const double 
     gn_add_row(s, J, r, gn_weight(kappa, r * r));
 }
 
+// a row on a scalar field: the residual e is the field's value at the moved point p and J = (p x g, g) with g its gradient
+// there, in gn_plane_row's component order; weighted by that residual.  g is taken as it is: no normalisation.
+__device__ __forceinline__ void gn_field_row(double (&s)[GN_NSUM], const double (&p)[3], const double (&g)[3], double e,
+                                             double kappa) {
+    const double J[6] = {p[1] * g[2] - p[2] * g[1], p[2] * g[0] - p[0] * g[2], p[0] * g[1] - p[1] * g[0], g[0], g[1], g[2]};
+    gn_add_row(s, J, e, gn_weight(kappa, e * e));
+}
+
 // the sums of a block of 256 threads -> partial[blk * GN_NSUM_PAD + k]; lanes 1..3 of a quad hold zeros; all threads call it
 __device__ __forceinline__ void gn_block_reduce(const double (&s)[GN_NSUM], double *partial, int blk) {
     __shared__ double sred[4][GN_NSUM];

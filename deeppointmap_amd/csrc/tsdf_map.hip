@@ -60,6 +60,7 @@
 //              the triangles of zero area it makes are kept.
 #include "gn_solve.h"
 #include "voxel_hash.h"
+#include "workspace.h"
 
 namespace {
 
@@ -452,6 +453,166 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_mesh_kernel(Tsdf M, unsigned min_
     }
 }
 
+// ------------------------------------------------------------------------------------------- the field at a point, registration
+// The trilinear interpolant of D between the 8 voxel centres round q (map frame) and its exact gradient inside that cell, in
+// fp32, every operation rounded once, no fmaf: include/dpm_hip.h (dpm_tsdf_sample) is the rule and tests/tsdf_register_restated.py
+// equals it bit for bit.  false -- the point HAS NO VALUE -- when the cell leaves the 21 bits (a NaN fails the comparison) or one
+// of the 8 corners is not qualified: a missing corner is never read as 0.  Lookups only.
+__device__ __forceinline__ bool field_at(const Tsdf &M, const float q[3], unsigned min_count, float &d, float grad[3], float &n2) {
+    float f[3], fl[3];
+    bool valid = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float g = __fdiv_rn(q[a], M.v) - 0.5f;
+        fl[a] = floorf(g);
+        valid = valid && fl[a] >= -1048576.f && fl[a] < 1048575.f;   // fl and fl + 1 fit the 21 bits
+        f[a] = g - fl[a];
+    }
+    if (!valid) return false;
+    const int i0[3] = {(int)fl[0] + 1048576, (int)fl[1] + 1048576, (int)fl[2] + 1048576};
+    float D[2][2][2];
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+        if (!voxel_value(M, i0[0] + (m & 1), i0[1] + ((m >> 1) & 1), i0[2] + (m >> 2), min_count, D[m & 1][(m >> 1) & 1][m >> 2])) return false;
+    float e[2][2], c[2][2], mm[2], b[2], t[2];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dz = 0; dz < 2; ++dz) {
+            e[dy][dz] = D[1][dy][dz] - D[0][dy][dz];
+            c[dy][dz] = D[0][dy][dz] + f[0] * e[dy][dz];
+        }
+#pragma unroll
+    for (int dz = 0; dz < 2; ++dz) {
+        mm[dz] = c[1][dz] - c[0][dz];
+        b[dz] = c[0][dz] + f[1] * mm[dz];
+        t[dz] = e[0][dz] + f[1] * (e[1][dz] - e[0][dz]);
+    }
+    const float hz = b[1] - b[0];
+    d = b[0] + f[2] * hz;
+    const float hy = mm[0] + f[2] * (mm[1] - mm[0]);
+    const float hx = t[0] + f[2] * (t[1] - t[0]);
+    grad[0] = __fdiv_rn(hx, M.v), grad[1] = __fdiv_rn(hy, M.v), grad[2] = __fdiv_rn(hz, M.v);
+    n2 = (grad[0] * grad[0] + grad[1] * grad[1]) + grad[2] * grad[2];
+    return true;
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_sample_kernel(Tsdf M, const float *xyz, const int32_t *count, int cap,
+                                                             const double *pose, unsigned min_count, float *d, float *grad,
+                                                             int32_t *flag) {
+    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (i >= cap) return;
+    float dv = 0.f, g[3] = {0.f, 0.f, 0.f}, n2;
+    int fl = -1;
+    if (i < min(max(count[0], 0), cap)) {
+        const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
+        float q[3];
+        gn_xform(P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], q);
+        fl = field_at(M, q, min_count, dv, g, n2) ? 1 : 0;
+        if (!fl) dv = 0.f, g[0] = g[1] = g[2] = 0.f;
+    }
+    d[i] = dv, flag[i] = fl;
+    grad[3 * (size_t)i] = g[0], grad[3 * (size_t)i + 1] = g[1], grad[3 * (size_t)i + 2] = g[2];
+}
+
+// Scan-to-field registration: the launch shape of csrc/local_map.hip's register_impl with the field in place of the search.
+struct TsRegHdr {   // start of the workspace (256 bytes), then one partial of GN_NSUM_PAD doubles per block
+    int done, n1;
+};
+
+struct TsRegArgs {
+    Tsdf M;
+    const float *xyz;
+    const int32_t *count;
+    int cap;
+    unsigned min_count;
+    float grad_min2;
+    TsRegHdr *hdr;
+    double *partial;
+    double *pose;
+    float *fitness, *rmse;
+    int32_t *iterations, *status;
+    int32_t *dbg_flag;      // (cap,) or NULL: 1 the row was given, 0 it was not, -1 past the count
+    double *dbg_system;     // (GN_NSUM,) or NULL
+};
+
+__global__ void ts_reg_init_kernel(TsRegArgs A, const double *init) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    gn_init_problem(0, init, A.pose, A.fitness, A.rmse, A.iterations, A.status);
+    A.hdr->done = 0, A.hdr->n1 = min(max(A.count[0], 0), A.cap);
+    gn_zero_system(0, A.dbg_system);
+}
+
+__global__ void ts_reg_stage_kernel(TsRegArgs A) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    A.hdr->done = 0;
+    *A.status = DPM_ICP_MAX_ITER;
+}
+
+// One lane per row, 256 rows a block: 8 find_slot probes and the sum / count loads of the corners they find, then the row into
+// the lane's own 29 fp64 sums.  Every lane may hold a row, so the butterfly runs all six offsets (gn_block_reduce stops at 4 for
+// kernels whose rows sit in lane 0 of a quad), then the four waves in the fixed tree.
+__global__ __launch_bounds__(TS_BLOCK) void ts_reg_accumulate_kernel(TsRegArgs A, float max_dist, double kappa) {
+    if (A.hdr->done) return;
+    const int blk = blockIdx.x, i = blk * TS_BLOCK + threadIdx.x, n1 = A.hdr->n1;
+    double s[GN_NSUM];
+#pragma unroll
+    for (int k = 0; k < GN_NSUM; ++k) s[k] = 0.0;
+    if (i < n1) {
+        const GnPose32 P = gn_load_pose(A.pose, A.M.ox, A.M.oy, A.M.oz);
+        float q[3], d, g[3], n2;
+        gn_xform(P, A.xyz[3 * (size_t)i], A.xyz[3 * (size_t)i + 1], A.xyz[3 * (size_t)i + 2], q);
+        // a NaN fails every comparison; n2 < FLT_MAX: finite
+        const bool row = field_at(A.M, q, A.min_count, d, g, n2) && fabsf(d) <= max_dist && n2 >= A.grad_min2 && n2 <= 3.402823466e38f;
+        if (A.dbg_flag) A.dbg_flag[i] = row ? 1 : 0;
+        if (row) {
+            const double p[3] = {q[0], q[1], q[2]}, gd[3] = {g[0], g[1], g[2]};
+            s[27] += 1.0;
+            gn_field_row(s, p, gd, (double)d, kappa);
+        }
+    } else if (i < A.cap && A.dbg_flag) {
+        A.dbg_flag[i] = -1;
+    }
+    __shared__ double sred[4][GN_NSUM];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < GN_NSUM; ++k) {
+        double v = s[k];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+        if (lane == 0) sred[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < GN_NSUM)
+        A.partial[(size_t)blk * GN_NSUM_PAD + threadIdx.x] =
+            (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
+}
+
+__global__ __launch_bounds__(64) void ts_reg_solve_kernel(TsRegArgs A, double tol_rot, double tol_trans) {
+    const int lane = threadIdx.x;
+    if (A.hdr->done) return;
+    __shared__ double S[GN_NSUM_PAD];
+    gn_sum_partials(A.partial, (A.cap + TS_BLOCK - 1) / TS_BLOCK, S, A.dbg_system, 0);
+    if (lane != 0) return;
+    // the rows were formed in the map frame, so the step acts on the pose there; a step that was not taken leaves the
+    // world pose's bytes alone
+    double local[12];
+    for (int k = 0; k < 12; ++k) local[k] = A.pose[k];
+    local[3] -= A.M.ox, local[7] -= A.M.oy, local[11] -= A.M.oz;
+    const int before = A.iterations[0];
+    gn_solve_step(S, A.hdr->n1, local, A.fitness, A.rmse, A.iterations, A.status, 0, &A.hdr->done, tol_rot, tol_trans);
+    if (A.iterations[0] == before) return;
+    local[3] += A.M.ox, local[7] += A.M.oy, local[11] += A.M.oz;
+    for (int k = 0; k < 12; ++k) A.pose[k] = local[k];
+}
+
+// the registration's workspace: the header in a 256-byte slice of its own, then the accumulate blocks' partials
+void ts_reg_layout(WsCursor &c, int cap, TsRegArgs &A) {
+    static_assert(sizeof(TsRegHdr) <= 256, "the header has a 256-byte slice");
+    A.hdr = c.take256<TsRegHdr>(1);
+    A.partial = c.take<double>((size_t)dpm_cdiv(cap, TS_BLOCK) * GN_NSUM_PAD);
+}
+
 inline bool tsdf_ok(const void *map, int cap_vox) {
     return map && ((uintptr_t)map & 15) == 0 && cap_vox >= 2 && cap_vox <= (1 << 24) && (cap_vox & (cap_vox - 1)) == 0;
 }
@@ -622,5 +783,59 @@ extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min
     const MeshOut O{vertex_keys, vertex_dirs, xyz, count, max_out};
     hipLaunchKernelGGL(ts_mesh_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, O);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_sample(const void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
+                               const int32_t *count, int cap, const double *pose, int min_count, float *d, float *grad,
+                               int32_t *flag, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(count && pose && cap >= 0 && min_count >= 1);
+    if (cap == 0) return DPM_OK;   // nothing to read or write: the row pointers may be null
+    DPM_CHECK_ARG(xyz && d && grad && flag);
+    hipLaunchKernelGGL(ts_sample_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, origin), xyz, count, cap, pose, (unsigned)min_count, d, grad, flag);
+    return dpm_launch_status();
+}
+
+extern "C" size_t dpm_tsdf_register_scratch_bytes(int cap) {
+    if (cap < 1) return 0;
+    WsCursor c(nullptr);
+    TsRegArgs A{};
+    ts_reg_layout(c, cap, A);
+    return c.bytes();
+}
+
+extern "C" int dpm_tsdf_register(const void *map, int cap_vox, double voxel, const double *origin, double truncation,
+                                 int min_count, double grad_min, const float *xyz, const int32_t *count, int cap,
+                                 const double *init_pose, const double *stage_max_dist, const int32_t *stage_max_iter,
+                                 int n_stages, double kernel_scale, double tol_rot, double tol_trans, double *pose,
+                                 float *fitness, float *rmse, int32_t *iterations, int32_t *status, int32_t *debug_flag,
+                                 double *debug_system, void *workspace, dpm_stream_t stream) {
+    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(truncation > 0.0 && truncation <= 64.0 && min_count >= 1 && grad_min >= 0.0 && grad_min < 1e18);
+    DPM_CHECK_ARG(xyz && count && init_pose && stage_max_dist && stage_max_iter && workspace && cap >= 1);
+    DPM_CHECK_ARG(pose && fitness && rmse && iterations && status && pose != init_pose);
+    DPM_CHECK_ARG(n_stages >= 1 && n_stages <= 16 && tol_rot >= 0.0 && tol_trans >= 0.0 && kernel_scale >= 0.0 && kernel_scale < 1e18);
+    for (int s = 0; s < n_stages; ++s)   // beyond the clamp the field is flat
+        DPM_CHECK_ARG(stage_max_dist[s] > 0.0 && stage_max_dist[s] <= truncation && stage_max_iter[s] >= 0);
+    hipStream_t st = (hipStream_t)stream;
+    TsRegArgs A{};
+    A.M = make_tsdf(map, cap_vox, voxel, origin);
+    A.xyz = xyz, A.count = count, A.cap = cap, A.min_count = (unsigned)min_count, A.grad_min2 = (float)(grad_min * grad_min);
+    WsCursor c(workspace);
+    ts_reg_layout(c, cap, A);
+    A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
+    A.dbg_flag = debug_flag, A.dbg_system = debug_system;
+    const double kappa = kernel_scale * kernel_scale;
+    hipLaunchKernelGGL(ts_reg_init_kernel, dim3(1), dim3(64), 0, st, A, init_pose);
+    for (int s = 0; s < n_stages; ++s) {
+        if (s > 0) hipLaunchKernelGGL(ts_reg_stage_kernel, dim3(1), dim3(64), 0, st, A);
+        for (int it = 0; it < stage_max_iter[s]; ++it) {
+            hipLaunchKernelGGL(ts_reg_accumulate_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, st, A,
+                               (float)stage_max_dist[s], kappa);
+            hipLaunchKernelGGL(ts_reg_solve_kernel, dim3(1), dim3(64), 0, st, A, tol_rot, tol_trans);
+        }
+    }
     return dpm_launch_status();
 }

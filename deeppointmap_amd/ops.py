@@ -2624,6 +2624,56 @@ def tsdf_mesh(table, cap_vox, voxel, min_count=1, max_out=None):
     return _counted(call, max_out)
 
 
+def tsdf_sample(table, cap_vox, voxel, origin, xyz, count, pose, min_count=1):
+    """dpm_tsdf_sample: xyz (cap,3) fp32, count (1,) int32, pose (4,4) fp64 on the GPU -> (d (cap,) fp32, grad (cap,3) fp32 in
+    the map frame's axes, flag (cap,) int32: 1 a value, 0 none, -1 past the count).  Lookups only; one launch, no host
+    synchronisation, capturable in a graph."""
+    o = _tsdf_args(table, cap_vox, origin)
+    _tsdf_frame_args("tsdf_sample", xyz, count, pose)
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    dev, cap = table.device, xyz.shape[0]
+    with torch.cuda.device(dev):
+        d = torch.empty(cap, device=dev, dtype=torch.float32)
+        grad = torch.empty(cap, 3, device=dev, dtype=torch.float32)
+        flag = torch.empty(cap, device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().dpm_tsdf_sample(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(count),
+                                               cap, _ptr(pose), int(min_count), _ptr(d) if cap else None, _ptr(grad) if cap else None,
+                                               _ptr(flag) if cap else None, _stream(table)), "dpm_tsdf_sample")
+    return d, grad, flag
+
+
+def tsdf_register(table, cap_vox, voxel, origin, truncation, xyz, count, init, schedule, kernel_scale=0.0, tol_rot=1e-7,
+                  tol_trans=1e-6, min_count=1, grad_min=0.5, debug=False):
+    """dpm_tsdf_register: xyz (cap,3) fp32 with cap >= 1, count (1,) int32, init (4,4) fp64 on the GPU; schedule = [(max_dist,
+    max_iter), ...] with every max_dist in (0, truncation] -> pose (4,4) fp64, fitness, rmse (1,) fp32, iterations, status (1,)
+    int32[, flag (cap,) int32, system (29,) fp64 with debug].  Lookups only; no host synchronisation, capturable in a graph."""
+    o = _tsdf_args(table, cap_vox, origin)
+    _tsdf_frame_args("tsdf_register", xyz, count, init)
+    if xyz.shape[0] < 1 or tuple(init.shape) != (4, 4):
+        raise ValueError("tsdf_register: xyz (cap,3) with cap >= 1, init (4,4)")
+    if int(min_count) < 1 or not 0.0 <= float(grad_min) < 1e18:
+        raise ValueError("tsdf_register: min_count >= 1, grad_min >= 0")
+    stages = [(float(d), int(n)) for d, n in schedule]
+    if any(not 0.0 < d <= float(truncation) for d, _ in stages):
+        raise ValueError("tsdf_register: every max_dist of the schedule must lie in (0, truncation] (beyond the clamp the field is flat)")
+    dist, iters, n_stages = _schedule_arrays(stages)
+    dev, cap, lib = table.device, xyz.shape[0], _lib.load()
+    with torch.cuda.device(dev):
+        pose, fitness, rmse, iterations, status = _registration_results(1, dev)
+        pose = pose[0]
+        flag = torch.full((cap,), -1, device=dev, dtype=torch.int32) if debug else None
+        system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
+        ws = torch.empty(lib.dpm_tsdf_register_scratch_bytes(cap), device=dev, dtype=torch.uint8)
+        _lib.check(lib.dpm_tsdf_register(
+            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), float(truncation), int(min_count), float(grad_min),
+            _ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), n_stages,
+            float(kernel_scale), float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations),
+            _ptr(status), _ptr(flag), _ptr(system), _ptr(ws), _stream(table)), "dpm_tsdf_register")
+    out = (pose, fitness, rmse, iterations, status)
+    return out + (flag, system) if debug else out
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Scan Context descriptors and their exhaustive search (csrc/scan_context.hip; loop_closure.py is the caller)
 # ------------------------------------------------------------------------------------------------------------

@@ -17,6 +17,13 @@ the incidence in 1/256ths; it needs a normal per return, in the sensor frame.  A
 truncation distance": lookups only, so the key set stays, and what was seen through is forgotten once the free observations
 outweigh it.  Carving is meant to run after the integrations; a later integrate simply adds to what is there.
 
+`TsdfMap.sample` reads the field at points -- the trilinear interpolant between the 8 voxel centres round each and its exact
+gradient inside that cell, defined only where all 8 voxels are qualified -- and `TsdfMap.register` is Gauss-Newton of a scan
+against it: the residual of a point is the field's value there, its Jacobian the gradient, so nothing is searched.  Both are
+lookups only.  `TsdfTracker` is frame-to-model odometry on one map: predict, register, read back once, fuse under the registered
+pose; a failed registration writes nothing.  The plane form is the one to register against: in a band fed by one plane its
+field is exactly linear, while the ray form's is not a distance off the ray's axis.
+
 LIMITS: carving reaches only voxels that exist and claims none; no weight cap or decay; the frame's pose is the origin of every
 ray (no per-point origins for sweeps that are not deskewed); the normals of the plane form are the caller's (or dpm_point_normals
 of the frame alone, `normals=<radius>`); marching tetrahedra, not marching cubes; the voxels live on the device (nothing is
@@ -31,6 +38,7 @@ import torch
 
 from . import augment, ops
 from .odometry import _pose_tensor
+from .refine import CONVERGED, MAX_ITER, NO_MATCH, IcpResult
 
 OVERFLOW = "the TSDF map is full (max_voxels={}): samples found no free slot and the map is undefined; raise max_voxels"
 FIX_ONE = 16777216.0    # 2^24: a sum is in units of 2^-24 m
@@ -350,3 +358,117 @@ class TsdfMap:
         return weld(*[t.cpu().numpy() for t in self._extract(ops.tsdf_mesh, self.voxel_size, min_count)])
 
     write_ply = staticmethod(write_ply)
+
+    # -- the field at points, and registration against it: lookups only, no host synchronisation
+    def sample(self, pcd, pose, length=None, min_count: float = 1):
+        """the field at the frame's rows under `pose` (the arguments of `integrate`) -> (d (N,) float32 metres, grad (N,3)
+        float32 in the map frame's axes, flag (N,) int32) on the device.  d is the trilinear interpolant of D between the 8
+        voxel centres round the point and grad its exact gradient inside that cell; flag 1: the point has a value -- all 8
+        voxels hold min_count full-weight samples --, 0: it has none (d and grad are zeros; a missing corner is never read as
+        0), -1: a row at or past the length.  One launch."""
+        min_count = self._min_count(min_count)
+        xyz, count = self._frame("sample", pcd, pose, length)
+        self._ready(xyz.device, pose)
+        return ops.tsdf_sample(*self._map(), xyz, count, _pose_tensor(pose, self.device), min_count)
+
+    def register(self, pcd, init, schedule=None, kernel_scale: float = 0.0, tol_rot: float = 1e-7, tol_trans: float = 1e-6,
+                 min_count: float = 1, grad_min: float = 0.5, debug: bool = False, length=None):
+        """Gauss-Newton of the frame (the arguments of `integrate`) against the field from `init` (4,4): the residual of a
+        point is the field's value there, its Jacobian the field's gradient, so no correspondence is searched.  schedule =
+        [(max_dist, max_iter), ...] (None: ((truncation, 30),)); a row is given when the point has a value with |d| <= max_dist
+        and |grad| >= grad_min, which keeps the flat, clamped parts of the field out; a max_dist above the truncation raises.
+        -> refine.IcpResult with one problem (pose (1,4,4) float64, ...), all on the device[, (flag (N,) int32, system (29,)
+        float64) with debug].  fitness = rows / length.  An empty or unallocated map gives NO_MATCH and the pose `init`."""
+        schedule = ((self.truncation, 30),) if schedule is None else [(float(d), int(n)) for d, n in schedule]
+        if any(not 0.0 < d <= self.truncation for d, _ in schedule):
+            raise ValueError("register: every max_dist of the schedule must lie in (0, truncation] (beyond the clamp the field is flat)")
+        min_count = self._min_count(min_count)
+        xyz, count = self._frame("register", pcd, init, length)
+        start = _pose_tensor(init, xyz.device if self.device is None else self.device)
+        if self.table is None or xyz.shape[0] == 0:      # nothing to look up: the kernel's answer to an empty table
+            dev = start.device
+            pose = start.clone().reshape(1, 4, 4)
+            pose[0, 3] = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=dev)
+            res = IcpResult(pose, torch.zeros(1, device=dev), torch.zeros(1, device=dev),
+                            torch.zeros(1, dtype=torch.int32, device=dev), torch.full((1,), NO_MATCH, dtype=torch.int32, device=dev))
+            extra = (torch.full((xyz.shape[0],), -1, dtype=torch.int32, device=dev), torch.zeros(ops.ICP_NSUM, dtype=torch.float64, device=dev))
+            return (res, extra) if debug else res
+        out = ops.tsdf_register(*self._map(), self.truncation, xyz, count, start, schedule, kernel_scale, tol_rot, tol_trans,
+                                min_count, grad_min, debug=debug)
+        res = IcpResult(out[0].reshape(1, 4, 4), *out[1:5])
+        return (res, out[5:]) if debug else res
+
+
+class TsdfStep(NamedTuple):
+    """what `TsdfTracker.step` did with a frame: the registration's status, fitness, rmse and iterations on the host, and whether
+    the frame was integrated"""
+    status: int
+    fitness: float
+    rmse: float
+    iterations: int
+    integrated: bool
+
+
+class TsdfTracker:
+    """Frame-to-model odometry on one TsdfMap: every frame is registered against the fused field (`TsdfMap.register`) and then
+    fused into it under the registered pose.  The constructor takes TsdfMap's arguments and schedule, kernel_scale, min_count,
+    grad_min (those of `register`), min_fitness and register_every: the registration reads every register_every-th row of the
+    frame, the integration all of them.  `poses` is the trajectory ((4,4) float64 on the host), `steps` a TsdfStep per frame,
+    `lost` the number of frames whose registration failed.
+
+    What it is NOT: no deskew (a sweep is taken as one rigid frame), no pruning (the map only grows, to max_voxels), no loop
+    closure, no coarse level (the start must lie within the truncation band), and no normals of its own: distance="plane"
+    needs them per frame, as `TsdfMap.integrate` does."""
+
+    def __init__(self, voxel_size: float = 0.2, truncation: Optional[float] = None, step: Optional[float] = None,
+                 max_voxels: int = 1 << 22, min_range: float = 0.0, max_range: float = 100.0, origin=None, device=None,
+                 distance: str = "ray", cos_min: float = 0.0, schedule=None, kernel_scale: float = 0.0, min_count: float = 1,
+                 grad_min: float = 0.5, min_fitness: float = 0.3, register_every: int = 1):
+        self.map = TsdfMap(voxel_size, truncation, step, max_voxels, min_range, max_range, origin, device, distance, cos_min)
+        if int(register_every) < 1:
+            raise ValueError("register_every >= 1")
+        self.schedule, self.kernel_scale, self.min_count, self.grad_min = schedule, float(kernel_scale), min_count, float(grad_min)
+        self.min_fitness, self.register_every = float(min_fitness), int(register_every)
+        self.poses, self.steps, self.lost = [], [], 0
+
+    def predict(self) -> np.ndarray:
+        """the constant-velocity prediction from the last two poses, float64 on the host (one pose: that pose)"""
+        if len(self.poses) < 2:
+            return self.poses[-1].copy()
+        return self.poses[-1] @ (np.linalg.inv(self.poses[-2]) @ self.poses[-1])
+
+    def step(self, pcd, normals=None, pose=None):
+        """one frame (an augment.PointCloud, or xyz (N,3) float32 on the GPU; normals as `TsdfMap.integrate` takes them) ->
+        (pose (4,4) float64, TsdfStep).  The first frame is integrated under `pose` (default: the identity).  A later frame starts from `pose` if given, else
+        from the prediction; it is registered, pose, status and fitness are fetched in ONE host read -- the step's only
+        synchronisation when the normals come as a tensor -- and when the status is CONVERGED or MAX_ITER with fitness >=
+        min_fitness the WHOLE frame is integrated under the registered pose.  Otherwise the start is kept as the pose,
+        nothing is integrated and `lost` counts the frame: a failed registration never writes to the map."""
+        m = self.map
+        xyz, length = m._frame("step", pcd, np.eye(4), None)
+        if not self.poses:
+            P = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
+            m.integrate(xyz, P, length, normals)
+            done = TsdfStep(CONVERGED, 1.0, 0.0, 0, True)
+        else:
+            start = self.predict() if pose is None else np.array(pose, np.float64).reshape(4, 4)
+            k = self.register_every
+            rows, count = xyz, length
+            if k > 1:                                   # rows 0, k, 2k, ... below the length: ceil(length / k) of them, formed on the device
+                rows, count = xyz[::k].contiguous(), torch.div(length + (k - 1), k, rounding_mode="floor").to(torch.int32)
+            res = m.register(rows, start, self.schedule, self.kernel_scale, min_count=self.min_count, grad_min=self.grad_min,
+                             length=count)
+            augment._SYNCS[0] += 1
+            host = torch.cat([res.pose.reshape(16), res.fitness.double(), res.rmse.double(), res.iterations.double(),
+                              res.status.double()]).cpu().numpy()
+            status, fitness = int(host[19]), float(host[16])
+            ok = status in (CONVERGED, MAX_ITER) and fitness >= self.min_fitness
+            P = host[:16].reshape(4, 4).copy() if ok else start
+            if ok:
+                m.integrate(xyz, P, length, normals)
+            else:
+                self.lost += 1
+            done = TsdfStep(status, fitness, float(host[17]), int(host[18]), ok)
+        self.poses.append(P)
+        self.steps.append(done)
+        return P, done

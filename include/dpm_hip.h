@@ -1208,6 +1208,48 @@ int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, 
  * counts as positive; the triangles of zero area it makes are kept. */
 int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
                   int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream);
+/* THE FIELD AT A POINT, and registration against it.  Lookups only: the table is never written.  A row (x, y, z) of a frame
+ * under `pose` is q = fma(R2, z, fma(R1, y, R0 * x)) + t in the map frame, as above.  In fp32, every operation rounded once, no
+ * fused multiply-add, divisions correctly rounded, with v = (float)voxel; per axis a:
+ *     g = q[a] / v - 0.5f,  fl = floorf(g);  the cell is VALID iff fl >= -1048576.f && fl < 1048575.f on every axis (fl and
+ *     fl + 1 then fit the 21 bits; a NaN fails);  i0 = (int)fl + 1048576;  f = g - fl, in [0, 1] (1 only through the rounding
+ *     of a tiny negative g, which is still valid).
+ * D[dx][dy][dz] is the field of the voxel (i0x + dx, i0y + dy, i0z + dz).  The point HAS A VALUE iff the cell is valid and all 8
+ * corner voxels are qualified (count >= min_count): a missing corner is never read as 0.  Then
+ *     e[dy][dz] = D[1][dy][dz] - D[0][dy][dz];   c[dy][dz] = D[0][dy][dz] + fx * e[dy][dz];
+ *     m[dz] = c[1][dz] - c[0][dz];               b[dz] = c[0][dz] + fy * m[dz];
+ *     hz = b[1] - b[0];                          d = b[0] + fz * hz;
+ *     hy = m[0] + fz * (m[1] - m[0]);
+ *     t[dz] = e[0][dz] + fy * (e[1][dz] - e[0][dz]);   hx = t[0] + fz * (t[1] - t[0]);
+ *     grad[a] = h[a] / v;                        n2 = (gx*gx + gy*gy) + gz*gz.
+ * d is the trilinear interpolant of D between the 8 voxel centres and grad its exact gradient inside the cell, in the map
+ * frame's axes.
+ *
+ * dpm_tsdf_sample: one lane per row, one launch, capturable.  xyz (cap,3) fp32, count (1,) int32 and pose (16 doubles) on the
+ * device; n = count clamped to [0, cap].  Rows below n: flag 1 with d and grad (cap,3), or flag 0 and zeros where the point has
+ * no value; rows in [n, cap): flag -1 and zeros (their xyz is not read).  cap = 0 is a no-op. */
+int dpm_tsdf_sample(const void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const int32_t *count,
+                    int cap, const double *pose, int min_count, float *d, float *grad, int32_t *flag, dpm_stream_t stream);
+/* dpm_tsdf_register: Gauss-Newton on the sum of D(T p)^2 over the frame's first count rows, from init_pose (device), with the
+ * schedule, the robust weight, the 29 fp64 sums, the solve, the stop rule, the DPM_ICP_* statuses and the launch shape of
+ * dpm_local_map_register: an init launch, a launch per later stage, and per iteration one accumulate launch (one lane per row)
+ * and one one-wave solve launch; no host synchronisation, capturable.  Every stage_max_dist must lie in (0, truncation], the
+ * map's truncation (beyond the clamp the field is flat); grad_min >= 0.  A row is given when the point has a value and
+ *     fabsf(d) <= (float)max_dist,   n2 >= (float)(grad_min * grad_min),   n2 finite        (a NaN fails by comparison).
+ * It enters in fp64: p = (double)q, g = (double)grad, e = (double)d, J = (p x g, g) in DPM_ICP_PLANE's component order, weighted
+ * w = (k / (k + e*e))^2 with k = kernel_scale^2 (0: w = 1); the count and the squared residuals are not weighted.  The gradient
+ * is not normalised: grad_min keeps the flat, clamped parts of the field out.  The sums are fp64 partials added in a fixed
+ * order (lanes, waves, blocks): no floating-point atomics, identical bytes on every run.  The step acts on the map-frame pose;
+ * NO_MATCH (also: empty map, count 0) and SINGULAR leave the pose's bytes where they were; fitness = rows / n.  pose (16),
+ * fitness, rmse, iterations, status: one value each, on the device.  Optional: debug_flag (cap,) int32 at the last evaluated
+ * pose -- 1 the row was given, 0 it was not, -1 past the count -- and debug_system (29).
+ * workspace: dpm_tsdf_register_scratch_bytes(cap) bytes (0 for cap < 1), any alignment. */
+size_t dpm_tsdf_register_scratch_bytes(int cap);
+int dpm_tsdf_register(const void *map, int cap_vox, double voxel, const double *origin, double truncation, int min_count,
+                      double grad_min, const float *xyz, const int32_t *count, int cap, const double *init_pose,
+                      const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages, double kernel_scale,
+                      double tol_rot, double tol_trans, double *pose, float *fitness, float *rmse, int32_t *iterations,
+                      int32_t *status, int32_t *debug_flag, double *debug_system, void *workspace, dpm_stream_t stream);
 
 /* ---------------------------------------------------------------- geometric loop closure ---- */
 
