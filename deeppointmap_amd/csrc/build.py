@@ -59,6 +59,7 @@ SOURCES = {
     "lidar_sim.hip": [],
     "map_eval.hip": [],
     "deskew.hip": [],
+    "gn_one.hip": [],
     "local_map.hip": [],
     "scan_context.hip": [],
     "tsdf_map.hip": [],

@@ -1,6 +1,7 @@
-// The Gauss-Newton step of the two registrations (icp.hip: batched scan pairs; local_map.hip: a scan against the rolling map),
-// written once.  The accumulate kernels keep their searches; what follows the match is here, and its order of operations is
-// part of the contract (the tests compare bytes and fp64 floors):
+// The Gauss-Newton step of the registrations (icp.hip: batched scan pairs; local_map.hip: a scan against the rolling map;
+// tsdf_map.hip: a scan against the field), written once.  The accumulate kernels keep their searches; what follows the match is
+// here, and its order of operations is part of the contract (the tests compare bytes and fp64 floors).  The kernels that run
+// it are icp.hip's own for a batch of pairs and gn_one.hip's (the driver of gn_one.h) for the two single scans against a map:
 //   the search pose: the fp64 pose minus an origin, rounded to fp32, and q = fma(R2, z, fma(R1, y, R0 * x)) + t;
 //   the rows of a match into the 29 fp64 sums S = [H upper triangle row-major (21), g (6), matches, sum of squared residuals]:
 //     H and g weighted (Geman-McClure), the count (the caller's s[27] += 1.0) and the squared residuals not;
@@ -81,7 +82,9 @@ __device__ __forceinline__ void gn_field_row(double (&s)[GN_NSUM], const double 
     gn_add_row(s, J, e, gn_weight(kappa, e * e));
 }
 
-// the sums of a block of 256 threads -> partial[blk * GN_NSUM_PAD + k]; lanes 1..3 of a quad hold zeros; all threads call it
+// the sums of a block of 256 threads -> partial[blk * GN_NSUM_PAD + k]; all threads call it.  LOW is the butterfly's lowest
+// offset: 4 where lanes 1..3 of a quad hold zeros (the rows sit in lane 0), 1 where every lane may hold a row
+template <int LOW = 4>
 __device__ __forceinline__ void gn_block_reduce(const double (&s)[GN_NSUM], double *partial, int blk) {
     __shared__ double sred[4][GN_NSUM];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -89,7 +92,7 @@ __device__ __forceinline__ void gn_block_reduce(const double (&s)[GN_NSUM], doub
     for (int k = 0; k < GN_NSUM; ++k) {
         double v = s[k];
 #pragma unroll
-        for (int off = 32; off >= 4; off >>= 1) v += __shfl_xor(v, off, 64);
+        for (int off = 32; off >= LOW; off >>= 1) v += __shfl_xor(v, off, 64);
         if (lane == 0) sred[w][k] = v;
     }
     __syncthreads();

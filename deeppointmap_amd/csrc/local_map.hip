@@ -43,8 +43,9 @@
 //               Lane 0 adds the point-to-point rows, weighted w = (kappa / (kappa + e.e))^2 (Geman-McClure, kappa =
 //               kernel_scale^2, 0 = unweighted), to the 29 fp64 sums of csrc/gn_solve.h: H and g weighted, the match count
 //               and the squared residuals not.  One partial per block.
-//   solve:      one wave adds the partials in block order; the step is taken on the pose in the map frame (where the rows
-//               were formed) and shifted back; a step not taken leaves the pose's bytes alone.
+//   solve:      (csrc/gn_one.h, the driver shared with csrc/tsdf_map.hip) one wave adds the partials in block order; the step
+//               is taken on the pose in the map frame (where the rows were formed) and shifted back; a step not taken leaves
+//               the pose's bytes alone.
 // The search pose is csrc/gn_solve.h's; the rows, the reduction, the solve and the start values are shared with csrc/icp.hip there.
 //
 // Voxel planes (dpm_local_map_planes): a cache derived from the map, one float4 (normal, w) and one count per SLOT of the
@@ -65,10 +66,9 @@
 // e = (nx*ex + ny*ey) + nz*ez, J = (p x n, n) -- gn_plane_row, the batched ICP's too -- weighted (kappa / (kappa + e*e))^2.
 // A match whose voxel has no such plane contributes nothing and is not counted.
 #include "cell_grid.h"
-#include "gn_solve.h"
+#include "gn_one.h"
 #include "sym3_jacobi.h"
 #include "voxel_hash.h"
-#include "workspace.h"
 
 namespace {
 
@@ -331,14 +331,10 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_planes_kernel(Map M, float r2, fl
 }
 
 // ------------------------------------------------------------------------------------------------------------ registration
-struct RegHdr {   // start of the workspace (256 bytes), then one partial of GN_NSUM_PAD doubles per block
-    int done, n1;
-};
-
-struct RegArgs {
+struct RegArgs {   // the accumulate kernels' arguments; hdr and partial are csrc/gn_one.h's
     Map M;
     Frame F;
-    RegHdr *hdr;
+    GnOneHdr *hdr;
     double *partial;
     double *pose;
     float *fitness, *rmse;
@@ -347,19 +343,6 @@ struct RegArgs {
     int32_t *dbg_sub;       // (cap,) or NULL
     double *dbg_system;     // (GN_NSUM,) or NULL
 };
-
-__global__ void lm_reg_init_kernel(RegArgs A, const double *init) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    gn_init_problem(0, init, A.pose, A.fitness, A.rmse, A.iterations, A.status);
-    A.hdr->done = 0, A.hdr->n1 = min(max(A.F.count[0], 0), A.F.cap);
-    gn_zero_system(0, A.dbg_system);
-}
-
-__global__ void lm_reg_stage_kernel(RegArgs A) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    A.hdr->done = 0;
-    *A.status = DPM_ICP_MAX_ITER;
-}
 
 // the plane cache of the current half and the gate a voxel's plane passes to give a row (all unused when !PLANE)
 struct PlaneArgs {
@@ -447,33 +430,12 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_accumulate_kernel(RegArgs A, floa
             (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
 }
 
-__global__ __launch_bounds__(64) void lm_solve_kernel(RegArgs A, double tol_rot, double tol_trans) {
-    const int lane = threadIdx.x;
-    if (A.hdr->done) return;
-    __shared__ double S[GN_NSUM_PAD];
-    gn_sum_partials(A.partial, (A.F.cap + 255) / 256, S, A.dbg_system, 0);
-    if (lane != 0) return;
-    // the rows were formed in the map frame, so the step acts on the pose there; a step that was not taken leaves the
-    // world pose's bytes alone
-    double local[12];
-    for (int k = 0; k < 12; ++k) local[k] = A.pose[k];
-    local[3] -= A.M.ox, local[7] -= A.M.oy, local[11] -= A.M.oz;
-    const int before = A.iterations[0];
-    gn_solve_step(S, A.hdr->n1, local, A.fitness, A.rmse, A.iterations, A.status, 0, &A.hdr->done, tol_rot, tol_trans);
-    if (A.iterations[0] == before) return;
-    local[3] += A.M.ox, local[7] += A.M.oy, local[11] += A.M.oz;
-    for (int k = 0; k < 12; ++k) A.pose[k] = local[k];
-}
-
 inline unsigned grid_for(size_t items) {
     const size_t b = (items + LM_BLOCK - 1) / LM_BLOCK;
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-inline bool map_ok(const void *map, int cap_vox, int subdiv) {
-    return map && ((uintptr_t)map & 15) == 0 && cap_vox >= 2 && cap_vox <= (1 << 24) && (cap_vox & (cap_vox - 1)) == 0 &&
-           subdiv >= 1 && subdiv <= 3;
-}
+inline bool map_ok(const void *map, int cap_vox, int subdiv) { return table_ok(map, cap_vox) && subdiv >= 1 && subdiv <= 3; }
 
 inline Map make_map(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin) {
     Map M;
@@ -484,10 +446,7 @@ inline Map make_map(void *map, int cap_vox, int subdiv, int half, double voxel, 
 }
 
 inline bool geometry_ok(int half, double voxel, const double *origin) {
-    if (!((half == 0 || half == 1) && origin && voxel > 0.0 && voxel < 1e18 && (float)voxel > 0.f)) return false;
-    for (int a = 0; a < 3; ++a)
-        if (!(origin[a] > -1e300 && origin[a] < 1e300)) return false;
-    return true;
+    return (half == 0 || half == 1) && voxel_ok(voxel) && origin_ok(origin);
 }
 
 }  // namespace
@@ -542,7 +501,7 @@ extern "C" int dpm_local_map_insert_frames(void *map, int cap_vox, int subdiv, i
                                            const double *centre, double radius, double min_range, double max_range,
                                            dpm_stream_t stream) {
     DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
-    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     DPM_CHECK_ARG(min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
     DPM_CHECK_ARG(!centre || (radius >= 0.0 && radius < 1e18));
     if (F == 0) return DPM_OK;
@@ -558,14 +517,6 @@ extern "C" int dpm_local_map_insert_frames(void *map, int cap_vox, int subdiv, i
 }
 
 namespace {
-
-// the registration's workspace: the register header in a 256-byte slice of its own, then the accumulate blocks' partials
-// (512 + 256 bytes per 256 points of capacity: the size the callers compute)
-void reg_layout(WsCursor &c, int cap, RegArgs &A) {
-    static_assert(sizeof(RegHdr) <= 256, "the header has a 256-byte slice");
-    A.hdr = c.take256<RegHdr>(1);
-    A.partial = c.take<double>((size_t)dpm_cdiv(cap, 256) * GN_NSUM_PAD);
-}
 
 // both registrations: PA = nullptr is point-to-point
 int register_impl(const PlaneArgs *PA, const void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
@@ -584,22 +535,17 @@ int register_impl(const PlaneArgs *PA, const void *map, int cap_vox, int subdiv,
     A.M = make_map((void *)map, cap_vox, subdiv, half, voxel, origin);
     A.F = Frame{xyz, nullptr, count, cap};
     WsCursor c(workspace);
-    reg_layout(c, cap, A);
+    gn_one_layout(c, cap, A.hdr, A.partial);
     A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
     A.dbg_key = debug_key, A.dbg_sub = debug_sub, A.dbg_system = debug_system;
     const double kappa = kernel_scale * kernel_scale;
     const PlaneArgs none{nullptr, nullptr, 0, 0.f};
-    hipLaunchKernelGGL(lm_reg_init_kernel, dim3(1), dim3(64), 0, st, A, init_pose);
-    for (int s = 0; s < n_stages; ++s) {
+    const GnOne G{A.hdr, A.partial, pose, fitness, rmse, iterations, status, debug_system, count, cap, A.M.ox, A.M.oy, A.M.oz};
+    return gn_one_run(G, init_pose, stage_max_iter, n_stages, tol_rot, tol_trans, st, [&](int s) {
         const float r2 = (float)(stage_max_dist[s] * stage_max_dist[s]);
-        if (s > 0) hipLaunchKernelGGL(lm_reg_stage_kernel, dim3(1), dim3(64), 0, st, A);
-        for (int it = 0; it < stage_max_iter[s]; ++it) {
-            if (PA) hipLaunchKernelGGL(lm_accumulate_kernel<true>, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa, *PA);
-            else hipLaunchKernelGGL(lm_accumulate_kernel<false>, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa, none);
-            hipLaunchKernelGGL(lm_solve_kernel, dim3(1), dim3(64), 0, st, A, tol_rot, tol_trans);
-        }
-    }
-    return dpm_launch_status();
+        if (PA) hipLaunchKernelGGL(lm_accumulate_kernel<true>, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa, *PA);
+        else hipLaunchKernelGGL(lm_accumulate_kernel<false>, dim3(dpm_cdiv(cap, 256)), dim3(LM_BLOCK), 0, st, A, r2, kappa, none);
+    });
 }
 
 }  // namespace

@@ -58,9 +58,8 @@
 //              or one non-negative corner gives a triangle, two and two a quadrilateral cut into two triangles; they are wound
 //              so that the normal (b - a) x (c - a) points to the positive side.  A corner with D == 0 counts as positive, and
 //              the triangles of zero area it makes are kept.
-#include "gn_solve.h"
+#include "gn_one.h"
 #include "voxel_hash.h"
-#include "workspace.h"
 
 namespace {
 
@@ -515,19 +514,15 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_sample_kernel(Tsdf M, const float
     grad[3 * (size_t)i] = g[0], grad[3 * (size_t)i + 1] = g[1], grad[3 * (size_t)i + 2] = g[2];
 }
 
-// Scan-to-field registration: the launch shape of csrc/local_map.hip's register_impl with the field in place of the search.
-struct TsRegHdr {   // start of the workspace (256 bytes), then one partial of GN_NSUM_PAD doubles per block
-    int done, n1;
-};
-
-struct TsRegArgs {
+// Scan-to-field registration: csrc/gn_one.h's driver, as csrc/local_map.hip's register_impl, with the field in place of the search.
+struct TsRegArgs {   // the accumulate kernel's arguments; hdr and partial are csrc/gn_one.h's
     Tsdf M;
     const float *xyz;
     const int32_t *count;
     int cap;
     unsigned min_count;
     float grad_min2;
-    TsRegHdr *hdr;
+    GnOneHdr *hdr;
     double *partial;
     double *pose;
     float *fitness, *rmse;
@@ -536,22 +531,9 @@ struct TsRegArgs {
     double *dbg_system;     // (GN_NSUM,) or NULL
 };
 
-__global__ void ts_reg_init_kernel(TsRegArgs A, const double *init) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    gn_init_problem(0, init, A.pose, A.fitness, A.rmse, A.iterations, A.status);
-    A.hdr->done = 0, A.hdr->n1 = min(max(A.count[0], 0), A.cap);
-    gn_zero_system(0, A.dbg_system);
-}
-
-__global__ void ts_reg_stage_kernel(TsRegArgs A) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    A.hdr->done = 0;
-    *A.status = DPM_ICP_MAX_ITER;
-}
-
 // One lane per row, 256 rows a block: 8 find_slot probes and the sum / count loads of the corners they find, then the row into
-// the lane's own 29 fp64 sums.  Every lane may hold a row, so the butterfly runs all six offsets (gn_block_reduce stops at 4 for
-// kernels whose rows sit in lane 0 of a quad), then the four waves in the fixed tree.
+// the lane's own 29 fp64 sums.  Every lane may hold a row, so the butterfly runs all six offsets (gn_block_reduce<1>; the default
+// stops at 4 for kernels whose rows sit in lane 0 of a quad), then the four waves in the fixed tree.
 __global__ __launch_bounds__(TS_BLOCK) void ts_reg_accumulate_kernel(TsRegArgs A, float max_dist, double kappa) {
     if (A.hdr->done) return;
     const int blk = blockIdx.x, i = blk * TS_BLOCK + threadIdx.x, n1 = A.hdr->n1;
@@ -573,57 +555,7 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_reg_accumulate_kernel(TsRegArgs A
     } else if (i < A.cap && A.dbg_flag) {
         A.dbg_flag[i] = -1;
     }
-    __shared__ double sred[4][GN_NSUM];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < GN_NSUM; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) sred[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < GN_NSUM)
-        A.partial[(size_t)blk * GN_NSUM_PAD + threadIdx.x] =
-            (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
-}
-
-__global__ __launch_bounds__(64) void ts_reg_solve_kernel(TsRegArgs A, double tol_rot, double tol_trans) {
-    const int lane = threadIdx.x;
-    if (A.hdr->done) return;
-    __shared__ double S[GN_NSUM_PAD];
-    gn_sum_partials(A.partial, (A.cap + TS_BLOCK - 1) / TS_BLOCK, S, A.dbg_system, 0);
-    if (lane != 0) return;
-    // the rows were formed in the map frame, so the step acts on the pose there; a step that was not taken leaves the
-    // world pose's bytes alone
-    double local[12];
-    for (int k = 0; k < 12; ++k) local[k] = A.pose[k];
-    local[3] -= A.M.ox, local[7] -= A.M.oy, local[11] -= A.M.oz;
-    const int before = A.iterations[0];
-    gn_solve_step(S, A.hdr->n1, local, A.fitness, A.rmse, A.iterations, A.status, 0, &A.hdr->done, tol_rot, tol_trans);
-    if (A.iterations[0] == before) return;
-    local[3] += A.M.ox, local[7] += A.M.oy, local[11] += A.M.oz;
-    for (int k = 0; k < 12; ++k) A.pose[k] = local[k];
-}
-
-// the registration's workspace: the header in a 256-byte slice of its own, then the accumulate blocks' partials
-void ts_reg_layout(WsCursor &c, int cap, TsRegArgs &A) {
-    static_assert(sizeof(TsRegHdr) <= 256, "the header has a 256-byte slice");
-    A.hdr = c.take256<TsRegHdr>(1);
-    A.partial = c.take<double>((size_t)dpm_cdiv(cap, TS_BLOCK) * GN_NSUM_PAD);
-}
-
-inline bool tsdf_ok(const void *map, int cap_vox) {
-    return map && ((uintptr_t)map & 15) == 0 && cap_vox >= 2 && cap_vox <= (1 << 24) && (cap_vox & (cap_vox - 1)) == 0;
-}
-
-inline bool voxel_ok(double voxel) { return voxel > 0.0 && voxel < 1e18 && (float)voxel > 0.f; }
-
-inline bool origin_ok(const double *origin) {
-    if (!origin) return false;
-    for (int a = 0; a < 3; ++a)
-        if (!(origin[a] > -1e300 && origin[a] < 1e300)) return false;
-    return true;
+    gn_block_reduce<1>(s, A.partial, blk);
 }
 
 inline Tsdf make_tsdf(const void *map, int cap_vox, double voxel, const double *origin) {
@@ -647,12 +579,12 @@ inline bool make_rays(double min_range, double max_range, double truncation, dou
 }  // namespace
 
 extern "C" size_t dpm_tsdf_bytes(int cap_vox) {
-    if (!tsdf_ok((const void *)16, cap_vox)) return 0;
+    if (!table_ok((const void *)16, cap_vox)) return 0;
     return 256 + (size_t)cap_vox * 20;
 }
 
 extern "C" int dpm_tsdf_init(void *map, int cap_vox, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox));
+    DPM_CHECK_ARG(table_ok(map, cap_vox));
     const unsigned g = dpm_cdiv(cap_vox, TS_BLOCK);
     hipLaunchKernelGGL(ts_clear_kernel, dim3(g > 8192 ? 8192 : g), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, 1.0, nullptr));
@@ -662,7 +594,7 @@ extern "C" int dpm_tsdf_init(void *map, int cap_vox, dpm_stream_t stream) {
 extern "C" int dpm_tsdf_integrate(void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
                                   const int32_t *count, int cap, const double *pose, double min_range, double max_range,
                                   double truncation, double step, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
     DPM_CHECK_ARG(xyz && count && pose && cap >= 0);
     Rays R;
     DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
@@ -676,8 +608,8 @@ extern "C" int dpm_tsdf_integrate_frames(void *map, int cap_vox, double voxel, c
                                          const int32_t *lengths, int capacity, int P, const int32_t *frames,
                                          const double *poses, int F, double min_range, double max_range, double truncation,
                                          double step, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     Rays R;
     DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
     if (F == 0) return DPM_OK;
@@ -693,7 +625,7 @@ inline bool cos_ok(double cos_min) { return cos_min >= 0.0 && cos_min <= 1.0; }
 extern "C" int dpm_tsdf_integrate_planes(void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
                                          const float *normals, const int32_t *count, int cap, const double *pose, double min_range,
                                          double max_range, double truncation, double step, double cos_min, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
     DPM_CHECK_ARG(xyz && normals && count && pose && cap >= 0 && cos_ok(cos_min));
     Rays R;
     DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
@@ -708,8 +640,8 @@ extern "C" int dpm_tsdf_integrate_planes_frames(void *map, int cap_vox, double v
                                                 const int32_t *frames, const double *poses, int F, double min_range,
                                                 double max_range, double truncation, double step, double cos_min,
                                                 dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin) && cos_ok(cos_min));
-    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin) && cos_ok(cos_min));
+    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     Rays R;
     DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
     if (F == 0) return DPM_OK;
@@ -730,7 +662,7 @@ inline bool make_carve(const Rays &R, double max_range, double step, int weight,
 extern "C" int dpm_tsdf_carve(void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const int32_t *count,
                               int cap, const double *pose, double min_range, double max_range, double truncation, double step,
                               int weight, double margin, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
     DPM_CHECK_ARG(xyz && count && pose && cap >= 0);
     Rays R;
     Carve C;
@@ -745,8 +677,8 @@ extern "C" int dpm_tsdf_carve_frames(void *map, int cap_vox, double voxel, const
                                      const int32_t *lengths, int capacity, int P, const int32_t *frames, const double *poses, int F,
                                      double min_range, double max_range, double truncation, double step, int weight, double margin,
                                      dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535);
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     Rays R;
     Carve C;
     DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R) && make_carve(R, max_range, step, weight, margin, C));
@@ -760,7 +692,7 @@ extern "C" int dpm_tsdf_carve_frames(void *map, int cap_vox, double voxel, const
 
 extern "C" int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long *keys, long long *sums, uint32_t *counts,
                                int32_t *count, int max_out, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && count && max_out >= 0);
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && count && max_out >= 0);
     DPM_CHECK_ARG(max_out == 0 || (keys && sums && counts));
     hipLaunchKernelGGL(ts_export_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, 1.0, nullptr), keys, sums, counts, count, max_out);
@@ -769,7 +701,7 @@ extern "C" int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long 
 
 extern "C" int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *keys,
                                 int32_t *axes, float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
     DPM_CHECK_ARG(max_out == 0 || (keys && axes && xyz && normals));
     hipLaunchKernelGGL(ts_surface_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, keys, axes, xyz, normals, count, max_out);
@@ -778,7 +710,7 @@ extern "C" int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int 
 
 extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
                              int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
     DPM_CHECK_ARG(max_out == 0 || (vertex_keys && vertex_dirs && xyz));
     const MeshOut O{vertex_keys, vertex_dirs, xyz, count, max_out};
     hipLaunchKernelGGL(ts_mesh_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
@@ -789,7 +721,7 @@ extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min
 extern "C" int dpm_tsdf_sample(const void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
                                const int32_t *count, int cap, const double *pose, int min_count, float *d, float *grad,
                                int32_t *flag, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
     DPM_CHECK_ARG(count && pose && cap >= 0 && min_count >= 1);
     if (cap == 0) return DPM_OK;   // nothing to read or write: the row pointers may be null
     DPM_CHECK_ARG(xyz && d && grad && flag);
@@ -801,8 +733,9 @@ extern "C" int dpm_tsdf_sample(const void *map, int cap_vox, double voxel, const
 extern "C" size_t dpm_tsdf_register_scratch_bytes(int cap) {
     if (cap < 1) return 0;
     WsCursor c(nullptr);
-    TsRegArgs A{};
-    ts_reg_layout(c, cap, A);
+    GnOneHdr *hdr;
+    double *partial;
+    gn_one_layout(c, cap, hdr, partial);
     return c.bytes();
 }
 
@@ -812,7 +745,7 @@ extern "C" int dpm_tsdf_register(const void *map, int cap_vox, double voxel, con
                                  int n_stages, double kernel_scale, double tol_rot, double tol_trans, double *pose,
                                  float *fitness, float *rmse, int32_t *iterations, int32_t *status, int32_t *debug_flag,
                                  double *debug_system, void *workspace, dpm_stream_t stream) {
-    DPM_CHECK_ARG(tsdf_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
     DPM_CHECK_ARG(truncation > 0.0 && truncation <= 64.0 && min_count >= 1 && grad_min >= 0.0 && grad_min < 1e18);
     DPM_CHECK_ARG(xyz && count && init_pose && stage_max_dist && stage_max_iter && workspace && cap >= 1);
     DPM_CHECK_ARG(pose && fitness && rmse && iterations && status && pose != init_pose);
@@ -824,18 +757,13 @@ extern "C" int dpm_tsdf_register(const void *map, int cap_vox, double voxel, con
     A.M = make_tsdf(map, cap_vox, voxel, origin);
     A.xyz = xyz, A.count = count, A.cap = cap, A.min_count = (unsigned)min_count, A.grad_min2 = (float)(grad_min * grad_min);
     WsCursor c(workspace);
-    ts_reg_layout(c, cap, A);
+    gn_one_layout(c, cap, A.hdr, A.partial);
     A.pose = pose, A.fitness = fitness, A.rmse = rmse, A.iterations = iterations, A.status = status;
     A.dbg_flag = debug_flag, A.dbg_system = debug_system;
     const double kappa = kernel_scale * kernel_scale;
-    hipLaunchKernelGGL(ts_reg_init_kernel, dim3(1), dim3(64), 0, st, A, init_pose);
-    for (int s = 0; s < n_stages; ++s) {
-        if (s > 0) hipLaunchKernelGGL(ts_reg_stage_kernel, dim3(1), dim3(64), 0, st, A);
-        for (int it = 0; it < stage_max_iter[s]; ++it) {
-            hipLaunchKernelGGL(ts_reg_accumulate_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, st, A,
-                               (float)stage_max_dist[s], kappa);
-            hipLaunchKernelGGL(ts_reg_solve_kernel, dim3(1), dim3(64), 0, st, A, tol_rot, tol_trans);
-        }
-    }
-    return dpm_launch_status();
+    const GnOne G{A.hdr, A.partial, pose, fitness, rmse, iterations, status, debug_system, count, cap, A.M.ox, A.M.oy, A.M.oz};
+    return gn_one_run(G, init_pose, stage_max_iter, n_stages, tol_rot, tol_trans, st, [&](int s) {
+        hipLaunchKernelGGL(ts_reg_accumulate_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, st, A,
+                           (float)stage_max_dist[s], kappa);
+    });
 }

@@ -51,3 +51,23 @@ __device__ __forceinline__ int claim_slot(unsigned long long *keys, int cap_vox,
     }
     return -1;
 }
+
+// ---- what the entry points of both maps refuse, on the host
+// a table: the caller's buffer (16-byte aligned) of cap_vox slots, a power of two in [2, 2^24]
+inline bool table_ok(const void *map, int cap_vox) {
+    return map && ((uintptr_t)map & 15) == 0 && cap_vox >= 2 && cap_vox <= (1 << 24) && (cap_vox & (cap_vox - 1)) == 0;
+}
+
+inline bool voxel_ok(double voxel) { return voxel > 0.0 && voxel < 1e18 && (float)voxel > 0.f; }
+
+inline bool origin_ok(const double *origin) {
+    if (!origin) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!(origin[a] > -1e300 && origin[a] < 1e300)) return false;
+    return true;
+}
+
+// F rows of a channel-major store (capacity,3,P); the pointers are checked by the caller, after its F == 0 return
+inline bool frame_list_ok(int capacity, int P, int F) {
+    return capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535;
+}

@@ -32,7 +32,51 @@ def _pose_tensor(pose, dev) -> torch.Tensor:
     return p.to(device=dev, dtype=torch.float64).contiguous()
 
 
-class LocalMap:
+class _HashedMap:
+    """What LocalMap and tsdf.TsdfMap are alike in: a table made at first use, an origin that defaults to the translation of
+    the first pose, lists of stored frames and the header's counters.  A subclass has max_voxels, origin, device, table and
+    _new() -> an empty table on self.device."""
+
+    def _ready(self, dev, pose=None):
+        if self.table is None:
+            self.device = dev if self.device is None else torch.device(self.device)
+            self.table = self._new()
+        if self.origin is None:
+            if pose is None:
+                self.origin = np.zeros(3)
+            else:
+                if isinstance(pose, torch.Tensor) and pose.is_cuda:   # only here: give `origin` to keep the pose on the device
+                    augment._SYNCS[0] += 1
+                    pose = pose.detach().cpu().numpy()
+                self.origin = np.asarray(pose, np.float64).reshape(4, 4)[:3, 3].copy()
+
+    @staticmethod
+    def _list(what, store, frames, poses):
+        """-> (rows (F,) int32 on the device, poses (F,4,4)) of a list of stored frames, checked: host rows are uploaded
+        (nothing is read back), rows on the device are taken as they are"""
+        dev = store.device
+        if isinstance(frames, torch.Tensor):
+            rows = frames.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            host = np.asarray(frames, np.int64).reshape(-1)
+            if host.size and not (0 <= host.min() and host.max() < store.shape[0]):
+                raise ValueError(f"{what}: frames are rows of the store")
+            rows = torch.from_numpy(host.astype(np.int32)).to(dev)
+        if not isinstance(poses, torch.Tensor):
+            poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4))
+        if poses.numel() != 16 * rows.numel() or rows.numel() > 65535:
+            raise ValueError(f"{what}: poses (F,4,4), F <= 65535")
+        return rows, poses
+
+    def _header(self, word: int) -> int:
+        """32-bit word `word` of the table's header, unsigned; 0 before the table exists.  One host synchronisation."""
+        if self.table is None:
+            return 0
+        augment._SYNCS[0] += 1
+        return int(self.table[4 * word:4 * word + 4].view(torch.int32).item()) & 0xFFFFFFFF
+
+
+class LocalMap(_HashedMap):
     """A rolling voxel map of `max_voxels` slots (a power of two) with voxels of `voxel_size` metres cut into
     subdivisions^3 sub-cells of one point each.  Coordinates are kept in fp32 relative to `origin` (three float64; default:
     the translation of the first inserted pose), so work far from the world's zero keeps fp32 accuracy.  Points are
@@ -61,19 +105,9 @@ class LocalMap:
         self._planes = None          # (planes, counts) of the current half, per slot: a cache derived from the map
         self._planes_stale = True    # set by insert and prune, so the host knows without a read
 
-    # -- plumbing
-    def _ready(self, dev, pose=None):
-        if self.table is None:
-            self.device = dev if self.device is None else torch.device(self.device)
-            self.table = ops.local_map_new(self.max_voxels, self.subdivisions, self.device)
-        if self.origin is None:
-            if pose is None:
-                self.origin = np.zeros(3)
-            else:
-                if isinstance(pose, torch.Tensor) and pose.is_cuda:
-                    augment._SYNCS[0] += 1
-                    pose = pose.detach().cpu().numpy()
-                self.origin = np.asarray(pose, np.float64)[:3, 3].copy()
+    # -- plumbing (_ready, _list and _header are _HashedMap's)
+    def _new(self):
+        return ops.local_map_new(self.max_voxels, self.subdivisions, self.device)
 
     def _args(self):
         return self.table, self.max_voxels, self.subdivisions, self.half, self.voxel_size, self.origin
@@ -114,22 +148,11 @@ class LocalMap:
         stamps = [int(s) for s in np.asarray(stamps).reshape(-1)]
         if len(set(stamps)) != len(stamps) or any(not 0 <= s < 0xFFFFFFFF for s in stamps):
             raise ValueError("insert_frames: stamps pairwise distinct, in [0, 2^32 - 1)")
-        dev = store.device
-        if isinstance(frames, torch.Tensor):
-            rows = frames.to(device=dev, dtype=torch.int32).contiguous()
-        else:
-            host = np.asarray(frames, np.int64).reshape(-1)
-            if host.size and not (0 <= host.min() and host.max() < store.shape[0]):
-                raise ValueError("insert_frames: frames are rows of the store")
-            rows = torch.from_numpy(host.astype(np.int32)).to(dev)
+        rows, poses = self._list("insert_frames", store, frames, poses)
         if len(stamps) != rows.numel():
             raise ValueError("insert_frames: one stamp per frame")
-        if not isinstance(poses, torch.Tensor):
-            poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4))
-        if poses.numel() != 16 * rows.numel():
-            raise ValueError("insert_frames: poses (F,4,4)")
         first = centre if centre is not None else (poses.reshape(-1, 4, 4)[0] if rows.numel() else None)
-        self._ready(dev, first)
+        self._ready(store.device, first)
         if rows.numel() == 0:
             return self
         ops.local_map_insert_frames(*self._args(), store, lengths, rows, poses.to(device=self.device, dtype=torch.float64).contiguous(),
@@ -187,10 +210,7 @@ class LocalMap:
     @property
     def overflow(self) -> int:
         """points that found no free slot so far (0: the map is defined)"""
-        if self.table is None:
-            return 0
-        augment._SYNCS[0] += 1
-        return int(self.table[:4].view(torch.int32).item())
+        return self._header(0)
 
     def check(self):
         n = self.overflow

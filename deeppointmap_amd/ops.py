@@ -2229,10 +2229,44 @@ def _local_map_args(table: torch.Tensor, cap_vox: int, subdiv: int, origin=None)
     _chk(table, torch.uint8, "table")
     if table.numel() != _lib.load().dpm_local_map_bytes(int(cap_vox), int(subdiv)) or table.numel() == 0:
         raise ValueError("table: dpm_local_map_bytes(cap_vox, subdiv) bytes, cap_vox a power of two in [2, 2^24], subdiv in 1..3")
-    if origin is None:
-        return None
-    o = (ctypes.c_double * 3)(*[float(v) for v in origin])
-    return o
+    return None if origin is None else (ctypes.c_double * 3)(*_origin3(origin))
+
+
+# what the local map and the TSDF map (below) take alike: a frame, a list of stored frames, one registration problem
+def _frame_args(what, xyz, count, pose):
+    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or count.numel() != 1 or pose.numel() != 16:
+        raise ValueError(f"{what}: xyz (cap,3), count (1,), pose (4,4)")
+
+
+def _frame_list_args(what, store, lengths, frames, poses) -> int:
+    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
+    _chk(poses, torch.float64, "poses")
+    F = frames.numel()
+    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
+            or frames.dim() != 1 or poses.numel() != 16 * F or F > 65535:
+        raise ValueError(f"{what}: store (capacity,3,P), lengths (capacity,), frames (F,) with F <= 65535, poses (F,4,4)")
+    return F
+
+
+def _register_one(what, entry, head, table, xyz, count, init, schedule, kernel_scale, tol_rot, tol_trans, debug, row_dtypes,
+                  ws_bytes):
+    """one scan against a map: entry(*head, the frame, init, the schedule, the results, the debug rows, system, workspace,
+    stream); `what` names it in an error.  row_dtypes: the per-row debug outputs, (cap,) each, -1 where nothing is written
+    -> (pose (4,4), fitness, rmse, iterations, status[, *rows, system (29,) fp64 with debug])"""
+    dist, iters, n_stages = _schedule_arrays(schedule)
+    dev, cap = table.device, xyz.shape[0]
+    with torch.cuda.device(dev):
+        pose, fitness, rmse, iterations, status = _registration_results(1, dev)
+        pose = pose[0]
+        rows = [torch.full((cap,), -1, device=dev, dtype=t) if debug else None for t in row_dtypes]
+        system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        _lib.check(entry(*head, _ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), n_stages,
+                         float(kernel_scale), float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse),
+                         _ptr(iterations), _ptr(status), *[_ptr(r) for r in rows], _ptr(system), _ptr(ws), _stream(table)), what)
+    out = (pose, fitness, rmse, iterations, status)
+    return (*out, *rows, system) if debug else out
 
 
 def local_map_new(cap_vox: int, subdiv: int, device) -> torch.Tensor:
@@ -2282,12 +2316,9 @@ def local_map_insert_frames(table, cap_vox, subdiv, half, voxel, origin, store, 
     of the store, poses (F,4,4) fp64, stamps (F,) int32 holding the uint32 stamps' bits, centre (4,4) fp64 or None (then
     radius is ignored), all on the GPU.  Two launches for any F, no host synchronisation, capturable in a graph."""
     o = _local_map_args(table, cap_vox, subdiv, origin)
-    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
-    _chk(poses, torch.float64, "poses"), _chk(stamps, torch.int32, "stamps")
-    F = frames.numel()
-    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
-            or frames.dim() != 1 or poses.numel() != 16 * F or stamps.shape != frames.shape:
-        raise ValueError("local_map_insert_frames: store (capacity,3,P), lengths (capacity,), frames (F,), poses (F,4,4), stamps (F,)")
+    F = _frame_list_args("local_map_insert_frames", store, lengths, frames, poses)
+    if _chk(stamps, torch.int32, "stamps").shape != frames.shape:
+        raise ValueError("local_map_insert_frames: stamps (F,), one per frame")
     if centre is not None:
         _chk(centre, torch.float64, "centre")
         if centre.numel() != 16:
@@ -2337,27 +2368,14 @@ def local_map_register(table, cap_vox, subdiv, half, voxel, origin, xyz, count, 
     _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(init, torch.float64, "init")
     if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1 or count.numel() != 1 or tuple(init.shape) != (4, 4):
         raise ValueError("local_map_register: xyz (cap,3) with cap >= 1, count (1,), init (4,4)")
-    dist, iters, n_stages = _schedule_arrays(schedule)
-    dev, cap = table.device, xyz.shape[0]
-    with torch.cuda.device(dev):
-        pose, fitness, rmse, iterations, status = _registration_results(1, dev)
-        pose = pose[0]
-        key = torch.full((cap,), -1, device=dev, dtype=torch.int64) if debug else None
-        sub = torch.full((cap,), -1, device=dev, dtype=torch.int32) if debug else None
-        system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
-        ws = torch.empty(512 + 256 * ((cap + 255) // 256), device=dev, dtype=torch.uint8)
-        head = (_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o))
-        tail = (_ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), n_stages,
-                float(kernel_scale), float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations),
-                _ptr(status), _ptr(key), _ptr(sub), _ptr(system), _ptr(ws), _stream(table))
-        if _plane is None:
-            _lib.check(_lib.load().dpm_local_map_register(*head, *tail), "dpm_local_map_register")
-        else:
-            planes, counts, min_points, max_ratio = _plane
-            _lib.check(_lib.load().dpm_local_map_register_planes(*head, _ptr(planes), _ptr(counts), min_points, max_ratio, *tail),
-                       "dpm_local_map_register_planes")
-    out = (pose, fitness, rmse, iterations, status)
-    return out + (key, sub, system) if debug else out
+    lib, head = _lib.load(), (_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o))
+    what, entry = "dpm_local_map_register", lib.dpm_local_map_register
+    if _plane is not None:
+        planes, counts, min_points, max_ratio = _plane
+        what, entry = "dpm_local_map_register_planes", lib.dpm_local_map_register_planes
+        head = (*head, _ptr(planes), _ptr(counts), min_points, max_ratio)
+    return _register_one(what, entry, head, table, xyz, count, init, schedule, kernel_scale, tol_rot, tol_trans, debug,
+                         (torch.int64, torch.int32), 512 + 256 * ((xyz.shape[0] + 255) // 256))
 
 
 def local_map_export(table, cap_vox, subdiv, half, max_out=None):
@@ -2437,9 +2455,7 @@ def tsdf_integrate(table, cap_vox, voxel, origin, xyz, count, pose, min_range, m
     synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or count.numel() != 1 or pose.numel() != 16:
-        raise ValueError("tsdf_integrate: xyz (cap,3), count (1,), pose (4,4)")
+    _frame_args("tsdf_integrate", xyz, count, pose)
     with torch.cuda.device(table.device):
         _lib.check(_lib.load().dpm_tsdf_integrate(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz),
                                                   _ptr(count), xyz.shape[0], _ptr(pose), *rays, _stream(table)),
@@ -2451,32 +2467,11 @@ def tsdf_integrate_frames(table, cap_vox, voxel, origin, store, lengths, frames,
     the store, poses (F,4,4) fp64, all on the GPU.  One launch for any F, no host synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
-    _chk(poses, torch.float64, "poses")
-    F = frames.numel()
-    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
-            or frames.dim() != 1 or poses.numel() != 16 * F or F > 65535:
-        raise ValueError("tsdf_integrate_frames: store (capacity,3,P), lengths (capacity,), frames (F,) with F <= 65535, poses (F,4,4)")
+    F = _frame_list_args("tsdf_integrate_frames", store, lengths, frames, poses)
     with torch.cuda.device(table.device):
         _lib.check(_lib.load().dpm_tsdf_integrate_frames(
             _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
             store.shape[2], _ptr(frames), _ptr(poses), F, *rays, _stream(table)), "dpm_tsdf_integrate_frames")
-
-
-def _tsdf_frame_args(what, xyz, count, pose):
-    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or count.numel() != 1 or pose.numel() != 16:
-        raise ValueError(f"{what}: xyz (cap,3), count (1,), pose (4,4)")
-
-
-def _tsdf_list_args(what, store, lengths, frames, poses) -> int:
-    _chk(store, torch.float32, "store"), _chk(lengths, torch.int32, "lengths"), _chk(frames, torch.int32, "frames")
-    _chk(poses, torch.float64, "poses")
-    F = frames.numel()
-    if store.dim() != 3 or store.shape[1] != 3 or store.shape[0] < 1 or store.shape[2] < 1 or lengths.shape != store.shape[:1] \
-            or frames.dim() != 1 or poses.numel() != 16 * F or F > 65535:
-        raise ValueError(f"{what}: store (capacity,3,P), lengths (capacity,), frames (F,) with F <= 65535, poses (F,4,4)")
-    return F
 
 
 def _tsdf_cos(cos_min) -> float:
@@ -2501,7 +2496,7 @@ def tsdf_integrate_planes(table, cap_vox, voxel, origin, xyz, normals, count, po
     synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _tsdf_frame_args("tsdf_integrate_planes", xyz, count, pose)
+    _frame_args("tsdf_integrate_planes", xyz, count, pose)
     if _chk(normals, torch.float32, "normals").shape != xyz.shape:
         raise ValueError("tsdf_integrate_planes: normals (cap,3), one per row of xyz")
     with torch.cuda.device(table.device):
@@ -2515,7 +2510,7 @@ def tsdf_integrate_planes_frames(table, cap_vox, voxel, origin, store, normals, 
     """dpm_tsdf_integrate_planes_frames: tsdf_integrate_frames' arguments and a normals store (capacity,P,3) fp32"""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    F = _tsdf_list_args("tsdf_integrate_planes_frames", store, lengths, frames, poses)
+    F = _frame_list_args("tsdf_integrate_planes_frames", store, lengths, frames, poses)
     if tuple(_chk(normals, torch.float32, "normals").shape) != (store.shape[0], store.shape[2], 3):
         raise ValueError("tsdf_integrate_planes_frames: normals (capacity,P,3)")
     with torch.cuda.device(table.device):
@@ -2531,7 +2526,7 @@ def tsdf_carve(table, cap_vox, voxel, origin, xyz, count, pose, min_range, max_r
     rays = tsdf_rays(truncation, step, min_range, max_range)
     w, g = tsdf_carve_args(weight, margin, step, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _tsdf_frame_args("tsdf_carve", xyz, count, pose)
+    _frame_args("tsdf_carve", xyz, count, pose)
     with torch.cuda.device(table.device):
         _lib.check(_lib.load().dpm_tsdf_carve(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(count),
                                               xyz.shape[0], _ptr(pose), *rays, w, g, _stream(table)), "dpm_tsdf_carve")
@@ -2543,7 +2538,7 @@ def tsdf_carve_frames(table, cap_vox, voxel, origin, store, lengths, frames, pos
     rays = tsdf_rays(truncation, step, min_range, max_range)
     w, g = tsdf_carve_args(weight, margin, step, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    F = _tsdf_list_args("tsdf_carve_frames", store, lengths, frames, poses)
+    F = _frame_list_args("tsdf_carve_frames", store, lengths, frames, poses)
     with torch.cuda.device(table.device):
         _lib.check(_lib.load().dpm_tsdf_carve_frames(
             _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
@@ -2629,7 +2624,7 @@ def tsdf_sample(table, cap_vox, voxel, origin, xyz, count, pose, min_count=1):
     the map frame's axes, flag (cap,) int32: 1 a value, 0 none, -1 past the count).  Lookups only; one launch, no host
     synchronisation, capturable in a graph."""
     o = _tsdf_args(table, cap_vox, origin)
-    _tsdf_frame_args("tsdf_sample", xyz, count, pose)
+    _frame_args("tsdf_sample", xyz, count, pose)
     if int(min_count) < 1:
         raise ValueError("min_count >= 1")
     dev, cap = table.device, xyz.shape[0]
@@ -2649,7 +2644,7 @@ def tsdf_register(table, cap_vox, voxel, origin, truncation, xyz, count, init, s
     max_iter), ...] with every max_dist in (0, truncation] -> pose (4,4) fp64, fitness, rmse (1,) fp32, iterations, status (1,)
     int32[, flag (cap,) int32, system (29,) fp64 with debug].  Lookups only; no host synchronisation, capturable in a graph."""
     o = _tsdf_args(table, cap_vox, origin)
-    _tsdf_frame_args("tsdf_register", xyz, count, init)
+    _frame_args("tsdf_register", xyz, count, init)
     if xyz.shape[0] < 1 or tuple(init.shape) != (4, 4):
         raise ValueError("tsdf_register: xyz (cap,3) with cap >= 1, init (4,4)")
     if int(min_count) < 1 or not 0.0 <= float(grad_min) < 1e18:
@@ -2657,21 +2652,10 @@ def tsdf_register(table, cap_vox, voxel, origin, truncation, xyz, count, init, s
     stages = [(float(d), int(n)) for d, n in schedule]
     if any(not 0.0 < d <= float(truncation) for d, _ in stages):
         raise ValueError("tsdf_register: every max_dist of the schedule must lie in (0, truncation] (beyond the clamp the field is flat)")
-    dist, iters, n_stages = _schedule_arrays(stages)
-    dev, cap, lib = table.device, xyz.shape[0], _lib.load()
-    with torch.cuda.device(dev):
-        pose, fitness, rmse, iterations, status = _registration_results(1, dev)
-        pose = pose[0]
-        flag = torch.full((cap,), -1, device=dev, dtype=torch.int32) if debug else None
-        system = torch.zeros(ICP_NSUM, device=dev, dtype=torch.float64) if debug else None
-        ws = torch.empty(lib.dpm_tsdf_register_scratch_bytes(cap), device=dev, dtype=torch.uint8)
-        _lib.check(lib.dpm_tsdf_register(
-            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), float(truncation), int(min_count), float(grad_min),
-            _ptr(xyz), _ptr(count), cap, _ptr(init), ctypes.addressof(dist), ctypes.addressof(iters), n_stages,
-            float(kernel_scale), float(tol_rot), float(tol_trans), _ptr(pose), _ptr(fitness), _ptr(rmse), _ptr(iterations),
-            _ptr(status), _ptr(flag), _ptr(system), _ptr(ws), _stream(table)), "dpm_tsdf_register")
-    out = (pose, fitness, rmse, iterations, status)
-    return out + (flag, system) if debug else out
+    lib = _lib.load()
+    head = (_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), float(truncation), int(min_count), float(grad_min))
+    return _register_one("dpm_tsdf_register", lib.dpm_tsdf_register, head, table, xyz, count, init, stages, kernel_scale, tol_rot,
+                         tol_trans, debug, (torch.int32,), lib.dpm_tsdf_register_scratch_bytes(xyz.shape[0]))
 
 
 # ------------------------------------------------------------------------------------------------------------

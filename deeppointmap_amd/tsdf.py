@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import augment, ops
-from .odometry import _pose_tensor
+from .odometry import _HashedMap, _pose_tensor
 from .refine import CONVERGED, MAX_ITER, NO_MATCH, IcpResult
 
 OVERFLOW = "the TSDF map is full (max_voxels={}): samples found no free slot and the map is undefined; raise max_voxels"
@@ -109,7 +109,7 @@ def write_ply(path, vertices, faces=None, normals=None) -> None:
             out.write(rec.tobytes())
 
 
-class TsdfMap:
+class TsdfMap(_HashedMap):
     """A TSDF of `max_voxels` slots (a power of two) with voxels of `voxel_size` metres.  truncation (default 3 voxel_size, at
     most 64 m): how far before and behind a return its ray is sampled, and the clamp of the distance; step (default
     voxel_size / 2): the spacing of the samples.  Coordinates are fp32 relative to `origin` (three float64; default: the
@@ -141,19 +141,9 @@ class TsdfMap:
         self.device = device
         self.table: Optional[torch.Tensor] = None
 
-    # -- plumbing
-    def _ready(self, dev, pose=None):
-        if self.table is None:
-            self.device = dev if self.device is None else torch.device(self.device)
-            self.table = ops.tsdf_new(self.max_voxels, self.device)
-        if self.origin is None:
-            if pose is None:
-                self.origin = np.zeros(3)
-            else:
-                if isinstance(pose, torch.Tensor) and pose.is_cuda:   # only here: give `origin` to keep the pose on the device
-                    augment._SYNCS[0] += 1
-                    pose = pose.detach().cpu().numpy()
-                self.origin = np.asarray(pose, np.float64).reshape(4, 4)[:3, 3].copy()
+    # -- plumbing (_ready, _list and _header are odometry._HashedMap's)
+    def _new(self):
+        return ops.tsdf_new(self.max_voxels, self.device)
 
     def _rays(self):
         return self.min_range, self.max_range, self.truncation, self.step
@@ -182,22 +172,6 @@ class TsdfMap:
         if tuple(np.shape(pose)) != (4, 4):
             raise ValueError("pose: (4,4)")
         return xyz, count
-
-    def _list(self, what, store, frames, poses):
-        """-> (rows (F,) int32 on the device, poses (F,4,4)) of a list of stored frames, checked"""
-        dev = store.device
-        if isinstance(frames, torch.Tensor):
-            rows = frames.to(device=dev, dtype=torch.int32).contiguous()
-        else:
-            host = np.asarray(frames, np.int64).reshape(-1)
-            if host.size and not (0 <= host.min() and host.max() < store.shape[0]):
-                raise ValueError(f"{what}: frames are rows of the store")
-            rows = torch.from_numpy(host.astype(np.int32)).to(dev)
-        if not isinstance(poses, torch.Tensor):
-            poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4))
-        if poses.numel() != 16 * rows.numel() or rows.numel() > 65535:
-            raise ValueError(f"{what}: poses (F,4,4), F <= 65535")
-        return rows, poses
 
     def _estimated(self, xyz, count, radius):
         """dpm_point_normals of the frame's valid rows alone -> (N,3), zeros past them.  Reads the length: one synchronisation."""
@@ -279,12 +253,6 @@ class TsdfMap:
         return self
 
     # -- read-back: one host synchronisation each
-    def _header(self, word: int) -> int:
-        if self.table is None:
-            return 0
-        augment._SYNCS[0] += 1
-        return int(self.table[4 * word:4 * word + 4].view(torch.int32).item()) & 0xFFFFFFFF
-
     def overflow(self) -> int:
         """samples that found no free slot so far (0: the map is defined)"""
         return self._header(0)

@@ -255,7 +255,8 @@ def test_the_python_layer_refuses_bad_lists():
     store, lengths = on_device(c)
     g = gpu_map(c)
     for kw in (dict(frames=[0, 1], stamps=[4, 4]), dict(frames=[0, 99]), dict(frames=[0, 1], stamps=[1]), dict(frames=[-1]),
-               dict(frames=[0], stamps=[0xFFFFFFFF]), dict(frames=torch.zeros(1, dtype=torch.int32, device=DEV))):
+               dict(frames=[0], stamps=[0xFFFFFFFF]), dict(frames=torch.zeros(1, dtype=torch.int32, device=DEV)),
+               dict(frames=[0] * 65536, stamps=list(range(65536)))):      # more entries than a launch takes: 65535
         kw.setdefault("poses", np.tile(np.eye(4), (len(kw["frames"]), 1, 1)))
         with pytest.raises(ValueError):
             g.insert_frames(store, lengths, **kw)
