@@ -181,6 +181,9 @@ SIGNATURES = {
     "dpm_tsdf_sample": (I, [P, I, D, P, P, P, I, P, I, P, P, P, P]),
     "dpm_tsdf_register_scratch_bytes": (c_size_t, [I]),
     "dpm_tsdf_register": (I, [P, I, D, P, D, I, D, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P]),
+    "dpm_tsdf_blocks_bytes": (c_size_t, [I]),
+    "dpm_tsdf_blocks": (I, [P, I, I, P, I, P]),
+    "dpm_tsdf_raycast": (I, [P, I, D, P, P, I, P, I, P, I, D, D, D, I, P, P, P, P]),
     "dpm_scan_context_build": (I, [P, P, I, I, I, D, D, D, P, P, P, P, P, P]),
     "dpm_scan_context_build_batched": (I, [P, P, I, I, I, I, D, D, D, P, P, P, P, P, P]),
     "dpm_scan_context_search_workspace_bytes": (c_size_t, [I, I, I]),

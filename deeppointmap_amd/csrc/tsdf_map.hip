@@ -58,6 +58,10 @@
 //              or one non-negative corner gives a triangle, two and two a quadrilateral cut into two triangles; they are wound
 //              so that the normal (b - a) x (c - a) points to the positive side.  A corner with D == 0 counts as positive, and
 //              the triangles of zero area it makes are kept.
+//   raycast    one lane per ray, grid y the pose, lookups only: the field (below) at t_k = t0 + (float)k * h along o + u * t, the
+//              first sign change between two valued samples in a row -> range, the unit gradient in the sensor frame, a flag
+//              (MISS 0, HIT 1, BACK 2).  blocks: the set of 8 x 8 x 8 blocks that hold a qualified voxel, one lane per slot;
+//              the marcher skips the lookups of a sample whose base voxel lies in a block the set does not hold.
 #include "gn_one.h"
 #include "voxel_hash.h"
 
@@ -558,6 +562,108 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_reg_accumulate_kernel(TsRegArgs A
     gn_block_reduce<1>(s, A.partial, blk);
 }
 
+// ------------------------------------------------------------------------------------------------------- ray-casting the field
+// The occupied-block set: the keys (x >> 3, y >> 3, z >> 3) of the 8 x 8 x 8 blocks that hold a voxel qualified at min_count, in a
+// second open-addressing set of cap_blocks slots behind a 256-byte header (word 0: claims that found no room).  Integer
+// compare-and-swap only, so membership is a function of the table's content and min_count alone.  A block key has 3 x 18 bits
+// and is never EMPTY.
+struct BlockSet {
+    unsigned char *base;     // nullptr: the plain form of the marcher
+    int cap;
+    __host__ __device__ unsigned long long *keys() const { return (unsigned long long *)(base + 256); }
+};
+
+__device__ __forceinline__ unsigned long long block_key(int x, int y, int z) { return pack_key(x >> 3, y >> 3, z >> 3); }
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_blocks_clear_kernel(BlockSet B) {
+    const size_t tid = (size_t)blockIdx.x * TS_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * TS_BLOCK;
+    if (tid < 64) ((unsigned *)B.base)[tid] = 0u;
+    for (size_t i = tid; i < (size_t)B.cap; i += stride) B.keys()[i] = EMPTY;
+}
+
+// one lane per slot of the table; the voxels of one block sit in unrelated slots, so nothing is merged before the claim
+__global__ __launch_bounds__(TS_BLOCK) void ts_blocks_kernel(Tsdf M, unsigned min_count, BlockSet B) {
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long key = M.keys()[slot];
+    if (key == EMPTY || M.count()[slot] < min_count) return;
+    if (claim_slot(B.keys(), B.cap, block_key(key_axis(key, 0), key_axis(key, 1), key_axis(key, 2))) < 0)
+        atomicAdd((unsigned *)B.base, 1u);
+}
+
+// The marcher: one lane per ray, grid y the pose; neighbouring lanes are neighbouring columns of one beam.  Sample k lies at
+// t_k = t0 + (float)k * h, p_k = o + u * t_k; its value and gradient are field_at's, and the ray ends at the first pair of valued
+// samples k - 1, k whose signs (d > 0) differ (include/dpm_hip.h is the rule; tests/tsdf_raycast_restated.py equals it bit for bit).
+// SKIP: a sample whose base voxel i0 -- field_at's own, formed by the same three operations -- lies in a block the set does not
+// hold cannot have a value (its corner (0,0,0) is not qualified), so field_at is not run for it.  The block's answer stays in two
+// registers while consecutive samples stay inside the block (16 samples at half-voxel steps along an axis): empty space costs
+// one probe of the set per block entered and none in between.  No sample is stepped over: every k forms its own p_k and i0, so
+// the bytes are those of the plain form.
+struct Cast {
+    float t0, h;
+    int K;
+    unsigned min_count;
+};
+
+template <bool SKIP>
+__global__ __launch_bounds__(TS_BLOCK) void ts_raycast_kernel(Tsdf M, BlockSet B, const double *poses, const float *dirs, int R,
+                                                              Cast C, float *range, float *normals, int32_t *flag) {
+    const int r = blockIdx.x * TS_BLOCK + threadIdx.x, f = blockIdx.y;
+    if (r >= R) return;
+    const GnPose32 P = gn_load_pose(poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
+    const float dx = dirs[3 * (size_t)r], dy = dirs[3 * (size_t)r + 1], dz = dirs[3 * (size_t)r + 2];
+    float u[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) u[a] = fmaf(P.R[3 * a + 2], dz, fmaf(P.R[3 * a + 1], dy, P.R[3 * a] * dx));
+    bool prev = false;
+    float dp = 0.f, gp[3] = {0.f, 0.f, 0.f};
+    unsigned long long held = EMPTY;      // the block of the last valid base voxel, and whether the set holds it
+    bool present = false;
+    int out = 0;
+    float rg = 0.f, n[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < C.K; ++k) {
+        const float t = C.t0 + (float)k * C.h;
+        const float p[3] = {P.t[0] + u[0] * t, P.t[1] + u[1] * t, P.t[2] + u[2] * t};
+        bool may = true;
+        if constexpr (SKIP) {
+            float fl[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                fl[a] = floorf(__fdiv_rn(p[a], M.v) - 0.5f);
+                may = may && fl[a] >= -1048576.f && fl[a] < 1048575.f;   // a NaN fails: no cell, no value
+            }
+            if (may) {
+                const unsigned long long bk = block_key((int)fl[0] + 1048576, (int)fl[1] + 1048576, (int)fl[2] + 1048576);
+                if (bk != held) held = bk, present = find_slot(B.keys(), B.cap, bk) >= 0;
+                may = present;
+            }
+        }
+        float d = 0.f, g[3] = {0.f, 0.f, 0.f}, n2;
+        const bool has = may && field_at(M, p, C.min_count, d, g, n2);
+        if (has && prev && (dp > 0.f) != (d > 0.f)) {
+            const float fr = __fdiv_rn(dp, dp - d);
+            rg = (C.t0 + (float)(k - 1) * C.h) + fr * C.h;
+            out = dp > 0.f ? 1 : 2;
+            float gm[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) gm[a] = gp[a] + fr * (g[a] - gp[a]);
+            const float len = sqrtf((gm[0] * gm[0] + gm[1] * gm[1]) + gm[2] * gm[2]);
+            if (len > 0.f && len <= 3.402823466e38f) {   // a NaN fails
+#pragma unroll
+                for (int a = 0; a < 3; ++a) gm[a] = __fdiv_rn(gm[a], len);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) n[j] = (P.R[j] * gm[0] + P.R[3 + j] * gm[1]) + P.R[6 + j] * gm[2];   // R^T: sensor frame
+            }
+            break;
+        }
+        prev = has;
+        if (has) dp = d, gp[0] = g[0], gp[1] = g[1], gp[2] = g[2];
+    }
+    const size_t at = (size_t)f * R + r;
+    range[at] = rg, flag[at] = out;
+    normals[3 * at] = n[0], normals[3 * at + 1] = n[1], normals[3 * at + 2] = n[2];
+}
+
 inline Tsdf make_tsdf(const void *map, int cap_vox, double voxel, const double *origin) {
     Tsdf M;
     M.base = (unsigned char *)map, M.cap_vox = cap_vox, M.v = (float)voxel;
@@ -766,4 +872,44 @@ extern "C" int dpm_tsdf_register(const void *map, int cap_vox, double voxel, con
         hipLaunchKernelGGL(ts_reg_accumulate_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, st, A,
                            (float)stage_max_dist[s], kappa);
     });
+}
+
+// a block set: the caller's buffer of dpm_tsdf_blocks_bytes(cap_blocks) bytes, under the table's own limits
+extern "C" size_t dpm_tsdf_blocks_bytes(int cap_blocks) {
+    if (!table_ok((const void *)16, cap_blocks)) return 0;
+    return 256 + (size_t)cap_blocks * 8;
+}
+
+extern "C" int dpm_tsdf_blocks(const void *map, int cap_vox, int min_count, void *blocks, int cap_blocks, dpm_stream_t stream) {
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && table_ok(blocks, cap_blocks) && min_count >= 1);
+    const BlockSet B{(unsigned char *)blocks, cap_blocks};
+    const unsigned g = dpm_cdiv(cap_blocks, TS_BLOCK);
+    hipLaunchKernelGGL(ts_blocks_clear_kernel, dim3(g > 8192 ? 8192 : g), dim3(TS_BLOCK), 0, (hipStream_t)stream, B);
+    hipLaunchKernelGGL(ts_blocks_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, 1.0, nullptr), (unsigned)min_count, B);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_raycast(const void *map, int cap_vox, double voxel, const double *origin, const void *blocks,
+                                int cap_blocks, const double *poses, int F, const float *dirs, int R, double min_range,
+                                double max_range, double step, int min_count, float *range, float *normals, int32_t *flag,
+                                dpm_stream_t stream) {
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
+    DPM_CHECK_ARG(!blocks || table_ok(blocks, cap_blocks));
+    DPM_CHECK_ARG(step > 0.0 && min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
+    const double samples = floor((max_range - min_range) / step) + 1.0;
+    DPM_CHECK_ARG(samples <= 65536.0 && min_count >= 1 && F >= 0 && F <= 65535 && R >= 0);
+    if (F == 0 || R == 0) return DPM_OK;   // nothing to read or write: the pointers may be null
+    DPM_CHECK_ARG(poses && dirs && range && normals && flag);
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    const BlockSet B{(unsigned char *)blocks, blocks ? cap_blocks : 0};
+    const Cast C{(float)min_range, (float)step, (int)samples, (unsigned)min_count};
+    const dim3 grid(dpm_cdiv(R, TS_BLOCK), F);
+    if (blocks)
+        hipLaunchKernelGGL(ts_raycast_kernel<true>, grid, dim3(TS_BLOCK), 0, (hipStream_t)stream, M, B, poses, dirs, R, C, range,
+                           normals, flag);
+    else
+        hipLaunchKernelGGL(ts_raycast_kernel<false>, grid, dim3(TS_BLOCK), 0, (hipStream_t)stream, M, B, poses, dirs, R, C, range,
+                           normals, flag);
+    return dpm_launch_status();
 }

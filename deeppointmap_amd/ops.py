@@ -2658,6 +2658,78 @@ def tsdf_register(table, cap_vox, voxel, origin, truncation, xyz, count, init, s
                          tol_trans, debug, (torch.int32,), lib.dpm_tsdf_register_scratch_bytes(xyz.shape[0]))
 
 
+TSDF_MAX_CAST_SAMPLES = 65536   # floor((max_range - min_range) / step) + 1 at most for a ray-cast
+TSDF_MISS, TSDF_HIT, TSDF_BACK = 0, 1, 2
+
+
+def tsdf_cast_args(min_range, max_range, step):
+    """the marcher's own arguments, checked as the entry point checks them -> three floats"""
+    lo, hi, h = float(min_range), float(max_range), float(step)
+    if not (h > 0.0 and 0.0 <= lo <= hi < 1e18):
+        raise ValueError("raycast: step > 0 and 0 <= min_range <= max_range")
+    if not (hi - lo) / h < TSDF_MAX_CAST_SAMPLES:      # floor(q) + 1 <= N  <=>  q < N
+        raise ValueError(f"raycast: floor((max_range - min_range) / step) + 1 <= {TSDF_MAX_CAST_SAMPLES}")
+    return lo, hi, h
+
+
+def _tsdf_blocks_args(blocks, cap_blocks):
+    _chk(blocks, torch.uint8, "blocks")
+    if blocks.numel() != _lib.load().dpm_tsdf_blocks_bytes(int(cap_blocks)) or blocks.numel() == 0:
+        raise ValueError("blocks: dpm_tsdf_blocks_bytes(cap_blocks) bytes, cap_blocks a power of two in [2, 2^24]")
+
+
+def tsdf_blocks(table, cap_vox, min_count, cap_blocks, out=None) -> torch.Tensor:
+    """dpm_tsdf_blocks: the occupied-block set of the table as it is now, for voxels qualified at min_count -> the uint8 buffer
+    tsdf_raycast takes (out: a buffer to build into).  Word 0 counts the claims that found no room.  Two launches, no host
+    synchronisation, capturable in a graph."""
+    _tsdf_args(table, cap_vox)
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    n = _lib.load().dpm_tsdf_blocks_bytes(int(cap_blocks))
+    if n == 0:
+        raise ValueError("cap_blocks: a power of two in [2, 2^24]")
+    with torch.cuda.device(table.device):
+        blocks = torch.empty(n, device=table.device, dtype=torch.uint8) if out is None else out
+        _tsdf_blocks_args(blocks, cap_blocks)
+        _lib.check(_lib.load().dpm_tsdf_blocks(_ptr(table), int(cap_vox), int(min_count), _ptr(blocks), int(cap_blocks),
+                                               _stream(table)), "dpm_tsdf_blocks")
+    return blocks
+
+
+def tsdf_raycast(table, cap_vox, voxel, origin, blocks, cap_blocks, poses, dirs, min_range, max_range, step, min_count=1, out=None):
+    """dpm_tsdf_raycast: poses (F,4,4) fp64 and dirs (R,3) fp32 (sensor frame, unit) on the GPU; blocks: None (the plain form)
+    or tsdf_blocks' buffer of this table and min_count -> (range (F,R) fp32, normals (F,R,3) fp32 in the sensor frame, flag (F,R)
+    int32: TSDF_MISS / TSDF_HIT / TSDF_BACK); out: those three to write into.  Lookups only; one launch, no host
+    synchronisation, capturable in a graph."""
+    lo, hi, h = tsdf_cast_args(min_range, max_range, step)
+    o = _tsdf_args(table, cap_vox, origin)
+    _chk(poses, torch.float64, "poses"), _chk(dirs, torch.float32, "dirs")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] > 65535:
+        raise ValueError("tsdf_raycast: poses (F,4,4), F <= 65535")
+    if dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise ValueError("tsdf_raycast: dirs (R,3)")
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    if blocks is not None:
+        _tsdf_blocks_args(blocks, cap_blocks)
+    dev, F, R = table.device, poses.shape[0], dirs.shape[0]
+    with torch.cuda.device(dev):
+        if out is None:
+            out = (torch.empty(F, R, device=dev, dtype=torch.float32), torch.empty(F, R, 3, device=dev, dtype=torch.float32),
+                   torch.empty(F, R, device=dev, dtype=torch.int32))
+        rng, nrm, flag = out
+        _chk(rng, torch.float32, "range"), _chk(nrm, torch.float32, "normals"), _chk(flag, torch.int32, "flag")
+        if rng.numel() != F * R or nrm.numel() != 3 * F * R or flag.numel() != F * R:
+            raise ValueError("tsdf_raycast: range (F,R), normals (F,R,3), flag (F,R)")
+        n = F * R
+        _lib.check(_lib.load().dpm_tsdf_raycast(
+            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), None if blocks is None else _ptr(blocks),
+            0 if blocks is None else int(cap_blocks), _ptr(poses) if F else None, F, _ptr(dirs) if R else None, R, lo, hi, h,
+            int(min_count), _ptr(rng) if n else None, _ptr(nrm) if n else None, _ptr(flag) if n else None, _stream(table)),
+            "dpm_tsdf_raycast")
+    return rng, nrm, flag
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Scan Context descriptors and their exhaustive search (csrc/scan_context.hip; loop_closure.py is the caller)
 # ------------------------------------------------------------------------------------------------------------

@@ -24,6 +24,15 @@ lookups only.  `TsdfTracker` is frame-to-model odometry on one map: predict, reg
 pose; a failed registration writes nothing.  The plane form is the one to register against: in a band fed by one plane its
 field is exactly linear, while the ray form's is not a distance off the ray's axis.
 
+`TsdfMap.raycast` looks at the map the way the sensor does: per pose and ray the range at which the field changes sign between
+two samples that both have a value, the unit normal there in the SENSOR frame and a flag (MISS, HIT from free space, BACK out of
+the back of a surface); one launch for any number of poses, lookups only.  An occupied-block set (the 8 x 8 x 8 blocks that hold
+a qualified voxel), built on first use and dropped by every write, lets empty space cost one probe per block entered; the bytes
+are those of `skip=False`.  `TsdfMap.render` compacts the HIT rays of one pose into a frame with ray indices and normals that
+`integrate(..., normals=)`, `register`, ScanContext and `transform_frames` take as they are; `TsdfTracker.predicted` renders at
+the predicted pose.  The step is fixed (no sphere tracing: the field is clamped at the truncation), a crossing needs two valued
+samples in a row, so sparse maps miss, and BACK ends the ray.
+
 LIMITS: carving reaches only voxels that exist and claims none; no weight cap or decay; the frame's pose is the origin of every
 ray (no per-point origins for sweeps that are not deskewed); the normals of the plane form are the caller's (or dpm_point_normals
 of the frame alone, `normals=<radius>`); marching tetrahedra, not marching cubes; the voxels live on the device (nothing is
@@ -109,6 +118,19 @@ def write_ply(path, vertices, faces=None, normals=None) -> None:
             out.write(rec.tobytes())
 
 
+class TsdfCast(NamedTuple):
+    """what `TsdfMap.raycast` saw, on the device: per pose and ray the range along the ray (metres), the unit normal in the
+    SENSOR frame (towards the field's positive side) and a flag -- MISS 0: no crossing, range and normal zeros; HIT 1: from free
+    space into a surface; BACK 2: out of the back of one"""
+    range: torch.Tensor      # (F,R) float32
+    normals: torch.Tensor    # (F,R,3) float32
+    flag: torch.Tensor       # (F,R) int32
+
+
+MISS, HIT, BACK = ops.TSDF_MISS, ops.TSDF_HIT, ops.TSDF_BACK
+BLOCKS_OVERFLOW = "the occupied-block set is full (max_blocks={}): ray-casts with skip=True are undefined; raise max_blocks"
+
+
 class TsdfMap(_HashedMap):
     """A TSDF of `max_voxels` slots (a power of two) with voxels of `voxel_size` metres.  truncation (default 3 voxel_size, at
     most 64 m): how far before and behind a return its ray is sampled, and the clamp of the distance; step (default
@@ -122,7 +144,7 @@ class TsdfMap(_HashedMap):
 
     def __init__(self, voxel_size: float = 0.2, truncation: Optional[float] = None, step: Optional[float] = None,
                  max_voxels: int = 1 << 22, min_range: float = 0.0, max_range: float = 100.0, origin=None, device=None,
-                 distance: str = "ray", cos_min: float = 0.0):
+                 distance: str = "ray", cos_min: float = 0.0, max_blocks: Optional[int] = None):
         if distance not in ("ray", "plane"):
             raise ValueError("distance is 'ray' or 'plane'")
         if not 0.0 <= float(cos_min) <= 1.0:
@@ -133,6 +155,11 @@ class TsdfMap(_HashedMap):
         if max_voxels < 2 or max_voxels > 1 << 24 or max_voxels & (max_voxels - 1):
             raise ValueError("max_voxels: a power of two in [2, 2^24]")
         self.voxel_size, self.max_voxels = float(voxel_size), int(max_voxels)
+        self.max_blocks = max(2, self.max_voxels // 2) if max_blocks is None else int(max_blocks)
+        if self.max_blocks < 2 or self.max_blocks > 1 << 24 or self.max_blocks & (self.max_blocks - 1):
+            raise ValueError("max_blocks: a power of two in [2, 2^24]")
+        self._blocks = {}     # min_count (count units) -> the occupied-block set of the table as it is; every write drops it
+        self._ray_tables = {}   # id of a LidarModel's direction table -> (the table, its copy on the device): uploaded once
         self.truncation = 3.0 * self.voxel_size if truncation is None else float(truncation)
         self.step = self.voxel_size / 2.0 if step is None else float(step)
         self.min_range, self.max_range = float(min_range), float(max_range)
@@ -143,6 +170,7 @@ class TsdfMap(_HashedMap):
 
     # -- plumbing (_ready, _list and _header are odometry._HashedMap's)
     def _new(self):
+        self._blocks = {}
         return ops.tsdf_new(self.max_voxels, self.device)
 
     def _rays(self):
@@ -198,6 +226,7 @@ class TsdfMap(_HashedMap):
         self._ready(xyz.device, pose)
         if xyz.shape[0] == 0:
             return self
+        self._blocks = {}
         if self.distance == "ray":
             ops.tsdf_integrate(*self._map(), xyz, count, _pose_tensor(pose, self.device), *self._rays())
         else:
@@ -219,6 +248,7 @@ class TsdfMap(_HashedMap):
         if rows.numel() == 0:
             return self
         poses = poses.to(device=self.device, dtype=torch.float64).contiguous()
+        self._blocks = {}
         if self.distance == "ray":
             ops.tsdf_integrate_frames(*self._map(), store, lengths, rows, poses, *self._rays())
         else:
@@ -239,6 +269,7 @@ class TsdfMap(_HashedMap):
         w, g = self._carve_args(weight, margin)
         if self.table is None or xyz.shape[0] == 0:      # an empty map holds nothing to carve
             return self
+        self._blocks = {}
         ops.tsdf_carve(*self._map(), xyz, count, _pose_tensor(pose, self.device), *self._rays(), w, g)
         return self
 
@@ -248,6 +279,7 @@ class TsdfMap(_HashedMap):
         w, g = self._carve_args(weight, margin)
         if self.table is None or rows.numel() == 0:
             return self
+        self._blocks = {}
         ops.tsdf_carve_frames(*self._map(), store, lengths, rows, poses.to(device=self.device, dtype=torch.float64).contiguous(),
                               *self._rays(), w, g)
         return self
@@ -276,6 +308,11 @@ class TsdfMap(_HashedMap):
         n = self.overflow()
         if n:
             raise ValueError(OVERFLOW.format(self.max_voxels) + f" ({n} samples)")
+        for blocks in self._blocks.values():          # one read per cached block set
+            augment._SYNCS[0] += 1
+            n = int(blocks[:4].view(torch.int32).item()) & 0xFFFFFFFF
+            if n:
+                raise ValueError(BLOCKS_OVERFLOW.format(self.max_blocks) + f" ({n} voxels)")
         return self
 
     def _extract(self, fn, *args):
@@ -366,6 +403,89 @@ class TsdfMap(_HashedMap):
         res = IcpResult(out[0].reshape(1, 4, 4), *out[1:5])
         return (res, out[5:]) if debug else res
 
+    # -- looking at the map as the sensor does: lookups only, no host synchronisation
+    def blocks(self, min_count: float = 1) -> torch.Tensor:
+        """the occupied-block set of the table as it is now for `min_count` (full-weight samples): built on first use, kept
+        until a method writes the table.  `check()` reports a set that ran out of room (max_blocks)."""
+        mc = self._min_count(min_count)
+        if self.table is None:
+            raise ValueError("blocks: the map holds no table yet")
+        if mc not in self._blocks:
+            self._blocks[mc] = ops.tsdf_blocks(self.table, self.max_voxels, mc, self.max_blocks)
+        return self._blocks[mc]
+
+    def _cast_device(self, dirs=None):
+        if self.device is not None:
+            return torch.device(self.device)
+        return dirs.device if dirs is not None and dirs.is_cuda else augment._device()
+
+    def _ray_table(self, model) -> torch.Tensor:
+        """model.directions() on the device, uploaded at its first use: later casts of the model copy nothing"""
+        table = model.directions()
+        held = self._ray_tables.get(id(table))
+        if held is None or held[0] is not table:      # a map lives on one device
+            held = self._ray_tables[id(table)] = (table, torch.from_numpy(table).to(self._cast_device()))
+        return held[1]
+
+    def raycast(self, poses, rays, min_range: Optional[float] = None, max_range: Optional[float] = None,
+                step: Optional[float] = None, min_count: float = 1, skip: bool = True) -> TsdfCast:
+        """what a sensor at each of `poses` ((4,4) or (F,4,4), sensor -> world; numpy, or a tensor -- on the GPU it is read
+        there) sees in the map along `rays`: a lidar_sim.LidarModel (its directions(), and its range limits as the defaults), or
+        (R,3) float32 unit directions in the sensor frame (numpy or tensor; the defaults are then the map's min_range and
+        max_range).  The ray is sampled every `step` metres (default: the map's) from min_range to max_range and ends at the
+        first sign change between two samples that both have a value (all 8 voxels round them hold min_count full-weight
+        samples) -> TsdfCast(range (F,R), normals (F,R,3) in the sensor frame, flag (F,R): MISS / HIT / BACK).  skip: pass
+        empty space by the occupied-block set (the same bytes as skip=False, which looks up every sample).  One launch (and the
+        set's two at first use).  An unallocated map gives MISS everywhere."""
+        mc = self._min_count(min_count)
+        if hasattr(rays, "directions"):
+            lo, hi, dirs = rays.min_range, rays.max_range, self._ray_table(rays)
+        else:
+            lo, hi, dirs = self.min_range, self.max_range, rays
+        lo, hi, h = ops.tsdf_cast_args(lo if min_range is None else min_range, hi if max_range is None else max_range,
+                                       self.step if step is None else step)
+        if not isinstance(poses, torch.Tensor):
+            poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64))
+        if poses.dim() == 2:
+            poses = poses[None]
+        if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] > 65535:
+            raise ValueError("raycast: poses (4,4) or (F,4,4), F <= 65535")
+        if not isinstance(dirs, torch.Tensor):
+            dirs = torch.from_numpy(np.ascontiguousarray(dirs))
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.dtype != torch.float32:
+            raise ValueError("raycast: rays is a LidarModel or (R,3) float32 directions")
+        dev = self._cast_device(dirs)
+        poses, dirs = poses.to(device=dev, dtype=torch.float64).contiguous(), dirs.to(dev).contiguous()
+        F, R = poses.shape[0], dirs.shape[0]
+        if self.table is None:
+            return TsdfCast(torch.zeros(F, R, device=dev), torch.zeros(F, R, 3, device=dev), torch.zeros(F, R, dtype=torch.int32, device=dev))
+        return TsdfCast(*ops.tsdf_raycast(*self._map(), self.blocks(min_count) if skip else None, self.max_blocks, poses, dirs,
+                                          lo, hi, h, mc))
+
+    def render(self, pose, model, min_count: float = 1):
+        """the scan `model` (a lidar_sim.LidarModel) would take of the map from `pose` (4,4) -> (augment.PointCloud, normals):
+        xyz = direction * range in the SENSOR frame of the HIT rays only, compacted in ray order on the device (the frame's
+        count stays there); idx = the ray index, so ring and column stay recoverable as for the simulator's frames; R, T = the
+        pose when it is on the host; normals (rays,3) float32 = the matching rows, zeros past the count.  Taken as it is by
+        ScanContext, transform_frames, `integrate(..., normals=)` and `register`."""
+        if tuple(np.shape(pose)) != (4, 4):
+            raise ValueError("render: pose (4,4)")
+        cast = self.raycast(pose, model, min_count=min_count)
+        dev = cast.range.device
+        dirs = self._ray_table(model)
+        n = dirs.shape[0]
+        host = None if isinstance(pose, torch.Tensor) else np.asarray(pose, np.float64)
+        pcd = augment.PointCloud.from_buffers(dirs * cast.range[0][:, None], torch.arange(n, device=dev, dtype=torch.int32),
+                                              torch.full((1,), n, device=dev, dtype=torch.int32),
+                                              R=None if host is None else host[:3, :3].copy(),
+                                              T=None if host is None else host[:3, 3:].copy(), host_n=None)
+        if n == 0:
+            return pcd, cast.normals[0]
+        pcd = augment.mask_select(pcd, u=(cast.flag[0] == HIT).to(torch.float32), ratio=0.5)    # keeps u >= ratio, in ray order
+        kept = torch.arange(n, device=dev) < pcd.count                                           # rows past the count are not defined
+        rows = torch.where(kept, pcd.idx.long(), torch.zeros_like(kept, dtype=torch.long))
+        return pcd, cast.normals[0][rows] * kept[:, None]
+
 
 class TsdfStep(NamedTuple):
     """what `TsdfTracker.step` did with a frame: the registration's status, fitness, rmse and iterations on the host, and whether
@@ -404,6 +524,13 @@ class TsdfTracker:
         if len(self.poses) < 2:
             return self.poses[-1].copy()
         return self.poses[-1] @ (np.linalg.inv(self.poses[-2]) @ self.poses[-1])
+
+    def predicted(self, model):
+        """the scan the map predicts for the next frame: `TsdfMap.render` at the constant-velocity prediction, with the
+        tracker's min_count -> (augment.PointCloud, normals).  `step` does not use it."""
+        if not self.poses:
+            raise ValueError("predicted: no frame yet")
+        return self.map.render(self.predict(), model, min_count=self.min_count)
 
     def step(self, pcd, normals=None, pose=None):
         """one frame (an augment.PointCloud, or xyz (N,3) float32 on the GPU; normals as `TsdfMap.integrate` takes them) ->

@@ -1250,6 +1250,40 @@ int dpm_tsdf_register(const void *map, int cap_vox, double voxel, const double *
                       const double *stage_max_dist, const int32_t *stage_max_iter, int n_stages, double kernel_scale,
                       double tol_rot, double tol_trans, double *pose, float *fitness, float *rmse, int32_t *iterations,
                       int32_t *status, int32_t *debug_flag, double *debug_system, void *workspace, dpm_stream_t stream);
+/* RAY-CASTING THE FIELD: what a sensor at a pose would see in the map.  Lookups only; one launch for any F (grid y = pose), no
+ * host synchronisation, capturable.  poses (F,16) fp64 and dirs (R,3) fp32 on the device; dirs are in the SENSOR frame, unit
+ * length expected and not renormalised.  range (F,R) fp32, normals (F,R,3) fp32, flag (F,R) int32.  F in [0, 65535]; F = 0 or
+ * R = 0 is a no-op.  In fp32, every operation rounded once, no fused multiply-add outside u's chain, divisions and square roots
+ * correctly rounded, with P the pose as above ((float)R and o = (float)(t - origin)):
+ *     u[a] = fma(R[a][2], dz, fma(R[a][1], dy, R[a][0] * dx))        (the point's chain without the translation);
+ *     h = (float)step,  t0 = (float)min_range,  K = floor((max_range - min_range) / step) + 1 on the host in double;
+ *     sample k = 0 .. K-1:  t_k = t0 + (float)k * h,  p_k[a] = o[a] + u[a] * t_k;  its value d_k and gradient g_k are those of
+ *     THE FIELD AT A POINT above at p_k: a sample HAS A VALUE only when its cell is valid and all 8 corners are qualified.
+ * With s(d) = d > 0 the ray ENDS at the smallest k >= 1 for which samples k-1 and k both have a value and s(d_{k-1}) != s(d_k); a
+ * sample without a value between two signs is no crossing.  flag = 1 (HIT) when s(d_{k-1}): from free space into the surface;
+ * flag = 2 (BACK) otherwise: out of the back of a surface.  In both cases
+ *     f = d_{k-1} / (d_{k-1} - d_k),   range = t_{k-1} + f * h,   g[a] = g_{k-1}[a] + f * (g_k[a] - g_{k-1}[a]),
+ *     len = sqrt((gx*gx + gy*gy) + gz*gz),   m[a] = g[a] / len   (zeros unless len > 0 and finite),
+ *     normal[j] = (R[0][j] * m[0] + R[1][j] * m[1]) + R[2][j] * m[2]:
+ * the unit gradient turned back into the SENSOR frame (the frame dpm_tsdf_integrate_planes takes normals in), pointing to the
+ * field's positive side.  No crossing within the K samples: flag = 0 (MISS), range and normal zeros.  A NaN or zero direction,
+ * and a ray that leaves the 21 bits, never get a value: MISS.  An empty table gives MISS everywhere.
+ * DPM_EINVAL: step <= 0, min_range < 0, max_range < min_range, K > 65536, min_count < 1.
+ *
+ * blocks: NULL (the plain form: the 8 lookups of every sample), or an occupied-block set built by dpm_tsdf_blocks FROM THIS
+ * TABLE AS IT IS NOW AND WITH THIS min_count.  The set holds the keys (x >> 3, y >> 3, z >> 3) (3 x 18 bits, packed as a voxel
+ * key) of the 8 x 8 x 8 blocks that hold a qualified voxel: dpm_tsdf_blocks_bytes(cap_blocks) = 256 + 8 cap_blocks bytes, 16-byte
+ * aligned, cap_blocks a power of two in [2, 2^24]: a 256-byte header (word 0: claims that found no room; the set is defined
+ * only while it is zero) and an open-addressing set with the table's hash and probing.  dpm_tsdf_blocks clears it and claims,
+ * one lane per slot of the table (two launches, capturable, integer compare-and-swap only): membership is a function of the
+ * table's content and min_count alone.  A sample whose base voxel i0 lies in a block the set does not hold cannot have a value
+ * (its corner (0,0,0) is not qualified), so the marcher skips its 8 lookups; every sample is still formed, none is stepped
+ * over, and the outputs equal those of the plain form byte for byte. */
+size_t dpm_tsdf_blocks_bytes(int cap_blocks);
+int dpm_tsdf_blocks(const void *map, int cap_vox, int min_count, void *blocks, int cap_blocks, dpm_stream_t stream);
+int dpm_tsdf_raycast(const void *map, int cap_vox, double voxel, const double *origin, const void *blocks, int cap_blocks,
+                     const double *poses, int F, const float *dirs, int R, double min_range, double max_range, double step,
+                     int min_count, float *range, float *normals, int32_t *flag, dpm_stream_t stream);
 
 /* ---------------------------------------------------------------- geometric loop closure ---- */
 
