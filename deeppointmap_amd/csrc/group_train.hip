@@ -19,6 +19,10 @@
 // zeros) and keeps per-lane partial sums of dgamma, dbeta and dW_rel.  Those leave the kernel as one partial per wave, and
 // reduce_kernel adds the partials in wave order.  Which points a wave owns depends on the shapes only, so two runs give identical
 // bytes.
+//
+// idx entries outside [0, N) are read as clamped, min(max(idx, 0), N - 1), in every kernel that reads idx, as the inference
+// kernels do.  Rows of P and xyz that idx never names are loaded by the backward (every point's row is) but enter no result: they
+// may hold anything, NaN included.
 #include "dpm_common.h"
 #include "workspace.h"
 

@@ -1486,7 +1486,9 @@ def group_train(P: torch.Tensor, xyz: torch.Tensor, centers: torch.Tensor, idx: 
     """The grouping layer for training: out[b,s,c] = max_k relu(LN_c(P[b, idx[b,s,k]] + W_rel (xyz[idx] - centre) / radius)),
     differentiable with respect to P, W_rel (Cout,3), gamma and beta (LayerNorm eps 1e-5, biased variance); the geometry gets
     no gradient.  P = fea W_f^T + b is the caller's, under autograd.  Forward and backward run in csrc/group_train.hip; what is
-    saved is P and a byte per output element, and two runs give identical bytes.  ValueError (naming `layer`) for a width
+    saved is P and a byte per output element, and two runs give identical bytes.  idx entries outside [0, N) are read as
+    clamped to it, as the inference kernels do.  Rows of P and xyz that idx never names are not read into any result and may
+    hold anything; their dP rows are exact zeros.  ValueError (naming `layer`) for a width
     outside GROUP_TRAIN_COUT or a neighbour count outside GROUP_TRAIN_K.  keep_slots: a list that receives the winning slots
     (group_train_winners turns them into point indices)."""
     return _GroupTrain.apply(P, W_rel, gamma, beta, xyz, centers, idx, radius, layer, keep_slots)
