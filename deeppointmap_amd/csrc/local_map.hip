@@ -32,7 +32,8 @@
 //            under poses[f] by the claim's rule, owner word (stamps[f] << 32) | i.  With a centre, a row is offered only when
 //            its voxel passes prune's test around it: the content is that of the inserts, in any order, followed by the
 //            prune, and the voxels the prune would drop never ask for a slot.  `outside` counts before the filter, `overflow`
-//            after it.
+//            after it.  One frame and the list are the two sources of csrc/scan_source.h; what claim and commit do with a
+//            row is written once, insert_row<COMMIT>, under lm_insert_kernel and lm_insert_frames_kernel.
 //
 // Registration: per iteration two launches, no host synchronisation, capturable on one stream.
 //   accumulate: four lanes per query, queries in ROW order.  The query is moved by the device pose rounded to fp32; lane l
@@ -67,6 +68,7 @@
 // A match whose voxel has no such plane contributes nothing and is not counted.
 #include "cell_grid.h"
 #include "gn_one.h"
+#include "scan_source.h"
 #include "sym3_jacobi.h"
 #include "voxel_hash.h"
 
@@ -124,7 +126,7 @@ __device__ __forceinline__ bool voxel_within(const Map &M, unsigned long long ke
     return (dx * dx + dy * dy) + dz * dz <= r2;
 }
 
-struct Frame {
+struct Frame {   // one frame as the insert and accumulate kernels take it (their code depends on this layout)
     const float *xyz;        // (cap,3)
     const int32_t *idx;      // (cap,) original row numbers
     const int32_t *count;    // (1,)
@@ -147,22 +149,44 @@ __device__ __forceinline__ bool row_cell(const Map &M, const GnPose32 &P, float 
     return true;
 }
 
-template <bool COMMIT>
-__global__ __launch_bounds__(LM_BLOCK) void lm_insert_kernel(Map M, Frame F, const double *pose, unsigned stamp, float lo2,
-                                                             float hi2) {
-    const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
-    const int n = min(max(F.count[0], 0), F.cap);
-    if (i >= n) return;
-    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
+// What the local map adds to a source of rows (csrc/scan_source.h): the owner word of row i and the filter of a rebuild.
+// One frame: stamped `stamp`, the low half its ORIGINAL row number idx[i]; no filter, so that test folds away.
+struct FrameOwner {
+    const int32_t *idx;   // (cap,)
+    unsigned stamp;
+    __device__ __forceinline__ unsigned long long word(int i) const { return ((unsigned long long)stamp << 32) | (unsigned)idx[i]; }
+    __device__ __forceinline__ const double *centre() const { return nullptr; }
+};
+
+// Entry f of a list: stamped stamps[f], the low half the column i; with a centre, a row is offered only when its voxel passes
+// prune's test around it.
+struct StoredRows {
+    StoredFrames rows;
+    const uint32_t *stamps;    // (F,)
+    const double *centre_;     // (16,) or NULL: no filter
+    __device__ __forceinline__ unsigned long long word(int i) const {
+        return ((unsigned long long)stamps[blockIdx.y] << 32) | (unsigned)i;
+    }
+    __device__ __forceinline__ const double *centre() const { return centre_; }
+};
+
+// Claim (!COMMIT) or commit of row i of `rows`, opened as o, owned as W says: what both insert kernels do with a row.
+template <bool COMMIT, typename Src, typename Owner>
+__device__ __forceinline__ void insert_row(const Map &M, const Src &rows, const SourceRows &o, int i, const Owner &W, float lo2,
+                                           float hi2, float r2) {
+    const GnPose32 P = gn_load_pose(o.pose, M.ox, M.oy, M.oz);
+    float x, y, z;
+    rows.point(o, i, x, y, z);
     unsigned long long key;
     int sub;
     float q[3];
     bool outside;
-    if (!row_cell(M, P, F.xyz[3 * (size_t)i], F.xyz[3 * (size_t)i + 1], F.xyz[3 * (size_t)i + 2], lo2, hi2, key, sub, q, outside)) {
+    if (!row_cell(M, P, x, y, z, lo2, hi2, key, sub, q, outside)) {
         if (!COMMIT && outside) atomicAdd(&M.hdr()->outside, 1u);
         return;
     }
-    const unsigned long long word = ((unsigned long long)stamp << 32) | (unsigned)F.idx[i];
+    if (W.centre() && !voxel_within(M, key, W.centre(), r2)) return;   // `outside` counts before the filter, `overflow` after it
+    const unsigned long long word = W.word(i);
     if (!COMMIT) {
         const int slot = claim_slot(M.keys(M.half), M.cap_vox, key);
         if (slot < 0) {
@@ -178,52 +202,26 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_insert_kernel(Map M, Frame F, con
     }
 }
 
-// a list of stored frames: row frames[f] of a channel-major store under poses[f], stamped stamps[f]
-struct FrameList {
-    const float *store;        // (capacity,3,P)
-    const int32_t *lengths;    // (capacity,)
-    int capacity, P;
-    const int32_t *frames;     // (F,) rows of the store
-    const double *poses;       // (F,16)
-    const uint32_t *stamps;    // (F,)
-    const double *centre;      // (16,) or NULL: no filter
-};
-
-// lm_insert_kernel over a list: blockIdx.y the list entry, x over the columns.  Hundreds of entries offer points to the same
-// sub-cells; reading the owner word first and skipping an offer it already beats gave the same bytes and no time
-// (profiles/local_map_rebuild_bench.md), so every offer is one atomicMin.
+// One frame.  The kernel's arguments are the parent form's, in its order, and not the source as one struct: with the pose and the
+// stamp inside the source the claim was slower on small frames (profiles/scan_source_isa.md).  The rows are read through OneFrame.
 template <bool COMMIT>
-__global__ __launch_bounds__(LM_BLOCK) void lm_insert_frames_kernel(Map M, FrameList L, float lo2, float hi2, float r2) {
-    const int f = blockIdx.y, i = blockIdx.x * LM_BLOCK + threadIdx.x;
-    const int row = L.frames[f];
-    if ((unsigned)row >= (unsigned)L.capacity) return;   // checked on the host where the list is there; never read out of bounds
-    const int n = min(max(L.lengths[row], 0), L.P);
-    if (i >= n) return;
-    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
-    const float *p = L.store + (size_t)row * 3 * L.P + i;
-    unsigned long long key;
-    int sub;
-    float q[3];
-    bool outside;
-    if (!row_cell(M, P, p[0], p[L.P], p[2 * (size_t)L.P], lo2, hi2, key, sub, q, outside)) {
-        if (!COMMIT && outside) atomicAdd(&M.hdr()->outside, 1u);
-        return;
-    }
-    if (L.centre && !voxel_within(M, key, L.centre, r2)) return;
-    const unsigned long long word = ((unsigned long long)L.stamps[f] << 32) | (unsigned)i;
-    if (!COMMIT) {
-        const int slot = claim_slot(M.keys(M.half), M.cap_vox, key);
-        if (slot < 0) {
-            atomicAdd(&M.hdr()->overflow, 1u);
-            return;
-        }
-        atomicMin(&M.owner(M.half)[(size_t)slot * M.S + sub], word);
-    } else {
-        const int slot = find_slot(M.keys(M.half), M.cap_vox, key);
-        if (slot < 0) return;   // counted as overflow by claim
-        const size_t c = (size_t)slot * M.S + sub;
-        if (M.owner(M.half)[c] == word) M.pts(M.half)[c] = make_float4(q[0], q[1], q[2], 0.f);
-    }
+__global__ __launch_bounds__(LM_BLOCK) void lm_insert_kernel(Map M, Frame F, const double *pose, unsigned stamp, float lo2,
+                                                             float hi2) {
+    const OneFrame S{F.xyz, F.count, F.cap, pose};
+    SourceRows o;
+    const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
+    if (!S.open(o) || i >= o.n) return;
+    insert_row<COMMIT>(M, S, o, i, FrameOwner{F.idx, stamp}, lo2, hi2, 0.f);
+}
+
+// A list of stored frames.  Hundreds of entries offer points to the same sub-cells; reading the owner word first and skipping an
+// offer it already beats gave the same bytes and no time (profiles/local_map_rebuild_bench.md), so every offer is one atomicMin.
+template <bool COMMIT>
+__global__ __launch_bounds__(LM_BLOCK) void lm_insert_frames_kernel(Map M, StoredRows L, float lo2, float hi2, float r2) {
+    SourceRows o;
+    const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
+    if (!L.rows.open(o) || i >= o.n) return;   // one test, not two returns: the form that was timed (profiles/scan_source_isa.md)
+    insert_row<COMMIT>(M, L.rows, o, i, L, lo2, hi2, r2);
 }
 
 // one thread per slot of the current half; survivors move to the other half (cleared before this launch)
@@ -470,17 +468,14 @@ extern "C" int dpm_local_map_insert(void *map, int cap_vox, int subdiv, int half
                                     const double *pose, unsigned stamp, double min_range, double max_range,
                                     dpm_stream_t stream) {
     DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
-    DPM_CHECK_ARG(xyz && idx && count && pose && cap >= 0 && stamp < 0xFFFFFFFFu);
-    DPM_CHECK_ARG(min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
-    if (cap == 0) return DPM_OK;
+    DPM_CHECK_ARG(idx && stamp < 0xFFFFFFFFu && range_ok(min_range, max_range));
     const Map M = make_map(map, cap_vox, subdiv, half, voxel, origin);
     const Frame F{xyz, idx, count, cap};
     const float lo2 = (float)(min_range * min_range), hi2 = (float)(max_range * max_range);
-    hipLaunchKernelGGL(lm_insert_kernel<false>, dim3(dpm_cdiv(cap, LM_BLOCK)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, F,
-                       pose, stamp, lo2, hi2);
-    hipLaunchKernelGGL(lm_insert_kernel<true>, dim3(dpm_cdiv(cap, LM_BLOCK)), dim3(LM_BLOCK), 0, (hipStream_t)stream, M, F,
-                       pose, stamp, lo2, hi2);
-    return dpm_launch_status();
+    return source_launch(OneFrame{xyz, count, cap, pose}, 1, LM_BLOCK, [&](dim3 grid) {
+        hipLaunchKernelGGL(lm_insert_kernel<false>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, F, pose, stamp, lo2, hi2);
+        hipLaunchKernelGGL(lm_insert_kernel<true>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, F, pose, stamp, lo2, hi2);
+    });
 }
 
 extern "C" int dpm_local_map_prune(void *map, int cap_vox, int subdiv, int half, double voxel, const double *origin,
@@ -501,19 +496,16 @@ extern "C" int dpm_local_map_insert_frames(void *map, int cap_vox, int subdiv, i
                                            const double *centre, double radius, double min_range, double max_range,
                                            dpm_stream_t stream) {
     DPM_CHECK_ARG(map_ok(map, cap_vox, subdiv) && geometry_ok(half, voxel, origin));
-    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
-    DPM_CHECK_ARG(min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
-    DPM_CHECK_ARG(!centre || (radius >= 0.0 && radius < 1e18));
-    if (F == 0) return DPM_OK;
-    DPM_CHECK_ARG(store && lengths && frames && poses && stamps);
+    DPM_CHECK_ARG(range_ok(min_range, max_range) && (!centre || (radius >= 0.0 && radius < 1e18)));
+    DPM_CHECK_ARG(F == 0 || stamps);   // an empty list may come with null pointers
     const Map M = make_map(map, cap_vox, subdiv, half, voxel, origin);
-    const FrameList L{store, lengths, capacity, P, frames, poses, stamps, centre};
+    const StoredRows L{{store, lengths, capacity, P, frames, poses}, stamps, centre};
     const float lo2 = (float)(min_range * min_range), hi2 = (float)(max_range * max_range);
     const float r2 = centre ? (float)(radius * radius) : 0.f;
-    const dim3 grid(dpm_cdiv(P, LM_BLOCK), F);
-    hipLaunchKernelGGL(lm_insert_frames_kernel<false>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, L, lo2, hi2, r2);
-    hipLaunchKernelGGL(lm_insert_frames_kernel<true>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, L, lo2, hi2, r2);
-    return dpm_launch_status();
+    return source_launch(L.rows, F, LM_BLOCK, [&](dim3 grid) {
+        hipLaunchKernelGGL(lm_insert_frames_kernel<false>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, L, lo2, hi2, r2);
+        hipLaunchKernelGGL(lm_insert_frames_kernel<true>, grid, dim3(LM_BLOCK), 0, (hipStream_t)stream, M, L, lo2, hi2, r2);
+    });
 }
 
 namespace {

@@ -22,7 +22,8 @@
 //              Integer atomics only, and integer addition commutes: what a key leads to is the same whatever the order of rows,
 //              frames or launches.  Slot positions are not, and nothing reads them.
 //   frames     the same rule over a list of stored frames: blockIdx.y the list entry, x over the P columns of a channel-major
-//              store (capacity,3,P), as dpm_local_map_insert_frames reads it.
+//              store (capacity,3,P), as dpm_local_map_insert_frames reads it.  Frame and list are the two sources of
+//              csrc/scan_source.h: integrate and carve are one kernel each, ts_integrate_kernel<PLANE, Src>, ts_carve_kernel<Src>.
 //   planes     integrate / frames with the distance to the TANGENT PLANE at the return in place of the distance along the ray
 //              (wrong by about d tan(incidence) for a centre d beside a slanted ray), weighted by the cosine of the incidence.
 //              A normal per row in the SENSOR frame, unit length expected, not renormalised, either sign: (cap,3) beside xyz, or
@@ -63,6 +64,7 @@
 //              (MISS 0, HIT 1, BACK 2).  blocks: the set of 8 x 8 x 8 blocks that hold a qualified voxel, one lane per slot;
 //              the marcher skips the lookups of a sample whose base voxel lies in a block the set does not hold.
 #include "gn_one.h"
+#include "scan_source.h"
 #include "voxel_hash.h"
 
 namespace {
@@ -193,59 +195,26 @@ __device__ __forceinline__ void integrate_ray(const Tsdf &M, const GnPose32 &P, 
     }
 }
 
-__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_kernel(Tsdf M, const float *xyz, const int32_t *count, int cap,
-                                                                const double *pose, Rays R) {
+// The rows of a source (csrc/scan_source.h), one lane each.  Two properties every source keeps: a lane without a row (i >= n) does
+// NOT leave -- it calls integrate_ray with row = false, because the wave walks the samples together for the segmented sum -- and
+// only the WHOLE BLOCK may leave, on a list entry outside the store.  PLANE: normals is the side array beside the source, (cap,3)
+// beside xyz or a store (capacity,P,3) beside the frame store.
+template <bool PLANE, typename Src>
+__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_kernel(Tsdf M, Src S, const float *normals, Rays R, float cos_min) {
+    SourceRows o;
+    if (!S.open(o)) return;
     const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    const int n = min(max(count[0], 0), cap);
-    const bool row = i < n;
-    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
-    integrate_ray<false>(M, P, row, row ? xyz[3 * (size_t)i] : 0.f, row ? xyz[3 * (size_t)i + 1] : 0.f, row ? xyz[3 * (size_t)i + 2] : 0.f, R);
-}
-
-// a list of stored frames: row frames[f] of a channel-major store under poses[f]
-struct TsFrameList {
-    const float *store;        // (capacity,3,P)
-    const int32_t *lengths;    // (capacity,)
-    int capacity, P;
-    const int32_t *frames;     // (F,) rows of the store
-    const double *poses;       // (F,16)
-};
-
-__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_frames_kernel(Tsdf M, TsFrameList L, Rays R) {
-    const int f = blockIdx.y, i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    const int row = L.frames[f];
-    if ((unsigned)row >= (unsigned)L.capacity) return;   // never read out of bounds; the whole block leaves
-    const int n = min(max(L.lengths[row], 0), L.P);
-    const bool has = i < n;
-    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
-    const float *p = L.store + (size_t)row * 3 * L.P + i;
-    integrate_ray<false>(M, P, has, has ? p[0] : 0.f, has ? p[L.P] : 0.f, has ? p[2 * (size_t)L.P] : 0.f, R);
-}
-
-// the plane-distance forms: normals (cap,3) beside xyz, or a store (capacity,P,3) beside the frame store
-__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_planes_kernel(Tsdf M, const float *xyz, const float *normals,
-                                                                       const int32_t *count, int cap, const double *pose, Rays R,
-                                                                       float cos_min) {
-    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    const int n = min(max(count[0], 0), cap);
-    const bool row = i < n;
-    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
-    const float *p = xyz + 3 * (size_t)i, *nr = normals + 3 * (size_t)i;
-    integrate_ray<true>(M, P, row, row ? p[0] : 0.f, row ? p[1] : 0.f, row ? p[2] : 0.f, R, row ? nr[0] : 0.f, row ? nr[1] : 0.f,
-                        row ? nr[2] : 0.f, cos_min);
-}
-
-__global__ __launch_bounds__(TS_BLOCK) void ts_integrate_planes_frames_kernel(Tsdf M, TsFrameList L, const float *normals, Rays R,
-                                                                              float cos_min) {
-    const int f = blockIdx.y, i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    const int row = L.frames[f];
-    if ((unsigned)row >= (unsigned)L.capacity) return;   // never read out of bounds; the whole block leaves
-    const int n = min(max(L.lengths[row], 0), L.P);
-    const bool has = i < n;
-    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
-    const float *p = L.store + (size_t)row * 3 * L.P + i, *nr = normals + ((size_t)row * L.P + i) * 3;
-    integrate_ray<true>(M, P, has, has ? p[0] : 0.f, has ? p[L.P] : 0.f, has ? p[2 * (size_t)L.P] : 0.f, R, has ? nr[0] : 0.f,
-                        has ? nr[1] : 0.f, has ? nr[2] : 0.f, cos_min);
+    const bool row = i < o.n;
+    const GnPose32 P = gn_load_pose(o.pose, M.ox, M.oy, M.oz);
+    float x = 0.f, y = 0.f, z = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    if (row) {
+        S.point(o, i, x, y, z);
+        if constexpr (PLANE) {
+            const float *nr = normals + 3 * S.side(o, i);
+            nx = nr[0], ny = nr[1], nz = nr[2];
+        }
+    }
+    integrate_ray<PLANE>(M, P, row, x, y, z, R, nx, ny, nz, cos_min);
 }
 
 // ---------------------------------------------------------------------------------------------------------- free-space carving
@@ -290,22 +259,17 @@ __device__ __forceinline__ void carve_ray(const Tsdf &M, const GnPose32 &P, floa
     }
 }
 
-__global__ __launch_bounds__(TS_BLOCK) void ts_carve_kernel(Tsdf M, const float *xyz, const int32_t *count, int cap,
-                                                            const double *pose, Rays R, Carve C) {
+// a lane leaves on its own: past the rows of its frame, or with its list entry
+template <typename Src>
+__global__ __launch_bounds__(TS_BLOCK) void ts_carve_kernel(Tsdf M, Src S, Rays R, Carve C) {
+    SourceRows o;
+    if (!S.open(o)) return;
     const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    if (i >= min(max(count[0], 0), cap)) return;
-    const GnPose32 P = gn_load_pose(pose, M.ox, M.oy, M.oz);
-    carve_ray(M, P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], R, C);
-}
-
-__global__ __launch_bounds__(TS_BLOCK) void ts_carve_frames_kernel(Tsdf M, TsFrameList L, Rays R, Carve C) {
-    const int f = blockIdx.y, i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    const int row = L.frames[f];
-    if ((unsigned)row >= (unsigned)L.capacity) return;   // never read out of bounds
-    if (i >= min(max(L.lengths[row], 0), L.P)) return;
-    const GnPose32 P = gn_load_pose(L.poses + 16 * (size_t)f, M.ox, M.oy, M.oz);
-    const float *p = L.store + (size_t)row * 3 * L.P + i;
-    carve_ray(M, P, p[0], p[L.P], p[2 * (size_t)L.P], R, C);
+    if (i >= o.n) return;
+    const GnPose32 P = gn_load_pose(o.pose, M.ox, M.oy, M.oz);
+    float x, y, z;
+    S.point(o, i, x, y, z);
+    carve_ray(M, P, x, y, z, R, C);
 }
 
 __global__ __launch_bounds__(TS_BLOCK) void ts_export_kernel(Tsdf M, unsigned long long *keys, long long *sums, uint32_t *counts,
@@ -673,13 +637,43 @@ inline Tsdf make_tsdf(const void *map, int cap_vox, double voxel, const double *
 
 // the gate and the samples of a ray from the host's doubles; false when they are refused
 inline bool make_rays(double min_range, double max_range, double truncation, double step, Rays &R) {
-    if (!(min_range >= 0.0 && max_range >= min_range && max_range < 1e18)) return false;
+    if (!range_ok(min_range, max_range)) return false;
     if (!(truncation > 0.0 && truncation <= 64.0 && step > 0.0 && (float)step > 0.f && (float)truncation > 0.f)) return false;
     const double n = ceil(truncation / step);
     if (!(n <= (double)MAX_STEPS)) return false;
     R.lo2 = (float)(min_range * min_range), R.hi2 = (float)(max_range * max_range);
     R.tau = (float)truncation, R.h = (float)step, R.n = (int)n;
     return true;
+}
+
+inline bool cos_ok(double cos_min) { return cos_min >= 0.0 && cos_min <= 1.0; }
+
+// the carve's constants from the host's arguments; false when they are refused
+inline bool make_carve(const Rays &R, double max_range, double step, int weight, double margin, Carve &C) {
+    if (!(weight >= 1 && weight <= 65535 && margin >= 0.0 && margin < 1e18 && max_range / step <= 65536.0)) return false;
+    C.add = (long long)weight * (long long)rintf(R.tau * FIX_ONE), C.weight = (unsigned)weight, C.margin = (float)margin;
+    return true;
+}
+
+// the map of an entry point that places points in it
+inline bool field_ok(const void *map, int cap_vox, double voxel, const double *origin) {
+    return table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin);
+}
+
+// the two fusion operations over a source of F entries: one launch, one lane per row
+template <bool PLANE, typename Src>
+int integrate_over(const Tsdf &M, const Src &S, int F, const float *normals, const Rays &R, double cos_min, dpm_stream_t stream) {
+    return source_launch(S, F, TS_BLOCK, [&](dim3 grid) {
+        hipLaunchKernelGGL((ts_integrate_kernel<PLANE, Src>), grid, dim3(TS_BLOCK), 0, (hipStream_t)stream, M, S, normals, R,
+                           (float)cos_min);
+    });
+}
+
+template <typename Src>
+int carve_over(const Tsdf &M, const Src &S, int F, const Rays &R, const Carve &C, dpm_stream_t stream) {
+    return source_launch(S, F, TS_BLOCK, [&](dim3 grid) {
+        hipLaunchKernelGGL(ts_carve_kernel<Src>, grid, dim3(TS_BLOCK), 0, (hipStream_t)stream, M, S, R, C);
+    });
 }
 
 }  // namespace
@@ -700,45 +694,30 @@ extern "C" int dpm_tsdf_init(void *map, int cap_vox, dpm_stream_t stream) {
 extern "C" int dpm_tsdf_integrate(void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
                                   const int32_t *count, int cap, const double *pose, double min_range, double max_range,
                                   double truncation, double step, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(xyz && count && pose && cap >= 0);
     Rays R;
-    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
-    if (cap == 0) return DPM_OK;
-    hipLaunchKernelGGL(ts_integrate_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, origin), xyz, count, cap, pose, R);
-    return dpm_launch_status();
+    DPM_CHECK_ARG(field_ok(map, cap_vox, voxel, origin) && make_rays(min_range, max_range, truncation, step, R));
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    return integrate_over<false>(M, OneFrame{xyz, count, cap, pose}, 1, nullptr, R, 0.0, stream);
 }
 
 extern "C" int dpm_tsdf_integrate_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
                                          const int32_t *lengths, int capacity, int P, const int32_t *frames,
                                          const double *poses, int F, double min_range, double max_range, double truncation,
                                          double step, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     Rays R;
-    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
-    if (F == 0) return DPM_OK;
-    DPM_CHECK_ARG(store && lengths && frames && poses);
-    const TsFrameList L{store, lengths, capacity, P, frames, poses};
-    hipLaunchKernelGGL(ts_integrate_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, origin), L, R);
-    return dpm_launch_status();
+    DPM_CHECK_ARG(field_ok(map, cap_vox, voxel, origin) && make_rays(min_range, max_range, truncation, step, R));
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    return integrate_over<false>(M, StoredFrames{store, lengths, capacity, P, frames, poses}, F, nullptr, R, 0.0, stream);
 }
-
-inline bool cos_ok(double cos_min) { return cos_min >= 0.0 && cos_min <= 1.0; }
 
 extern "C" int dpm_tsdf_integrate_planes(void *map, int cap_vox, double voxel, const double *origin, const float *xyz,
                                          const float *normals, const int32_t *count, int cap, const double *pose, double min_range,
                                          double max_range, double truncation, double step, double cos_min, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(xyz && normals && count && pose && cap >= 0 && cos_ok(cos_min));
     Rays R;
-    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
-    if (cap == 0) return DPM_OK;
-    hipLaunchKernelGGL(ts_integrate_planes_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, origin), xyz, normals, count, cap, pose, R, (float)cos_min);
-    return dpm_launch_status();
+    DPM_CHECK_ARG(field_ok(map, cap_vox, voxel, origin) && make_rays(min_range, max_range, truncation, step, R));
+    DPM_CHECK_ARG(normals && cos_ok(cos_min));
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    return integrate_over<true>(M, OneFrame{xyz, count, cap, pose}, 1, normals, R, cos_min, stream);
 }
 
 extern "C" int dpm_tsdf_integrate_planes_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
@@ -746,54 +725,34 @@ extern "C" int dpm_tsdf_integrate_planes_frames(void *map, int cap_vox, double v
                                                 const int32_t *frames, const double *poses, int F, double min_range,
                                                 double max_range, double truncation, double step, double cos_min,
                                                 dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin) && cos_ok(cos_min));
-    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     Rays R;
-    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R));
-    if (F == 0) return DPM_OK;
-    DPM_CHECK_ARG(store && normals && lengths && frames && poses);
-    const TsFrameList L{store, lengths, capacity, P, frames, poses};
-    hipLaunchKernelGGL(ts_integrate_planes_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, origin), L, normals, R, (float)cos_min);
-    return dpm_launch_status();
-}
-
-// the carve's constants from the host's arguments; false when they are refused
-inline bool make_carve(const Rays &R, double max_range, double step, int weight, double margin, Carve &C) {
-    if (!(weight >= 1 && weight <= 65535 && margin >= 0.0 && margin < 1e18 && max_range / step <= 65536.0)) return false;
-    C.add = (long long)weight * (long long)rintf(R.tau * FIX_ONE), C.weight = (unsigned)weight, C.margin = (float)margin;
-    return true;
+    DPM_CHECK_ARG(field_ok(map, cap_vox, voxel, origin) && make_rays(min_range, max_range, truncation, step, R));
+    DPM_CHECK_ARG((F == 0 || normals) && cos_ok(cos_min));   // an empty list may come with null pointers
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    return integrate_over<true>(M, StoredFrames{store, lengths, capacity, P, frames, poses}, F, normals, R, cos_min, stream);
 }
 
 extern "C" int dpm_tsdf_carve(void *map, int cap_vox, double voxel, const double *origin, const float *xyz, const int32_t *count,
                               int cap, const double *pose, double min_range, double max_range, double truncation, double step,
                               int weight, double margin, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(xyz && count && pose && cap >= 0);
     Rays R;
     Carve C;
-    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R) && make_carve(R, max_range, step, weight, margin, C));
-    if (cap == 0) return DPM_OK;
-    hipLaunchKernelGGL(ts_carve_kernel, dim3(dpm_cdiv(cap, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, origin), xyz, count, cap, pose, R, C);
-    return dpm_launch_status();
+    DPM_CHECK_ARG(field_ok(map, cap_vox, voxel, origin) && make_rays(min_range, max_range, truncation, step, R) &&
+                  make_carve(R, max_range, step, weight, margin, C));
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    return carve_over(M, OneFrame{xyz, count, cap, pose}, 1, R, C, stream);
 }
 
 extern "C" int dpm_tsdf_carve_frames(void *map, int cap_vox, double voxel, const double *origin, const float *store,
                                      const int32_t *lengths, int capacity, int P, const int32_t *frames, const double *poses, int F,
                                      double min_range, double max_range, double truncation, double step, int weight, double margin,
                                      dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
-    DPM_CHECK_ARG(frame_list_ok(capacity, P, F));
     Rays R;
     Carve C;
-    DPM_CHECK_ARG(make_rays(min_range, max_range, truncation, step, R) && make_carve(R, max_range, step, weight, margin, C));
-    if (F == 0) return DPM_OK;
-    DPM_CHECK_ARG(store && lengths && frames && poses);
-    const TsFrameList L{store, lengths, capacity, P, frames, poses};
-    hipLaunchKernelGGL(ts_carve_frames_kernel, dim3(dpm_cdiv(P, TS_BLOCK), F), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, origin), L, R, C);
-    return dpm_launch_status();
+    DPM_CHECK_ARG(field_ok(map, cap_vox, voxel, origin) && make_rays(min_range, max_range, truncation, step, R) &&
+                  make_carve(R, max_range, step, weight, margin, C));
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, origin);
+    return carve_over(M, StoredFrames{store, lengths, capacity, P, frames, poses}, F, R, C, stream);
 }
 
 extern "C" int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long *keys, long long *sums, uint32_t *counts,
@@ -896,7 +855,7 @@ extern "C" int dpm_tsdf_raycast(const void *map, int cap_vox, double voxel, cons
                                 dpm_stream_t stream) {
     DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && origin_ok(origin));
     DPM_CHECK_ARG(!blocks || table_ok(blocks, cap_blocks));
-    DPM_CHECK_ARG(step > 0.0 && min_range >= 0.0 && max_range >= min_range && max_range < 1e18);
+    DPM_CHECK_ARG(step > 0.0 && range_ok(min_range, max_range));
     const double samples = floor((max_range - min_range) / step) + 1.0;
     DPM_CHECK_ARG(samples <= 65536.0 && min_count >= 1 && F >= 0 && F <= 65535 && R >= 0);
     if (F == 0 || R == 0) return DPM_OK;   // nothing to read or write: the pointers may be null

@@ -66,8 +66,3 @@ inline bool origin_ok(const double *origin) {
         if (!(origin[a] > -1e300 && origin[a] < 1e300)) return false;
     return true;
 }
-
-// F rows of a channel-major store (capacity,3,P); the pointers are checked by the caller, after its F == 0 return
-inline bool frame_list_ok(int capacity, int P, int F) {
-    return capacity >= 1 && P >= 1 && (size_t)capacity * 3 * (size_t)P < ((size_t)1 << 40) && F >= 0 && F <= 65535;
-}

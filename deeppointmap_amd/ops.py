@@ -2235,10 +2235,12 @@ def _local_map_args(table: torch.Tensor, cap_vox: int, subdiv: int, origin=None)
 
 
 # what the local map and the TSDF map (below) take alike: a frame, a list of stored frames, one registration problem
-def _frame_args(what, xyz, count, pose):
-    _chk(xyz, torch.float32, "xyz"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or count.numel() != 1 or pose.numel() != 16:
-        raise ValueError(f"{what}: xyz (cap,3), count (1,), pose (4,4)")
+def _frame_args(what, xyz, count, pose, idx=None):
+    _chk(xyz, torch.float32, "xyz"), idx is None or _chk(idx, torch.int32, "idx"), _chk(count, torch.int32, "count")
+    _chk(pose, torch.float64, "pose")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or (idx is not None and idx.shape != xyz.shape[:1]) or count.numel() != 1 \
+            or pose.numel() != 16:
+        raise ValueError(f"{what}: xyz (cap,3), {'' if idx is None else 'idx (cap,), '}count (1,), pose (4,4)")
 
 
 def _frame_list_args(what, store, lengths, frames, poses) -> int:
@@ -2249,6 +2251,26 @@ def _frame_list_args(what, store, lengths, frames, poses) -> int:
             or frames.dim() != 1 or poses.numel() != 16 * F or F > 65535:
         raise ValueError(f"{what}: store (capacity,3,P), lengths (capacity,), frames (F,) with F <= 65535, poses (F,4,4)")
     return F
+
+
+# The two sources of rows (csrc/scan_source.h) as the C entry points take them: the first pointer, then the rest; an operation's
+# per-row side arrays (normals, idx) sit between the two, and a list's F follows its per-entry arrays, in the operation's tail.
+def _one_frame(what, xyz, count, pose, idx=None):
+    _frame_args(what, xyz, count, pose, idx)
+    return _ptr(xyz), (_ptr(count), xyz.shape[0], _ptr(pose))
+
+
+def _stored_frames(what, store, lengths, frames, poses):
+    F = _frame_list_args(what, store, lengths, frames, poses)
+    return (_ptr(store), (_ptr(lengths), store.shape[0], store.shape[2], _ptr(frames), _ptr(poses))), F
+
+
+def _source_call(entry, table, head, o, source, side, tail):
+    """lib.<entry>(table, *head, origin, the source with its side arrays in their place, *tail, stream)"""
+    first, rest = source
+    with torch.cuda.device(table.device):
+        _lib.check(getattr(_lib.load(), entry)(_ptr(table), *head, ctypes.addressof(o), first, *side, *rest, *tail, _stream(table)),
+                   entry)
 
 
 def _register_one(what, entry, head, table, xyz, count, init, schedule, kernel_scale, tol_rot, tol_trans, debug, row_dtypes,
@@ -2292,13 +2314,8 @@ def local_map_clear(table, cap_vox, subdiv) -> torch.Tensor:
 def local_map_insert(table, cap_vox, subdiv, half, voxel, origin, xyz, idx, count, pose, stamp, min_range, max_range):
     """dpm_local_map_insert: xyz (cap,3) fp32, idx (cap,) int32, count (1,) int32, pose (4,4) fp64, all on the GPU"""
     o = _local_map_args(table, cap_vox, subdiv, origin)
-    _chk(xyz, torch.float32, "xyz"), _chk(idx, torch.int32, "idx"), _chk(count, torch.int32, "count"), _chk(pose, torch.float64, "pose")
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or idx.shape != xyz.shape[:1] or count.numel() != 1 or pose.numel() != 16:
-        raise ValueError("local_map_insert: xyz (cap,3), idx (cap,), count (1,), pose (4,4)")
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_local_map_insert(_ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o),
-                                                    _ptr(xyz), _ptr(idx), _ptr(count), xyz.shape[0], _ptr(pose), int(stamp),
-                                                    float(min_range), float(max_range), _stream(table)), "dpm_local_map_insert")
+    _source_call("dpm_local_map_insert", table, (int(cap_vox), int(subdiv), int(half), float(voxel)), o,
+                 _one_frame("local_map_insert", xyz, count, pose, idx), (_ptr(idx),), (int(stamp), float(min_range), float(max_range)))
 
 
 def local_map_prune(table, cap_vox, subdiv, half, voxel, origin, pose, radius):
@@ -2318,19 +2335,15 @@ def local_map_insert_frames(table, cap_vox, subdiv, half, voxel, origin, store, 
     of the store, poses (F,4,4) fp64, stamps (F,) int32 holding the uint32 stamps' bits, centre (4,4) fp64 or None (then
     radius is ignored), all on the GPU.  Two launches for any F, no host synchronisation, capturable in a graph."""
     o = _local_map_args(table, cap_vox, subdiv, origin)
-    F = _frame_list_args("local_map_insert_frames", store, lengths, frames, poses)
+    source, F = _stored_frames("local_map_insert_frames", store, lengths, frames, poses)
     if _chk(stamps, torch.int32, "stamps").shape != frames.shape:
         raise ValueError("local_map_insert_frames: stamps (F,), one per frame")
     if centre is not None:
         _chk(centre, torch.float64, "centre")
         if centre.numel() != 16:
             raise ValueError("local_map_insert_frames: centre (4,4)")
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_local_map_insert_frames(
-            _ptr(table), int(cap_vox), int(subdiv), int(half), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths),
-            store.shape[0], store.shape[2], _ptr(frames), _ptr(poses), _ptr(stamps), F, _ptr(centre),
-            0.0 if centre is None else float(radius), float(min_range), float(max_range), _stream(table)),
-            "dpm_local_map_insert_frames")
+    _source_call("dpm_local_map_insert_frames", table, (int(cap_vox), int(subdiv), int(half), float(voxel)), o, source, (),
+                 (_ptr(stamps), F, _ptr(centre), 0.0 if centre is None else float(radius), float(min_range), float(max_range)))
 
 
 def local_map_planes(table, cap_vox, subdiv, half, voxel, origin, plane_radius, planes=None, counts=None):
@@ -2457,11 +2470,7 @@ def tsdf_integrate(table, cap_vox, voxel, origin, xyz, count, pose, min_range, m
     synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _frame_args("tsdf_integrate", xyz, count, pose)
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_tsdf_integrate(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz),
-                                                  _ptr(count), xyz.shape[0], _ptr(pose), *rays, _stream(table)),
-                   "dpm_tsdf_integrate")
+    _source_call("dpm_tsdf_integrate", table, (int(cap_vox), float(voxel)), o, _one_frame("tsdf_integrate", xyz, count, pose), (), rays)
 
 
 def tsdf_integrate_frames(table, cap_vox, voxel, origin, store, lengths, frames, poses, min_range, max_range, truncation, step):
@@ -2469,11 +2478,8 @@ def tsdf_integrate_frames(table, cap_vox, voxel, origin, store, lengths, frames,
     the store, poses (F,4,4) fp64, all on the GPU.  One launch for any F, no host synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    F = _frame_list_args("tsdf_integrate_frames", store, lengths, frames, poses)
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_tsdf_integrate_frames(
-            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
-            store.shape[2], _ptr(frames), _ptr(poses), F, *rays, _stream(table)), "dpm_tsdf_integrate_frames")
+    source, F = _stored_frames("tsdf_integrate_frames", store, lengths, frames, poses)
+    _source_call("dpm_tsdf_integrate_frames", table, (int(cap_vox), float(voxel)), o, source, (), (F, *rays))
 
 
 def _tsdf_cos(cos_min) -> float:
@@ -2498,13 +2504,11 @@ def tsdf_integrate_planes(table, cap_vox, voxel, origin, xyz, normals, count, po
     synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _frame_args("tsdf_integrate_planes", xyz, count, pose)
+    source = _one_frame("tsdf_integrate_planes", xyz, count, pose)
     if _chk(normals, torch.float32, "normals").shape != xyz.shape:
         raise ValueError("tsdf_integrate_planes: normals (cap,3), one per row of xyz")
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_tsdf_integrate_planes(
-            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(normals), _ptr(count), xyz.shape[0],
-            _ptr(pose), *rays, _tsdf_cos(cos_min), _stream(table)), "dpm_tsdf_integrate_planes")
+    _source_call("dpm_tsdf_integrate_planes", table, (int(cap_vox), float(voxel)), o, source, (_ptr(normals),),
+                 (*rays, _tsdf_cos(cos_min)))
 
 
 def tsdf_integrate_planes_frames(table, cap_vox, voxel, origin, store, normals, lengths, frames, poses, min_range, max_range,
@@ -2512,39 +2516,31 @@ def tsdf_integrate_planes_frames(table, cap_vox, voxel, origin, store, normals, 
     """dpm_tsdf_integrate_planes_frames: tsdf_integrate_frames' arguments and a normals store (capacity,P,3) fp32"""
     rays = tsdf_rays(truncation, step, min_range, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    F = _frame_list_args("tsdf_integrate_planes_frames", store, lengths, frames, poses)
+    source, F = _stored_frames("tsdf_integrate_planes_frames", store, lengths, frames, poses)
     if tuple(_chk(normals, torch.float32, "normals").shape) != (store.shape[0], store.shape[2], 3):
         raise ValueError("tsdf_integrate_planes_frames: normals (capacity,P,3)")
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_tsdf_integrate_planes_frames(
-            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(normals), _ptr(lengths), store.shape[0],
-            store.shape[2], _ptr(frames), _ptr(poses), F, *rays, _tsdf_cos(cos_min), _stream(table)),
-            "dpm_tsdf_integrate_planes_frames")
+    _source_call("dpm_tsdf_integrate_planes_frames", table, (int(cap_vox), float(voxel)), o, source, (_ptr(normals),),
+                 (F, *rays, _tsdf_cos(cos_min)))
 
 
 def tsdf_carve(table, cap_vox, voxel, origin, xyz, count, pose, min_range, max_range, truncation, step, weight, margin):
     """dpm_tsdf_carve: tsdf_integrate's arguments, weight (count units) and margin (metres).  Lookups only; one launch, no
     host synchronisation, capturable in a graph."""
     rays = tsdf_rays(truncation, step, min_range, max_range)
-    w, g = tsdf_carve_args(weight, margin, step, max_range)
+    carve = tsdf_carve_args(weight, margin, step, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    _frame_args("tsdf_carve", xyz, count, pose)
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_tsdf_carve(_ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(xyz), _ptr(count),
-                                              xyz.shape[0], _ptr(pose), *rays, w, g, _stream(table)), "dpm_tsdf_carve")
+    _source_call("dpm_tsdf_carve", table, (int(cap_vox), float(voxel)), o, _one_frame("tsdf_carve", xyz, count, pose), (),
+                 (*rays, *carve))
 
 
 def tsdf_carve_frames(table, cap_vox, voxel, origin, store, lengths, frames, poses, min_range, max_range, truncation, step, weight,
                       margin):
     """dpm_tsdf_carve_frames: tsdf_integrate_frames' arguments, weight and margin"""
     rays = tsdf_rays(truncation, step, min_range, max_range)
-    w, g = tsdf_carve_args(weight, margin, step, max_range)
+    carve = tsdf_carve_args(weight, margin, step, max_range)
     o = _tsdf_args(table, cap_vox, origin)
-    F = _frame_list_args("tsdf_carve_frames", store, lengths, frames, poses)
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.load().dpm_tsdf_carve_frames(
-            _ptr(table), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(store), _ptr(lengths), store.shape[0],
-            store.shape[2], _ptr(frames), _ptr(poses), F, *rays, w, g, _stream(table)), "dpm_tsdf_carve_frames")
+    source, F = _stored_frames("tsdf_carve_frames", store, lengths, frames, poses)
+    _source_call("dpm_tsdf_carve_frames", table, (int(cap_vox), float(voxel)), o, source, (), (F, *rays, *carve))
 
 
 def _counted(call, max_out):
