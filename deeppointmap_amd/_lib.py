@@ -176,6 +176,8 @@ SIGNATURES = {
     "dpm_tsdf_carve": (I, [P, I, D, P, P, P, I, P, D, D, D, D, I, D, P]),
     "dpm_tsdf_carve_frames": (I, [P, I, D, P, P, P, I, I, P, P, I, D, D, D, D, I, D, P]),
     "dpm_tsdf_export": (I, [P, I, P, P, P, P, I, P]),
+    "dpm_tsdf_evict": (I, [P, P, I, D, P, P, D, I, P, P, P, P, I, P]),
+    "dpm_tsdf_absorb": (I, [P, I, P, P, P, I, P]),
     "dpm_tsdf_surface": (I, [P, I, D, I, P, P, P, P, P, I, P]),
     "dpm_tsdf_mesh": (I, [P, I, D, I, P, P, P, P, I, P]),
     "dpm_tsdf_sample": (I, [P, I, D, P, P, P, I, P, I, P, P, P, P]),

@@ -42,6 +42,10 @@
 //              max_range / step <= 65536.  A function of (the map before, the set of frames); meant to run after the
 //              integrations, and a later integrate adds to what is there.
 //   export     (key, sum, count) of every occupied slot in arrival order + their number; Python sorts.
+//   evict      one lane per slot, into a second cleared table: the voxels of tiles NEAR a pose (2^b voxels per axis, the tile's
+//              centre within the radius: csrc/voxel_hash.h) are kept, the others listed for the host -- or kept when the list
+//              is full.  absorb: one lane per record, sum += s and count += c by integrate's atomics.  Integer addition: a
+//              voxel split between table and host adds back to the same bytes ("rolling the map").
 //
 // Field: D(slot) = (float)((double)sum / ((double)count * 2^24)).  A voxel is QUALIFIED when count >= min_count (>= 1).
 //   surface    one lane per slot.  For a qualified voxel k0 and an axis a with k1 = k0 + e_a qualified and (D0 < 0) != (D1 < 0):
@@ -281,6 +285,81 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_export_kernel(Tsdf M, unsigned lo
     const int pos = atomicAdd(count, 1);
     if (pos < 0 || pos >= max_out) return;
     keys[pos] = key, sums[pos] = M.sum()[slot], counts[pos] = M.count()[slot];
+}
+
+// ------------------------------------------------------------------------------------------------------------ rolling the map
+// Nothing can be deleted from a table whose empty key ends a probe, so a map is rolled by REBUILDING it: evict moves the voxels of
+// the tiles (csrc/voxel_hash.h) near a pose into a second, cleared table and lists the others for the host; absorb adds listed
+// records back.  A voxel is (key, int64 sum, uint32 count) and every write is an integer add, so a voxel's content split between
+// the table and the host adds back to the same bytes.
+struct EvictOut {
+    unsigned long long *keys;
+    long long *sums;
+    uint32_t *counts;
+    int32_t *count;
+    int max_out;
+};
+
+// dst cleared, src's three counters carried over, the list's counter zeroed
+__global__ __launch_bounds__(TS_BLOCK) void ts_evict_clear_kernel(Tsdf S, Tsdf D, int32_t *count) {
+    const size_t tid = (size_t)blockIdx.x * TS_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * TS_BLOCK;
+    if (tid < 64) ((unsigned *)D.base)[tid] = tid < 3 ? ((const unsigned *)S.base)[tid] : 0u;
+    if (tid == 0) count[0] = 0;
+    for (size_t i = tid; i < (size_t)D.cap_vox; i += stride) D.keys()[i] = EMPTY, D.sum()[i] = 0, D.count()[i] = 0u;
+}
+
+// One lane per slot of src.  A lane past the table or on an empty slot does NOT leave before the ballot: the far voxels of a wave
+// take their list positions with one atomic (the first far lane adds their number, every far lane adds its rank among them), as
+// integrate_ray keeps the wave together for its sums.  A far voxel whose position is at or past max_out stays: it is claimed in
+// dst like a near one, so nothing is dropped.  Keys are unique in src, so the values are stored plainly.
+__global__ __launch_bounds__(TS_BLOCK) void ts_evict_kernel(Tsdf S, Tsdf D, const double *pose, float r2, int b, EvictOut O) {
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x, lane = threadIdx.x & 63;
+    const unsigned long long key = slot < S.cap_vox ? S.keys()[slot] : EMPTY;
+    const bool held = key != EMPTY;
+    const bool far = held && !tile_near(key, b, S.v, pose, S.ox, S.oy, S.oz, r2);
+    const unsigned long long wants = __ballot(far);
+    int base = 0;
+    const int first = wants ? __ffsll((long long)wants) - 1 : 0;
+    if (far && lane == first) base = atomicAdd(O.count, (int)__popcll(wants));
+    base = __shfl(base, first, 64);
+    if (!held) return;
+    const long long sum = S.sum()[slot];
+    const unsigned count = S.count()[slot];
+    if (far) {
+        const int pos = base + (int)__popcll(wants & ((1ull << lane) - 1ull));
+        if (pos >= 0 && pos < O.max_out) {
+            O.keys[pos] = key, O.sums[pos] = sum, O.counts[pos] = count;
+            return;
+        }
+    }
+    const int to = claim_slot(D.keys(), D.cap_vox, key);   // never full: no more keys than src holds
+    if (to < 0) {
+        atomicAdd(&D.hdr()->overflow, 1u);
+        return;
+    }
+    D.sum()[to] = sum, D.count()[to] = count;
+}
+
+// One lane per record: the slot found or claimed, then the integer atomics of integrate, so equal keys in the list and keys the
+// table holds add, in any order to the same bytes.  A key with bit 63 set cannot be a voxel (EMPTY is one): header word 1.
+__global__ __launch_bounds__(TS_BLOCK) void ts_absorb_kernel(Tsdf M, const unsigned long long *keys, const long long *sums,
+                                                             const uint32_t *counts, int n) {
+    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = keys[i];
+    if (key >> 63) {
+        atomicAdd(&M.hdr()->outside, 1u);
+        return;
+    }
+    const unsigned count = counts[i];
+    if (count == 0u) return;
+    const int slot = claim_slot(M.keys(), M.cap_vox, key);
+    if (slot < 0) {
+        atomicAdd(&M.hdr()->overflow, 1u);
+        return;
+    }
+    atomicAdd((unsigned long long *)&M.sum()[slot], (unsigned long long)sums[i]);
+    atomicAdd(&M.count()[slot], count);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the field
@@ -761,6 +840,31 @@ extern "C" int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long 
     DPM_CHECK_ARG(max_out == 0 || (keys && sums && counts));
     hipLaunchKernelGGL(ts_export_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, 1.0, nullptr), keys, sums, counts, count, max_out);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_evict(const void *src, void *dst, int cap_vox, double voxel, const double *origin, const double *pose,
+                              double radius, int tile_bits, unsigned long long *keys_out, long long *sums_out,
+                              uint32_t *counts_out, int32_t *count_out, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(field_ok(src, cap_vox, voxel, origin) && table_ok(dst, cap_vox) && src != dst);
+    DPM_CHECK_ARG(pose && radius >= 0.0 && radius < 1e18 && tile_bits >= 3 && tile_bits <= 10 && count_out && max_out >= 0);
+    DPM_CHECK_ARG(max_out == 0 || (keys_out && sums_out && counts_out));
+    const Tsdf S = make_tsdf(src, cap_vox, voxel, origin), D = make_tsdf(dst, cap_vox, voxel, origin);
+    const EvictOut O{keys_out, sums_out, counts_out, count_out, max_out};
+    const unsigned g = dpm_cdiv(cap_vox, TS_BLOCK);
+    hipLaunchKernelGGL(ts_evict_clear_kernel, dim3(g > 8192 ? 8192 : g), dim3(TS_BLOCK), 0, (hipStream_t)stream, S, D, count_out);
+    hipLaunchKernelGGL(ts_evict_kernel, dim3(g), dim3(TS_BLOCK), 0, (hipStream_t)stream, S, D, pose, (float)(radius * radius),
+                       tile_bits, O);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_absorb(void *map, int cap_vox, const unsigned long long *keys, const long long *sums,
+                               const uint32_t *counts, int n, dpm_stream_t stream) {
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && n >= 0);
+    if (n == 0) return DPM_OK;   // nothing to read: the lists may be null
+    DPM_CHECK_ARG(keys && sums && counts);
+    hipLaunchKernelGGL(ts_absorb_kernel, dim3(dpm_cdiv(n, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, 1.0, nullptr), keys, sums, counts, n);
     return dpm_launch_status();
 }
 

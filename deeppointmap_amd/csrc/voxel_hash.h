@@ -28,6 +28,26 @@ __device__ __forceinline__ void voxel_centre(unsigned long long key, float v, fl
     for (int a = 0; a < 3; ++a) c[a] = ((float)(key_axis(key, a) - 1048576) + 0.5f) * v;
 }
 
+// The tile of voxel `key`: the cube of 2^b voxels per axis that share key_axis(key, a) >> b (the BIASED index, so tiles are cut
+// at multiples of 2^b voxels from the low end of the 21 bits, and 2^20 is such a multiple for every b <= 20); the host names it
+// pack_key(x >> b, y >> b, z >> b).  Its centre, per axis c = ((float)(first index of the tile, unbiased) + 0.5f * (float)2^b) * v,
+// every operation rounded once.
+__device__ __forceinline__ void tile_centre(unsigned long long key, int b, float v, float c[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = ((float)(((key_axis(key, a) >> b) << b) - 1048576) + 0.5f * (float)(1 << b)) * v;
+}
+
+// a tile is NEAR a pose when its centre lies within sqrt(r2) of the pose's map-frame translation (ox, oy, oz the map's origin):
+// csrc/local_map.hip's voxel_within on the tile's centre
+__device__ __forceinline__ bool tile_near(unsigned long long key, int b, float v, const double *pose, double ox, double oy, double oz,
+                                          float r2) {
+    const float tx = (float)(pose[3] - ox), ty = (float)(pose[7] - oy), tz = (float)(pose[11] - oz);
+    float c[3];
+    tile_centre(key, b, v, c);
+    const float dx = c[0] - tx, dy = c[1] - ty, dz = c[2] - tz;
+    return (dx * dx + dy * dy) + dz * dz <= r2;
+}
+
 // slot of `key` in a table nobody is writing, or -1
 __device__ __forceinline__ int find_slot(const unsigned long long *keys, int cap_vox, unsigned long long key) {
     int slot = (int)(mix64(key) & (unsigned long long)(cap_vox - 1));

@@ -2574,6 +2574,48 @@ def tsdf_export(table, cap_vox, max_out=None):
     return _counted(call, max_out)
 
 
+TSDF_TILE_BITS = (3, 10)    # a tile has 2^b voxels per axis, b in this range
+
+
+def tsdf_evict(src, dst, cap_vox, voxel, origin, pose, radius, tile_bits, keys, sums, counts, count):
+    """dpm_tsdf_evict: src -> dst (a second table of the same cap_vox, not src), pose (4,4) fp64 on the GPU.  keys, sums (n,)
+    int64 and counts (n,) int32 on the GPU are the list (max_out = n; n = 0: nothing leaves), count (1,) int32 receives the
+    number of voxels that wanted out -- it is zeroed by the call and NOT read here.  Two launches, no host synchronisation,
+    capturable in a graph."""
+    o = _tsdf_args(src, cap_vox, origin)
+    _tsdf_args(dst, cap_vox)
+    if o is None or dst.device != src.device or dst.data_ptr() == src.data_ptr():
+        raise ValueError("tsdf_evict: an origin, and dst a second table on src's device")
+    _chk(pose, torch.float64, "pose")
+    if pose.numel() != 16:
+        raise ValueError("tsdf_evict: pose (4,4)")
+    if not (0.0 <= float(radius) < 1e18 and TSDF_TILE_BITS[0] <= int(tile_bits) <= TSDF_TILE_BITS[1]):
+        raise ValueError(f"tsdf_evict: radius >= 0, tile_bits in [{TSDF_TILE_BITS[0]}, {TSDF_TILE_BITS[1]}]")
+    n = _chk(keys, torch.int64, "keys").numel()
+    if _chk(sums, torch.int64, "sums").numel() != n or _chk(counts, torch.int32, "counts").numel() != n:
+        raise ValueError("tsdf_evict: keys, sums, counts of one length")
+    if _chk(count, torch.int32, "count").numel() != 1:
+        raise ValueError("tsdf_evict: count (1,)")
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.load().dpm_tsdf_evict(_ptr(src), _ptr(dst), int(cap_vox), float(voxel), ctypes.addressof(o), _ptr(pose),
+                                              float(radius), int(tile_bits), _ptr(keys) if n else None, _ptr(sums) if n else None,
+                                              _ptr(counts) if n else None, _ptr(count), n, _stream(src)), "dpm_tsdf_evict")
+
+
+def tsdf_absorb(table, cap_vox, keys, sums, counts):
+    """dpm_tsdf_absorb: keys, sums (n,) int64 and counts (n,) int32 (the uint32 counts' bits) on the GPU are added to the
+    table.  One launch, no host synchronisation, capturable in a graph; n = 0 launches nothing."""
+    _tsdf_args(table, cap_vox)
+    n = _chk(keys, torch.int64, "keys").numel()
+    if _chk(sums, torch.int64, "sums").numel() != n or _chk(counts, torch.int32, "counts").numel() != n:
+        raise ValueError("tsdf_absorb: keys, sums, counts of one length")
+    if n == 0:
+        return
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dpm_tsdf_absorb(_ptr(table), int(cap_vox), _ptr(keys), _ptr(sums), _ptr(counts), n, _stream(table)),
+                   "dpm_tsdf_absorb")
+
+
 def tsdf_surface(table, cap_vox, voxel, min_count=1, max_out=None):
     """dpm_tsdf_surface -> (count, keys (n,) int64, axes (n,) int32, xyz (n,3) fp32 map-frame, normals (n,3) fp32) in no
     defined order; max_out as in _counted"""

@@ -35,8 +35,10 @@ samples in a row, so sparse maps miss, and BACK ends the ray.
 
 LIMITS: carving reaches only voxels that exist and claims none; no weight cap or decay; the frame's pose is the origin of every
 ray (no per-point origins for sweeps that are not deskewed); the normals of the plane form are the caller's (or dpm_point_normals
-of the frame alone, `normals=<radius>`); marching tetrahedra, not marching cubes; the voxels live on the device (nothing is
-streamed to the host).
+of the frame alone, `normals=<radius>`); marching tetrahedra, not marching cubes; the voxels live on the device unless
+the map is rolled: `TsdfMap.roll` evicts the tiles far from the sensor to a `TsdfArchive` on the host and absorbs them when the
+sensor comes back (integer addition: `merged_export` is the unrolled map's export, byte for byte; a rolling map costs twice the
+table); meshing a map larger than the table is by region (`TsdfArchive.records` + `absorb`), with the seams the caller's.
 """
 from __future__ import annotations
 
@@ -127,6 +129,130 @@ class TsdfCast(NamedTuple):
     flag: torch.Tensor       # (F,R) int32
 
 
+# -- rolling the map: tiles, and the host archive of the voxels that left the device -------------------------------------------
+KEY_BIAS, _AXIS = 1 << 20, (1 << 21) - 1
+NO_RECORDS = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.uint32))
+
+
+def tile_of(keys, tile_bits: int) -> np.ndarray:
+    """voxel keys -> the keys of their tiles, pack_key(x >> b, y >> b, z >> b): the cube of 2^b voxels per axis"""
+    k, b = np.asarray(keys, np.int64), int(tile_bits)
+    return ((k & _AXIS) >> b) | ((((k >> 21) & _AXIS) >> b) << 21) | ((((k >> 42) & _AXIS) >> b) << 42)
+
+
+def tile_near(tile_keys, tile_bits: int, centre_map_xyz, radius: float, voxel_size: float) -> np.ndarray:
+    """dpm_tsdf_evict's test restated in numpy float32, every operation rounded once: per axis c = ((float)((t << b) - 2^20) +
+    0.5f * (float)2^b) * v, d = c - (float)centre, NEAR when (dx*dx + dy*dy) + dz*dz <= (float)(radius * radius).
+    centre_map_xyz: the pose's translation minus the map's origin, float64."""
+    t, b = np.asarray(tile_keys, np.int64), int(tile_bits)
+    v, half = np.float32(voxel_size), np.float32(0.5) * np.float32(1 << b)
+    at = np.asarray(centre_map_xyz, np.float64).reshape(3).astype(np.float32)
+    d = [((((t >> (21 * a)) & _AXIS) << b) - KEY_BIAS).astype(np.float32) for a in range(3)]
+    d = [(d[a] + half) * v - at[a] for a in range(3)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= np.float32(float(radius) * float(radius))
+
+
+def merge_records(keys, sums, counts):
+    """records in any order -> sorted by key with equal keys added (int64 and uint32 addition, wrapping as the device's)"""
+    k = np.asarray(keys).astype(np.int64, copy=False).reshape(-1)
+    s, c = np.asarray(sums, np.int64).reshape(-1), np.asarray(counts).astype(np.uint32, copy=False).reshape(-1)
+    if not k.size == s.size == c.size:
+        raise ValueError("records: keys, sums and counts of one length")
+    if k.size == 0:
+        return tuple(a.copy() for a in NO_RECORDS)
+    order = np.argsort(k, kind="stable")
+    k, s, c = k[order], s[order], c[order]
+    first = np.flatnonzero(np.concatenate([[True], k[1:] != k[:-1]]))
+    with np.errstate(over="ignore"):
+        return k[first], np.add.reduceat(s, first, dtype=np.int64), np.add.reduceat(c, first, dtype=np.uint32)
+
+
+class TsdfArchive:
+    """The voxels of a rolled TsdfMap that are not on the device, on the host in numpy: per tile key (`tile_of`, 2^tile_bits
+    voxels per axis) the records (key, sum, count) sorted by key, equal keys added.  The map it serves writes voxel_size,
+    origin, distance, truncation and step into it at the first `TsdfMap.roll` (`save` / `load` carry them), and a map that
+    differs in voxel_size, origin or distance is refused from then on: records of another grid or another unit cannot add."""
+    META = ("voxel_size", "origin", "distance", "truncation", "step")
+
+    def __init__(self, tile_bits: int = 5):
+        if not ops.TSDF_TILE_BITS[0] <= int(tile_bits) <= ops.TSDF_TILE_BITS[1]:
+            raise ValueError(f"tile_bits in [{ops.TSDF_TILE_BITS[0]}, {ops.TSDF_TILE_BITS[1]}]")
+        self.tile_bits = int(tile_bits)
+        self.tiles = {}                       # tile key (int) -> (keys, sums, counts)
+        self.voxel_size = self.origin = self.distance = self.truncation = self.step = None
+
+    def __len__(self) -> int:
+        return sum(len(t[0]) for t in self.tiles.values())
+
+    def bind(self, m: "TsdfMap"):
+        """take the map's geometry at first use; later, refuse a map of another voxel_size, origin or distance"""
+        if m.origin is None:
+            raise ValueError("archive: the map has no origin yet")
+        if self.voxel_size is None:
+            self.voxel_size, self.origin, self.distance = m.voxel_size, m.origin.copy(), m.distance
+            self.truncation, self.step = m.truncation, m.step
+        elif (self.voxel_size != m.voxel_size or self.distance != m.distance
+              or np.asarray(self.origin, np.float64).tobytes() != np.asarray(m.origin, np.float64).tobytes()):
+            raise ValueError(f"archive: it holds voxels of voxel_size {self.voxel_size}, origin {self.origin}, distance "
+                             f"'{self.distance}'; the map has {m.voxel_size}, {m.origin}, '{m.distance}'")
+        return self
+
+    def add(self, keys, sums, counts):
+        k, s, c = merge_records(keys, sums, counts)
+        if k.size and k.min() < 0:
+            raise ValueError("archive: a key with bit 63 set is no voxel")
+        tiles = tile_of(k, self.tile_bits)
+        order = np.argsort(tiles, kind="stable")              # keeps the key order inside a tile
+        tiles, k, s, c = tiles[order], k[order], s[order], c[order]
+        edges = np.flatnonzero(np.concatenate([[True], tiles[1:] != tiles[:-1], [True]])) if k.size else []
+        for lo, hi in zip(edges[:-1], edges[1:]):
+            t, new = int(tiles[lo]), (k[lo:hi], s[lo:hi], c[lo:hi])
+            held = self.tiles.get(t)
+            self.tiles[t] = new if held is None else merge_records(*[np.concatenate(p) for p in zip(held, new)])
+        return self
+
+    def tiles_near(self, centre_map_xyz, radius: float, voxel_size: Optional[float] = None) -> np.ndarray:
+        """the keys of the held tiles that are NEAR the centre (`tile_near`: the kernel's test), sorted"""
+        v = self.voxel_size if voxel_size is None else voxel_size
+        t = np.array(sorted(self.tiles), np.int64)
+        return t[tile_near(t, self.tile_bits, centre_map_xyz, radius, v)] if t.size else t
+
+    def take(self, tile_keys):
+        """the records of these tiles, sorted by key; the tiles leave the archive (a tile it does not hold gives nothing)"""
+        out = [self.tiles.pop(int(t)) for t in np.unique(np.asarray(tile_keys, np.int64)) if int(t) in self.tiles]
+        return merge_records(*[np.concatenate(p) for p in zip(*out)]) if out else tuple(a.copy() for a in NO_RECORDS)
+
+    def records(self):
+        """everything held, sorted by key; nothing leaves"""
+        out = list(self.tiles.values())
+        return merge_records(*[np.concatenate(p) for p in zip(*out)]) if out else tuple(a.copy() for a in NO_RECORDS)
+
+    def save(self, path):
+        """one .npz: the records and voxel_size, origin, distance, truncation, step, tile_bits"""
+        if self.voxel_size is None:
+            raise ValueError("archive: no map has used it yet (voxel_size, origin and distance are unknown)")
+        k, s, c = self.records()
+        with open(path, "wb") as out:
+            np.savez(out, keys=k, sums=s, counts=c, voxel_size=np.float64(self.voxel_size), origin=np.asarray(self.origin, np.float64),
+                     distance=np.array(self.distance), truncation=np.float64(self.truncation), step=np.float64(self.step),
+                     tile_bits=np.int64(self.tile_bits))
+
+    @classmethod
+    def load(cls, path) -> "TsdfArchive":
+        with np.load(path, allow_pickle=False) as z:
+            a = cls(int(z["tile_bits"]))
+            a.voxel_size, a.origin, a.distance = float(z["voxel_size"]), z["origin"].astype(np.float64).reshape(3), str(z["distance"])
+            a.truncation, a.step = float(z["truncation"]), float(z["step"])
+            return a.add(z["keys"], z["sums"], z["counts"])
+
+
+def merged_export(m: "TsdfMap", archive: TsdfArchive):
+    """the sorted union of the map's export and the archive's records with equal keys added: what the map would export had it
+    never been rolled"""
+    return merge_records(*[np.concatenate(p) for p in zip(m.export(), archive.records())])
+
+
 MISS, HIT, BACK = ops.TSDF_MISS, ops.TSDF_HIT, ops.TSDF_BACK
 BLOCKS_OVERFLOW = "the occupied-block set is full (max_blocks={}): ray-casts with skip=True are undefined; raise max_blocks"
 
@@ -160,6 +286,8 @@ class TsdfMap(_HashedMap):
             raise ValueError("max_blocks: a power of two in [2, 2^24]")
         self._blocks = {}     # min_count (count units) -> the occupied-block set of the table as it is; every write drops it
         self._ray_tables = {}   # id of a LidarModel's direction table -> (the table, its copy on the device): uploaded once
+        self._spare = self._stage = None    # a rolling map's second table and its staging list: made by the first `evict`, kept
+        self.wanted = 0                     # voxels the last `evict` wanted out (above its list's length: the rest stayed)
         self.truncation = 3.0 * self.voxel_size if truncation is None else float(truncation)
         self.step = self.voxel_size / 2.0 if step is None else float(step)
         self.min_range, self.max_range = float(min_range), float(max_range)
@@ -282,6 +410,115 @@ class TsdfMap(_HashedMap):
         self._blocks = {}
         ops.tsdf_carve_frames(*self._map(), store, lengths, rows, poses.to(device=self.device, dtype=torch.float64).contiguous(),
                               *self._rays(), w, g)
+        return self
+
+    # -- rolling: far tiles leave for the host and come back by addition
+    def evict(self, pose, radius: float, tile_bits: int = 5, max_out: Optional[int] = None):
+        """the voxels of every tile (2^tile_bits voxels per axis) whose centre is farther than `radius` metres from the
+        translation of `pose` ((4,4); numpy, or a tensor -- on the GPU it is read there) leave the map -> (keys int64, sums
+        int64, counts uint32) numpy, sorted by key.  The table is rebuilt into a second one (nothing can be deleted in place),
+        made at the first call and kept with a staging list of max_voxels // 4 records: A ROLLING MAP COSTS TWICE THE TABLE, and
+        24 bytes for every four slots.  The two tables change places.  max_out (default: the staging list's length): at most so
+        many voxels leave; those that found no room STAY in the map for the next call, and `wanted` is the number that wanted
+        out.  Two launches and one host synchronisation, the read of that number."""
+        if not ops.TSDF_TILE_BITS[0] <= int(tile_bits) <= ops.TSDF_TILE_BITS[1] or not 0.0 <= float(radius) < 1e18:
+            raise ValueError(f"evict: radius >= 0, tile_bits in [{ops.TSDF_TILE_BITS[0]}, {ops.TSDF_TILE_BITS[1]}]")
+        if max_out is not None and int(max_out) < 0:
+            raise ValueError("evict: max_out >= 0")
+        if tuple(np.shape(pose)) != (4, 4):
+            raise ValueError("pose: (4,4)")
+        self.wanted = 0
+        if self.table is None:
+            return tuple(a.copy() for a in NO_RECORDS)
+        dev = self.table.device
+        if self._spare is None:
+            n = max(1, self.max_voxels // 4)
+            with torch.cuda.device(dev):
+                self._spare = torch.empty_like(self.table)
+                self._stage = (torch.empty(n, device=dev, dtype=torch.int64), torch.empty(n, device=dev, dtype=torch.int64),
+                               torch.empty(n, device=dev, dtype=torch.int32), torch.empty(1, device=dev, dtype=torch.int32))
+        keys, sums, counts, count = self._stage
+        n = keys.numel() if max_out is None else int(max_out)
+        if n > keys.numel():                       # a longer list than the one kept: made for this call
+            with torch.cuda.device(dev):
+                keys, sums, counts = (torch.empty(n, device=dev, dtype=t.dtype) for t in (keys, sums, counts))
+        ops.tsdf_evict(self.table, self._spare, self.max_voxels, self.voxel_size, self.origin, _pose_tensor(pose, self.device),
+                       radius, tile_bits, keys[:n], sums[:n], counts[:n], count)
+        self.table, self._spare = self._spare, self.table
+        self._blocks = {}
+        augment._SYNCS[0] += 1
+        self.wanted = int(count.item())
+        n = min(self.wanted, n)
+        return merge_records(keys[:n].cpu().numpy(), sums[:n].cpu().numpy(), counts[:n].cpu().numpy().view(np.uint32))
+
+    def absorb(self, keys, sums=None, counts=None):
+        """records (key, sum, count) -- numpy, or tensors on the device (int64, int64, int32 holding the uint32 bits) -- are
+        added to the map: equal keys and keys the map holds add, in any order to the same bytes; count 0 is skipped, a key with
+        bit 63 set is counted in `outside()`.  absorb(archive) takes EVERYTHING a TsdfArchive holds out of it, after checking
+        voxel_size, origin and distance.  One launch, no host synchronisation."""
+        if isinstance(keys, TsdfArchive):
+            if sums is not None or counts is not None:
+                raise ValueError("absorb: an archive, or keys, sums and counts")
+            archive = keys
+            if archive.voxel_size is None:
+                raise ValueError("absorb: the archive was never used by a map")
+            if self.origin is None:
+                self.origin = np.asarray(archive.origin, np.float64).copy()
+            archive.bind(self)
+            keys, sums, counts = archive.take(list(archive.tiles))
+        elif sums is None or counts is None:
+            raise ValueError("absorb: keys, sums and counts")
+        dev = self.device if self.device is not None else (keys.device if isinstance(keys, torch.Tensor) else augment._device())
+        self._ready(torch.device(dev))
+        if not isinstance(keys, torch.Tensor):
+            k = np.ascontiguousarray(np.asarray(keys).astype(np.int64, copy=False).reshape(-1))      # uint64 keys: the same bits
+            s = np.ascontiguousarray(np.asarray(sums, np.int64).reshape(-1))
+            c = np.ascontiguousarray(np.asarray(counts).astype(np.uint32, copy=False).reshape(-1)).view(np.int32)
+            if not k.size == s.size == c.size:
+                raise ValueError("absorb: keys, sums and counts of one length")
+            keys, sums, counts = (torch.from_numpy(a).to(self.table.device) for a in (k, s, c))
+        if keys.numel():
+            self._blocks = {}
+            ops.tsdf_absorb(self.table, self.max_voxels, keys, sums, counts)
+        return self
+
+    def reach(self, tile_bits: int = 5) -> float:
+        """R0: no ray of a frame at a pose touches a voxel, by `integrate` or `carve`, outside the tiles whose centre lies within
+        R0 of the pose's translation.  A sample lies within max_range + ceil(truncation / step) * step of it (a carve's, before
+        the return), inside its voxel, inside its tile, so within sqrt(3)/2 tile sides of the tile's centre; a voxel_size is
+        added for the fp32 rounding of the samples and of the test.  The distance along the ray is taken no smaller than the
+        carve's default margin, truncation + voxel_size."""
+        along = max(float(np.ceil(self.truncation / self.step)) * self.step, self.truncation + self.voxel_size)
+        return self.max_range + along + 0.5 * np.sqrt(3.0) * (1 << int(tile_bits)) * self.voxel_size + self.voxel_size
+
+    def roll(self, pose, archive: TsdfArchive, keep_radius: Optional[float] = None, load_radius: Optional[float] = None,
+             slack: float = 10.0):
+        """move the map's window to `pose` ((4,4) ON THE HOST: the archive's lookup is there): `evict(pose, keep_radius)` ->
+        `archive.add` -> `archive.take(archive.tiles_near(pose, load_radius))` -> `absorb`.  Defaults: load_radius = `reach()` +
+        slack and keep_radius = load_radius + slack; keep_radius < load_radius raises (a tile would be loaded and evicted by
+        turns).  THE GUARANTEE, under the default radii and while the sensor stays within `slack` of the last roll's centre:
+        every tile a frame can touch is whole on the device, so integrate, carve and every read within `reach()` of the sensor
+        give the bytes of a map that never rolled, and `merged_export` equals that map's export.  With smaller radii
+        integrate alone is still exact in `merged_export` (addition), carve and the reads are not.  Not guaranteed: anything
+        once `overflow()` is non-zero; reads beyond the window."""
+        if isinstance(pose, torch.Tensor):
+            raise ValueError("roll: pose on the host (the archive is looked up there)")
+        P = np.asarray(pose, np.float64)
+        if P.shape != (4, 4):
+            raise ValueError("pose: (4,4)")
+        if not float(slack) >= 0.0:
+            raise ValueError("roll: slack >= 0")
+        load = self.reach(archive.tile_bits) + float(slack) if load_radius is None else float(load_radius)
+        keep = load + float(slack) if keep_radius is None else float(keep_radius)
+        if not keep >= load >= 0.0:
+            raise ValueError("roll: keep_radius >= load_radius >= 0")
+        if self.origin is None:
+            self.origin = P[:3, 3].copy() if archive.origin is None else np.asarray(archive.origin, np.float64).copy()
+        archive.bind(self)
+        archive.add(*self.evict(P, keep, archive.tile_bits))
+        back = archive.take(archive.tiles_near(P[:3, 3] - self.origin, load, self.voxel_size))
+        if len(back[0]):
+            self.absorb(*back)
         return self
 
     # -- read-back: one host synchronisation each
@@ -504,17 +741,30 @@ class TsdfTracker:
     frame, the integration all of them.  `poses` is the trajectory ((4,4) float64 on the host), `steps` a TsdfStep per frame,
     `lost` the number of frames whose registration failed.
 
-    What it is NOT: no deskew (a sweep is taken as one rigid frame), no pruning (the map only grows, to max_voxels), no loop
-    closure, no coarse level (the start must lie within the truncation band), and no normals of its own: distance="plane"
-    needs them per frame, as `TsdfMap.integrate` does."""
+    archive: a TsdfArchive (True: a new one of `tile_bits`) makes the map ROLL: at the start pose of a frame, before its
+    registration, whenever that pose's translation is at least slack / 2 from the centre of the last roll (the first frame's
+    pose counts as one), `TsdfMap.roll(start, archive, slack=slack)` sends the far tiles to the host and fetches the near ones, so
+    the trajectory may be longer than max_voxels covers; `rolls` counts them.  The poses and steps are those of the tracker
+    without an archive, byte for byte, while that one does not overflow and the frames' rows lie within max_range: a
+    registration reads the field at every row, and beyond the window the rolled map's tiles are on the host.  It costs the
+    second table and one more synchronisation per roll.  Without an archive nothing changes.
+
+    What it is NOT: no deskew (a sweep is taken as one rigid frame), no pruning without an archive (the map then only grows, to
+    max_voxels), no loop closure, no coarse level (the start must lie within the truncation band), and no normals of its own:
+    distance="plane" needs them per frame, as `TsdfMap.integrate` does."""
 
     def __init__(self, voxel_size: float = 0.2, truncation: Optional[float] = None, step: Optional[float] = None,
                  max_voxels: int = 1 << 22, min_range: float = 0.0, max_range: float = 100.0, origin=None, device=None,
                  distance: str = "ray", cos_min: float = 0.0, schedule=None, kernel_scale: float = 0.0, min_count: float = 1,
-                 grad_min: float = 0.5, min_fitness: float = 0.3, register_every: int = 1):
+                 grad_min: float = 0.5, min_fitness: float = 0.3, register_every: int = 1, archive=None, slack: float = 10.0,
+                 tile_bits: int = 5):
         self.map = TsdfMap(voxel_size, truncation, step, max_voxels, min_range, max_range, origin, device, distance, cos_min)
         if int(register_every) < 1:
             raise ValueError("register_every >= 1")
+        if not float(slack) > 0.0:
+            raise ValueError("slack > 0")
+        self.archive = TsdfArchive(tile_bits) if archive is True else archive
+        self.slack, self.rolls, self._rolled = float(slack), 0, None    # _rolled: the centre of the last roll
         self.schedule, self.kernel_scale, self.min_count, self.grad_min = schedule, float(kernel_scale), min_count, float(grad_min)
         self.min_fitness, self.register_every = float(min_fitness), int(register_every)
         self.poses, self.steps, self.lost = [], [], 0
@@ -544,9 +794,13 @@ class TsdfTracker:
         if not self.poses:
             P = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
             m.integrate(xyz, P, length, normals)
+            self._rolled = P[:3, 3].copy()
             done = TsdfStep(CONVERGED, 1.0, 0.0, 0, True)
         else:
             start = self.predict() if pose is None else np.array(pose, np.float64).reshape(4, 4)
+            if self.archive is not None and np.linalg.norm(start[:3, 3] - self._rolled) >= 0.5 * self.slack:
+                m.roll(start, self.archive, slack=self.slack)
+                self._rolled, self.rolls = start[:3, 3].copy(), self.rolls + 1
             k = self.register_every
             rows, count = xyz, length
             if k > 1:                                   # rows 0, k, 2k, ... below the length: ceil(length / k) of them, formed on the device

@@ -1189,6 +1189,35 @@ int dpm_tsdf_carve_frames(void *map, int cap_vox, double voxel, const double *or
  * only counts). */
 int dpm_tsdf_export(const void *map, int cap_vox, unsigned long long *keys, long long *sums, uint32_t *counts, int32_t *count,
                     int max_out, dpm_stream_t stream);
+/* ROLLING THE MAP.  A TILE is the cube of 2^b voxels per axis (b = tile_bits in [3, 10]) that share key_axis >> b, the BIASED
+ * index; its centre per axis, in fp32 with every operation rounded once, is
+ *     c = ((float)(((index >> b) << b) - 1048576) + 0.5f * (float)(1 << b)) * (float)voxel,
+ * and it is NEAR a pose when, with d = c - (float)(pose[3 | 7 | 11] - origin) per axis,
+ *     (dx*dx + dy*dy) + dz*dz <= (float)(radius * radius):
+ * dpm_local_map_prune's test on the tile's centre.  A NaN fails: every tile is then far.
+ *
+ * dpm_tsdf_evict rebuilds the table `src` into `dst`, a second buffer of dpm_tsdf_bytes(cap_vox) bytes that is not src: dst is
+ * cleared, src's header words 0 to 2 are copied into it and count_out[0] is set to 0 (first launch); then, one lane per slot of
+ * src (second launch), a voxel of a NEAR tile is claimed in dst and its sum and count stored; a voxel of any other tile takes a
+ * position in the list -- keys_out (max_out,) uint64, sums_out (max_out,) int64, counts_out (max_out,) uint32, in no defined
+ * order -- and is written there when its position is below max_out; OTHERWISE IT STAYS, claimed in dst like a near voxel.
+ * count_out (1,) int32 ends as the number of voxels that wanted out, which may exceed max_out; which of them found room is
+ * not defined.  In every case the multiset (key, sum, count) of dst and the first min(count_out, max_out) records together is
+ * that of src: nothing is dropped, nothing is changed.  src keeps its bytes; the caller swaps the buffers.  max_out = 0 with
+ * null lists is legal (a plain rebuild).  pose: 16 doubles on the device.  No host synchronisation, capturable.
+ * DPM_EINVAL: src == dst, tile_bits outside [3, 10], radius < 0, and what dpm_tsdf_integrate refuses of map, voxel and origin.
+ *
+ * dpm_tsdf_absorb adds n records (keys (n,) uint64, sums (n,) int64, counts (n,) uint32 on the device) to the table, one lane
+ * per record in one launch: a record whose key has bit 63 set (no voxel's key has; the empty key does) adds one to header word
+ * 1 and is skipped; a record with count == 0 is skipped; otherwise the slot is found or claimed and sum += s, count += c by
+ * dpm_tsdf_integrate's integer atomics.  No free slot: header word 0 counts the record.  Equal keys inside the list and keys the
+ * table holds add, and the result is the same bytes for any order of records.  n = 0 is a no-op (null lists are legal).  After
+ * an evict, absorbing its list into dst gives the sorted export of src, byte for byte. */
+int dpm_tsdf_evict(const void *src, void *dst, int cap_vox, double voxel, const double *origin, const double *pose,
+                   double radius, int tile_bits, unsigned long long *keys_out, long long *sums_out, uint32_t *counts_out,
+                   int32_t *count_out, int max_out, dpm_stream_t stream);
+int dpm_tsdf_absorb(void *map, int cap_vox, const unsigned long long *keys, const long long *sums, const uint32_t *counts, int n,
+                    dpm_stream_t stream);
 /* Zero crossings along the axes, one lane per slot, in no defined order, count / max_out as above.  A record is written for
  * a qualified voxel k0 and an axis a when k1 = k0 + e_a is qualified and (D0 < 0) != (D1 < 0): keys = k0, axes = a, xyz
  * (max_out,3) = k0's centre with f * voxel added on axis a, f = D0 / (D0 - D1) (fp32, correctly rounded; map frame).
