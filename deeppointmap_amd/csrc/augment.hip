@@ -49,11 +49,8 @@ __global__ __launch_bounds__(256) void sel_count_kernel(const K keep, int *__res
         const long long c = c0 + k;
         if (c < n && keep.src(c) >= 0) ++cnt;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) bcount[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    const int total = block_total<4>(cnt, s);
+    if (threadIdx.x == 0) bcount[blockIdx.x] = total;
 }
 
 template <class K>

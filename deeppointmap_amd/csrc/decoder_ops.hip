@@ -2,7 +2,7 @@
 // dual-softmax pairing + top-k, pair gather, correspondence sets + iterative weighted Kabsch
 // (fp64 3x3 SVD on device), row mean.  fp32 like the reference unless stated.
 // Compiled with -ffp-contract=off: every fused multiply-add is an explicit fmaf().
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "topk_emulate.h"
 #include "workspace.h"
 #include <algorithm>
@@ -652,13 +652,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(const float *__restric
             // scan of the lane sums finds the lane, its four bins are then walked
             const int top = 255 - 4 * t;
             const unsigned c0 = hist[top], c1 = hist[top - 1], c2 = hist[top - 2], c3 = hist[top - 3];
-            unsigned inc = c0 + c1 + c2 + c3;
-            const unsigned own = inc;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned o = __shfl_up(inc, off, 64);
-                if (t >= off) inc += o;
-            }
+            const unsigned own = c0 + c1 + c2 + c3, inc = wave_scan_inclusive(own);
             const unsigned rem0 = s_krem;
             const unsigned long long hit = __ballot(inc >= rem0);
             const int L = __builtin_ctzll(hit);  // k <= n: some lane always reaches rem0
@@ -956,8 +950,7 @@ constexpr int KB = 256;  // threads
 
 template <typename T>
 __device__ T block_sum(T v, T *scratch /* KB/64 entries */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -967,8 +960,7 @@ __device__ T block_sum(T v, T *scratch /* KB/64 entries */) {
 }
 
 __device__ float block_max(float v, float *scratch /* KB/64 entries */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    v = wave_max(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -33,15 +33,30 @@ static inline int dpm_knob(const char *name, int dflt) {
 static inline constexpr int dpm_knob(const char *, int dflt) { return dflt; }
 #endif
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ---- wave64 reductions by the xor butterfly, offsets 32 down to 1: every lane ends with the result.  T: int, unsigned, float,
+// double, long long, unsigned long long.  The floating-point sums depend on that order (their restatements repeat it).
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T a, T b) { return a + b; }); }
+template <typename T>
+__device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, [](T a, T b) { return b < a ? b : a; }); }
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, [](T a, T b) { return b > a ? b : a; }); }
+__device__ __forceinline__ float wave_min(float v) { return wave_reduce(v, [](float a, float b) { return fminf(a, b); }); }
+__device__ __forceinline__ float wave_max(float v) { return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
+// the smallest v over the wave and its i; among equal v the smallest i
+__device__ __forceinline__ void wave_argmin(float &v, int &i) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(i, off, 64);
+        if (ov < v || (ov == v && oi < i)) v = ov, i = oi;
+    }
 }
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

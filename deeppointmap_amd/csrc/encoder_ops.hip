@@ -2,7 +2,7 @@
 // input staging, grouped MLP + LayerNorm + ReLU + max (SetAbstraction / LocalAggregation),
 // linear, LayerNorm, 3-NN feature propagation.  fp32 throughout, like the reference.
 // Compiled with -ffp-contract=off: every fused multiply-add is an explicit fmaf().
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "topk_emulate.h"
 
 namespace {
@@ -49,11 +49,8 @@ __global__ __launch_bounds__(256) void count_valid_kernel(const uint8_t *__restr
     } else {
         for (int i = t; i < N; i += 256) c += p[i] ? 0 : 1;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((t & 63) == 0) s_w[t >> 6] = c;
-    __syncthreads();
-    if (t == 0) lengths[b] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    const int total = block_total<4>(c, s_w);
+    if (t == 0) lengths[b] = total;
 }
 
 __global__ __launch_bounds__(256) void to_channel_first_kernel(const float *__restrict__ x, int R, int C,
@@ -294,12 +291,7 @@ __global__ __launch_bounds__(256) void three_interp_cat_kernel(
         // smallest head over the lanes, ties to the smallest index
         float md = d0;
         int mi = i0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float od = __shfl_xor(md, off, 64);
-            const int oi = __shfl_xor(mi, off, 64);
-            if (od < md || (od == md && oi < mi)) md = od, mi = oi;
-        }
+        wave_argmin(md, mi);
         bd[k] = md, bi[k] = mi == 0x7fffffff ? 0 : mi;
         if (i0 == mi && mi != 0x7fffffff) d0 = d1, i0 = i1, d1 = d2, i1 = i2, d2 = INF, i2 = 0x7fffffff;  // pop
     }
@@ -314,8 +306,7 @@ __global__ __launch_bounds__(256) void three_interp_cat_kernel(
             d += (x * x + y * y) + z * z;
             eq += d == t3;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) eq += __shfl_xor(eq, off, 64);
+        eq = wave_sum(eq);
         const int taken = 1 + (bd[1] == t3) + (bd[0] == t3);
         if (eq > taken) {  // wave-uniform
             VI *row = reinterpret_cast<VI *>(s_rows_raw) + (size_t)(threadIdx.x >> 6) * S;

@@ -23,6 +23,7 @@
 //    force, bit for bit, including the first-index tie rule (buckets track the smallest
 //    original index among their maxima).  The caller's workspace holds the sorted read-only
 //    float4 (x, y, z, original index) array and the running `closest` array.
+#include "block_scan.h"
 #include "fps_util.h"
 
 #pragma clang fp contract(off)
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(FB) void fps_bucket_sort_kernel(const float *__rest
     __shared__ int s_hist[CELLS];
     __shared__ float s_red[4][FB / 64];
     __shared__ int s_wsum[FB / 64];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int b = blockIdx.x, t = threadIdx.x;
     const float *xyz = xyz_all + (size_t)b * N * 3;
     float4 *pts = pts_all + (size_t)b * N;
     float *closest = closest_all + (size_t)b * N;
@@ -175,20 +176,10 @@ __global__ __launch_bounds__(FB) void fps_bucket_sort_kernel(const float *__rest
         const float x = xyz[3 * i], y = xyz[3 * i + 1];
         lox = fminf(lox, x), hix = fmaxf(hix, x), loy = fminf(loy, y), hiy = fmaxf(hiy, y);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lox = fminf(lox, __shfl_xor(lox, off, 64));
-        loy = fminf(loy, __shfl_xor(loy, off, 64));
-        hix = fmaxf(hix, __shfl_xor(hix, off, 64));
-        hiy = fmaxf(hiy, __shfl_xor(hiy, off, 64));
-    }
-    if (lane == 0) s_red[0][w] = lox, s_red[1][w] = loy, s_red[2][w] = hix, s_red[3][w] = hiy;
+    box_put(lox, loy, hix, hiy, s_red);
     for (int c = t; c < CELLS; c += FB) s_hist[c] = 0;
     __syncthreads();
-    for (int k = 0; k < FB / 64; ++k) {
-        lox = fminf(lox, s_red[0][k]), loy = fminf(loy, s_red[1][k]);
-        hix = fmaxf(hix, s_red[2][k]), hiy = fmaxf(hiy, s_red[3][k]);
-    }
+    box_get(lox, loy, hix, hiy, s_red);
     const float sxc = (hix > lox) ? 64.f / (hix - lox) : 0.f;
     const float syc = (hiy > loy) ? 64.f / (hiy - loy) : 0.f;
     auto cell_of = [&](float x, float y) -> int {
@@ -201,17 +192,7 @@ __global__ __launch_bounds__(FB) void fps_bucket_sort_kernel(const float *__rest
     // exclusive scan of the 4096 counters: 4 per thread -> wave scan -> cross-wave offsets
     int c0 = s_hist[4 * t], c1 = s_hist[4 * t + 1], c2 = s_hist[4 * t + 2], c3 = s_hist[4 * t + 3];
     const int tsum = c0 + c1 + c2 + c3;
-    int inc = tsum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wsum[w] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < w; ++k) base += s_wsum[k];
-    const int excl = base + inc - tsum;
+    const int excl = block_scan_exclusive(tsum, s_wsum);
     s_hist[4 * t] = excl;
     s_hist[4 * t + 1] = excl + c0;
     s_hist[4 * t + 2] = excl + c0 + c1;

@@ -255,9 +255,7 @@ __global__ __launch_bounds__(256) void group_train_bwd_kernel(
         const long long pc = live ? pt : points - 1;
         const int b = (int)(pc / N);
         const int beg = live ? offsets[pc] : 0, len = live ? offsets[pc + 1] - beg : 0;
-        int maxlen = len;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, 64));
+        const int maxlen = wave_reduce(len, [](int a, int b) { return max(a, b); });
         float4 p[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) p[v] = *reinterpret_cast<const float4 *>(P_all + (size_t)pc * COUT + 4 * (gl + G * v));

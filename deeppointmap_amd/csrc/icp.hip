@@ -57,7 +57,7 @@ __device__ __forceinline__ double *partial_of(const IcpArgs &a, int p) { return 
 
 // One workgroup per pair: frame indices and counts, the target's xy bounds, the grid header, and the cell counters zeroed.
 __global__ __launch_bounds__(1024) void icp_setup_kernel(IcpArgs A, float radius) {
-    const int pair = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int pair = blockIdx.x, t = threadIdx.x;
     IcpHdr *hdr = hdr_of(A, pair);
     const int fs = min(max(A.src[pair], 0), A.F - 1), fd = min(max(A.dst[pair], 0), A.F - 1);
     const int n1 = min(max(A.lengths[fs], 0), A.N), n2 = min(max(A.lengths[fd], 0), A.N);
@@ -67,20 +67,12 @@ __global__ __launch_bounds__(1024) void icp_setup_kernel(IcpArgs A, float radius
         const float x = p2[i], y = p2[(size_t)A.N + i];
         lox = fminf(lox, x), hix = fmaxf(hix, x), loy = fminf(loy, y), hiy = fmaxf(hiy, y);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lox = fminf(lox, __shfl_xor(lox, off, 64)), loy = fminf(loy, __shfl_xor(loy, off, 64));
-        hix = fmaxf(hix, __shfl_xor(hix, off, 64)), hiy = fmaxf(hiy, __shfl_xor(hiy, off, 64));
-    }
     __shared__ float red[4][16];
     __shared__ int s_ncell;
-    if (lane == 0) red[0][w] = lox, red[1][w] = loy, red[2][w] = hix, red[3][w] = hiy;
+    box_put(lox, loy, hix, hiy, red);
     __syncthreads();
     if (t == 0) {
-        for (int k = 1; k < 16; ++k) {
-            lox = fminf(lox, red[0][k]), loy = fminf(loy, red[1][k]);
-            hix = fmaxf(hix, red[2][k]), hiy = fmaxf(hiy, red[3][k]);
-        }
+        box_get(lox, loy, hix, hiy, red, 1);
         // an empty target, or one with a non-finite coordinate (its bounds are no numbers to divide by): one empty-handed cell
         const bool usable = n2 > 0 && hix - lox < 3e38f && hiy - loy < 3e38f && hix - lox >= 0.f && hiy - loy >= 0.f;
         int gx = 1, gy = 1, H = 1;

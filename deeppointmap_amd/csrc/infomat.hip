@@ -9,6 +9,7 @@
 // cells around it (65 536^2 = 4.3e9 pair evaluations become ~6e6).  Summing the three outer
 // products gives a matrix that depends on ten moments (n, sum x, y, z, xx, yy, zz, xy, xz, yz);
 // they are accumulated in fp64 and rounded once to the fp32 6x6 the reference returns.
+#include "block_scan.h"
 #include "cell_grid.h"
 #include "workspace.h"
 #include <type_traits>
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(256) void grid_bounds_kernel(PairArgs A) {
         lox = fminf(lox, xs[u]), hix = fmaxf(hix, xs[u]), loy = fminf(loy, ys[u]), hiy = fmaxf(hiy, ys[u]);
         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(xs[u]), fabsf(ys[u])), fabsf(zs[u])));
     }
+    // written out, not box_put + wave_max: with the fifth value in a butterfly of its own the kernel takes 64 VGPRs for 61
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         lox = fminf(lox, __shfl_xor(lox, off, 64)), loy = fminf(loy, __shfl_xor(loy, off, 64));
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(256) void grid_offsets_kernel(PairArgs A) {
     const int gy = hdr->gy, chunks = (A.N2 + GB_CHUNK - 1) / GB_CHUNK;
     int *hist = pair_rowhist(A, pair), *rowstart = pair_rowstart(A, pair);
     __shared__ int wsum[4];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     // thread t owns rows 2t and 2t + 1 (gy <= GMAX = 512)
     int tot[2] = {0, 0};
 #pragma unroll
@@ -212,16 +214,7 @@ __global__ __launch_bounds__(256) void grid_offsets_kernel(PairArgs A) {
             for (int c = 0; c < chunks; ++c) tot[k] += hist[(size_t)c * GMAX + r];
     }
     const int sum = tot[0] + tot[1];
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int k = 0; k < w; ++k) run += wsum[k];
+    int run = block_scan_exclusive(sum, wsum);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int r = 2 * t + k;
@@ -271,13 +264,7 @@ __global__ __launch_bounds__(256) void grid_cells_kernel(PairArgs A) {
     const int per = (gx + 63) / 64, a = min(lane * per, gx), b = min(a + per, gx);
     int sum = 0;
     for (int k = a; k < b; ++k) sum += c[k];
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    int run = lo + inc - sum;
+    int run = lo + wave_scan_inclusive(sum) - sum;
     for (int k = a; k < b; ++k) {
         const int n = c[k];
         c[k] = run, run += n;
@@ -481,7 +468,7 @@ __global__ __launch_bounds__(256) void nn1_match_kernel(PairArgs A, float r2, in
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
-        long long v = m[k];
+        long long v = m[k];   // written out: through wave_sum this kernel, the longest of the chain, ran 18 % longer
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
         if (lane == 0) sred[w][k] = v;
@@ -500,8 +487,7 @@ __global__ __launch_bounds__(64) void infomat_finalize_kernel(PairArgs A) {
     for (int k = 0; k < 10; ++k) {
         long long v = 0;
         for (int b = lane; b < nblk; b += 64) v += part[(size_t)b * 10 + k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        v = wave_sum(v);
         if (lane == 0) s[k] = v;
     }
     __syncthreads();

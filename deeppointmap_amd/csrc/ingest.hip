@@ -59,11 +59,8 @@ __global__ __launch_bounds__(256) void ingest_count_kernel(const long long *__re
         const long long c = c0 + k;
         if (c < fr.rows && keeps(fr, (int)c)) ++cnt;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) bcount[(size_t)f * nblk + blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    const int total = block_total<4>(cnt, s);
+    if (threadIdx.x == 0) bcount[(size_t)f * nblk + blockIdx.x] = total;
 }
 
 // grid (F), one wave: exclusive scan of a frame's chunk counts in place, the total is the frame's count
@@ -74,12 +71,7 @@ __global__ __launch_bounds__(64) void ingest_scan_kernel(int nblk, int *__restri
     for (int b0 = 0; b0 < nblk; b0 += 64) {
         const int b = b0 + lane;
         const int v = b < nblk ? bc[b] : 0;
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const int inc = wave_scan_inclusive(v);
         if (b < nblk) bc[b] = carry + inc - v;
         carry += __shfl(inc, 63, 64);
     }

@@ -290,7 +290,7 @@ __device__ __forceinline__ void emit_heap_result(LdsF hv, LdsI hi, int K, float 
     const float myv = mv;
     const int myi = mi;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int off = 32; off > 0; off >>= 1) {   // wave_argmin written out: through the helper knn_tie_nth_kernel timed slower
         const float ov = __shfl_xor(mv, off, 64);
         const int oi = __shfl_xor(mi, off, 64);
         if (ov < mv || (ov == mv && oi < mi)) mv = ov, mi = oi;
@@ -535,6 +535,7 @@ __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float *__res
         lox = fminf(lox, x), hix = fmaxf(hix, x), loy = fminf(loy, y), hiy = fmaxf(hiy, y);
         m2 = fmaxf(m2, sq3(x, y, z));
     });
+    // written out, not box_put / box_get: with the fifth value folded apart the kernel timed 1.5 % slower
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         lox = fminf(lox, __shfl_xor(lox, off, 64)), loy = fminf(loy, __shfl_xor(loy, off, 64));
@@ -1335,12 +1336,6 @@ __global__ __launch_bounds__(WPB * 64) void knn_self_kernel(const float *__restr
 // the sign is arbitrary -- the caller only uses |n_i . n_j|); fewer than 3 points in range -> (0,0,1).
 // One wave per point over the 3x3 cells of a grid with cell edge >= r.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <bool DC>  // DC: as in knn_self_kernel
 __global__ __launch_bounds__(WPB * 64) void point_normals_kernel(const float *__restrict__ pts, int N, float r2,
                                                                  const int32_t *__restrict__ count, int kmin,
@@ -1374,7 +1369,7 @@ __global__ __launch_bounds__(WPB * 64) void point_normals_kernel(const float *__
         }
     }
 #pragma unroll
-    for (int k = 0; k < 10; ++k) m[k] = wave_sum_f64(m[k]);
+    for (int k = 0; k < 10; ++k) m[k] = wave_sum(m[k]);
     if (lane != 0) return;
     float nx = 0.f, ny = 0.f, nz = 1.f;
     if (m[0] >= 3.0) {

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void lidar_cull_kernel(const double *__restric
                                                          float *__restrict__ plane, int32_t *__restrict__ status,
                                                          const double *__restrict__ poses1, int A, float *__restrict__ table) {
     __shared__ int s_w[4];
-    const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int f = blockIdx.x, t = threadIdx.x;
     const double *M = poses + 16 * (size_t)f;
     if constexpr (MOVING) {
         // every thread derives the frame's motion itself (a few dozen float64 operations); the reach grows by the travel
@@ -76,16 +76,7 @@ __global__ __launch_bounds__(256) void lidar_cull_kernel(const double *__restric
             const double sz = ez - q[8], reach = max_range + q[9];
             keep = (ex * ex + ey * ey) + sz * sz <= reach * reach;
         }
-        int inc = keep;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        int pos = base + inc - (int)keep;
-        for (int k = 0; k < w; ++k) pos += s_w[k];
+        const int pos = block_scan_exclusive((int)keep, s_w, base);
         base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
         __syncthreads();
         if (keep && pos < max_kept) {
@@ -248,8 +239,7 @@ __global__ __launch_bounds__(256) void lidar_emit_kernel(const float *__restrict
         total += k;
         before += r < c0 ? k : 0;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64), total += __shfl_xor(total, off, 64);
+    before = wave_sum(before), total = wave_sum(total);
     if (lane == 0) s_a[w] = before, s_b[w] = total;
     // thread t owns CH / 256 CONSECUTIVE rays so that the block-level order is the ray order
     bool keep[CH / 256];

@@ -120,9 +120,7 @@ __global__ __launch_bounds__(1024) void nn_setup_kernel(NnArgs A, float radius) 
         lo[2] = fminf(lo[2], z), hi[2] = fmaxf(hi[2], z);
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lo[k] = fminf(lo[k], __shfl_xor(lo[k], off, 64)), hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off, 64));
+    for (int k = 0; k < 3; ++k) lo[k] = wave_min(lo[k]), hi[k] = wave_max(hi[k]);
     __shared__ float red[6][16];
     __shared__ int s_ncell;
     if (lane == 0)
@@ -259,12 +257,7 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float *__restr
     __shared__ double sred[4][NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(v, off, 64);
-            v = k == 4 ? (o > v ? o : v) : v + o;
-        }
+        const double v = k == 4 ? wave_max(s[k]) : wave_sum(s[k]);
         if (lane == 0) sred[w][k] = v;
     }
     __syncthreads();

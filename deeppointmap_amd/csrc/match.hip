@@ -13,7 +13,7 @@
 // exact top-k of the whole matrix under the rule of dpm_dual_softmax_topk -- which stays for N > 256 (map-vs-map).
 // S is bit-identical to gemm_nt_mfma_kernel's (same instruction, same k order); the column sums are folded as
 // sum_s psum_s * exp(pmax_s - cmax) instead of one pass against the final maximum (last-bit differences).
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "workspace.h"
 
 namespace {
@@ -188,13 +188,7 @@ __device__ __forceinline__ void pick_bin(const unsigned *hist, unsigned *sc /* [
     const int t = threadIdx.x;   // t < 64
     const int first = DESC ? 255 - 4 * t : 4 * t, step = DESC ? -1 : 1;
     const unsigned c0 = hist[first], c1 = hist[first + step], c2 = hist[first + 2 * step], c3 = hist[first + 3 * step];
-    unsigned inc = c0 + c1 + c2 + c3;
-    const unsigned own = inc;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_up(inc, off, 64);
-        if (t >= off) inc += o;
-    }
+    const unsigned own = c0 + c1 + c2 + c3, inc = wave_scan_inclusive(own);
     const unsigned rem0 = sc[2];
     const unsigned long long hit = __ballot(inc >= rem0);
     const int L = hit ? __builtin_ctzll(hit) : 63;

@@ -95,11 +95,8 @@ __global__ __launch_bounds__(256) void pre_count_kernel(const float *__restrict_
             if (g != 0x7fffffff && keep_point(xyz, stride, g, dmin, dmax)) ++cnt;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) bcount[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    const int total = block_total<4>(cnt, s);
+    if (threadIdx.x == 0) bcount[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(1024) void pre_scan_kernel(PreHdr *__restrict__ hdr, int *__restrict__ bcount, int max_blocks) {
@@ -210,8 +207,7 @@ __global__ __launch_bounds__(1024) void stat_filter_kernel(const float *__restri
     if (DC) N = min(max(count[0], 0), N);
     const bool pass = DC && N <= kmin;  // uniform over the workgroup
     auto block_sum = [&](double v) -> double {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        v = wave_sum(v);
         __syncthreads();
         if (lane == 0) s_red[w] = v;
         __syncthreads();

@@ -98,15 +98,6 @@ __global__ __launch_bounds__(64) void sc_finish_kernel(const float *__restrict__
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
 __device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v) {
     const unsigned lo = __shfl_up((unsigned)v, 1, 64), hi = __shfl_up((unsigned)(v >> 32), 1, 64);
     return ((unsigned long long)hi << 32) | lo;
@@ -213,7 +204,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void sc_search_kernel(const float *_
             const int used = __popcll(mq & rot);
             const float d = used ? fmaxf(1.f - S / (float)used, 0.f) : 1.f;
             unsigned long long key = lane < sectors ? ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)lane : SC_PAD;
-            key = wave_min_u64(key);
+            key = wave_min(key);
             sc_insert(lkey, lshift, (key & 0xFFFFFFFF00000000ull) | (unsigned)c, (int)(key & 0xFFFFFFFFu), K);
         }
     }
@@ -251,7 +242,7 @@ __global__ __launch_bounds__(64) void sc_merge_kernel(const unsigned long long *
             const unsigned long long v = pk[i];
             if ((first || v > last) && v < best) best = v;
         }
-        best = wave_min_u64(best);
+        best = wave_min(best);
         if (best == SC_PAD) {   // fewer than K candidates: (inf, -1, -1) from here on
             if (lane == 0)
                 for (int kk = k; kk < K; ++kk) dist[q * K + kk] = __uint_as_float(0x7F800000u), row[q * K + kk] = -1, shift[q * K + kk] = -1;

@@ -31,7 +31,7 @@
 //
 // Memory: header 256 B + per slot 40 B (key 8, sums 24, first 4, count 4) with N + N/4 (+64) slots, + N/4 bytes of
 // bitmask / prefix: <= 51 B per input point (+ 8 KB).
-#include "dpm_common.h"
+#include "block_scan.h"
 #include "workspace.h"
 
 namespace {
@@ -142,14 +142,8 @@ __global__ __launch_bounds__(VM_BLOCK) void vm_bounds_kernel(const float *const 
         }
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off, 64));
-        }
-        bad += __shfl_xor(bad, off, 64);
-    }
+    for (int a = 0; a < 3; ++a) mn[a] = wave_min(mn[a]), mx[a] = wave_max(mx[a]);
+    bad = wave_sum(bad);
     if (lane_id() == 0 && g0 < n) {
         Header *h = reinterpret_cast<Header *>(ws);
 #pragma unroll
@@ -280,12 +274,7 @@ __global__ __launch_bounds__(VM_BLOCK) void vm_insert_kernel(const float *const 
         flush(carry, L, ws, cas);
         ++runs;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        runs += __shfl_xor(runs, off, 64);
-        cas += __shfl_xor(cas, off, 64);
-        badkey += __shfl_xor(badkey, off, 64);
-    }
+    runs = wave_sum(runs), cas = wave_sum(cas), badkey = wave_sum(badkey);
     if (lane == 0) {
         Header *h = reinterpret_cast<Header *>(ws);
         atomicAdd(&h->runs, (unsigned long long)runs);
@@ -311,12 +300,7 @@ __global__ __launch_bounds__(VM_BLOCK) void vm_mark_kernel(unsigned char *__rest
 // exclusive block scan of one value per thread (256 threads); returns the block total through *total
 __device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *lds /* 4 */, unsigned *total) {
     const int lane = lane_id(), wave = threadIdx.x >> 6;
-    unsigned x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned u = __shfl_up(x, d, 64);
-        if (lane >= d) x += u;
-    }
+    const unsigned x = wave_scan_inclusive(v);
     if (lane == 63) lds[wave] = x;
     __syncthreads();
     unsigned before = 0, all = 0;

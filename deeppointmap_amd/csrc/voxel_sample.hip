@@ -169,10 +169,8 @@ __global__ __launch_bounds__(256) void vox_count_kernel(const VoxHdr *__restrict
         const long long cell = (long long)chunk * CH + k * 256 + t;
         n += (cell < nc && c[cell] != 0u) ? 1 : 0;
     }
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if ((t & 63) == 0) s[t >> 6] = n;
-    __syncthreads();
-    if (t == 0) bcount[(size_t)b * nchunk + chunk] = s[0] + s[1] + s[2] + s[3];
+    const int total = block_total<4>(n, s);
+    if (t == 0) bcount[(size_t)b * nchunk + chunk] = total;
 }
 
 // exclusive scan of a frame's chunk counts (in place) + number of occupied voxels
