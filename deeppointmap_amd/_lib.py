@@ -180,6 +180,9 @@ SIGNATURES = {
     "dpm_tsdf_absorb": (I, [P, I, P, P, P, I, P]),
     "dpm_tsdf_surface": (I, [P, I, D, I, P, P, P, P, P, I, P]),
     "dpm_tsdf_mesh": (I, [P, I, D, I, P, P, P, P, I, P]),
+    "dpm_tsdf_surface_tiles": (I, [P, I, D, I, I, P, I, P, P, P, P, P, I, P]),
+    "dpm_tsdf_mesh_indexed_bytes": (c_size_t, [I]),
+    "dpm_tsdf_mesh_indexed": (I, [P, I, D, I, I, P, I, P, P, P, P, P, P, I, I, P, P]),
     "dpm_tsdf_sample": (I, [P, I, D, P, P, P, I, P, I, P, P, P, P]),
     "dpm_tsdf_register_scratch_bytes": (c_size_t, [I]),
     "dpm_tsdf_register": (I, [P, I, D, P, D, I, D, P, P, I, P, P, P, I, D, D, D, P, P, P, P, P, P, P, P, P]),

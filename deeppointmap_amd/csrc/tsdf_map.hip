@@ -63,13 +63,20 @@
 //              or one non-negative corner gives a triangle, two and two a quadrilateral cut into two triangles; they are wound
 //              so that the normal (b - a) x (c - a) points to the positive side.  A corner with D == 0 counts as positive, and
 //              the triangles of zero area it makes are kept.
+//   indexed    the same mesh with the weld done here: a vertex (key of p, direction) is (slot of p << 3) | direction, a 7-bit mask
+//              per slot says which exist, a scan over the masks' popcounts numbers them; faces are index triples, a vertex carries
+//              surface's normal of its edge.  Six launches, integer atomics only ("the indexed mesh" below).
+//   tiles      surface and the indexed mesh given a sorted list of tile keys emit only what is anchored at a voxel of one of those
+//              tiles, and read whatever that needs: single-tile calls partition the result ("Meshing beyond the table").
 //   raycast    one lane per ray, grid y the pose, lookups only: the field (below) at t_k = t0 + (float)k * h along o + u * t, the
 //              first sign change between two valued samples in a row -> range, the unit gradient in the sensor frame, a flag
 //              (MISS 0, HIT 1, BACK 2).  blocks: the set of 8 x 8 x 8 blocks that hold a qualified voxel, one lane per slot;
 //              the marcher skips the lookups of a sample whose base voxel lies in a block the set does not hold.
+#include "block_scan.h"
 #include "gn_one.h"
 #include "scan_source.h"
 #include "voxel_hash.h"
+#include "workspace.h"
 
 namespace {
 
@@ -389,6 +396,50 @@ __device__ __forceinline__ void add_grad(const Tsdf &M, const int x[3], float D,
     }
 }
 
+// the normal of a crossing between the qualified voxels x0 and x1: g = grad(x0) + grad(x1) divided per axis by its length, or zeros
+__device__ __forceinline__ void edge_normal(const Tsdf &M, const int x0[3], float D0, const int x1[3], float D1, unsigned min_count,
+                                            float n[3]) {
+    float g0[3] = {0.f, 0.f, 0.f}, g1[3] = {0.f, 0.f, 0.f};
+    add_grad(M, x0, D0, min_count, g0);
+    add_grad(M, x1, D1, min_count, g1);
+    const float gx = g0[0] + g1[0], gy = g0[1] + g1[1], gz = g0[2] + g1[2];
+    const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
+    const bool unit = len > 0.f;
+    n[0] = unit ? __fdiv_rn(gx, len) : 0.f;
+    n[1] = unit ? __fdiv_rn(gy, len) : 0.f;
+    n[2] = unit ? __fdiv_rn(gz, len) : 0.f;
+}
+
+// Ownership by tiles (csrc/voxel_hash.h): an extraction that is given a sorted list of n tile keys emits only what is anchored at
+// a voxel k0 whose tile, pack_key(x >> b, y >> b, z >> b), is in the list; n == 0: everything.  A list of up to OWN_LDS keys is
+// staged in LDS by own_stage, which EVERY thread of the block calls before any leaves (it holds a barrier); a longer one is
+// searched where it lies.
+constexpr int OWN_LDS = 1024;
+
+struct Owners {
+    const unsigned long long *tiles;
+    int n, b;
+};
+
+__device__ __forceinline__ const unsigned long long *own_stage(const Owners &O, unsigned long long *lds) {
+    if (O.n == 0 || O.n > OWN_LDS) return O.tiles;
+    for (int i = threadIdx.x; i < O.n; i += TS_BLOCK) lds[i] = O.tiles[i];
+    __syncthreads();
+    return lds;
+}
+
+__device__ __forceinline__ bool owned(const Owners &O, const unsigned long long *list, unsigned long long k0) {
+    if (O.n == 0) return true;
+    const unsigned long long t = pack_key(key_axis(k0, 0) >> O.b, key_axis(k0, 1) >> O.b, key_axis(k0, 2) >> O.b);
+    int lo = 0, hi = O.n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (list[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < O.n && list[lo] == t;
+}
+
 __global__ __launch_bounds__(TS_BLOCK) void ts_surface_kernel(Tsdf M, unsigned min_count, unsigned long long *keys, int32_t *axes,
                                                               float *xyz, float *normals, int32_t *count, int max_out) {
     const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
@@ -418,6 +469,38 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_surface_kernel(Tsdf M, unsigned m
         normals[3 * (size_t)pos] = unit ? __fdiv_rn(gx, len) : 0.f;
         normals[3 * (size_t)pos + 1] = unit ? __fdiv_rn(gy, len) : 0.f;
         normals[3 * (size_t)pos + 2] = unit ? __fdiv_rn(gz, len) : 0.f;
+    }
+}
+
+// ts_surface_kernel's records, in its order, of the owned voxels.  The older kernel stays as it was written, so that its instructions
+// do (scripts/isa_diff.py against the parent commit); what the two share is edge_normal's rule.
+__global__ __launch_bounds__(TS_BLOCK) void ts_surface_tiles_kernel(Tsdf M, unsigned min_count, Owners W, unsigned long long *keys,
+                                                                    int32_t *axes, float *xyz, float *normals, int32_t *count,
+                                                                    int max_out) {
+    __shared__ unsigned long long own[OWN_LDS];
+    const unsigned long long *list = own_stage(W, own);
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long k0 = M.keys()[slot];
+    float D0;
+    if (k0 == EMPTY || !slot_value(M, slot, min_count, D0) || !owned(W, list, k0)) return;
+    const int x0[3] = {key_axis(k0, 0), key_axis(k0, 1), key_axis(k0, 2)};
+    float c[3];
+    voxel_centre(k0, M.v, c);
+    for (int a = 0; a < 3; ++a) {
+        const int x1[3] = {x0[0] + (a == 0), x0[1] + (a == 1), x0[2] + (a == 2)};
+        float D1;
+        if (!voxel_value(M, x1[0], x1[1], x1[2], min_count, D1) || (D0 < 0.f) == (D1 < 0.f)) continue;
+        const int pos = atomicAdd(count, 1);
+        if (pos < 0 || pos >= max_out) continue;
+        const float f = __fdiv_rn(D0, D0 - D1);
+        float n[3];
+        edge_normal(M, x0, D0, x1, D1, min_count, n);
+        keys[pos] = k0, axes[pos] = a;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) xyz[3 * (size_t)pos + b] = b == a ? c[b] + f * M.v : c[b];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) normals[3 * (size_t)pos + b] = n[b];
     }
 }
 
@@ -459,6 +542,37 @@ __device__ __forceinline__ void put_triangle(const MeshOut &O, const Cell &C, co
     put_vertex(O, C, m, flip ? b0 : c0, flip ? b1 : c1, pos, 2);
 }
 
+// The triangles of a cell whose corner m has bit m of `neg` set when D[m] < 0, each handed to emit(m, a0, a1, b0, b1, c0, c1, flip):
+// put_triangle's arguments, m the four nested corners of the tetrahedron it lies in.  ts_mesh_kernel's walk, for the indexed mesh
+// below; ts_mesh_kernel keeps its own copy so that its instructions stay (scripts/isa_diff.py against the parent commit).
+template <typename Emit>
+__device__ __forceinline__ void march_cell(int neg, Emit emit) {
+    for (int t = 0; t < 6; ++t) {
+        // the t-th permutation (a, b, c) of the axes in lexicographic order; odd ones give a left-handed tetrahedron
+        const int a = t >> 1, b = (0x489 >> (2 * t)) & 3;   // b = 1, 2, 0, 2, 0, 1
+        const bool odd = (0x26 >> t) & 1;                    // t = 1, 2, 5
+        const int m[4] = {0, 1 << a, (1 << a) | (1 << b), 7};
+        int nm = 0;
+        for (int i = 0; i < 4; ++i) nm |= ((neg >> m[i]) & 1) << i;
+        const int cnt = __popc(nm);
+        if (cnt == 0 || cnt == 4) continue;
+        if (cnt != 2) {
+            // corner A alone on its side; (A, B, C, D) with B < C < D is an even permutation when A is even
+            const int A = __ffs(cnt == 1 ? nm : (~nm & 15)) - 1;
+            const int B = A == 0 ? 1 : 0, Cc = A <= 1 ? 2 : 1, Dd = A == 3 ? 2 : 3;
+            emit(m, A, B, A, Cc, A, Dd, ((A & 1) != 0) ^ odd ^ (cnt == 3));
+        } else {
+            // A < B negative, Cc < Dd positive; the parity of (A, B, Cc, Dd) is that of its inversions
+            const int A = __ffs(nm) - 1, B = 31 - __clz(nm), pm = ~nm & 15, Cc = __ffs(pm) - 1, Dd = 31 - __clz(pm);
+            const int inv = (A > Cc) + (A > Dd) + (B > Cc) + (B > Dd);
+            const bool swap = ((inv & 1) != 0) ^ odd;
+            const int P = swap ? Dd : Cc, Q = swap ? Cc : Dd;
+            emit(m, A, P, A, Q, B, Q, false);
+            emit(m, A, P, B, Q, B, P, false);
+        }
+    }
+}
+
 __global__ __launch_bounds__(TS_BLOCK) void ts_mesh_kernel(Tsdf M, unsigned min_count, MeshOut O) {
     const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
     if (slot >= M.cap_vox) return;
@@ -497,6 +611,123 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_mesh_kernel(Tsdf M, unsigned min_
             put_triangle(O, C, m, A, P, B, Q, B, P, false);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------- the indexed mesh
+// The same cells and triangles with the weld done here: a vertex is named (key of p, direction) and p is a slot of this table, so
+// (slot << 3) | direction is a vertex id that needs no sorting of names.  Six launches, integer atomics only:
+//   clear     the mask words and the two counts
+//   cells     ts_mesh_kernel's walk over the cells whose base voxel is owned: a triangle takes its position by atomicAdd and is
+//             written as three ids; every id sets bit `direction` of its slot's byte of the mask (atomicOr on the 32-bit word)
+//   count     the popcounts of the masks summed per block of 256 slots
+//   scan      one block: the exclusive scan of those sums in place, and V, their total
+//   vertices  one lane per slot: the block's sum + the scan inside the block is the slot's first vertex index; per used
+//             direction, ascending, the name, put_vertex's position and ts_surface_kernel's normal of the edge p - q
+//   remap     one lane per written id: first[slot] + the used directions below it
+// Which index a vertex gets follows the slots, and the slots follow the order of arrival: the caller sorts by name.
+struct MeshIdx {
+    unsigned *mask;          // cap_vox bytes in 32-bit words: byte s = the used directions of slot s
+    int32_t *first;          // (cap_vox,) the first vertex index of slot s
+    int32_t *block_first;    // (cap_vox / 256 rounded up,)
+    int32_t *counts;         // V, F
+    unsigned long long *vkeys;
+    int32_t *vdirs;
+    float *xyz, *normals;
+    int32_t *faces;          // (max_f,3)
+    int max_v, max_f;
+};
+
+constexpr int SCAN_BLOCK = 1024;
+
+__device__ __forceinline__ unsigned slot_mask(const MeshIdx &X, int slot) { return ((const unsigned char *)X.mask)[slot]; }
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_mesh_clear_kernel(MeshIdx X, int words) {
+    const size_t tid = (size_t)blockIdx.x * TS_BLOCK + threadIdx.x, stride = (size_t)gridDim.x * TS_BLOCK;
+    if (tid < 2) X.counts[tid] = 0;
+    for (size_t i = tid; i < (size_t)words; i += stride) X.mask[i] = 0u;
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_mesh_cells_kernel(Tsdf M, unsigned min_count, Owners W, MeshIdx X) {
+    __shared__ unsigned long long own[OWN_LDS];
+    const unsigned long long *list = own_stage(W, own);
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long k0 = M.keys()[slot];
+    float D[8];
+    int at[8];
+    if (k0 == EMPTY || !slot_value(M, slot, min_count, D[0]) || !owned(W, list, k0)) return;
+    at[0] = slot;
+    int neg = D[0] < 0.f;
+    for (int m = 1; m < 8; ++m) {
+        const int x = key_axis(k0, 0) + (m & 1), y = key_axis(k0, 1) + ((m >> 1) & 1), z = key_axis(k0, 2) + (m >> 2);
+        if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) return;
+        at[m] = find_slot(M.keys(), M.cap_vox, pack_key(x, y, z));
+        if (!slot_value(M, at[m], min_count, D[m])) return;
+        neg |= (D[m] < 0.f) << m;
+    }
+    if (neg == 0 || neg == 255) return;
+    march_cell(neg, [&](const int m[4], int a0, int a1, int b0, int b1, int c0, int c1, bool flip) {
+        const int e[3][2] = {{a0, a1}, {flip ? c0 : b0, flip ? c1 : b1}, {flip ? b0 : c0, flip ? b1 : c1}};
+        const int pos = atomicAdd(&X.counts[1], 1);
+        const bool room = pos >= 0 && pos < X.max_f;
+        for (int j = 0; j < 3; ++j) {
+            const int p = m[min(e[j][0], e[j][1])], d = m[max(e[j][0], e[j][1])] ^ p;
+            const int dir = d == 1 ? 0 : d == 2 ? 1 : d == 4 ? 2 : d == 3 ? 3 : d == 5 ? 4 : d == 6 ? 5 : 6, s = at[p];
+            atomicOr(&X.mask[s >> 2], (1u << dir) << (8 * (s & 3)));   // also without room: V is counted in full
+            if (room) X.faces[3 * (size_t)pos + j] = (s << 3) | dir;
+        }
+    });
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_mesh_count_kernel(int cap_vox, MeshIdx X) {
+    __shared__ int part[TS_BLOCK / 64];
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const int total = block_total<TS_BLOCK / 64>(slot < cap_vox ? __popc(slot_mask(X, slot)) : 0, part);
+    if (threadIdx.x == 0) X.block_first[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(SCAN_BLOCK) void ts_mesh_scan_kernel(int blocks, int per, MeshIdx X) {
+    __shared__ int wsum[SCAN_BLOCK / 64];
+    const int total = block_scan_runs(X.block_first, blocks, per, wsum);
+    if (threadIdx.x == SCAN_BLOCK - 1) X.counts[0] = total;
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_mesh_vertices_kernel(Tsdf M, unsigned min_count, MeshIdx X) {
+    __shared__ int wsum[TS_BLOCK / 64];
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    const unsigned mask = slot < M.cap_vox ? slot_mask(X, slot) : 0u;
+    int idx = block_scan_exclusive((int)__popc(mask), wsum, (int)X.block_first[blockIdx.x]);
+    if (slot >= M.cap_vox) return;
+    X.first[slot] = idx;
+    if (mask == 0u) return;
+    const unsigned long long key = M.keys()[slot];
+    float Dp = 0.f, c[3];
+    slot_value(M, slot, min_count, Dp);      // a marked slot is a qualified corner of a meshed cell, and so is every q below
+    voxel_centre(key, M.v, c);
+    const int x0[3] = {key_axis(key, 0), key_axis(key, 1), key_axis(key, 2)};
+    for (int dir = 0; dir < 7; ++dir) {
+        if (!((mask >> dir) & 1u)) continue;
+        const int at = idx++;
+        if (at >= X.max_v) continue;
+        const int d = (0x7653421 >> (4 * dir)) & 7;      // q ^ p of the direction: 1, 2, 4, 3, 5, 6, 7
+        const int x1[3] = {x0[0] + (d & 1), x0[1] + ((d >> 1) & 1), x0[2] + (d >> 2)};
+        float Dq = 0.f, n[3];
+        voxel_value(M, x1[0], x1[1], x1[2], min_count, Dq);
+        const float f = __fdiv_rn(Dp, Dp - Dq);
+        edge_normal(M, x0, Dp, x1, Dq, min_count, n);
+        X.vkeys[at] = key, X.vdirs[at] = dir;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) X.xyz[3 * (size_t)at + b] = (d >> b) & 1 ? c[b] + f * M.v : c[b];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) X.normals[3 * (size_t)at + b] = n[b];
+    }
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void ts_mesh_remap_kernel(MeshIdx X) {
+    const size_t i = (size_t)blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (i >= 3 * (size_t)min(max(X.counts[1], 0), X.max_f)) return;
+    const int id = X.faces[i], s = id >> 3;
+    X.faces[i] = X.first[s] + (int)__popc(slot_mask(X, s) & ((1u << (id & 7)) - 1u));
 }
 
 // ------------------------------------------------------------------------------------------- the field at a point, registration
@@ -884,6 +1115,63 @@ extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min
     const MeshOut O{vertex_keys, vertex_dirs, xyz, count, max_out};
     hipLaunchKernelGGL(ts_mesh_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
                        make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, O);
+    return dpm_launch_status();
+}
+
+// the owner list of an entry point: nothing (everything is owned), or n sorted tile keys on the device
+static bool owners_ok(int tile_bits, const unsigned long long *tiles, int n_tiles) {
+    return n_tiles >= 0 && (n_tiles == 0 || (tiles && tile_bits >= 3 && tile_bits <= 10));
+}
+
+extern "C" int dpm_tsdf_surface_tiles(const void *map, int cap_vox, double voxel, int min_count, int tile_bits,
+                                      const unsigned long long *tiles, int n_tiles, unsigned long long *keys, int32_t *axes,
+                                      float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
+    DPM_CHECK_ARG(owners_ok(tile_bits, tiles, n_tiles) && (max_out == 0 || (keys && axes && xyz && normals)));
+    const Owners W{n_tiles ? tiles : nullptr, n_tiles, tile_bits};
+    hipLaunchKernelGGL(ts_surface_tiles_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, W, keys, axes, xyz, normals, count, max_out);
+    return dpm_launch_status();
+}
+
+// the indexed mesh's workspace: the mask bytes, a first index per slot, a sum per block of slots
+static void mesh_indexed_layout(WsCursor &c, int cap_vox, MeshIdx &X) {
+    X.mask = c.take256<unsigned>(dpm_cdiv(cap_vox, 4));
+    X.first = c.take256<int32_t>((size_t)cap_vox);
+    X.block_first = c.take256<int32_t>(dpm_cdiv(cap_vox, TS_BLOCK));
+}
+
+extern "C" size_t dpm_tsdf_mesh_indexed_bytes(int cap_vox) {
+    if (!table_ok((const void *)16, cap_vox)) return 0;
+    WsCursor c(nullptr);
+    MeshIdx X;
+    mesh_indexed_layout(c, cap_vox, X);
+    return c.bytes();
+}
+
+extern "C" int dpm_tsdf_mesh_indexed(const void *map, int cap_vox, double voxel, int min_count, int tile_bits,
+                                     const unsigned long long *tiles, int n_tiles, unsigned long long *vertex_keys,
+                                     int32_t *vertex_dirs, float *xyz, float *normals, int32_t *faces, int32_t *counts, int max_v,
+                                     int max_f, void *workspace, dpm_stream_t stream) {
+    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && counts && workspace);
+    DPM_CHECK_ARG(owners_ok(tile_bits, tiles, n_tiles) && max_v >= 0 && max_f >= 0 && max_f <= 0x7FFFFFFF / 3);
+    DPM_CHECK_ARG((max_v == 0 || (vertex_keys && vertex_dirs && xyz && normals)) && (max_f == 0 || faces));
+    hipStream_t st = (hipStream_t)stream;
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, nullptr);
+    const Owners W{n_tiles ? tiles : nullptr, n_tiles, tile_bits};
+    MeshIdx X{};
+    WsCursor c(workspace);
+    mesh_indexed_layout(c, cap_vox, X);
+    X.counts = counts, X.vkeys = vertex_keys, X.vdirs = vertex_dirs, X.xyz = xyz, X.normals = normals, X.faces = faces;
+    X.max_v = max_v, X.max_f = max_f;
+    const unsigned g = dpm_cdiv(cap_vox, TS_BLOCK), words = dpm_cdiv(cap_vox, 4), gw = dpm_cdiv(words, TS_BLOCK);
+    hipLaunchKernelGGL(ts_mesh_clear_kernel, dim3(gw > 8192 ? 8192 : gw), dim3(TS_BLOCK), 0, st, X, (int)words);
+    hipLaunchKernelGGL(ts_mesh_cells_kernel, dim3(g), dim3(TS_BLOCK), 0, st, M, (unsigned)min_count, W, X);
+    hipLaunchKernelGGL(ts_mesh_count_kernel, dim3(g), dim3(TS_BLOCK), 0, st, cap_vox, X);
+    hipLaunchKernelGGL(ts_mesh_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, (int)g, (int)dpm_cdiv(g, SCAN_BLOCK), X);
+    hipLaunchKernelGGL(ts_mesh_vertices_kernel, dim3(g), dim3(TS_BLOCK), 0, st, M, (unsigned)min_count, X);
+    if (max_f > 0)   // a counting call wrote no id
+        hipLaunchKernelGGL(ts_mesh_remap_kernel, dim3(dpm_cdiv(3 * (size_t)max_f, TS_BLOCK)), dim3(TS_BLOCK), 0, st, X);
     return dpm_launch_status();
 }
 

@@ -456,13 +456,21 @@ class GeometricSlam:
         steps = self.odometry.steps
         return [i for i in range(len(self._corrected)) if i >= len(steps) or steps[i].status in (CONVERGED, MAX_ITER)]
 
-    def surface_map(self, voxel_size: float = 0.2, distance: str = "ray", carve: float = 0.0, **kw):
+    def surface_map(self, voxel_size: float = 0.2, distance: str = "ray", carve: float = 0.0, archive=None, slack: float = 10.0,
+                    **kw):
         """-> tsdf.TsdfMap(voxel_size, distance=distance, **kw) holding the loop closer's stored frames fused under the
         corrected `poses`, in one TsdfMap.integrate_frames call and without a host synchronisation.  distance="plane": the
         distance to the tangent plane at each return, with the loop closer's normals of the stored frames (dpm_point_normals
         at its normals_radius; computed here, one launch a frame, for the rows that have none yet).  carve > 0: afterwards one
         TsdfMap.carve_frames call over the same rows with that weight (in full-weight samples).  LIMIT: these are the loop
-        closer's thinned copies, at most points_per_frame a frame (and `sample`d), not the frames `step` was given."""
+        closer's thinned copies, at most points_per_frame a frame (and `sample`d), not the frames `step` was given.
+        archive: a tsdf.TsdfArchive makes the map ROLL, so that the run may be longer than max_voxels covers: the rows are cut
+        into consecutive chunks whose poses stay within `slack` metres of the chunk's first, and per chunk the map is rolled
+        to that pose (`TsdfMap.roll` with its default radii and this slack: one synchronisation) and the chunk integrated.
+        carve > 0: a second pass over the chunks, roll and carve_frames -- a carve reaches only the voxels that exist, and
+        every frame's have to exist before any is carved, as in the call without an archive.  The map comes back with the
+        archive filled, and by `roll`'s guarantee tsdf.merged_export(map, archive) is the export of the call without an
+        archive, byte for byte; tsdf.merged_mesh and merged_surface give its surface.  Without an archive nothing changes."""
         from .tsdf import TsdfMap
         out = TsdfMap(voxel_size=voxel_size, distance=distance, **kw)
         if not carve >= 0:
@@ -473,7 +481,22 @@ class GeometricSlam:
             if distance == "plane":
                 lc._normals_for(rows, force=True)
                 normals = lc.normals
-            out.integrate_frames(lc.store, lc.lengths, rows, self.poses[rows], normals=normals)
-            if carve > 0:
-                out.carve_frames(lc.store, lc.lengths, rows, self.poses[rows], weight=carve)
+            if archive is None:
+                out.integrate_frames(lc.store, lc.lengths, rows, self.poses[rows], normals=normals)
+                if carve > 0:
+                    out.carve_frames(lc.store, lc.lengths, rows, self.poses[rows], weight=carve)
+                return out
+            if not float(slack) > 0.0:
+                raise ValueError("slack > 0")
+            poses, chunks = self.poses, []
+            for r in rows:
+                if not chunks or np.linalg.norm(poses[r][:3, 3] - poses[chunks[-1][0]][:3, 3]) > float(slack):
+                    chunks.append([])
+                chunks[-1].append(r)
+            for chunk in chunks:
+                out.roll(poses[chunk[0]], archive, slack=slack)
+                out.integrate_frames(lc.store, lc.lengths, chunk, poses[chunk], normals=normals)
+            for chunk in chunks if carve > 0 else ():
+                out.roll(poses[chunk[0]], archive, slack=slack)
+                out.carve_frames(lc.store, lc.lengths, chunk, poses[chunk], weight=carve)
         return out

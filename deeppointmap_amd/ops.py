@@ -2659,6 +2659,77 @@ def tsdf_mesh(table, cap_vox, voxel, min_count=1, max_out=None):
     return _counted(call, max_out)
 
 
+def _tsdf_owners(what, tiles, tile_bits, dev):
+    """the owner list of a tile-owned extraction -> (pointer or None, n, tile_bits): tiles (n,) int64 on the device, SORTED and
+    unique (the caller's word: nothing is read here); None or empty: everything is owned"""
+    if tiles is None or tiles.numel() == 0:
+        return None, 0, int(tile_bits)
+    if _chk(tiles, torch.int64, "tiles").dim() != 1 or tiles.device != dev:
+        raise ValueError(f"{what}: tiles (n,) int64 on the table's device")
+    if not TSDF_TILE_BITS[0] <= int(tile_bits) <= TSDF_TILE_BITS[1]:
+        raise ValueError(f"{what}: tile_bits in [{TSDF_TILE_BITS[0]}, {TSDF_TILE_BITS[1]}]")
+    return _ptr(tiles), tiles.numel(), int(tile_bits)
+
+
+def tsdf_surface_tiles(table, cap_vox, voxel, min_count=1, tiles=None, tile_bits=5, max_out=None):
+    """dpm_tsdf_surface_tiles -> tsdf_surface's outputs for the records whose voxel k0 lies in one of `tiles` ((n,) int64 tile
+    keys on the device, sorted ascending and unique; None or empty: every record); max_out as in _counted"""
+    _tsdf_args(table, cap_vox)
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    dev, lib = table.device, _lib.load()
+    own, n_own, b = _tsdf_owners("tsdf_surface_tiles", tiles, tile_bits, dev)
+
+    def call(n):
+        with torch.cuda.device(dev):
+            count = torch.zeros(1, device=dev, dtype=torch.int32)
+            keys = torch.empty(n, device=dev, dtype=torch.int64)
+            axes = torch.empty(n, device=dev, dtype=torch.int32)
+            xyz = torch.empty(n, 3, device=dev, dtype=torch.float32)
+            normals = torch.empty(n, 3, device=dev, dtype=torch.float32)
+            _lib.check(lib.dpm_tsdf_surface_tiles(_ptr(table), int(cap_vox), float(voxel), int(min_count), b, own, n_own,
+                                                  _ptr(keys) if n else None, _ptr(axes) if n else None, _ptr(xyz) if n else None,
+                                                  _ptr(normals) if n else None, _ptr(count), n, _stream(table)),
+                       "dpm_tsdf_surface_tiles")
+        return count, keys, axes, xyz, normals
+    return _counted(call, max_out)
+
+
+def tsdf_mesh_indexed(table, cap_vox, voxel, min_count=1, tiles=None, tile_bits=5, max_out=None):
+    """dpm_tsdf_mesh_indexed -> ((V, F), vertex_keys (v,) int64, vertex_dirs (v,) int32, xyz (v,3) fp32 map-frame, normals (v,3)
+    fp32, faces (f,3) int32) in the table's slot order; tiles as in tsdf_surface_tiles.  max_out in _counted's manner with a
+    pair: None: counted first, then written whole; (0, 0): the counts alone, as (V, F); (max_v, max_f): outputs cut to min(V,
+    max_v) and min(F, max_f) rows, V and F as counted, nothing written beyond either maximum (a face may then name a vertex at
+    or past max_v).  One read of the two counts, a host synchronisation, in every case."""
+    _tsdf_args(table, cap_vox)
+    if int(min_count) < 1:
+        raise ValueError("min_count >= 1")
+    dev, lib = table.device, _lib.load()
+    own, n_own, b = _tsdf_owners("tsdf_mesh_indexed", tiles, tile_bits, dev)
+
+    def call(nv, nf):
+        with torch.cuda.device(dev):
+            counts = torch.empty(2, device=dev, dtype=torch.int32)
+            work = torch.empty(lib.dpm_tsdf_mesh_indexed_bytes(int(cap_vox)), device=dev, dtype=torch.uint8)
+            vkeys = torch.empty(nv, device=dev, dtype=torch.int64)
+            vdirs = torch.empty(nv, device=dev, dtype=torch.int32)
+            xyz = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+            normals = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+            faces = torch.empty(nf, 3, device=dev, dtype=torch.int32)
+            _lib.check(lib.dpm_tsdf_mesh_indexed(_ptr(table), int(cap_vox), float(voxel), int(min_count), b, own, n_own,
+                                                 _ptr(vkeys) if nv else None, _ptr(vdirs) if nv else None, _ptr(xyz) if nv else None,
+                                                 _ptr(normals) if nv else None, _ptr(faces) if nf else None, _ptr(counts), nv, nf,
+                                                 _ptr(work), _stream(table)), "dpm_tsdf_mesh_indexed")
+        return counts, vkeys, vdirs, xyz, normals, faces
+    if max_out is None or tuple(int(n) for n in max_out) == (0, 0):
+        V, F = (int(n) for n in call(0, 0)[0].tolist())
+        return (V, F) if max_out is not None else ((V, F), *call(V, F)[1:])
+    nv, nf = (int(n) for n in max_out)
+    counts, *out = call(nv, nf)
+    V, F = (int(n) for n in counts.tolist())
+    return ((V, F), *[t[:min(V, nv)] for t in out[:4]], out[4][:min(F, nf)])
+
+
 def tsdf_sample(table, cap_vox, voxel, origin, xyz, count, pose, min_count=1):
     """dpm_tsdf_sample: xyz (cap,3) fp32, count (1,) int32, pose (4,4) fp64 on the GPU -> (d (cap,) fp32, grad (cap,3) fp32 in
     the map frame's axes, flag (cap,) int32: 1 a value, 0 none, -1 past the count).  Lookups only; one launch, no host

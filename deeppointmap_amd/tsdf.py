@@ -38,7 +38,12 @@ ray (no per-point origins for sweeps that are not deskewed); the normals of the 
 of the frame alone, `normals=<radius>`); marching tetrahedra, not marching cubes; the voxels live on the device unless
 the map is rolled: `TsdfMap.roll` evicts the tiles far from the sensor to a `TsdfArchive` on the host and absorbs them when the
 sensor comes back (integer addition: `merged_export` is the unrolled map's export, byte for byte; a rolling map costs twice the
-table); meshing a map larger than the table is by region (`TsdfArchive.records` + `absorb`), with the seams the caller's.
+table).
+
+`TsdfMap.mesh_indexed` is `mesh` welded on the device (vertices, faces, per-vertex normals and vertex names in `weld`'s order,
+one synchronisation), and with `tiles=` it meshes only the cells those tiles own.  `merged_mesh` / `merged_surface` mesh a map
+larger than the table -- the map's voxels and an archive's, in batches of tiles through one scratch table, merged by vertex name
+on the host -- with the bytes of the map that never rolled: no seams.
 """
 from __future__ import annotations
 
@@ -65,6 +70,16 @@ class TsdfSurface(NamedTuple):
     axes: torch.Tensor       # (M,) int32
     origin: np.ndarray       # (3,) float64
     xyz_map: torch.Tensor    # (3,M) float32, map frame
+
+
+class TsdfMesh(NamedTuple):
+    """an indexed triangle mesh in `weld`'s order: vertices sorted by name (key, direction), every face rotated so that its
+    smallest index leads, faces sorted by row.  Map frame: world = vertices + origin."""
+    vertices: torch.Tensor      # (V,3) float32
+    faces: torch.Tensor         # (F,3) int32; (b - a) x (c - a) points to free space
+    normals: torch.Tensor       # (V,3) float32: the field's unit gradient on the vertex's edge; (0,0,0) where it has none
+    vertex_keys: torch.Tensor   # (V,) int64: the voxel p of the edge p - q the vertex lies on
+    vertex_dirs: torch.Tensor   # (V,) int32: 0..6, which q
 
 
 def field_values(sums, counts) -> np.ndarray:
@@ -251,6 +266,181 @@ def merged_export(m: "TsdfMap", archive: TsdfArchive):
     """the sorted union of the map's export and the archive's records with equal keys added: what the map would export had it
     never been rolled"""
     return merge_records(*[np.concatenate(p) for p in zip(m.export(), archive.records())])
+
+
+# -- meshing beyond the table: batches of owner tiles through one scratch table, merged on the host by vertex name -----------
+def records_by_tile(keys, sums, counts, tile_bits: int) -> dict:
+    """records -> {tile key: (keys, sums, counts) sorted by key, equal keys added}"""
+    k, s, c = merge_records(keys, sums, counts)
+    tiles = tile_of(k, tile_bits)
+    order = np.argsort(tiles, kind="stable")
+    tiles, k, s, c = tiles[order], k[order], s[order], c[order]
+    edges = np.flatnonzero(np.concatenate([[True], tiles[1:] != tiles[:-1], [True]])) if k.size else []
+    return {int(tiles[lo]): (k[lo:hi], s[lo:hi], c[lo:hi]) for lo, hi in zip(edges[:-1], edges[1:])}
+
+
+def _axes(keys):
+    k = np.asarray(keys, np.int64)
+    return [(k >> (21 * a)) & _AXIS for a in range(3)]
+
+
+def _pack(x, y, z):
+    return np.asarray(x, np.int64) | (np.asarray(y, np.int64) << 21) | (np.asarray(z, np.int64) << 42)
+
+
+def _halo(keys, owners, tile_bits: int) -> np.ndarray:
+    """which voxels x does a cell or crossing anchored in one of the `owners` (sorted tile keys) read: tile_of(x - d) is an
+    owner for some d in {-1, 0, 1, 2}^3 with x - d inside the 21 bits.  Per axis x - 2 .. x + 1 meets at most two tiles (a
+    tile has at least 8 voxels), the one of the lowest and the one of the highest coordinate that exists: 8 candidates."""
+    b, x = int(tile_bits), _axes(keys)
+    ends = [(np.maximum(x[a] - 2, 0) >> b, np.minimum(x[a] + 1, _AXIS) >> b) for a in range(3)]
+    out = np.zeros(len(x[0]), bool)
+    for i in range(8):
+        out |= np.isin(_pack(ends[0][i & 1], ends[1][(i >> 1) & 1], ends[2][i >> 2]), owners)
+    return out
+
+
+def _neighbours(owners, tile_bits: int) -> np.ndarray:
+    """the tiles within one tile of an owner on every axis that are no owners themselves, sorted"""
+    t, top = _axes(owners), _AXIS >> int(tile_bits)
+    out = []
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dz in (-1, 0, 1):
+                n = [t[0] + dx, t[1] + dy, t[2] + dz]
+                ok = np.all([(c >= 0) & (c <= top) for c in n], axis=0)
+                out.append(_pack(n[0][ok], n[1][ok], n[2][ok]))
+    return np.setdiff1d(np.concatenate(out), owners)
+
+
+def _needed_parts(by_tile: dict, owner_tiles, tile_bits: int):
+    owners = np.unique(np.asarray(owner_tiles, np.int64).reshape(-1))
+    parts = [by_tile[int(t)] for t in owners if int(t) in by_tile]
+    for t in _neighbours(owners, tile_bits):
+        held = by_tile.get(int(t))
+        if held is not None:
+            keep = _halo(held[0], owners, tile_bits)
+            if keep.any():
+                parts.append(tuple(a[keep] for a in held))
+    return parts
+
+
+def needed_records(by_tile: dict, owner_tiles, tile_bits: int):
+    """what `mesh_indexed(tiles=owner_tiles)` and `surface(tiles=owner_tiles)` read, out of {tile key: records}: the owner tiles'
+    own voxels and the HALO -- every voxel x of another tile with tile_of(x - d) among the owners for some d in {-1, 0, 1,
+    2}^3: the 8 corners of an owned cell and the neighbours at +-1 of both ends of its edges, which the normals read.
+    Coordinates outside the 21 bits do not exist.  -> (keys, sums, counts) sorted by key.  Host, numpy."""
+    parts = _needed_parts(by_tile, owner_tiles, tile_bits)
+    return merge_records(*[np.concatenate(p) for p in zip(*parts)]) if parts else tuple(a.copy() for a in NO_RECORDS)
+
+
+def plan_batches(by_tile: dict, tile_bits: int, scratch_voxels: int):
+    """the tiles of {tile key: records} in sorted order, grouped greedily into batches whose `needed_records` -- owners and
+    halo -- number at most scratch_voxels // 2 -> [sorted tile keys (int64), ...]; every tile is in exactly one batch.  Half
+    the table is a CONDITION for the open-addressing table to stay fast and free of overflow, not a measurement of it.  A
+    single tile that does not fit raises ValueError."""
+    room, out = int(scratch_voxels) // 2, []
+    batch, own, halo = [], 0, {}          # the open batch: its tiles, their voxels, {neighbour tile: voxels of it the batch reads}
+
+    def grown(t):
+        """(records needed, halo) of the open batch with tile t added: only t's neighbours read anything new"""
+        owners = np.array(sorted(batch + [t]), np.int64)
+        h = {n: c for n, c in halo.items() if n != t}
+        for n in _neighbours(np.array([t], np.int64), tile_bits).tolist():
+            if n in by_tile and n not in batch:
+                h[n] = int(_halo(by_tile[n][0], owners, tile_bits).sum())
+        return own + len(by_tile[t][0]) + sum(h.values()), h
+
+    for t in sorted(by_tile):
+        size, h = grown(t)
+        if batch and size > room:
+            out.append(np.array(batch, np.int64))
+            batch, own, halo = [], 0, {}
+            size, h = grown(t)
+        if size > room:
+            raise ValueError(f"tile {t} needs {size} voxels with its halo, more than half of scratch_voxels={scratch_voxels}; "
+                             f"raise scratch_voxels or lower tile_bits")
+        batch, own, halo = batch + [t], own + len(by_tile[t][0]), h
+    if batch:
+        out.append(np.array(batch, np.int64))
+    return out
+
+
+def weld_indexed(batches):
+    """indexed meshes of disjoint sets of cells -- [(vertices (v,3), faces (f,3), normals (v,3), vertex_keys (v,), vertex_dirs
+    (v,)), ...], numpy -- merged by vertex name -> the same five in `weld`'s order.  A name has one position and one normal:
+    a vertex on a seam comes with equal bytes from both sides, and the first is kept."""
+    batches = [b for b in batches if len(b[3])]
+    if not batches:
+        return (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.float32), np.zeros(0, np.int64),
+                np.zeros(0, np.int32))
+    p, n = (np.concatenate([np.asarray(b[j], np.float32).reshape(-1, 3) for b in batches]) for j in (0, 2))
+    k = np.concatenate([np.asarray(b[3], np.int64).reshape(-1) for b in batches])
+    d = np.concatenate([np.asarray(b[4], np.int32).reshape(-1) for b in batches])
+    base = np.cumsum([0] + [len(b[3]) for b in batches[:-1]])
+    faces = np.concatenate([np.asarray(b[1], np.int64).reshape(-1, 3) + o for b, o in zip(batches, base)])
+    order = np.lexsort((d, k))
+    ks, ds = k[order], d[order]
+    first = np.concatenate([[True], (ks[1:] != ks[:-1]) | (ds[1:] != ds[:-1])])
+    index = np.empty(k.size, np.int64)
+    index[order] = np.cumsum(first) - 1
+    faces = index[faces]
+    lead = faces.argmin(axis=1)
+    faces = np.stack([faces[np.arange(len(faces)), (lead + j) % 3] for j in range(3)], axis=1)
+    faces = faces[np.lexsort((faces[:, 2], faces[:, 1], faces[:, 0]))]
+    keep = order[first]
+    return (np.ascontiguousarray(p[keep]), np.ascontiguousarray(faces.astype(np.int32)), np.ascontiguousarray(n[keep]), k[keep], d[keep])
+
+
+def _batched(m: "TsdfMap", archive, scratch_voxels, batches, extract):
+    """extract(scratch map, owner tiles, tile_bits) per batch (`batches`: lists of owner tiles; None: `plan_batches`) over the
+    union of the map's export and the archive's records, each batch absorbed into ONE scratch TsdfMap on m's grid, cleared in
+    between -> the results"""
+    b = 5 if archive is None else archive.tile_bits
+    parts = [m.export()] + ([] if archive is None else [archive.records()])
+    by_tile = records_by_tile(*[np.concatenate(p) for p in zip(*parts)], b)
+    n = m.max_voxels if scratch_voxels is None else int(scratch_voxels)
+    out, scratch = [], None
+    for owners in (plan_batches(by_tile, b, n) if batches is None else batches):
+        if scratch is None:
+            scratch = TsdfMap(m.voxel_size, m.truncation, m.step, n, m.min_range, m.max_range, origin=m.origin,
+                              device=m.device if m.table is None else m.table.device, distance=m.distance, cos_min=m.cos_min)
+        else:
+            ops.tsdf_clear(scratch.table, scratch.max_voxels)
+        scratch.absorb(*needed_records(by_tile, owners, b)).check()
+        out.append(extract(scratch, owners, b))
+    return out
+
+
+def merged_mesh(m: "TsdfMap", archive: Optional[TsdfArchive] = None, min_count: float = 1, scratch_voxels: Optional[int] = None,
+                batches=None):
+    """the mesh of a map larger than the table -> (vertices (V,3) float32, faces (F,3) int32, normals (V,3) float32) numpy, in
+    `weld`'s order.  The records of `m.export()` and `archive.records()` (None: the map alone; neither is changed) are cut
+    into batches of tiles (`plan_batches`; scratch_voxels: a power of two, default m.max_voxels); each batch's
+    `needed_records` go into one scratch TsdfMap, `mesh_indexed(tiles=owners)` meshes the cells it owns, and the batches are
+    merged by vertex name (`weld_indexed`).  THE GUARANTEE: vertices and faces are the bytes of `mesh()`, normals those of
+    `mesh_indexed().normals`, of the map that never rolled -- a voxel is (key, sum, count) with additive writes, and an owned
+    cell reads nothing outside its batch's records.  Two host synchronisations a batch (check, V and F) and its copy.
+    batches: the owner tiles of each batch, every tile once, in place of the planner's (a batch that does not fit raises)."""
+    got = _batched(m, archive, scratch_voxels, batches, lambda s, owners, b: [t.cpu().numpy() for t in s.mesh_indexed(min_count, owners, b)])
+    return weld_indexed(got)[:3]
+
+
+def merged_surface(m: "TsdfMap", archive: Optional[TsdfArchive] = None, min_count: float = 1,
+                   scratch_voxels: Optional[int] = None, batches=None) -> TsdfSurface:
+    """`merged_mesh` for the zero crossings: `surface(tiles=owners)` per batch -> TsdfSurface with HOST tensors, sorted by (key,
+    axis): the bytes of `surface()` of the map that never rolled"""
+    got = _batched(m, archive, scratch_voxels, batches, lambda s, owners, b: s.surface(min_count, owners, b))
+    origin = np.zeros(3) if m.origin is None else m.origin.copy()
+    keys = torch.cat([g.keys.cpu() for g in got]) if got else torch.zeros(0, dtype=torch.int64)
+    axes = torch.cat([g.axes.cpu() for g in got]) if got else torch.zeros(0, dtype=torch.int32)
+    local = torch.cat([g.xyz_map.cpu() for g in got], dim=1) if got else torch.zeros(3, 0)
+    normals = torch.cat([g.normals.cpu() for g in got], dim=1) if got else torch.zeros(3, 0)
+    order = torch.sort(axes, stable=True).indices
+    order = order[torch.sort(keys[order], stable=True).indices]
+    local = local[:, order].contiguous()
+    world = (local.double() + torch.from_numpy(origin)[:, None]).float()
+    return TsdfSurface(world, normals[:, order].contiguous(), keys[order], axes[order], origin, local)
 
 
 MISS, HIT, BACK = ops.TSDF_MISS, ops.TSDF_HIT, ops.TSDF_BACK
@@ -575,20 +765,63 @@ class TsdfMap(_HashedMap):
         ok = counts >= np.uint32(min_count)
         return keys[ok], field_values(sums[ok], counts[ok])
 
-    def surface(self, min_count: float = 1) -> TsdfSurface:
-        """the zero crossings of the field along the axes between qualified voxels, with normals from the field's gradient"""
+    def surface(self, min_count: float = 1, tiles=None, tile_bits: int = 5) -> TsdfSurface:
+        """the zero crossings of the field along the axes between qualified voxels, with normals from the field's gradient.
+        tiles (as `mesh_indexed` takes them): only the crossings whose voxel k0 lies in one of these tiles, with the bytes
+        they have among all of them."""
         min_count = self._min_count(min_count)
         if self.table is None:
             dev = self.device if self.device is not None else "cpu"
             z = torch.zeros(3, 0, dtype=torch.float32, device=dev)
             return TsdfSurface(z, z.clone(), torch.zeros(0, dtype=torch.int64, device=dev),
                                torch.zeros(0, dtype=torch.int32, device=dev), np.zeros(3) if self.origin is None else self.origin, z.clone())
-        keys, axes, xyz, normals = self._extract(ops.tsdf_surface, self.voxel_size, min_count)
+        if tiles is None:
+            keys, axes, xyz, normals = self._extract(ops.tsdf_surface, self.voxel_size, min_count)
+        else:
+            keys, axes, xyz, normals = self._extract(ops.tsdf_surface_tiles, self.voxel_size, min_count,
+                                                     self._owners("surface", tiles, tile_bits), tile_bits)
         order = torch.sort(axes, stable=True).indices
         order = order[torch.sort(keys[order], stable=True).indices]
         local = xyz[order].t().contiguous()
         world = (local.double() + torch.from_numpy(self.origin).to(local.device)[:, None]).float()
         return TsdfSurface(world, normals[order].t().contiguous(), keys[order], axes[order], self.origin.copy(), local)
+
+    def _owners(self, what, tiles, tile_bits):
+        """tile keys (any order, repeats allowed) -> (n,) int64 on the table's device, sorted and unique, as the kernels need"""
+        if not ops.TSDF_TILE_BITS[0] <= int(tile_bits) <= ops.TSDF_TILE_BITS[1]:
+            raise ValueError(f"{what}: tile_bits in [{ops.TSDF_TILE_BITS[0]}, {ops.TSDF_TILE_BITS[1]}]")
+        t = np.unique(np.asarray(tiles.cpu() if isinstance(tiles, torch.Tensor) else tiles, np.int64).reshape(-1))
+        if t.size == 0:
+            raise ValueError(f"{what}: tiles names no tile (None: every tile)")
+        return torch.from_numpy(t).to(self.table.device)
+
+    def mesh_indexed(self, min_count: float = 1, tiles=None, tile_bits: int = 5) -> TsdfMesh:
+        """`mesh` welded on the device -> TsdfMesh, on the device, in `weld`'s order: vertices sorted by name (key, direction),
+        every face rotated so that its smallest index leads, faces sorted by row; with tiles=None `vertices` and `faces` have
+        the bytes of `mesh()`.  `normals`: per vertex, `surface`'s rule on the edge the vertex lies on (its bytes on the axis
+        edges).  tiles: tile keys (`tile_of`, 2^tile_bits voxels per axis; host array or tensor, any order) -- only the cells
+        whose base voxel lies in one of them are meshed; what such a cell reads is not cut, so its vertices may be named by
+        voxels of a neighbouring tile.  One host synchronisation, the read of V and F; the sorts run on the device."""
+        min_count = self._min_count(min_count)
+        if self.table is None:
+            dev = self.device if self.device is not None else "cpu"
+            z = torch.zeros(0, 3, dtype=torch.float32, device=dev)
+            return TsdfMesh(z, torch.zeros(0, 3, dtype=torch.int32, device=dev), z.clone(), torch.zeros(0, dtype=torch.int64, device=dev),
+                            torch.zeros(0, dtype=torch.int32, device=dev))
+        own = None if tiles is None else self._owners("mesh_indexed", tiles, tile_bits)
+        augment._SYNCS[0] += 1
+        _, keys, dirs, xyz, normals, faces = ops.tsdf_mesh_indexed(self.table, self.max_voxels, self.voxel_size, min_count, own, tile_bits)
+        order = torch.sort(dirs, stable=True).indices
+        order = order[torch.sort(keys[order], stable=True).indices]
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.numel(), device=order.device)
+        faces = rank[faces.long()]
+        lead = faces.argmin(dim=1, keepdim=True)                      # a triangle's three names differ: no ties
+        faces = torch.gather(faces, 1, (lead + torch.arange(3, device=faces.device)) % 3)
+        rows = torch.arange(faces.shape[0], device=faces.device)
+        for col in (2, 1, 0):
+            rows = rows[torch.sort(faces[rows, col], stable=True).indices]
+        return TsdfMesh(xyz[order], faces[rows].to(torch.int32), normals[order], keys[order], dirs[order])
 
     def mesh(self, min_count: float = 1):
         """(vertices (V,3) float32 in the map frame -- world = vertices + origin --, faces (F,3) int32) from marching

@@ -1237,6 +1237,35 @@ int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, 
  * counts as positive; the triangles of zero area it makes are kept. */
 int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
                   int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream);
+/* TILE-OWNED EXTRACTION.  tiles: n_tiles keys of tiles (ROLLING THE MAP above: pack_key(x >> b, y >> b, z >> b) of the biased
+ * indices, b = tile_bits in [3, 10]) on the device, SORTED ascending and unique.  A record of dpm_tsdf_surface, or a cell of
+ * dpm_tsdf_mesh, is OWNED when the tile of its voxel k0 (the crossing's lower voxel, the cell's corner 0) is in the list, found
+ * by binary search; n_tiles = 0 (tiles may then be NULL, tile_bits is not looked at) owns everything.  What an owned record or
+ * cell READS is not cut: the 8 corners and, for the normals, the neighbours at +-1 of both ends of an edge, which lie in
+ * k0 + {-1, 0, 1, 2}^3, whatever tile holds them.
+ *
+ * dpm_tsdf_surface_tiles: dpm_tsdf_surface's records, bytes and count / max_out rule, of the owned k0 only.
+ *
+ * dpm_tsdf_mesh_indexed: the owned cells of dpm_tsdf_mesh -- the same cells, triangles, positions and winding -- as an INDEXED
+ * mesh.  A vertex (key of p, direction) exists once: vertex_keys (max_v,) uint64, vertex_dirs (max_v,) int32, xyz (max_v,3) =
+ * dpm_tsdf_mesh's position of that name, normals (max_v,3) = for the edge between voxels p and q the rule of dpm_tsdf_surface
+ * with k0 = p, k1 = q: g = grad(p) + grad(q), divided per axis by sqrt((gx*gx + gy*gy) + gz*gz), (0, 0, 0) when the root is 0;
+ * on the axis edges (direction 0, 1, 2) these are dpm_tsdf_surface's bytes for (key, axis).  faces (max_f,3) int32: a triangle's
+ * three vertex indices in dpm_tsdf_mesh's winding.  counts (2,) int32 = V, F, ZEROED BY THE CALL; either may exceed its maximum:
+ * then vertices at and past max_v and faces at and past max_f are not written (a written face may name an index >= max_v);
+ * max_v = max_f = 0 only counts.  The vertices of a slot of the table are consecutive, directions ascending, and slots follow
+ * each other in table order, so the order of vertices and faces depends on the order the voxels arrived in: sort by name for a
+ * canonical form.  Six launches (clear; cells: ids (slot << 3 | direction) and a 7-bit mask per slot by 32-bit atomicOr; block
+ * sums; their scan; vertices; remap), integer atomics only, no host synchronisation, capturable.
+ * workspace: dpm_tsdf_mesh_indexed_bytes(cap_vox) bytes (0 for a cap_vox no table can have), any alignment. */
+int dpm_tsdf_surface_tiles(const void *map, int cap_vox, double voxel, int min_count, int tile_bits,
+                           const unsigned long long *tiles, int n_tiles, unsigned long long *keys, int32_t *axes, float *xyz,
+                           float *normals, int32_t *count, int max_out, dpm_stream_t stream);
+size_t dpm_tsdf_mesh_indexed_bytes(int cap_vox);
+int dpm_tsdf_mesh_indexed(const void *map, int cap_vox, double voxel, int min_count, int tile_bits,
+                          const unsigned long long *tiles, int n_tiles, unsigned long long *vertex_keys, int32_t *vertex_dirs,
+                          float *xyz, float *normals, int32_t *faces, int32_t *counts, int max_v, int max_f, void *workspace,
+                          dpm_stream_t stream);
 /* THE FIELD AT A POINT, and registration against it.  Lookups only: the table is never written.  A row (x, y, z) of a frame
  * under `pose` is q = fma(R2, z, fma(R1, y, R0 * x)) + t in the map frame, as above.  In fp32, every operation rounded once, no
  * fused multiply-add, divisions correctly rounded, with v = (float)voxel; per axis a:
