@@ -440,13 +440,24 @@ __device__ __forceinline__ bool owned(const Owners &O, const unsigned long long 
     return lo < O.n && list[lo] == t;
 }
 
-__global__ __launch_bounds__(TS_BLOCK) void ts_surface_kernel(Tsdf M, unsigned min_count, unsigned long long *keys, int32_t *axes,
-                                                              float *xyz, float *normals, int32_t *count, int max_out) {
-    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
-    if (slot >= M.cap_vox) return;
-    const unsigned long long k0 = M.keys()[slot];
-    float D0;
-    if (k0 == EMPTY || !slot_value(M, slot, min_count, D0)) return;
+// An edge runs from a voxel p to the voxel q = p + d, d = dx | dy << 1 | dz << 2 not 0.  Its direction code, and d of a code:
+// 1, 2, 4 (the axes) <-> 0, 1, 2; 3, 5, 6 (the face diagonals) <-> 3, 4, 5; 7 (the body diagonal) <-> 6.
+__host__ __device__ constexpr int edge_dir(int d) { return (0x65423100 >> (4 * d)) & 7; }
+__host__ __device__ constexpr int dir_edge(int dir) { return (0x7653421 >> (4 * dir)) & 7; }
+constexpr bool dirs_invert(int d = 7) { return d == 0 || (dir_edge(edge_dir(d)) == d && edge_dir(d) < 7 && dirs_invert(d - 1)); }
+static_assert(dirs_invert() && edge_dir(4) == 2 && edge_dir(3) == 3 && edge_dir(7) == 6, "edge_dir and dir_edge invert each other");
+
+// the point of the edge p - q where the field changes sign: f = Dp / (Dp - Dq), p's centre c with f * v added on every axis of d
+__device__ __forceinline__ void edge_point(const float c[3], int d, float Dp, float Dq, float v, float *xyz) {
+    const float f = __fdiv_rn(Dp, Dp - Dq);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) xyz[b] = (d >> b) & 1 ? c[b] + f * v : c[b];
+}
+
+// the records of the qualified voxel k0 with value D0: one per axis whose neighbour k1 is qualified with the other sign
+__device__ __forceinline__ void put_crossings(const Tsdf &M, unsigned min_count, unsigned long long k0, float D0,
+                                              unsigned long long *keys, int32_t *axes, float *xyz, float *normals, int32_t *count,
+                                              int max_out) {
     const int x0[3] = {key_axis(k0, 0), key_axis(k0, 1), key_axis(k0, 2)};
     float c[3];
     voxel_centre(k0, M.v, c);
@@ -456,24 +467,26 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_surface_kernel(Tsdf M, unsigned m
         if (!voxel_value(M, x1[0], x1[1], x1[2], min_count, D1) || (D0 < 0.f) == (D1 < 0.f)) continue;
         const int pos = atomicAdd(count, 1);
         if (pos < 0 || pos >= max_out) continue;
-        const float f = __fdiv_rn(D0, D0 - D1);
-        float g0[3] = {0.f, 0.f, 0.f}, g1[3] = {0.f, 0.f, 0.f};
-        add_grad(M, x0, D0, min_count, g0);
-        add_grad(M, x1, D1, min_count, g1);
-        const float gx = g0[0] + g1[0], gy = g0[1] + g1[1], gz = g0[2] + g1[2];
-        const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
-        const bool unit = len > 0.f;
+        float n[3];
+        edge_normal(M, x0, D0, x1, D1, min_count, n);   // every read before the first write
         keys[pos] = k0, axes[pos] = a;
+        edge_point(c, 1 << a, D0, D1, M.v, &xyz[3 * (size_t)pos]);
 #pragma unroll
-        for (int b = 0; b < 3; ++b) xyz[3 * (size_t)pos + b] = b == a ? c[b] + f * M.v : c[b];
-        normals[3 * (size_t)pos] = unit ? __fdiv_rn(gx, len) : 0.f;
-        normals[3 * (size_t)pos + 1] = unit ? __fdiv_rn(gy, len) : 0.f;
-        normals[3 * (size_t)pos + 2] = unit ? __fdiv_rn(gz, len) : 0.f;
+        for (int b = 0; b < 3; ++b) normals[3 * (size_t)pos + b] = n[b];
     }
 }
 
-// ts_surface_kernel's records, in its order, of the owned voxels.  The older kernel stays as it was written, so that its instructions
-// do (scripts/isa_diff.py against the parent commit); what the two share is edge_normal's rule.
+__global__ __launch_bounds__(TS_BLOCK) void ts_surface_kernel(Tsdf M, unsigned min_count, unsigned long long *keys, int32_t *axes,
+                                                              float *xyz, float *normals, int32_t *count, int max_out) {
+    const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
+    if (slot >= M.cap_vox) return;
+    const unsigned long long k0 = M.keys()[slot];
+    float D0;
+    if (k0 == EMPTY || !slot_value(M, slot, min_count, D0)) return;
+    put_crossings(M, min_count, k0, D0, keys, axes, xyz, normals, count, max_out);
+}
+
+// ts_surface_kernel's records, in its order, of the owned voxels
 __global__ __launch_bounds__(TS_BLOCK) void ts_surface_tiles_kernel(Tsdf M, unsigned min_count, Owners W, unsigned long long *keys,
                                                                     int32_t *axes, float *xyz, float *normals, int32_t *count,
                                                                     int max_out) {
@@ -484,24 +497,7 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_surface_tiles_kernel(Tsdf M, unsi
     const unsigned long long k0 = M.keys()[slot];
     float D0;
     if (k0 == EMPTY || !slot_value(M, slot, min_count, D0) || !owned(W, list, k0)) return;
-    const int x0[3] = {key_axis(k0, 0), key_axis(k0, 1), key_axis(k0, 2)};
-    float c[3];
-    voxel_centre(k0, M.v, c);
-    for (int a = 0; a < 3; ++a) {
-        const int x1[3] = {x0[0] + (a == 0), x0[1] + (a == 1), x0[2] + (a == 2)};
-        float D1;
-        if (!voxel_value(M, x1[0], x1[1], x1[2], min_count, D1) || (D0 < 0.f) == (D1 < 0.f)) continue;
-        const int pos = atomicAdd(count, 1);
-        if (pos < 0 || pos >= max_out) continue;
-        const float f = __fdiv_rn(D0, D0 - D1);
-        float n[3];
-        edge_normal(M, x0, D0, x1, D1, min_count, n);
-        keys[pos] = k0, axes[pos] = a;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) xyz[3 * (size_t)pos + b] = b == a ? c[b] + f * M.v : c[b];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) normals[3 * (size_t)pos + b] = n[b];
-    }
+    put_crossings(M, min_count, k0, D0, keys, axes, xyz, normals, count, max_out);
 }
 
 // ------------------------------------------------------------------------------------------------------- marching tetrahedra
@@ -522,14 +518,12 @@ struct Cell {
 __device__ __forceinline__ void put_vertex(const MeshOut &O, const Cell &C, const int m[4], int i0, int i1, int pos, int j) {
     const int p = m[min(i0, i1)], q = m[max(i0, i1)], d = q ^ p;
     const unsigned long long key = pack_key(C.x[0] + (p & 1), C.x[1] + ((p >> 1) & 1), C.x[2] + (p >> 2));
-    const float f = __fdiv_rn(C.D[p], C.D[p] - C.D[q]);
     float c[3];
     voxel_centre(key, C.v, c);
     const size_t at = 3 * (size_t)pos + j;
     O.vkeys[at] = key;
-    O.vdirs[at] = d == 1 ? 0 : d == 2 ? 1 : d == 4 ? 2 : d == 3 ? 3 : d == 5 ? 4 : d == 6 ? 5 : 6;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) O.xyz[3 * at + b] = (d >> b) & 1 ? c[b] + f * C.v : c[b];
+    O.vdirs[at] = edge_dir(d);
+    edge_point(c, d, C.D[p], C.D[q], C.v, &O.xyz[3 * at]);
 }
 
 // the triangle on the edges (a0,a1), (b0,b1), (c0,c1); flip: the last two change places
@@ -543,8 +537,7 @@ __device__ __forceinline__ void put_triangle(const MeshOut &O, const Cell &C, co
 }
 
 // The triangles of a cell whose corner m has bit m of `neg` set when D[m] < 0, each handed to emit(m, a0, a1, b0, b1, c0, c1, flip):
-// put_triangle's arguments, m the four nested corners of the tetrahedron it lies in.  ts_mesh_kernel's walk, for the indexed mesh
-// below; ts_mesh_kernel keeps its own copy so that its instructions stay (scripts/isa_diff.py against the parent commit).
+// put_triangle's arguments, m the four nested corners of the tetrahedron it lies in.
 template <typename Emit>
 __device__ __forceinline__ void march_cell(int neg, Emit emit) {
     for (int t = 0; t < 6; ++t) {
@@ -573,44 +566,35 @@ __device__ __forceinline__ void march_cell(int neg, Emit emit) {
     }
 }
 
+// The cell anchored at the qualified voxel k0 of `slot`, D[0] its value: D and the slot of every corner, bit m of neg set when
+// D[m] < 0.  false at the first corner that lies outside the 21 bits, has no slot or is not qualified.
+__device__ __forceinline__ bool load_cell(const Tsdf &M, unsigned min_count, int slot, unsigned long long k0, float D[8], int at[8],
+                                          int &neg) {
+    at[0] = slot;
+    neg = D[0] < 0.f;
+    for (int m = 1; m < 8; ++m) {
+        const int x = key_axis(k0, 0) + (m & 1), y = key_axis(k0, 1) + ((m >> 1) & 1), z = key_axis(k0, 2) + (m >> 2);
+        if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) return false;
+        at[m] = find_slot(M.keys(), M.cap_vox, pack_key(x, y, z));
+        if (!slot_value(M, at[m], min_count, D[m])) return false;
+        neg |= (D[m] < 0.f) << m;
+    }
+    return true;
+}
+
 __global__ __launch_bounds__(TS_BLOCK) void ts_mesh_kernel(Tsdf M, unsigned min_count, MeshOut O) {
     const int slot = blockIdx.x * TS_BLOCK + threadIdx.x;
     if (slot >= M.cap_vox) return;
     const unsigned long long k0 = M.keys()[slot];
     Cell C;
     C.v = M.v;
+    int at[8], neg;
     if (k0 == EMPTY || !slot_value(M, slot, min_count, C.D[0])) return;
+    if (!load_cell(M, min_count, slot, k0, C.D, at, neg) || neg == 0 || neg == 255) return;
     for (int a = 0; a < 3; ++a) C.x[a] = key_axis(k0, a);
-    int neg = C.D[0] < 0.f;
-    for (int m = 1; m < 8; ++m) {
-        if (!voxel_value(M, C.x[0] + (m & 1), C.x[1] + ((m >> 1) & 1), C.x[2] + (m >> 2), min_count, C.D[m])) return;
-        neg |= (C.D[m] < 0.f) << m;
-    }
-    if (neg == 0 || neg == 255) return;
-    for (int t = 0; t < 6; ++t) {
-        // the t-th permutation (a, b, c) of the axes in lexicographic order; odd ones give a left-handed tetrahedron
-        const int a = t >> 1, b = (0x489 >> (2 * t)) & 3;   // b = 1, 2, 0, 2, 0, 1
-        const bool odd = (0x26 >> t) & 1;                    // t = 1, 2, 5
-        const int m[4] = {0, 1 << a, (1 << a) | (1 << b), 7};
-        int nm = 0;
-        for (int i = 0; i < 4; ++i) nm |= ((neg >> m[i]) & 1) << i;
-        const int cnt = __popc(nm);
-        if (cnt == 0 || cnt == 4) continue;
-        if (cnt != 2) {
-            // corner A alone on its side; (A, B, C, D) with B < C < D is an even permutation when A is even
-            const int A = __ffs(cnt == 1 ? nm : (~nm & 15)) - 1;
-            const int B = A == 0 ? 1 : 0, Cc = A <= 1 ? 2 : 1, Dd = A == 3 ? 2 : 3;
-            put_triangle(O, C, m, A, B, A, Cc, A, Dd, ((A & 1) != 0) ^ odd ^ (cnt == 3));
-        } else {
-            // A < B negative, Cc < Dd positive; the parity of (A, B, Cc, Dd) is that of its inversions
-            const int A = __ffs(nm) - 1, B = 31 - __clz(nm), pm = ~nm & 15, Cc = __ffs(pm) - 1, Dd = 31 - __clz(pm);
-            const int inv = (A > Cc) + (A > Dd) + (B > Cc) + (B > Dd);
-            const bool swap = ((inv & 1) != 0) ^ odd;
-            const int P = swap ? Dd : Cc, Q = swap ? Cc : Dd;
-            put_triangle(O, C, m, A, P, A, Q, B, Q, false);
-            put_triangle(O, C, m, A, P, B, Q, B, P, false);
-        }
-    }
+    march_cell(neg, [&](const int m[4], int a0, int a1, int b0, int b1, int c0, int c1, bool flip) {
+        put_triangle(O, C, m, a0, a1, b0, b1, c0, c1, flip);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------- the indexed mesh
@@ -654,25 +638,15 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_mesh_cells_kernel(Tsdf M, unsigne
     if (slot >= M.cap_vox) return;
     const unsigned long long k0 = M.keys()[slot];
     float D[8];
-    int at[8];
+    int at[8], neg;
     if (k0 == EMPTY || !slot_value(M, slot, min_count, D[0]) || !owned(W, list, k0)) return;
-    at[0] = slot;
-    int neg = D[0] < 0.f;
-    for (int m = 1; m < 8; ++m) {
-        const int x = key_axis(k0, 0) + (m & 1), y = key_axis(k0, 1) + ((m >> 1) & 1), z = key_axis(k0, 2) + (m >> 2);
-        if ((unsigned)x > 0x1FFFFFu || (unsigned)y > 0x1FFFFFu || (unsigned)z > 0x1FFFFFu) return;
-        at[m] = find_slot(M.keys(), M.cap_vox, pack_key(x, y, z));
-        if (!slot_value(M, at[m], min_count, D[m])) return;
-        neg |= (D[m] < 0.f) << m;
-    }
-    if (neg == 0 || neg == 255) return;
+    if (!load_cell(M, min_count, slot, k0, D, at, neg) || neg == 0 || neg == 255) return;
     march_cell(neg, [&](const int m[4], int a0, int a1, int b0, int b1, int c0, int c1, bool flip) {
         const int e[3][2] = {{a0, a1}, {flip ? c0 : b0, flip ? c1 : b1}, {flip ? b0 : c0, flip ? b1 : c1}};
         const int pos = atomicAdd(&X.counts[1], 1);
         const bool room = pos >= 0 && pos < X.max_f;
         for (int j = 0; j < 3; ++j) {
-            const int p = m[min(e[j][0], e[j][1])], d = m[max(e[j][0], e[j][1])] ^ p;
-            const int dir = d == 1 ? 0 : d == 2 ? 1 : d == 4 ? 2 : d == 3 ? 3 : d == 5 ? 4 : d == 6 ? 5 : 6, s = at[p];
+            const int p = m[min(e[j][0], e[j][1])], dir = edge_dir(m[max(e[j][0], e[j][1])] ^ p), s = at[p];
             atomicOr(&X.mask[s >> 2], (1u << dir) << (8 * (s & 3)));   // also without room: V is counted in full
             if (room) X.faces[3 * (size_t)pos + j] = (s << 3) | dir;
         }
@@ -709,15 +683,13 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_mesh_vertices_kernel(Tsdf M, unsi
         if (!((mask >> dir) & 1u)) continue;
         const int at = idx++;
         if (at >= X.max_v) continue;
-        const int d = (0x7653421 >> (4 * dir)) & 7;      // q ^ p of the direction: 1, 2, 4, 3, 5, 6, 7
+        const int d = dir_edge(dir);
         const int x1[3] = {x0[0] + (d & 1), x0[1] + ((d >> 1) & 1), x0[2] + (d >> 2)};
         float Dq = 0.f, n[3];
         voxel_value(M, x1[0], x1[1], x1[2], min_count, Dq);
-        const float f = __fdiv_rn(Dp, Dp - Dq);
         edge_normal(M, x0, Dp, x1, Dq, min_count, n);
         X.vkeys[at] = key, X.vdirs[at] = dir;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) X.xyz[3 * (size_t)at + b] = (d >> b) & 1 ? c[b] + f * M.v : c[b];
+        edge_point(c, d, Dp, Dq, M.v, &X.xyz[3 * (size_t)at]);
 #pragma unroll
         for (int b = 0; b < 3; ++b) X.normals[3 * (size_t)at + b] = n[b];
     }
@@ -1099,23 +1071,9 @@ extern "C" int dpm_tsdf_absorb(void *map, int cap_vox, const unsigned long long 
     return dpm_launch_status();
 }
 
-extern "C" int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *keys,
-                                int32_t *axes, float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
-    DPM_CHECK_ARG(max_out == 0 || (keys && axes && xyz && normals));
-    hipLaunchKernelGGL(ts_surface_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, keys, axes, xyz, normals, count, max_out);
-    return dpm_launch_status();
-}
-
-extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
-                             int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
-    DPM_CHECK_ARG(max_out == 0 || (vertex_keys && vertex_dirs && xyz));
-    const MeshOut O{vertex_keys, vertex_dirs, xyz, count, max_out};
-    hipLaunchKernelGGL(ts_mesh_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, O);
-    return dpm_launch_status();
+// what surface and mesh are given: a table, a voxel size, a qualifying count, a counter and room for max_out >= 0 records
+static bool extract_ok(const void *map, int cap_vox, double voxel, int min_count, const int32_t *count, int max_out) {
+    return table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0;
 }
 
 // the owner list of an entry point: nothing (everything is owned), or n sorted tile keys on the device
@@ -1123,15 +1081,41 @@ static bool owners_ok(int tile_bits, const unsigned long long *tiles, int n_tile
     return n_tiles >= 0 && (n_tiles == 0 || (tiles && tile_bits >= 3 && tile_bits <= 10));
 }
 
+// both surface entry points; W: the owners of the tiles form, or null
+static int surface_launch(const void *map, int cap_vox, double voxel, int min_count, const Owners *W, unsigned long long *keys,
+                          int32_t *axes, float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(extract_ok(map, cap_vox, voxel, min_count, count, max_out) && (max_out == 0 || (keys && axes && xyz && normals)));
+    const Tsdf M = make_tsdf(map, cap_vox, voxel, nullptr);
+    const dim3 grid(dpm_cdiv(cap_vox, TS_BLOCK)), block(TS_BLOCK);
+    if (W)
+        hipLaunchKernelGGL(ts_surface_tiles_kernel, grid, block, 0, (hipStream_t)stream, M, (unsigned)min_count, *W, keys, axes, xyz,
+                           normals, count, max_out);
+    else
+        hipLaunchKernelGGL(ts_surface_kernel, grid, block, 0, (hipStream_t)stream, M, (unsigned)min_count, keys, axes, xyz, normals,
+                           count, max_out);
+    return dpm_launch_status();
+}
+
+extern "C" int dpm_tsdf_surface(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *keys,
+                                int32_t *axes, float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
+    return surface_launch(map, cap_vox, voxel, min_count, nullptr, keys, axes, xyz, normals, count, max_out, stream);
+}
+
+extern "C" int dpm_tsdf_mesh(const void *map, int cap_vox, double voxel, int min_count, unsigned long long *vertex_keys,
+                             int32_t *vertex_dirs, float *xyz, int32_t *count, int max_out, dpm_stream_t stream) {
+    DPM_CHECK_ARG(extract_ok(map, cap_vox, voxel, min_count, count, max_out) && (max_out == 0 || (vertex_keys && vertex_dirs && xyz)));
+    const MeshOut O{vertex_keys, vertex_dirs, xyz, count, max_out};
+    hipLaunchKernelGGL(ts_mesh_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
+                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, O);
+    return dpm_launch_status();
+}
+
 extern "C" int dpm_tsdf_surface_tiles(const void *map, int cap_vox, double voxel, int min_count, int tile_bits,
                                       const unsigned long long *tiles, int n_tiles, unsigned long long *keys, int32_t *axes,
                                       float *xyz, float *normals, int32_t *count, int max_out, dpm_stream_t stream) {
-    DPM_CHECK_ARG(table_ok(map, cap_vox) && voxel_ok(voxel) && min_count >= 1 && count && max_out >= 0);
-    DPM_CHECK_ARG(owners_ok(tile_bits, tiles, n_tiles) && (max_out == 0 || (keys && axes && xyz && normals)));
+    DPM_CHECK_ARG(owners_ok(tile_bits, tiles, n_tiles));
     const Owners W{n_tiles ? tiles : nullptr, n_tiles, tile_bits};
-    hipLaunchKernelGGL(ts_surface_tiles_kernel, dim3(dpm_cdiv(cap_vox, TS_BLOCK)), dim3(TS_BLOCK), 0, (hipStream_t)stream,
-                       make_tsdf(map, cap_vox, voxel, nullptr), (unsigned)min_count, W, keys, axes, xyz, normals, count, max_out);
-    return dpm_launch_status();
+    return surface_launch(map, cap_vox, voxel, min_count, &W, keys, axes, xyz, normals, count, max_out, stream);
 }
 
 // the indexed mesh's workspace: the mask bytes, a first index per slot, a sum per block of slots

@@ -2616,13 +2616,13 @@ def tsdf_absorb(table, cap_vox, keys, sums, counts):
                    "dpm_tsdf_absorb")
 
 
-def tsdf_surface(table, cap_vox, voxel, min_count=1, max_out=None):
-    """dpm_tsdf_surface -> (count, keys (n,) int64, axes (n,) int32, xyz (n,3) fp32 map-frame, normals (n,3) fp32) in no
-    defined order; max_out as in _counted"""
+def _tsdf_surface(entry, table, cap_vox, voxel, min_count, owners, max_out):
+    """both surface entry points: the four outputs allocated, `entry` called with `owners` (its arguments between min_count and
+    the outputs) -> (count, keys, axes, xyz, normals); max_out as in _counted"""
     _tsdf_args(table, cap_vox)
     if int(min_count) < 1:
         raise ValueError("min_count >= 1")
-    dev, lib = table.device, _lib.load()
+    dev, fn = table.device, getattr(_lib.load(), entry)
 
     def call(n):
         with torch.cuda.device(dev):
@@ -2631,11 +2631,17 @@ def tsdf_surface(table, cap_vox, voxel, min_count=1, max_out=None):
             axes = torch.empty(n, device=dev, dtype=torch.int32)
             xyz = torch.empty(n, 3, device=dev, dtype=torch.float32)
             normals = torch.empty(n, 3, device=dev, dtype=torch.float32)
-            _lib.check(lib.dpm_tsdf_surface(_ptr(table), int(cap_vox), float(voxel), int(min_count), _ptr(keys) if n else None,
-                                            _ptr(axes) if n else None, _ptr(xyz) if n else None, _ptr(normals) if n else None,
-                                            _ptr(count), n, _stream(table)), "dpm_tsdf_surface")
+            _lib.check(fn(_ptr(table), int(cap_vox), float(voxel), int(min_count), *owners, _ptr(keys) if n else None,
+                          _ptr(axes) if n else None, _ptr(xyz) if n else None, _ptr(normals) if n else None, _ptr(count), n,
+                          _stream(table)), entry)
         return count, keys, axes, xyz, normals
     return _counted(call, max_out)
+
+
+def tsdf_surface(table, cap_vox, voxel, min_count=1, max_out=None):
+    """dpm_tsdf_surface -> (count, keys (n,) int64, axes (n,) int32, xyz (n,3) fp32 map-frame, normals (n,3) fp32) in no
+    defined order; max_out as in _counted"""
+    return _tsdf_surface("dpm_tsdf_surface", table, cap_vox, voxel, min_count, (), max_out)
 
 
 def tsdf_mesh(table, cap_vox, voxel, min_count=1, max_out=None):
@@ -2675,24 +2681,8 @@ def tsdf_surface_tiles(table, cap_vox, voxel, min_count=1, tiles=None, tile_bits
     """dpm_tsdf_surface_tiles -> tsdf_surface's outputs for the records whose voxel k0 lies in one of `tiles` ((n,) int64 tile
     keys on the device, sorted ascending and unique; None or empty: every record); max_out as in _counted"""
     _tsdf_args(table, cap_vox)
-    if int(min_count) < 1:
-        raise ValueError("min_count >= 1")
-    dev, lib = table.device, _lib.load()
-    own, n_own, b = _tsdf_owners("tsdf_surface_tiles", tiles, tile_bits, dev)
-
-    def call(n):
-        with torch.cuda.device(dev):
-            count = torch.zeros(1, device=dev, dtype=torch.int32)
-            keys = torch.empty(n, device=dev, dtype=torch.int64)
-            axes = torch.empty(n, device=dev, dtype=torch.int32)
-            xyz = torch.empty(n, 3, device=dev, dtype=torch.float32)
-            normals = torch.empty(n, 3, device=dev, dtype=torch.float32)
-            _lib.check(lib.dpm_tsdf_surface_tiles(_ptr(table), int(cap_vox), float(voxel), int(min_count), b, own, n_own,
-                                                  _ptr(keys) if n else None, _ptr(axes) if n else None, _ptr(xyz) if n else None,
-                                                  _ptr(normals) if n else None, _ptr(count), n, _stream(table)),
-                       "dpm_tsdf_surface_tiles")
-        return count, keys, axes, xyz, normals
-    return _counted(call, max_out)
+    own, n_own, b = _tsdf_owners("tsdf_surface_tiles", tiles, tile_bits, table.device)
+    return _tsdf_surface("dpm_tsdf_surface_tiles", table, cap_vox, voxel, min_count, (b, own, n_own), max_out)
 
 
 def tsdf_mesh_indexed(table, cap_vox, voxel, min_count=1, tiles=None, tile_bits=5, max_out=None):

@@ -89,6 +89,36 @@ def field_values(sums, counts) -> np.ndarray:
                 / (np.asarray(counts).astype(np.uint32).astype(np.float64) * FIX_ONE)).astype(np.float32)
 
 
+def _first_index(k, d):
+    """a vertex name (key, direction) a row -> (each row's index among the distinct names, sorted; the first row of each of them)"""
+    order = np.lexsort((d, k))
+    first = np.concatenate([[True], (np.diff(k[order]) != 0) | (np.diff(d[order]) != 0)])
+    index = np.empty(k.size, np.int64)
+    index[order] = np.cumsum(first) - 1
+    return index, order[first]
+
+
+def _canonical_faces(faces):
+    """(F,3) indices -> int32, each face rotated so that its smallest index leads, the faces sorted by row"""
+    lead = faces.argmin(axis=1)
+    faces = np.stack([faces[np.arange(len(faces)), (lead + j) % 3] for j in range(3)], axis=1)
+    return np.ascontiguousarray(faces[np.lexsort((faces[:, 2], faces[:, 1], faces[:, 0]))].astype(np.int32))
+
+
+def _by_name(keys, minor):
+    """device: the order that sorts rows by (key, then direction or axis)"""
+    order = torch.sort(minor, stable=True).indices
+    return order[torch.sort(keys[order], stable=True).indices]
+
+
+def _surface_of(keys, axes, xyz_map, normals, origin) -> TsdfSurface:
+    """surface rows in any order (xyz_map and normals (n,3), map frame) -> TsdfSurface sorted by (key, axis), world = map + origin"""
+    order = _by_name(keys, axes)
+    local = xyz_map[order].t().contiguous()
+    world = (local.double() + torch.from_numpy(origin).to(local.device)[:, None]).float()
+    return TsdfSurface(world, normals[order].t().contiguous(), keys[order], axes[order], origin, local)
+
+
 def weld(vertex_keys, vertex_dirs, xyz):
     """triangles as (n,3) vertex names (key, direction) + (n,3,3) positions -> (vertices (V,3) float32 sorted by name, faces
     (F,3) int32, each rotated so that its smallest vertex comes first, sorted by row).  A name has one position."""
@@ -96,17 +126,8 @@ def weld(vertex_keys, vertex_dirs, xyz):
     p = np.asarray(xyz, np.float32).reshape(-1, 3)
     if k.size == 0:
         return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
-    order = np.lexsort((d, k))
-    ks, ds = k[order], d[order]
-    first = np.concatenate([[True], (ks[1:] != ks[:-1]) | (ds[1:] != ds[:-1])])
-    index = np.empty(k.size, np.int64)
-    index[order] = np.cumsum(first) - 1
-    vertices = p[order][first]
-    faces = index.reshape(-1, 3)
-    lead = faces.argmin(axis=1)
-    faces = np.stack([faces[np.arange(len(faces)), (lead + j) % 3] for j in range(3)], axis=1)
-    faces = faces[np.lexsort((faces[:, 2], faces[:, 1], faces[:, 0]))]
-    return np.ascontiguousarray(vertices), np.ascontiguousarray(faces.astype(np.int32))
+    index, keep = _first_index(k, d)
+    return np.ascontiguousarray(p[keep]), _canonical_faces(index.reshape(-1, 3))
 
 
 def write_ply(path, vertices, faces=None, normals=None) -> None:
@@ -379,17 +400,8 @@ def weld_indexed(batches):
     d = np.concatenate([np.asarray(b[4], np.int32).reshape(-1) for b in batches])
     base = np.cumsum([0] + [len(b[3]) for b in batches[:-1]])
     faces = np.concatenate([np.asarray(b[1], np.int64).reshape(-1, 3) + o for b, o in zip(batches, base)])
-    order = np.lexsort((d, k))
-    ks, ds = k[order], d[order]
-    first = np.concatenate([[True], (ks[1:] != ks[:-1]) | (ds[1:] != ds[:-1])])
-    index = np.empty(k.size, np.int64)
-    index[order] = np.cumsum(first) - 1
-    faces = index[faces]
-    lead = faces.argmin(axis=1)
-    faces = np.stack([faces[np.arange(len(faces)), (lead + j) % 3] for j in range(3)], axis=1)
-    faces = faces[np.lexsort((faces[:, 2], faces[:, 1], faces[:, 0]))]
-    keep = order[first]
-    return (np.ascontiguousarray(p[keep]), np.ascontiguousarray(faces.astype(np.int32)), np.ascontiguousarray(n[keep]), k[keep], d[keep])
+    index, keep = _first_index(k, d)
+    return np.ascontiguousarray(p[keep]), _canonical_faces(index[faces]), np.ascontiguousarray(n[keep]), k[keep], d[keep]
 
 
 def _batched(m: "TsdfMap", archive, scratch_voxels, batches, extract):
@@ -431,16 +443,9 @@ def merged_surface(m: "TsdfMap", archive: Optional[TsdfArchive] = None, min_coun
     """`merged_mesh` for the zero crossings: `surface(tiles=owners)` per batch -> TsdfSurface with HOST tensors, sorted by (key,
     axis): the bytes of `surface()` of the map that never rolled"""
     got = _batched(m, archive, scratch_voxels, batches, lambda s, owners, b: s.surface(min_count, owners, b))
-    origin = np.zeros(3) if m.origin is None else m.origin.copy()
-    keys = torch.cat([g.keys.cpu() for g in got]) if got else torch.zeros(0, dtype=torch.int64)
-    axes = torch.cat([g.axes.cpu() for g in got]) if got else torch.zeros(0, dtype=torch.int32)
-    local = torch.cat([g.xyz_map.cpu() for g in got], dim=1) if got else torch.zeros(3, 0)
-    normals = torch.cat([g.normals.cpu() for g in got], dim=1) if got else torch.zeros(3, 0)
-    order = torch.sort(axes, stable=True).indices
-    order = order[torch.sort(keys[order], stable=True).indices]
-    local = local[:, order].contiguous()
-    world = (local.double() + torch.from_numpy(origin)[:, None]).float()
-    return TsdfSurface(world, normals[:, order].contiguous(), keys[order], axes[order], origin, local)
+    rows = [(g.keys.cpu(), g.axes.cpu(), g.xyz_map.cpu().t(), g.normals.cpu().t()) for g in got]
+    rows = rows or [(torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int32), torch.zeros(0, 3), torch.zeros(0, 3))]
+    return _surface_of(*[torch.cat(c) for c in zip(*rows)], np.zeros(3) if m.origin is None else m.origin.copy())
 
 
 MISS, HIT, BACK = ops.TSDF_MISS, ops.TSDF_HIT, ops.TSDF_BACK
@@ -772,19 +777,13 @@ class TsdfMap(_HashedMap):
         min_count = self._min_count(min_count)
         if self.table is None:
             dev = self.device if self.device is not None else "cpu"
-            z = torch.zeros(3, 0, dtype=torch.float32, device=dev)
-            return TsdfSurface(z, z.clone(), torch.zeros(0, dtype=torch.int64, device=dev),
-                               torch.zeros(0, dtype=torch.int32, device=dev), np.zeros(3) if self.origin is None else self.origin, z.clone())
+            z = torch.zeros(0, 3, dtype=torch.float32, device=dev)
+            return _surface_of(z[:, 0].long(), z[:, 0].int(), z, z, np.zeros(3) if self.origin is None else self.origin)
         if tiles is None:
-            keys, axes, xyz, normals = self._extract(ops.tsdf_surface, self.voxel_size, min_count)
+            rows = self._extract(ops.tsdf_surface, self.voxel_size, min_count)
         else:
-            keys, axes, xyz, normals = self._extract(ops.tsdf_surface_tiles, self.voxel_size, min_count,
-                                                     self._owners("surface", tiles, tile_bits), tile_bits)
-        order = torch.sort(axes, stable=True).indices
-        order = order[torch.sort(keys[order], stable=True).indices]
-        local = xyz[order].t().contiguous()
-        world = (local.double() + torch.from_numpy(self.origin).to(local.device)[:, None]).float()
-        return TsdfSurface(world, normals[order].t().contiguous(), keys[order], axes[order], self.origin.copy(), local)
+            rows = self._extract(ops.tsdf_surface_tiles, self.voxel_size, min_count, self._owners("surface", tiles, tile_bits), tile_bits)
+        return _surface_of(*rows, self.origin.copy())
 
     def _owners(self, what, tiles, tile_bits):
         """tile keys (any order, repeats allowed) -> (n,) int64 on the table's device, sorted and unique, as the kernels need"""
@@ -811,8 +810,7 @@ class TsdfMap(_HashedMap):
         own = None if tiles is None else self._owners("mesh_indexed", tiles, tile_bits)
         augment._SYNCS[0] += 1
         _, keys, dirs, xyz, normals, faces = ops.tsdf_mesh_indexed(self.table, self.max_voxels, self.voxel_size, min_count, own, tile_bits)
-        order = torch.sort(dirs, stable=True).indices
-        order = order[torch.sort(keys[order], stable=True).indices]
+        order = _by_name(keys, dirs)
         rank = torch.empty_like(order)
         rank[order] = torch.arange(order.numel(), device=order.device)
         faces = rank[faces.long()]

@@ -6,6 +6,8 @@ tests/test_tsdf_mesh_host.py shows the host side on the CPU.  Every map has at m
   indexed     mesh_indexed equals mesh() and the restatement on wall, lattice and sphere at min_count 1 and 3 and on a 6 x 6 x 6
               block of constructed records that meets every tetrahedron case and every missing-corner exit; the same bytes a
               second time and with the frames, rows or records in reversed order.
+  key ends    that block against either end of the 21 bits, where a cell's corners and a normal's neighbours leave the keys:
+              mesh_indexed, mesh(), surface() and surface(tiles=) equal the restatements, byte for byte, in either record order.
   normals     on axis edges surface()'s bytes; unit or zero; the restatement's float32 bytes; within max(3 |r32 - r64|, 1e-6) of
               its float64 form.
   ownership   single-tile calls partition the sphere's mesh and surface: counts add up, merged they are the whole, byte for byte.
@@ -28,7 +30,7 @@ import tsdf_cases as C  # noqa: E402
 import tsdf_mesh_restated as MR  # noqa: E402
 import tsdf_restated as R  # noqa: E402
 from test_tsdf_host import fuse  # noqa: E402
-from test_tsdf_mesh_host import B, log, same  # noqa: E402
+from test_tsdf_mesh_host import BLOCK_ENDS, B, block_restated, log, same  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -122,6 +124,34 @@ def test_a_block_of_constructed_records_meets_every_case():
     log(f"gpu indexed block: {len(keys)} records, {len(fld[0])} qualified, {len(cases)} (pattern, parity) cases, exits at corners "
         f"{sorted(exits)}: {len(want[0])} vertices, {len(want[1])} faces: mesh() and the restatement, byte for byte, in either order")
     assert len(want[1]) > 20
+
+
+@pytest.mark.parametrize("corner", BLOCK_ENDS)
+def test_the_block_at_either_end_of_the_keys(corner):
+    """the cells and crossings whose neighbours would lie past coordinate 2^21 - 1, or below 0, on a table of 1024 slots"""
+    from deeppointmap_amd import tsdf
+    (keys, sums, counts), want, surf = block_restated(corner)
+    tiles = np.unique(tsdf.tile_of(keys, B))
+    got = []
+    for k, s, n in ((keys, sums, counts), (keys[::-1], sums[::-1], counts[::-1])):
+        m = tsdf.TsdfMap(0.5, max_voxels=1 << 10, origin=np.zeros(3), device=DEV).absorb(k.copy(), s.copy(), n.copy()).check()
+        got.append(host(m.mesh_indexed(2)))
+        for x, y, what in zip(got[-1], want, FIELDS):
+            log(f"gpu block at {corner}: {what}: {len(x)} rows, {-1 if x.shape != y.shape else int((x != y).sum())} entries differ from "
+                f"the restatement (-1: shapes)")
+        assert typed(got[-1]) and same(got[-1], want) and same(m.mesh(2), want[:2])
+        whole, owned = m.surface(2), m.surface(2, tiles=tiles, tile_bits=B)
+        rows = (whole.keys, whole.axes, whole.xyz_map.t().contiguous(), whole.normals.t().contiguous())
+        for x, y, what in zip(host(rows), surf, ("keys", "axes", "positions", "normals")):
+            log(f"gpu block at {corner}: surface {what}: {len(x)} rows, {-1 if x.shape != y.shape else int((x != y).sum())} entries "
+                f"differ from the restatement (-1: shapes)")
+            assert same((x,), (y,)), what
+        assert same(host((owned.keys, owned.axes, owned.xyz_map, owned.normals, owned.xyz)),
+                    host((whole.keys, whole.axes, whole.xyz_map, whole.normals, whole.xyz)))
+        assert m.outside() == 0 and m.overflow() == 0
+    assert same(got[0], got[1]) and len(want[1]) > 20 and len(surf[0]) > 20 and len(tiles) >= 1
+    log(f"gpu block at {corner}: {len(want[0])} vertices, {len(want[1])} faces, {len(surf[0])} crossings in {len(tiles)} tiles: "
+        f"mesh_indexed, mesh(), surface() and surface(tiles=) are the restatements, byte for byte, in either order")
 
 
 # -------------------------------------------------------------------------------------------------------------------- normals

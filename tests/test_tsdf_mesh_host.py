@@ -8,8 +8,11 @@ voxels (tile_bits 3, the minimum).
              seam vertex comes with two different sets of bytes; with a halo one layer thinner at -1, or at +2, it does not.
   weld       weld_indexed over per-batch indexed meshes equals tsdf.weld of the concatenated soups, byte for byte.
   planner    never more than half the scratch table, every tile exactly once, sorted; a tile too large raises.
+  key ends   the constructed 6 x 6 x 6 block placed against either end of the 21 bits restates to the faces, directions, axes and
+             normal bytes it has in the middle; only keys and positions move (the yardstick of the GPU test at those placements).
 Everything observed goes to test_logs/tsdf_mesh.log.
 """
+import functools
 import os
 import sys
 
@@ -25,6 +28,8 @@ import tsdf_restated as R  # noqa: E402
 from test_tsdf_host import fuse  # noqa: E402
 
 B = 3     # tile_bits: tiles of 8 voxels a side
+BLOCK_BASE = (5, -3, 6)
+BLOCK_ENDS = ((2 ** 20 - 6,) * 3, (-2 ** 20,) * 3)     # biased coordinates 2097146 .. 2097151 and 0 .. 5: the ends of the 21 bits
 
 
 def log(line):
@@ -52,6 +57,16 @@ def sphere():
 def same(a, b):
     return all(np.asarray(x).dtype == np.asarray(y).dtype and np.asarray(x).shape == np.asarray(y).shape
                and np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(a, b))
+
+
+@functools.lru_cache(maxsize=None)
+def block_restated(corner):
+    """the constructed block (tsdf_mesh_restated.block_records, seed 0) with its first voxel at the unbiased `corner`, at min_count 2
+    and voxel 0.5 -> (its records, the restated indexed mesh, the restated surface): computed once, never written to"""
+    keys, sums, counts = MR.block_records(0, corner=corner)
+    order = np.argsort(keys)
+    fld = R.field((keys[order], sums[order], counts[order]), 2)
+    return (keys, sums, counts), MR.indexed(fld, 0.5), R.surface(fld, 0.5)
 
 
 # ----------------------------------------------------------------------------------------------------------------------- halo
@@ -167,3 +182,25 @@ def test_a_tile_too_large_for_the_scratch_raises(sphere):
         tsdf.plan_batches(by_tile, B, 2 * biggest - 2)
     assert tsdf.plan_batches(by_tile, B, 2 * biggest)
     assert tsdf.plan_batches({}, B, 64) == []
+
+
+# ------------------------------------------------------------------------------------------------------------------- key ends
+@pytest.mark.parametrize("corner", BLOCK_ENDS)
+def test_the_block_at_either_end_of_the_keys_restates_as_in_the_middle(corner):
+    """A placement moves every key by one offset and nothing else: a voxel past either end of the 21 bits does not exist, like the
+    voxels round the block in the middle.  Positions: a centre ((i - 2^20) + 0.5) * 0.5 is exact in float32 and c + f * v is rounded
+    once, so a coordinate is within half an ulp of its exact value: at most 2^-5 at |x| <= 2^19, the block at the ends (below 1e-6
+    in the middle)."""
+    (_, mesh0, surf0), (records, mesh, surf) = block_restated(BLOCK_BASE), block_restated(corner)
+    shift = np.asarray(corner) - np.asarray(BLOCK_BASE)
+    v, f, n, k, d = mesh
+    assert len(records[0]) == 195 and (len(v), len(f), len(surf[0])) == (len(mesh0[0]), len(mesh0[1]), len(surf0[0]))
+    assert same((f, n, d), (mesh0[1], mesh0[2], mesh0[4])) and same((surf[1], surf[3]), (surf0[1], surf0[3]))
+    assert np.array_equal(MR.coords(k), MR.coords(mesh0[3]) + shift) and np.array_equal(MR.coords(surf[0]), MR.coords(surf0[0]) + shift)
+    x = MR.coords(records[0])
+    assert x.min() == (0 if corner[0] < 0 else MR.AXIS - 5) and x.max() == (5 if corner[0] < 0 else MR.AXIS)
+    bound = 2.0 ** -5 + 1e-6
+    moved = [float(np.abs(a.astype(np.float64) - 0.5 * shift - b.astype(np.float64)).max()) for a, b in ((v, mesh0[0]), (surf[2], surf0[2]))]
+    log(f"host block at {corner}: {len(v)} vertices, {len(f)} faces, {len(surf[0])} crossings: faces, directions, axes and normal bytes "
+        f"of the block at {BLOCK_BASE}; keys moved by {shift.tolist()}, positions by 0.5 times that within {max(moved):.3e} (bound {bound:.3e})")
+    assert max(moved) <= bound and v.tobytes() != mesh0[0].tobytes() and len(f) > 20 and len(surf[0]) > 20
