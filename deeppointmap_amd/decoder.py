@@ -55,7 +55,8 @@ class Decoder(ParamTree):
         # meanwhile fails with "operation not permitted when stream is capturing" (measured with three threads on one
         # Decoder, in every capture mode) -- so shapes are only captured while the process has ONE Python thread: the
         # reference's single-thread SlamSystem.step, bench.py, the rank-0 consumer.  Its multi-thread mode (one Decoder
-        # shared by the odometry / mapping / loop threads, core.py:55-57) keeps launching eagerly.
+        # shared by the odometry / mapping / loop threads, core.py:55-57) replays what `capture_registration_graphs`
+        # captured before the threads started, and launches every other shape eagerly.
         self.graph_min_hits = 2   # eager calls of a shape before it is captured (0 = never capture)
         self.graph_max = 6        # captured shapes kept per decoder
         self._graphs: Dict[tuple, dict] = {}
@@ -132,31 +133,33 @@ class Decoder(ParamTree):
         t = ops.to_channel_first(d, row_multiple=4)           # (B,M,C) view of a (B,M,ld) buffer
         return t.as_strided((B * M, C), (t.stride(1), 1), t.storage_offset()), B, M
 
-    def _self_attn(self, pre: str, xp, B, M, norm: str = None, post=None, mask=None):
-        """x + MHA(x, x, x) (norm None) or LN_norm(x + MHA(x, x, x)) + post, the out-projection carrying the norm;
-        mask (B,M) uint8 = key_padding_mask"""
-        E = self.model_channel
-        a = ops.qkv_attention(xp, self.p(pre + ".in_proj_weight"), self.p(pre + ".in_proj_bias"), B, M, HEADS) if mask is None else None
-        if a is None:
-            qkv = ops.linear(xp, self.p(pre + ".in_proj_weight"), self.p(pre + ".in_proj_bias"))
-            a = ops.attention(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], B, M, M, HEADS, key_mask=mask)
-        if norm is not None:
-            return self._lin_ln(pre + ".out_proj", norm, a, xp, post)
-        return ops.linear(a, self.p(pre + ".out_proj.weight"), self.p(pre + ".out_proj.bias"), residual=xp)
+    def _attention_cores(self, pre: str, z, cross: bool, B, M, N=None, mask=None):
+        """The q | k | v projection `pre` of the rows z and the attention cores on it -> (rows, E), before the out-projection.
+        Self attention: every sequence attends itself; cross attention: its partner on the other side.
 
-    def _cross_attn(self, pre: str, xq, xkv, B, M, N, norm: str = None, mask=None, tail=None):
-        """mask (B,N) uint8: key_padding_mask of the key / value side; tail = (block prefix, post): the result goes through the
-        rest of the block as well (`_block_tail`)"""
+        N None: z holds B sequences of M tokens each (for cross attention sources then targets, the partner of sequence b being
+        sequence (b + B/2) mod B), mask (B,M) uint8 = their key_padding_mask.  One launch: the projection writes the cores'
+        operand planes where ops.qkv_attention applies (no mask, 32-wide heads, M % 64 == 0, enough rows), otherwise one
+        projection and one core launch.
+        N given: z = [B sequences of M tokens ; B sequences of N tokens], mask = (source (B,M), target (B,N)).  One projection
+        over all rows and one core launch per side, writing into the row ranges of one output."""
         E = self.model_channel
         w, b = self.p(pre + ".in_proj_weight"), self.p(pre + ".in_proj_bias")
-        q = ops.linear(xq, w[:E], b[:E])
-        kv = ops.linear(xkv, w[E:], b[E:])
-        a = ops.attention(q, kv[:, :E], kv[:, E:], B, M, N, HEADS, key_mask=mask)
-        if tail is not None:
-            return self._block_tail(tail[0], a, xq, tail[1])
-        if norm is not None:
-            return self._lin_ln(pre + ".out_proj", norm, a, xq)
-        return ops.linear(a, self.p(pre + ".out_proj.weight"), self.p(pre + ".out_proj.bias"), residual=xq)
+        if N is None:
+            shift = B // 2 if cross else 0
+            a = ops.qkv_attention(z, w, b, B, M, HEADS, kv_shift=shift) if mask is None else None
+            if a is None:
+                qkv = ops.linear(z, w, b)
+                a = ops.attention(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], B, M, M, HEADS, kv_shift=shift, key_mask=mask)
+            return a
+        ms, md = (None, None) if mask is None else mask
+        qkv = ops.linear(z, w, b)
+        a = torch.empty(z.shape[0], E, device=z.device, dtype=torch.float32)
+        src, dst = slice(0, B * M), slice(B * M, None)
+        # (cross: both directions read the pre-update tensors, descriptor_attention.py:41-44)
+        for rows, keys, L, Lk, km in ((src, dst, M, N, md), (dst, src, N, M, ms)) if cross else ((src, src, M, M, ms), (dst, dst, N, N, md)):
+            ops.attention(qkv[rows, :E], qkv[keys, E:2 * E], qkv[keys, 2 * E:], B, L, Lk, HEADS, out=a[rows], key_mask=km)
+        return a
 
     def _descriptor_attention_forward(self, src_descriptor, dst_descriptor, src_padding_mask=None,
                                       dst_padding_mask=None):
@@ -179,122 +182,93 @@ class Decoder(ParamTree):
                     raise ValueError(f"padding mask must be a bool tensor of shape ({B}, {L})")
                 return m.contiguous().view(torch.uint8)
             ms, md = as_mask(src_padding_mask, M), as_mask(dst_padding_mask, N)
-        C, E = self.in_channel, self.model_channel
+        C = self.in_channel
         xyz_s, xyz_d = ts[:, C:C + 3], td[:, C:C + 3]
-        if M == N:
-            x, y = self._attention_layers_joint(ts, td, B, M, mask=None if ms is None else torch.cat([ms, md]))
-            return x, xyz_s, y, xyz_d, B, M, N
-        if self.stack_sides:
-            x, y = self._attention_layers_stacked(ts, td, B, M, N, ms, md)
-            return x, xyz_s, y, xyz_d, B, M, N
-        ps, pd = ops.posemb(xyz_s, self._dimt(dev), E), ops.posemb(xyz_d, self._dimt(dev), E)
+        walk = self._attention_layers if M == N or self.stack_sides else self._attention_layers_per_side
+        x, y = walk(ts, td, B, M, N, ms, md)
+        return x, xyz_s, y, xyz_d, B, M, N
+
+    def _attention_layers_per_side(self, ts, td, B, M, N, ms=None, md=None):
+        """The plain form of the attention stack, one side at a time: what `_attention_layers` is held to bit for bit, at M == N
+        as well (`stack_sides = False` runs it for M != N)."""
+        C, E, dev = self.in_channel, self.model_channel, self.device
+        ps, pd = ops.posemb(ts[:, C:C + 3], self._dimt(dev), E), ops.posemb(td[:, C:C + 3], self._dimt(dev), E)
         # x + pos enters every layer: fold the addition into the producing kernel's epilogue
         xp = ops.linear(ts[:, :C], self.p("projection.weight"), self.p("projection.bias"), residual=ps)
         yp = ops.linear(td[:, :C], self.p("projection.weight"), self.p("projection.bias"), residual=pd)
-        for l in range(self.attention_layers):
-            pre = f"descriptor_attention.{l}"
-            last = l == self.attention_layers - 1
-            # self attention: LN1(x + attn(x)), then + pos for the cross block   (descriptor_attention.py:31-40)
-            x1 = self._self_attn(pre + ".self_attn", xp, B, M, norm=pre + ".norm1", post=ps, mask=ms)
-            y1 = self._self_attn(pre + ".self_attn", yp, B, N, norm=pre + ".norm1", post=pd, mask=md)
-            # cross attention, both directions read the pre-update tensors      (descriptor_attention.py:41-44)
-            # ... LN2, then the MLP: LN3(mlp(x) + x); the next layer starts with + pos   (descriptor_attention.py:47-48)
-            xp = self._cross_attn(pre + ".cross_attn", x1, y1, B, M, N, mask=md, tail=(pre, None if last else ps))
-            yp = self._cross_attn(pre + ".cross_attn", y1, x1, B, N, M, mask=ms, tail=(pre, None if last else pd))
-        return xp, xyz_s, yp, xyz_d, B, M, N
 
-    def _attention_layers_stacked(self, ts, td, B, M, N, ms=None, md=None):
-        """The two-sided loop of `_descriptor_attention_forward` for M != N (scan-to-map: a 4096-token tile against a
-        256-token scan) with the source and target rows stacked into one (B*M + B*N)-row matrix: the layers share their
-        weights between the sides, so every projection / LayerNorm / MLP is ONE launch over all rows instead of one per
-        side -- the target side's launches (256 rows: pure launch latency) disappear -- and only the attention cores run
-        per side, writing into the row ranges of one output.  Row-wise kernels give bit-identical rows whatever the
-        row count, so the result equals the per-side loop bit for bit (`stack_sides = False` runs that one)."""
-        C, E, dev = self.in_channel, self.model_channel, self.device
-        R1 = B * M
-        z_in = torch.cat([ts, td], dim=0)
-        pos = ops.posemb(z_in[:, C:C + 3], self._dimt(dev), E)
-        zp = ops.linear(z_in[:, :C], self.p("projection.weight"), self.p("projection.bias"), residual=pos)
+        def cross(pre, xq, xkv, L, Lk, mask):   # one direction: queries of one side, keys / values (and their mask) of the other
+            w, b = self.p(pre + ".in_proj_weight"), self.p(pre + ".in_proj_bias")
+            q = ops.linear(xq, w[:E], b[:E])
+            kv = ops.linear(xkv, w[E:], b[E:])
+            return ops.attention(q, kv[:, :E], kv[:, E:], B, L, Lk, HEADS, key_mask=mask)
         for l in range(self.attention_layers):
             pre = f"descriptor_attention.{l}"
             last = l == self.attention_layers - 1
             sa, ca = pre + ".self_attn", pre + ".cross_attn"
-            qkv = ops.linear(zp, self.p(sa + ".in_proj_weight"), self.p(sa + ".in_proj_bias"))
-            a = torch.empty(zp.shape[0], E, device=dev, dtype=torch.float32)
-            ops.attention(qkv[:R1, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, M, M, HEADS, out=a[:R1], key_mask=ms)
-            ops.attention(qkv[R1:, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, N, N, HEADS, out=a[R1:], key_mask=md)
-            z1 = self._lin_ln(sa + ".out_proj", pre + ".norm1", a, zp, pos)
-            qkv = ops.linear(z1, self.p(ca + ".in_proj_weight"), self.p(ca + ".in_proj_bias"))
-            a = torch.empty(zp.shape[0], E, device=dev, dtype=torch.float32)
-            # both directions read the pre-update tensors (descriptor_attention.py:41-44)
-            ops.attention(qkv[:R1, :E], qkv[R1:, E:2 * E], qkv[R1:, 2 * E:], B, M, N, HEADS, out=a[:R1], key_mask=md)
-            ops.attention(qkv[R1:, :E], qkv[:R1, E:2 * E], qkv[:R1, 2 * E:], B, N, M, HEADS, out=a[R1:], key_mask=ms)
-            zp = self._block_tail(pre, a, z1, None if last else pos)
-        return zp[:R1], zp[R1:]
+            # self attention: LN1(x + attn(x)), then + pos for the cross block   (descriptor_attention.py:31-40)
+            x1 = self._lin_ln(sa + ".out_proj", pre + ".norm1", self._attention_cores(sa, xp, False, B, M, mask=ms), xp, ps)
+            y1 = self._lin_ln(sa + ".out_proj", pre + ".norm1", self._attention_cores(sa, yp, False, B, N, mask=md), yp, pd)
+            # cross attention, both directions read the pre-update tensors      (descriptor_attention.py:41-44)
+            # ... LN2, then the MLP: LN3(mlp(x) + x); the next layer starts with + pos   (descriptor_attention.py:47-48)
+            xp = self._block_tail(pre, cross(ca, x1, y1, M, N, md), x1, None if last else ps)
+            yp = self._block_tail(pre, cross(ca, y1, x1, N, M, ms), y1, None if last else pd)
+        return xp, yp
 
-    def _attention_layers_joint(self, ts, td, B, M, frames=None, mask=None):
-        """Same arithmetic as the two-sided loop above for M == N, with the source and target tokens stacked into one
-        (2*B*M)-row matrix: the layers share their weights between the two sides (descriptor_attention.py:31-48), so
-        every projection / LayerNorm / MLP is ONE launch over all rows, self attention is one launch over 2B
-        sequences, and only cross attention needs one launch per direction (queries of one half, keys/values of the
-        other).  Row-wise kernels give bit-identical rows whatever the row count, so the results equal the split path.
+    def _attention_layers(self, ts, td, B, M, N, ms=None, md=None, first=None):
+        """The attention stack (descriptor_attention.py:31-48) over the stacked rows [B*M source ; B*N target]: the layers share
+        their weights between the sides, so every projection / LayerNorm / MLP is ONE launch over all rows -- the target side's
+        launches of a scan-to-map pair (256 rows against 4096: pure launch latency) disappear -- and only the attention cores
+        depend on the side sizes (`_attention_cores`: one launch over 2B sequences when M == N, one per side otherwise).
+        Row-wise kernels give bit-identical rows whatever the row count, so the result equals `_attention_layers_per_side` bit
+        for bit.  ms (B,M) / md (B,N) uint8: the sides' key_padding_mask.
 
-        mask (2B,M) uint8: key_padding_mask of the stacked sequences (sources then targets).
-
-        frames = (tu (U*M,131), sidx, didx): the pairs are (frame sidx[p], frame didx[p]) of U distinct frames.
-        Everything up to and including the FIRST self-attention block depends on a frame alone, so it runs once per
-        frame (consecutive-frame odometry uses every frame twice) and its rows are then gathered per pair."""
-        C, E, R = self.in_channel, self.model_channel, B * M
-        dev = self.device
-        if frames is not None:
-            tu, sidx, didx = frames
-            U = tu.shape[0] // M
-            pos_u = ops.posemb(tu[:, C:C + 3], self._dimt(dev), E)
-            zu = ops.linear(tu[:, :C], self.p("projection.weight"), self.p("projection.bias"), residual=pos_u)
-            pre = "descriptor_attention.0"
-            z1u = self._self_attn(pre + ".self_attn", zu, U, M, norm=pre + ".norm1", post=pos_u)
-            order = sidx if didx is None else torch.cat([sidx, didx])  # (2B,) int32: sources then targets
-            pos = ops.gather_frames(pos_u, order, M, E).view(2 * R, E)
-            z1_first = ops.gather_frames(z1u, order, M, E).view(2 * R, E)
-            # the first cross-attention block's q | k | v projection sees the frame alone as well: once per frame, the
-            # attention kernel picks a pair's sequences through `order` (row-wise kernel: the same rows bit for bit)
-            ca0 = pre + ".cross_attn"
-            # (the indexed attention kernel exists for 32-wide heads without masks; other widths project per pair side)
-            a_first = qkv_u = None
-            if self.dedup_frames and E // HEADS == 32 and mask is None:
-                a_first = ops.qkv_attention(z1u, self.p(ca0 + ".in_proj_weight"), self.p(ca0 + ".in_proj_bias"), 2 * B, M, HEADS,
-                                            kv_shift=B, seq_index=order)
-                if a_first is None:
-                    qkv_u = ops.linear(z1u, self.p(ca0 + ".in_proj_weight"), self.p(ca0 + ".in_proj_bias"))
-            zp = None
-        else:
-            z_in = torch.cat([ts, td], dim=0)                       # (2R, 131): [src tokens ; dst tokens]
+        first = (pos, z1, a) from `_frame_prefix` (ts, td unused): the stacked position embedding, the first block's rows after
+        norm1 and its cross-attention output (None: computed here from z1)."""
+        C, E, dev = self.in_channel, self.model_channel, self.device
+        seqs, Lt, mask = (2 * B, None, None if ms is None else torch.cat([ms, md])) if M == N else \
+            (B, N, None if ms is None else (ms, md))
+        if first is None:
+            z_in = torch.cat([ts, td], dim=0)                       # [src tokens ; dst tokens]
             pos = ops.posemb(z_in[:, C:C + 3], self._dimt(dev), E)
             zp = ops.linear(z_in[:, :C], self.p("projection.weight"), self.p("projection.bias"), residual=pos)
-            z1_first = qkv_u = a_first = None
+        else:
+            pos, z1, a = first
         for l in range(self.attention_layers):
             pre = f"descriptor_attention.{l}"
             last = l == self.attention_layers - 1
-            if l == 0 and z1_first is not None:
-                z1 = z1_first
-            else:
-                z1 = self._self_attn(pre + ".self_attn", zp, 2 * B, M, norm=pre + ".norm1", post=pos, mask=mask)
-            ca = pre + ".cross_attn"
-            # both directions in one launch: sequence b (source of pair b, or target of pair b - B) reads the keys and
-            # values of sequence (b + B) mod 2B, its partner
-            if l == 0 and z1_first is not None and a_first is not None:
-                a = a_first
-            elif l == 0 and z1_first is not None and qkv_u is not None:
-                a = ops.attention(qkv_u[:, :E], qkv_u[:, E:2 * E], qkv_u[:, 2 * E:], 2 * B, M, M, HEADS, kv_shift=B,
-                                  seq_index=order)
-            else:
-                a = ops.qkv_attention(z1, self.p(ca + ".in_proj_weight"), self.p(ca + ".in_proj_bias"), 2 * B, M, HEADS,
-                                      kv_shift=B) if mask is None else None
-                if a is None:
-                    qkv = ops.linear(z1, self.p(ca + ".in_proj_weight"), self.p(ca + ".in_proj_bias"))  # q | k | v of every token
-                    a = ops.attention(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], 2 * B, M, M, HEADS, kv_shift=B, key_mask=mask)
+            sa, ca = pre + ".self_attn", pre + ".cross_attn"
+            if l > 0 or first is None:
+                z1 = self._lin_ln(sa + ".out_proj", pre + ".norm1", self._attention_cores(sa, zp, False, seqs, M, Lt, mask), zp, pos)
+                a = None
+            if a is None:
+                a = self._attention_cores(ca, z1, True, seqs, M, Lt, mask)
             zp = self._block_tail(pre, a, z1, None if last else pos)
-        return zp[:R], zp[R:]
+        return zp[:B * M], zp[B * M:]
+
+    def _frame_prefix(self, tu, order, B, M):
+        """What the first block computes from a frame alone, for pairs (frame order[p], frame order[B + p]) of the U distinct
+        frames tu (U*M,131), once per frame (consecutive-frame odometry uses every frame twice) -> `first` of `_attention_layers`.
+        Projection, position embedding and the first self-attention block; their rows are then gathered per pair.  The first
+        cross-attention block's q | k | v projection sees the frame alone as well: the attention kernel picks a pair's sequences
+        through `order` (row-wise kernels: the same rows bit for bit).  That kernel exists for 32-wide heads; other widths, and
+        `dedup_frames = False`, project per pair side in the walk."""
+        C, E, dev = self.in_channel, self.model_channel, self.device
+        pos_u = ops.posemb(tu[:, C:C + 3], self._dimt(dev), E)
+        zu = ops.linear(tu[:, :C], self.p("projection.weight"), self.p("projection.bias"), residual=pos_u)
+        sa, ca = "descriptor_attention.0.self_attn", "descriptor_attention.0.cross_attn"
+        z1u = self._lin_ln(sa + ".out_proj", "descriptor_attention.0.norm1",
+                           self._attention_cores(sa, zu, False, tu.shape[0] // M, M), zu, pos_u)
+        pos = ops.gather_frames(pos_u, order, M, E).view(2 * B * M, E)
+        z1 = ops.gather_frames(z1u, order, M, E).view(2 * B * M, E)
+        a = None
+        if self.dedup_frames and E // HEADS == 32:
+            w, b = self.p(ca + ".in_proj_weight"), self.p(ca + ".in_proj_bias")
+            a = ops.qkv_attention(z1u, w, b, 2 * B, M, HEADS, kv_shift=B, seq_index=order)
+            if a is None:
+                qkv = ops.linear(z1u, w, b)
+                a = ops.attention(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], 2 * B, M, M, HEADS, kv_shift=B, seq_index=order)
+        return pos, z1, a
 
     # -- public API ----------------------------------------------------------------------------
     def train(self, mode: bool = True):
@@ -457,7 +431,7 @@ class Decoder(ParamTree):
             order = pairs[2] if len(pairs) > 2 else torch.cat([sidx, didx])
             tu, U, M = self._stage(src_descriptor, dev)
             N, B, C = M, sidx.numel(), self.in_channel
-            x, y = self._attention_layers_joint(None, None, B, M, frames=(tu, order, None))
+            x, y = self._attention_layers(None, None, B, M, N, first=self._frame_prefix(tu, order, B, M))
             xyz_sd = ops.gather_frames(tu, order, M, 3, ld=tu.stride(0), offset=C).view(2 * B * M, 3)
             xyz_s, xyz_d = xyz_sd[:B * M], xyz_sd[B * M:]
         else:
@@ -476,7 +450,7 @@ class Decoder(ParamTree):
         if (M == N and x.is_contiguous() and y.is_contiguous() and
                 x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr() and
                 y.storage_offset() == x.storage_offset() + x.numel()):
-            # the joint attention path left src and dst rows back to back: the head (shared weights, row-wise
+            # the attention walk left src and dst rows back to back: the head (shared weights, row-wise
             # kernels) runs once over both halves
             z = x.as_strided((2 * B * M, E), (E, 1), x.storage_offset())
             ab = ops.l2_normalize(self._lin("similarity_head.2", self._lin("similarity_head.0", z, ops.ACT_RELU)))
@@ -534,18 +508,31 @@ class Decoder(ParamTree):
             self._stamp_params = list(self._flat.values())
         return (self._epoch, ops.derived_generation(), tuple([p._version for p in self._stamp_params]))
 
+    def _stale(self, key, e: dict, stamp=None) -> bool:
+        """(under the lock) The one rule by which a graph of either kind is dropped: an entry whose graph was captured under
+        another weights stamp (the weights moved or changed) leaves `_graphs` where it is found, and its graph, the graph's
+        private pool and its static buffers are freed with it (a replay in flight on another thread keeps them until it ends)."""
+        if e["graph"] is None or e["stamp"] == (self._weights_stamp() if stamp is None else stamp):
+            return False
+        del self._graphs[key]
+        return True
+
+    def captured(self, M: int, N: int) -> bool:
+        """a live graph of an (M, N) registration exists: captured, of either kind, under the weights as they are now"""
+        with self._graph_lock:
+            stamp = self._weights_stamp()
+            return any(k[:2] == (M, N) and v["graph"] is not None and v["stamp"] == stamp for k, v in self._graphs.items())
+
     def _graph_entry(self, key, M: int, N: int, num_sample, dev):
-        """The graph of shape `key`, captured now if the shape has been seen often enough; None = run eagerly."""
+        """The calling thread's graph of shape `key`, captured now if the shape has been seen often enough; None = run eagerly."""
         with self._graph_lock:
             e = self._graphs.get(key)
-            if e is None:
-                e = self._graphs[key] = dict(hits=0, graph=None, used=0)
+            if e is None or self._stale(key, e):   # (a dropped graph leaves its hit count: the shape is captured again at once)
+                e = self._graphs[key] = dict(hits=e["hits"] if e else 0, graph=None, used=0)
             e["hits"] += 1
             e["used"] = max((v["used"] for v in self._graphs.values()), default=0) + 1
             if e["graph"] is not None:
-                if e["stamp"] == self._weights_stamp():
-                    return e
-                e["graph"] = None            # the weights moved or changed: capture again
+                return e
             if self.graph_min_hits <= 0 or e["hits"] <= self.graph_min_hits or threading.active_count() > 1:
                 return None
             self._make_room()
@@ -584,10 +571,12 @@ class Decoder(ParamTree):
         captures never happen once a second thread exists, and without this call such a process runs every registration eagerly
         (~51 launches, 0.86-1.0 ms of host time per 256 x 256 pair against 0.46 ms replayed).  Replays of one graph from different
         threads are put in order on the device (an event per graph), results are bit-identical to the eager path.  Returns the number
-        of graphs captured.  Graphs captured here are not subject to `graph_max`; `invalidate_caches()` / new weights drop them
-        like the others (they are not captured again behind the caller's back: call this again).  `copies` > 1 captures that many
-        instances per shape (each with its own static buffers): threads that ask for the same shape at the same time then replay
-        different instances side by side on the device instead of queueing behind one."""
+        of graphs captured.  Graphs captured here are not subject to `graph_max`.  After `invalidate_caches()` / new weights they
+        are dropped by the rule of all graphs (`_stale`): the first registration that asks for the shape removes its stale instances
+        from `_graphs`, which frees their graphs and buffers, and goes on as if none had been captured ahead -- unlike a thread's own
+        graphs they are not captured again behind the caller's back: call this again (it captures what is missing or stale).
+        `copies` > 1 captures that many instances per shape (each with its own static buffers): threads that ask for the same shape
+        at the same time then replay different instances side by side on the device instead of queueing behind one."""
         dev = self._require_gpu()
         if threading.active_count() > 1:
             raise RuntimeError("capture_registration_graphs must run before the process starts its worker threads")
@@ -601,7 +590,7 @@ class Decoder(ParamTree):
                     key = (M, N, k, dev.index, None, c)        # None: no owner thread; c: the instance
                     with self._graph_lock:
                         e = self._graphs.get(key)
-                        if e is not None and e.get("graph") is not None and e["stamp"] == self._weights_stamp():
+                        if e is not None and e["graph"] is not None and not self._stale(key, e):
                             continue
                         e = self._graphs[key] = dict(hits=0, graph=None, used=0, pinned=True, lock=threading.Lock(), done=None)
                     if self._capture(e, M, N, num_sample, dev) is not None:
@@ -611,17 +600,19 @@ class Decoder(ParamTree):
     def _shared_graph(self, M: int, N: int, k: int, dev):
         """an instance of the ahead-of-time graph of this shape, LOCKED for the caller (an idle one if there is one, else the first)"""
         first, stamp, c = None, None, 0
-        while True:
-            e = self._graphs.get((M, N, k, dev.index, None, c))
-            if e is None:
-                break
-            if e.get("graph") is not None:
-                stamp = self._weights_stamp() if stamp is None else stamp
-                if e["stamp"] == stamp:
-                    if e["lock"].acquire(blocking=False):
-                        return e
-                    first = e if first is None else first
-            c += 1
+        with self._graph_lock:
+            while True:
+                key = (M, N, k, dev.index, None, c)
+                e = self._graphs.get(key)
+                if e is None:
+                    break
+                if e["graph"] is not None:
+                    stamp = self._weights_stamp() if stamp is None else stamp
+                    if not self._stale(key, e, stamp):
+                        if e["lock"].acquire(blocking=False):
+                            return e
+                        first = e if first is None else first
+                c += 1
         if first is not None:
             first["lock"].acquire()
         return first
@@ -648,26 +639,26 @@ class Decoder(ParamTree):
                     entry = self._shared_graph(M, N, k, dev)    # captured ahead of time for every thread, or ...
                     if entry is None:                           # ... this thread's own, captured when the shape keeps coming back
                         entry = self._graph_entry((M, N, k, dev.index, threading.get_ident()), M, N, num_sample, dev)
-            if entry is not None and entry.get("lock") is not None:
+
+            def replay():   # one sequence for both kinds of graph: inputs into the static buffers, replay, the result row out
+                entry["src"].copy_(src_descriptor, non_blocking=True)
+                entry["dst"].copy_(dst_descriptor, non_blocking=True)
+                entry["graph"].replay()
+                return entry["res"][0].clone()          # the static buffer belongs to the next replay
+            if entry is None:
+                res = self._register(src_descriptor, dst_descriptor, num_sample, header_out, trace,
+                                     masks=(src_padding_mask, dst_padding_mask))[0]
+            elif entry.get("lock") is None:
+                res = replay()
+            else:
                 try:   # (locked by _shared_graph) one graph, several threads on their own streams: replays in order on the device too
                     st = torch.cuda.current_stream(dev)
                     if entry["done"] is not None:
                         st.wait_event(entry["done"])
-                    entry["src"].copy_(src_descriptor, non_blocking=True)
-                    entry["dst"].copy_(dst_descriptor, non_blocking=True)
-                    entry["graph"].replay()
-                    res = entry["res"][0].clone()
+                    res = replay()
                     entry["done"] = st.record_event()
                 finally:
                     entry["lock"].release()
-            elif entry is not None:
-                entry["src"].copy_(src_descriptor, non_blocking=True)
-                entry["dst"].copy_(dst_descriptor, non_blocking=True)
-                entry["graph"].replay()
-                res = entry["res"][0].clone()           # the static buffer belongs to the next replay
-            else:
-                res = self._register(src_descriptor, dst_descriptor, num_sample, header_out, trace,
-                                     masks=(src_padding_mask, dst_padding_mask))[0]
             head = res[:ops.RES_HDR].cpu()  # the one host sync of the call: rmse is a python float in the contract
         n_in, rmse = int(head[14]), float(head[12])
         R, T, cf = res[0:9].view(3, 3), res[9:12].view(3, 1), res[ops.RES_HDR:ops.RES_HDR + n_in]

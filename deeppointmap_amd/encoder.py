@@ -45,6 +45,16 @@ class Encoder(ParamTree):
         # positions agrees with the pick order).  Only the first level is computed; False runs every level
         # (tests assert both give identical tensors).
         self.nested_fps = self.all_fps and all(b <= a for a, b in zip(self.encoder_cfg.npoint, self.encoder_cfg.npoint[1:]))
+        # Neighbour queries repeat: a SetAbstraction asks, for the FPS-picked subset of a level's points, exactly what the preceding
+        # LocalAggregation answered for ALL of them when radius and K coincide (they do in every shipped config), and consecutive
+        # LocalAggregations of a stage may share (radius, K) too.  The plan, per downsampling level: sa = the SetAbstraction's
+        # (radius, K), answered = the previous level's LocalAggregations hold it, la = the distinct LocalAggregation keys in
+        # order, block = the key of each InvResMLP block (`_level_queries` resolves it, `presample` sorts its searches' grids)
+        self._plan, prev = [], []
+        for radii, ks in zip(self.encoder_cfg.radius_list, self.encoder_cfg.nsample_list):
+            sa, *block = [(float(r), int(k)) for r, k in zip(radii, ks)]
+            self._plan.append(dict(sa=sa, answered=sa in prev, la=list(dict.fromkeys(block)), block=block))
+            prev = self._plan[-1]["la"]
         # presample() also answers the neighbour queries (coordinates only): a pipeline knob -- where they run moves
         # work between the geometry and the feature stage, the results are the same tensors either way
         self.presample_neighbours = False
@@ -136,51 +146,55 @@ class Encoder(ParamTree):
                     fidx, cur, cur_len = sampled0 if (i == 0 and sampled0 is not None) else self._sample_level(i, cur, cur_len)
                     out[f"fidx{i}"], out[f"xyz{i}"], out[f"len{i}"] = fidx, cur, cur_len
             # The search grids of the neighbour queries depend on coordinates and radii only: they are sorted here,
-            # next to the sampling, and forward() runs just the searches.  Same bookkeeping as forward(): a
-            # SetAbstraction whose (radius, K) the previous level's LocalAggregation already answered needs none.
-            grids, pts_i, len_i, answered = {}, xyz, lengths, set()
-            for i in range(n_levels):
-                radii, ks = self.encoder_cfg.radius_list[i], self.encoder_cfg.nsample_list[i]
-                if (float(radii[0]), int(ks[0])) not in answered and pts_i.shape[1] >= ops.GRID_MIN_N:
-                    grids[("sa", i)] = ops.knn_grid(pts_i, len_i, radii[0])
-                pts_i, len_i, answered = out[f"xyz{i}"], out[f"len{i}"], set()
-                for j in range(1, len(radii)):
-                    key = (float(radii[j]), int(ks[j]))
-                    if key not in answered and pts_i.shape[1] >= ops.GRID_MIN_N:
-                        grids[("la", i, key)] = ops.knn_grid(pts_i, len_i, radii[j])
-                    answered.add(key)
+            # next to the sampling, and forward() runs just the searches: one grid per search of the plan (a
+            # SetAbstraction whose (radius, K) the previous level's LocalAggregation already answered needs none).
+            grids, pts_i, len_i = {}, xyz, lengths
+            for i, lv in enumerate(self._plan[:n_levels]):
+                if not lv["answered"] and pts_i.shape[1] >= ops.GRID_MIN_N:
+                    grids[("sa", i)] = ops.knn_grid(pts_i, len_i, lv["sa"][0])
+                pts_i, len_i = out[f"xyz{i}"], out[f"len{i}"]
+                for key in lv["la"] if pts_i.shape[1] >= ops.GRID_MIN_N else ():
+                    grids[("la", i, key)] = ops.knn_grid(pts_i, len_i, key[0])
             out["grids"] = grids
-            if n_levels == len(self.encoder_cfg.npoint):
-                if self.presample_neighbours:
-                    out["knn"] = self._neighbour_queries(out)
-                elif self.presample_neighbours_from is not None:
-                    out["knn"] = self._neighbour_queries(out, first_level=int(self.presample_neighbours_from))
+            ahead = 0 if self.presample_neighbours else self.presample_neighbours_from
+            if n_levels == len(self.encoder_cfg.npoint) and ahead is not None:
+                out["knn"] = self._neighbour_queries(out, first_level=int(ahead))
         return out
 
     def _neighbour_queries(self, samp: dict, first_level: int = 0) -> dict:
         """The neighbour queries of the downsampling levels from `first_level` on -- they depend on coordinates only, like the
-        sampling.  Same reuse rules as forward(): ("sa", i) / ("la", i, (radius, K)) -> idx (a reused answer is a copy of rows
-        of an identical query: the same tensors whether a level's first query finds a predecessor here or not)."""
-        enc, grids, knn = self.encoder_cfg, samp.get("grids", {}), {}
-        xyz, lengths, self_q = samp["xyz"], samp["lengths"], {}
-        for i in range(len(enc.npoint)):
-            radii, ks = enc.radius_list[i], enc.nsample_list[i]
-            fidx, new_xyz, new_len = samp[f"fidx{i}"], samp[f"xyz{i}"], samp[f"len{i}"]
-            if i < first_level:
-                xyz, lengths, self_q = new_xyz, new_len, {}
-                continue
-            prev = self_q.get((float(radii[0]), int(ks[0])))
-            knn[("sa", i)] = ops.knn_hybrid(xyz, lengths, new_xyz, ks[0], radii[0], reuse_idx=prev,
-                                            center_src=fidx if prev is not None else None,
-                                            grid=grids.get(("sa", i)) if prev is None else None)
-            self_q = {}
-            for j in range(1, len(radii)):
-                key = (float(radii[j]), int(ks[j]))
-                if key not in self_q:
-                    self_q[key] = ops.knn_hybrid(new_xyz, new_len, new_xyz, ks[j], radii[j], grid=grids.get(("la", i, key)))
-                knn[("la", i, key)] = self_q[key]
-            xyz, lengths = new_xyz, new_len
+        sampling.  forward()'s own resolver answers them: ("sa", i) / ("la", i, (radius, K)) -> idx (a reused answer is a copy of
+        rows of an identical query: the same tensors whether a level's first query finds a predecessor here or not)."""
+        knn, self_q, level = {}, {}, (samp["xyz"], samp["lengths"])
+        for i in range(len(self._plan)):
+            sampled, own = (samp[f"fidx{i}"], samp[f"xyz{i}"], samp[f"len{i}"]), {}
+            if i >= first_level:
+                knn[("sa", i)], *_ = self._level_queries(i, level, sampled, self_q, own, {}, samp.get("grids", {}))
+                knn.update((("la", i, key), idx) for key, idx in own.items())
+            level, self_q = sampled[1:], own
         return knn
+
+    def _level_queries(self, i: int, level, sampled, self_q: dict, own: dict, knn: dict, grids: dict):
+        """The neighbour queries of downsampling level i, resolved by the plan: yields the SetAbstraction's idx (B,S,K), then the
+        LocalAggregation idx (B,S,K) of each InvResMLP block -- each answered when it is asked for, so the searches stay where
+        they were among the level's launches.  level = (xyz, lengths) the level samples from, sampled = (fidx, new_xyz, new_len)
+        its picks; self_q = the self-queries of `level` (the previous level's LocalAggregations), (radius, K) -> idx (B,N,K); `own`
+        receives those of the sampled level.  An answer presampled into `knn` is taken; a SetAbstraction whose key self_q holds
+        copies its rows (only padded centres are searched); every other query is a search, in the grid presample() sorted for it
+        (`grids`) where there is one."""
+        lv = self._plan[i]
+        (xyz, lengths), (fidx, new_xyz, new_len) = level, sampled
+        gidx = knn.get(("sa", i))
+        if gidx is None:
+            prev = self_q.get(lv["sa"])
+            gidx = ops.knn_hybrid(xyz, lengths, new_xyz, lv["sa"][1], lv["sa"][0], reuse_idx=prev,
+                                  center_src=fidx if prev is not None else None, grid=grids.get(("sa", i)) if prev is None else None)
+        yield gidx
+        for key in lv["block"]:
+            if key not in own:
+                own[key] = knn[("la", i, key)] if ("la", i, key) in knn else ops.knn_hybrid(
+                    new_xyz, new_len, new_xyz, key[1], key[0], grid=grids.get(("la", i, key)))
+            yield own[key]
 
     @torch.no_grad()
     def forward(self, points: torch.Tensor, points_padding: torch.Tensor, trace: Optional[dict] = None,
@@ -222,18 +236,17 @@ class Encoder(ParamTree):
             else:  # extra input channels: point-major copy of the first in_channel rows
                 fea = ops.linear(pts[:, :self.in_channel].transpose(1, 2).contiguous(), w0, self.p("point_mlp0.bias"))
             levels = [(xyz, fea, lengths)] if resume is None else resume["levels"]
-            # Neighbour queries repeat: a SetAbstraction asks, for the FPS-picked subset of a level's points, exactly
-            # what the preceding LocalAggregation answered for ALL of them when radius and K coincide (they do in every
-            # shipped config), and consecutive LocalAggregations of a stage may share (radius, K) too.  `self_q`
-            # remembers the self-queries of the current level: (radius, K) -> idx (B,N,K).
+            # `self_q` remembers the self-queries of the current level for the next one's SetAbstraction (`_level_queries`):
+            # (radius, K) -> idx (B,N,K)
             self_q = {} if resume is None else resume["self_q"]
+            grids, knn = samp.get("grids", {}), samp.get("knn", {})
             for i, npoint in enumerate(enc.npoint):
                 if resume is not None and i < resume["next"]:
                     continue
                 if stop_level is not None and i >= stop_level:
                     return dict(samp=samp, levels=levels, self_q=self_q, next=i)
                 xyz, fea, lengths = levels[-1]
-                radii, ks = enc.radius_list[i], enc.nsample_list[i]
+                radii = enc.radius_list[i]
                 pre = f"downsampler.{i}"
                 if f"fidx{i}" in samp:
                     fidx, new_xyz, new_len = samp[f"fidx{i}"], samp[f"xyz{i}"], samp[f"len{i}"]
@@ -242,14 +255,10 @@ class Encoder(ParamTree):
                 # (self._price_tail > 0: levels 3+ and the upsamplers are computed that many extra times, results identical --
                 # scripts/price_tail.py measures what the launch-bound tail of the encoder costs a pipelined step)
                 for _rep in range(1 + (self._price_tail if i >= 3 else 0)):
-                    prev = self_q.get((float(radii[0]), int(ks[0])))
-                    grids, knn = samp.get("grids", {}), samp.get("knn", {})
-                    gidx = knn.get(("sa", i))
-                    if gidx is None:
-                        gidx = ops.knn_hybrid(xyz, lengths, new_xyz, ks[0], radii[0], reuse_idx=prev,
-                                              center_src=fidx if prev is not None else None,
-                                              grid=grids.get(("sa", i)) if prev is None else None)
-                    self_q = {}  # from here on the level is the sampled one
+                    own = {}
+                    queries = self._level_queries(i, (xyz, lengths), (fidx, new_xyz, new_len), self_q, own, knn, grids)
+                    gidx = next(queries)
+                    self_q = own  # from here on the level is the sampled one
                     if fea is None:
                         m = pre + ".sa.mlp"
                         new_fea = ops.group_mlp_max_from_xyz(xyz, w0, self.p("point_mlp0.bias"), new_xyz, gidx,
@@ -260,13 +269,8 @@ class Encoder(ParamTree):
                     if trace is not None:
                         trace[pre + ".fps.idx"], trace[pre + ".fps.new"] = fidx, new_xyz
                         trace[pre + ".sa.idx"], trace[pre + ".sa.out"] = gidx, new_fea
-                    for j in range(1, len(radii)):
+                    for j, lidx in enumerate(queries, 1):
                         q = f"{pre}.irm.{j - 1}"
-                        key = (float(radii[j]), int(ks[j]))
-                        if key not in self_q:
-                            self_q[key] = knn[("la", i, key)] if ("la", i, key) in knn else ops.knn_hybrid(
-                                new_xyz, new_len, new_xyz, ks[j], radii[j], grid=grids.get(("la", i, key)))
-                        lidx = self_q[key]
                         t = self._group(q + ".la.mlp", radii[j], new_xyz, new_fea, new_xyz, lidx)
                         pair = ops.pwconv_pair(t, self.p(q + ".pw_conv.0.weight"), self.p(q + ".pw_conv.0.bias"),
                                                self.p(q + ".pw_conv.1.ln.weight"), self.p(q + ".pw_conv.1.ln.bias"),
@@ -399,9 +403,8 @@ class Encoder(ParamTree):
             recompute = keep is None and xyz.shape[0] * xyz.shape[1] >= self.train_checkpoint_rows
             levels = [(xyz, fea, lengths)]
             for i in range(len(enc.npoint)):
-                radii, ks = enc.radius_list[i], enc.nsample_list[i]
                 new_xyz, new_len = samp[f"xyz{i}"], samp[f"len{i}"]
-                lidx = [knn[("la", i, (float(radii[j]), int(ks[j])))] for j in range(1, len(radii))]
+                lidx = [knn[("la", i, key)] for key in self._plan[i]["block"]]
                 if recompute:
                     new_fea = checkpoint(self._train_stage, i, xyz, fea, new_xyz, knn[("sa", i)], lidx, None, use_reentrant=False)
                 else:

@@ -29,6 +29,6 @@ for M, N in [(256, 256), (4096, 256), (4096, 4096)]:
     dec.graph_min_hits = 2
     tg, og = timed(s, d)
     same = all(torch.equal(a, b) for a, b in zip(oe[:3], og[:3])) and oe[3] == og[3]
-    captured = any(v["graph"] is not None for k, v in dec._graphs.items() if k[:2] == (M, N))
+    captured = dec.captured(M, N)
     print(f'registration_forward {M}x{N}: eager {te:.2f} ms | graph {tg:.2f} ms (captured: {captured}, identical: {same})  '
           f'k={oe[2].shape[0]} inliers, rmse {oe[3]:.3f}')

@@ -404,6 +404,53 @@ def test_stacked_sides_equal_the_per_side_loop(dec):
         assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[2]), (B, M, N, masked)
 
 
+@pytest.mark.parametrize("B,M,N,masked", [(4, 256, 256, False), (2, 48, 48, False), (2, 48, 48, True), (2, 96, 32, False),
+                                          (2, 96, 32, True)])
+def test_attention_walk_equals_the_per_side_loop(dec, B, M, N, masked):
+    """Decoder._attention_layers (every row-wise layer once over the stacked rows, the cores of `_attention_cores`) against the
+    plain per-side loop on the same staged rows, bit for bit: equal sides where the q | k | v projection writes the cores'
+    operand planes (4 x 256 x 256: 2048 rows, M % 64 == 0) and where it does not (48 tokens), unequal sides, each with and
+    without padding masks (the last 5 source and the last 3 target tokens)."""
+    gen = torch.Generator().manual_seed(40)
+    s = torch.cat([torch.rand(B, 128, M, generator=gen), 60 * torch.randn(B, 3, M, generator=gen)], 1)
+    d = torch.cat([torch.rand(B, 128, N, generator=gen), 60 * torch.randn(B, 3, N, generator=gen)], 1)
+    dev = torch.device(DEV)
+    ts, td = dec._stage(s, dev)[0], dec._stage(d, dev)[0]
+    ms = md = None
+    if masked:
+        ms, md = torch.zeros(B, M, dtype=torch.uint8, device=DEV), torch.zeros(B, N, dtype=torch.uint8, device=DEV)
+        ms[:, M - 5:], md[:, N - 3:] = 1, 1
+    x, y = dec._attention_layers(ts, td, B, M, N, ms, md)
+    xs, ys = dec._attention_layers_per_side(ts, td, B, M, N, ms, md)
+    assert tuple(x.shape) == (B * M, 256) and tuple(y.shape) == (B * N, 256)
+    assert torch.equal(x, xs) and torch.equal(y, ys)
+
+
+def test_a_stale_graph_captured_ahead_is_dropped_where_it_is_found(cfg_full):
+    """The drop rule of the captured graphs (Decoder._stale) on a graph captured ahead of time: after invalidate_caches() the
+    first registration of the shape removes it from `_graphs` (nothing else would: such graphs are not bounded by graph_max),
+    answers with the eager call's bits, and capture_registration_graphs captures the shape anew."""
+    import threading
+    from deeppointmap_amd.decoder import Decoder
+    from deeppointmap_amd.weights import init_procedural
+    if threading.active_count() > 1:
+        pytest.skip("graphs are only captured in single-threaded processes (decoder.py)")
+    dec = init_procedural(Decoder(cfg_full)).to(DEV)
+    gen = torch.Generator().manual_seed(5)
+    s, d = (torch.cat([torch.rand(128, 64, generator=gen), 60 * torch.randn(3, 64, generator=gen)]).to(DEV) for _ in range(2))
+    dec.graph_min_hits = 0
+    want = dec.registration_forward(s, d, num_sample=0.5)
+    dec.graph_min_hits = 2
+    assert dec.capture_registration_graphs([(64, 64, 0.5)]) == 1 and dec.captured(64, 64)
+    dec.invalidate_caches()
+    assert not dec.captured(64, 64)
+    got = dec.registration_forward(s, d, num_sample=0.5)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(got[2], want[2]) and got[3] == want[3]
+    stamp = dec._weights_stamp()
+    assert not [k for k, v in dec._graphs.items() if k[:2] == (64, 64) and v["graph"] is not None and v["stamp"] != stamp]
+    assert dec.capture_registration_graphs([(64, 64, 0.5)]) == 1 and dec.captured(64, 64)
+
+
 def test_pairs_entry_equals_batched_entry(dec):
     """registration_forward_pairs shares the per-frame decoder prefix between the pairs a frame takes part in; rows
     are computed by row-wise kernels, so the result must equal the gathered-batch entry point bit for bit."""
@@ -557,7 +604,7 @@ def test_registration_forward_replays_a_captured_graph_bit_for_bit(cfg_full):
         eager = [dec.registration_forward(s, d, num_sample=0.5) for s, d in inputs]
         dec.graph_min_hits = 2
         replay = [dec.registration_forward(s, d, num_sample=0.5) for s, d in inputs]
-        assert any(v["graph"] is not None for k, v in dec._graphs.items() if k[:2] == (M, N))
+        assert dec.captured(M, N)
         for e, r in zip(eager, replay):
             assert torch.equal(e[0], r[0]) and torch.equal(e[1], r[1]) and torch.equal(e[2], r[2]) and e[3] == r[3]
     # weights edited in place: the captured graph would still read the right memory, but the stamp says "changed" and the

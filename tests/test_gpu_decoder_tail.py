@@ -190,7 +190,7 @@ def test_registration_forward_knob_on_off_and_graph_replay(ops, cfg_full, monkey
     dec.graph_min_hits = 2
     replays = [dec.registration_forward(s, d, num_sample=0.5) for _ in range(4)]
     if threading.active_count() == 1:      # (graphs are only captured in single-threaded processes, decoder.py)
-        assert any(v["graph"] is not None for k, v in dec._graphs.items() if k[:2] == (256, 256))
+        assert dec.captured(256, 256)
     assert all(same(r, eager) for r in replays)
     dec.graph_min_hits = 0
 

@@ -124,6 +124,39 @@ def test_neighbour_queries_in_the_geometry_pass_change_nothing(cfg_full):
     assert torch.equal(coor0, coor1) and torch.equal(fea0, fea1) and torch.equal(mask0, mask1)
 
 
+def test_presample_variants_give_the_plain_forward_bytes(cfg_full):
+    """Wherever the neighbour queries of a level are answered -- inside forward, in presample() (all levels or from level 2 on),
+    behind a presample() of one or two sampling levels, in either half of a forward split at level 2 -- one resolver answers
+    them from one plan (Encoder._level_queries, Encoder._plan): coor, fea and padding are the plain forward's bytes.  And
+    presample() sorts exactly the grids of the plan's searches over frames of at least GRID_MIN_N points."""
+    from deeppointmap_amd import ops
+    enc = make_encoder(cfg_full)
+    pts, pad = synthetic.frames(2, 20000)
+    pad[1, 14000:] = True
+    want = enc(pts, pad)
+
+    def same(got):
+        return len(got) == 3 and all(torch.equal(g, w) for g, w in zip(got, want))
+    assert same(enc(pts, pad, presampled=enc.presample(pts, pad, levels=1)))
+    assert same(enc(pts, pad, presampled=enc.presample(pts, pad, levels=2)))
+    enc.presample_neighbours_from = 2
+    pre = enc.presample(pts, pad)
+    assert {k[1] for k in pre["knn"]} == set(range(2, len(enc._plan)))
+    assert same(enc(pts, pad, presampled=pre))
+    enc.presample_neighbours_from = None
+    assert same(enc(pts, pad, resume=enc(pts, pad, stop_level=2)))
+    # the grids: a SetAbstraction searches the level it samples from unless the previous level's LocalAggregations hold its
+    # key, every distinct LocalAggregation key searches the sampled level
+    sizes = [pts.shape[2]] + list(cfg_full.encoder.npoint)
+    searches = set()
+    for i, lv in enumerate(enc._plan):
+        if not lv["answered"] and sizes[i] >= ops.GRID_MIN_N:
+            searches.add(("sa", i))
+        if sizes[i + 1] >= ops.GRID_MIN_N:
+            searches.update(("la", i, key) for key in lv["la"])
+    assert searches and set(enc.presample(pts, pad)["grids"]) == searches
+
+
 def test_encoder_extra_input_channels_vs_oracle(cfg_reduced):
     """in_channel > 3 (e.g. intensity as a fourth point channel; no shipped config uses it): point_mlp0 is then a
     real GEMM over the input channels and the first set abstraction reads materialised features.  Checked against
