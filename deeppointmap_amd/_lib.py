@@ -39,6 +39,7 @@ SIGNATURES = {
     "dpm_knn_hybrid_reuse": (I, [P, P, P, I, I, I, I, D, P, P, P, P, P]),
     "dpm_knn_build_grid": (I, [P, P, I, I, D, P, P]),
     "dpm_knn_hybrid_prebuilt": (I, [P, P, P, I, I, I, I, D, P, P, P]),
+    "dpm_knn_debug_census": (I, [P, I, I, P, P]),
     "dpm_ball_query": (I, [P, P, P, I, I, I, I, D, P, P]),
     "dpm_voxel_sampler_bounds": (I, [P, P, I, I, I, D, D, P, P]),
     "dpm_voxel_sampler_workspace_bytes": (c_size_t, [I, I, LL]),

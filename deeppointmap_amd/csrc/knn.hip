@@ -12,6 +12,9 @@
 // (the K=3 sgemm is an fma chain in k order; verified equal on 3.3e7 pairs in the build container),
 // so radius cuts and K-th-neighbour cuts fall exactly where the reference's fall.  This file is
 // compiled with -ffp-contract=off; every fused operation below is an explicit fmaf.
+// (The chain is the sgemm's main path.  A remainder row of the centre matrix -- the one row of S = 1, row 16 of S = 17 --
+// takes another path in some host BLAS builds and rounds differently there; such rows follow the chain here.  DESIGN.md,
+// "Exits of the neighbour search"; tests/knn_paths_restated.py writes the chain out.)
 // Padded points (index >= lengths[b]) are ignored: the reference moves them to 3*max|coord|,
 // which is never nearer than any valid point, so they can only ever be masked out.
 //
@@ -21,8 +24,10 @@
 // where the expanded form quantises distances to ~1e-7) but one flipped neighbour moves the final
 // pose by ~1e-4 m, so rows flagged with a boundary tie are re-run through a sequential emulation
 // of heap-select (make_heap over the first K points, then pop/replace in index order) and give
-// exactly the reference's set.  For K*64 > N the reference uses std::nth_element; ties there
-// keep the smaller index (none occur on the shipped shapes).
+// exactly the reference's set.  For K*64 > N the reference uses std::nth_element, replayed the same
+// way (nth_select_exact); only a tied row that finds the tie queue full there keeps the smaller indices
+// (finish(); pinned by tests/test_gpu_knn_paths.py, case tieq_overflow_nth).  Among several points at
+// the row's MINIMUM distance the nearest (slot 0, and the filler of unused slots) is the smallest index.
 //
 // Two search strategies, same candidate logic:
 //  * BRUTE (N < 1024): one wave handles 4 centres and streams all points of the frame.
@@ -1589,6 +1594,21 @@ extern "C" int dpm_knn_hybrid_prebuilt(const float *points, const int32_t *lengt
 extern "C" int dpm_knn_hybrid(const float *points, const int32_t *lengths, const float *centers, int B, int N,
                               int S, int K, double radius, int32_t *idx, void *workspace, dpm_stream_t stream) {
     return dpm_knn_hybrid_reuse(points, lengths, centers, B, N, S, K, radius, idx, workspace, nullptr, nullptr, stream);
+}
+
+// What the last build + search on this workspace did, for tests and debugging: two device-to-device copies of words the
+// kernels keep anyway (nothing is counted for this; the workspace is only read).  out, 8 B + 2 words: per frame the
+// KnnGrid header (lox, loy, inv_cs as floats, g, err2 as a float, H, h, 0), then tie_count[0] (tied rows offered to the tie
+// queue: a row the fast search found the queue full for is offered again by the full search and counts twice) and
+// tie_count[1] (rows the fast search left to the full one).
+extern "C" int dpm_knn_debug_census(const void *workspace, int B, int N, int32_t *out, dpm_stream_t stream) {
+    static_assert(sizeof(KnnGrid) == 8 * sizeof(int32_t), "the census is documented as 8 words per frame");
+    DPM_CHECK_ARG(workspace && out && B >= 1 && N >= GRID_MIN_N);
+    hipStream_t st = (hipStream_t)stream;
+    const KnnWs w = carve(const_cast<void *>(workspace), B, N);
+    hipError_t e = hipMemcpyAsync(out, w.hdr, (size_t)B * sizeof(KnnGrid), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out + 8 * (size_t)B, w.tie_count, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+    return e == hipSuccess ? DPM_OK : (int)e;
 }
 
 // ---- self kNN (pre-processing filters) ------------------------------------------------------------------

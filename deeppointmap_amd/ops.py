@@ -194,6 +194,22 @@ def knn_hybrid(points: torch.Tensor, lengths: torch.Tensor, centers: torch.Tenso
     return idx
 
 
+def knn_grid_census(grid: torch.Tensor, B: int, N: int) -> dict:
+    """What the last knn_grid + knn_hybrid(..., grid=grid) on this workspace did (tests, debugging; one host read):
+    {"frames": B dicts of the grid header (lox, loy, inv_cs, g, err2, H, h), "tie": tied rows offered to the tie queue,
+    "todo": rows the fast search left to the full search}."""
+    lib = _lib.load()
+    if grid.dtype != torch.uint8 or not grid.is_cuda or grid.numel() != lib.dpm_knn_workspace_bytes(B, N) or N < GRID_MIN_N:
+        raise ValueError("grid must be the knn_grid workspace of the (B, N) given")
+    out = torch.empty(8 * B + 2, device=grid.device, dtype=torch.int32)
+    _lib.check(lib.dpm_knn_debug_census(_ptr(grid), B, N, _ptr(out), _stream(grid)), "dpm_knn_debug_census")
+    words = out.cpu()
+    hdr_i, hdr_f = words[:8 * B].view(B, 8), words[:8 * B].view(torch.float32).view(B, 8)
+    frames = [dict(lox=float(hdr_f[b, 0]), loy=float(hdr_f[b, 1]), inv_cs=float(hdr_f[b, 2]), g=int(hdr_i[b, 3]),
+                   err2=float(hdr_f[b, 4]), H=int(hdr_i[b, 5]), h=int(hdr_i[b, 6])) for b in range(B)]
+    return dict(frames=frames, tie=int(words[8 * B]), todo=int(words[8 * B + 1]))
+
+
 def ball_query(points: torch.Tensor, lengths: torch.Tensor, centers: torch.Tensor, K: int, radius: float) -> torch.Tensor:
     """points (B,N,3), centers (B,S,3) -> idx (B,S,K) int32: first K indices within the radius, padded with the first."""
     _chk(points, torch.float32, "points"), _chk(centers, torch.float32, "centers"), _chk(lengths, torch.int32, "lengths")

@@ -121,6 +121,13 @@ int dpm_knn_build_grid(const float *points, const int32_t *lengths, int B, int N
                        dpm_stream_t stream);
 int dpm_knn_hybrid_prebuilt(const float *points, const int32_t *lengths, const float *centers, int B, int N,
                             int S, int K, double radius, int32_t *idx, void *workspace, dpm_stream_t stream);
+/* Read-only census of what the last build and search on `workspace` (B frames of N >= 1024 points) did, for tests and
+ * debugging: out (device, 8 B + 2 32-bit words) receives per frame the grid header -- lox, loy, 1 / cell edge (floats),
+ * cells per axis, the margin err2 of the expanded-form distance (float), the half-widths H of the covering and h of the
+ * inner block, 0 -- then the number of tied rows offered to the tie queue (a row offered while the queue is full is offered
+ * once more by the full search) and the number of rows the fast search left to the full search.  Two copies in stream
+ * order; no kernel counts anything for it. */
+int dpm_knn_debug_census(const void *workspace, int B, int N, int32_t *out, dpm_stream_t stream);
 
 /* Querier.ball_query / ball_query_t3d == pytorch3d.ops.ball_query (utils.py:57-73,99-110): the K
  * smallest indices among the valid points within `radius` (expanded-form distance, like the
